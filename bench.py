@@ -1,6 +1,6 @@
 """bench.py -- frames/s of 368x368, 3-scale VNect inference on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N>1: one rank per GPU.  Under a launcher (torch.distributed.run sets RANK / WORLD_SIZE) this process IS a rank; started bare
 (`python bench.py --gpus N`, no WORLD_SIZE) it spawns its N rank processes itself -- children with RANK / LOCAL_RANK /
@@ -305,6 +305,11 @@ def main():
                     help="parity evidence for the N > 1 tests (tests/test_gpu_multigpu.py): behind the timed region every rank runs 8 more "
                          "frames of its stream on fresh filter banks at fixed timestamps and writes PREFIX.<leg>.rank<r>.npz (j2, j3); a "
                          "single-GPU run of the same seeds must reproduce them bit for bit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the headline's timed region, write what its LAST timed step returned to the caller -- the joints of "
+                         "Handle.infer_resident -- as DIR/joints_2d.npy (21x2 float64) and DIR/joints_3d.npy (21x3 float32); rank r > 0 of "
+                         "an N > 1 job adds .rank<r> before .npy.  Frames, weights and timestamps are fixed by the arguments, so two builds "
+                         "run with the same arguments can be compared output for output")
     ap.add_argument("--no-bind", action="store_true",
                     help="N > 1: leave every rank's host thread where the scheduler puts it.  Default: before its first GPU call a rank binds "
                          "itself to the cores local to its GPU (/sys/bus/pci/devices/<bdf>/local_cpulist) and reports the mask in `ranks[]`")
@@ -450,6 +455,7 @@ def main():
         torch.cuda.synchronize()
 
     own = [0.0, 0.0]
+    last = [None]   # (j2, j3) of the last timed step of the latest timed region
 
     def timed(hh, steps, warmup):
         """W untimed frames, then EXACTLY `steps` synchronous frames between barrier + synchronize; MAX over ranks."""
@@ -465,6 +471,7 @@ def main():
         barrier()
         own[1] = time.perf_counter() - t0 - own[0]   # what the closing barrier + synchronize took on this rank (INSIDE the region by the contract)
         elapsed = grp.max_over_ranks(time.perf_counter() - t0)
+        last[0] = (j2, j3)
         assert np.all(np.isfinite(j2)) and np.all(np.isfinite(j3))
         return elapsed, np.diff(np.array(stamps)) * 1e3
 
@@ -518,6 +525,11 @@ def main():
 
     elapsed, lat = timed(h, args.steps, args.warmup)
     own_elapsed, own_close = own[0], own[1]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = ".rank%d" % rank if rank else ""
+        np.save(os.path.join(args.dump_outputs, "joints_2d%s.npy" % sfx), np.asarray(last[0][0], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "joints_3d%s.npy" % sfx), np.asarray(last[0][1], dtype=np.float32))
     dump_joints(h, ("pyramid_" + args.exchange) if args.pyramid else "replica")
 
     # pipelined rate of the same stream (three frames in flight on three lanes: they overlap, only the filter kernels stay
