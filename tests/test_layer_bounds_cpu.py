@@ -1,0 +1,201 @@
+"""The per-element gate of tests/layer_ref.py is not vacuous (CPU, no GPU needed).
+
+A CPU stand-in for the device computes every tensor of a keep_activations plan from its inputs the way the HIP launches do:
+torch float32 accumulation, bf16 round-to-nearest-even at the kernels' rounding points (every stored activation of a bf16 handle
+but the fp32 final maps), the BN scale / shift of plan::fold_bn, the bone lengths from the stored deltas.  The clean stand-in must
+pass the gate on every tensor in fp32 and in bf16; each planted fault must fail it on exactly the tensor it was planted in (the
+stand-in recomputes everything behind a fault from the faulty tensor, as a device would, so only that tensor's own launch is
+wrong).  One scale at 368 x 368, synthetic weights.
+"""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import helpers, layer_ref
+from tests.layer_ref import TABLE
+
+# fault -> (tensor, precision).  (a) truncating store, (b) bias lost on 4 channels of a 1x1 layer, (c) the first 64-element K chunk
+# lost in the last tile (64 output pixels) of a 3x3 layer, (d) a block output rounded before the shortcut add and again after it,
+# (e) a 3x3 layer's top output row read without its SAME padding row (image rows 0..2 instead of pad, 0, 1), (f) one low-magnitude
+# channel of an fp32 layer 1e-3 off
+FAULTS = {
+    "truncate": ("res4b_branch2a", "bf16"),
+    "bias": ("res3b_branch2a", "bf16"),
+    "kchunk": ("res4b_branch2b", "bf16"),
+    "double_round": ("res3c", "bf16"),
+    "pad_row": ("res2b_branch2b", "bf16"),
+    "channel": ("res5a_branch1_new", "fp32"),
+}
+
+
+def _trunc_bf16(t):
+    return (t.view(torch.int32) & -65536).view(torch.float32)
+
+
+def _rne_bf16(t):
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def _low_channel(y):
+    """the channel with the smallest nonzero maximum of |y| (NCHW)"""
+    m = y.abs().amax(dim=(0, 2, 3))
+    m = torch.where(m > 0, m, torch.full_like(m, float("inf")))
+    return int(torch.argmin(m))
+
+
+def device_forward(weights, batch, prec, fault=None):
+    """Every tensor of TABLE (name -> NHWC float32 numpy) as a device with fp32 accumulation computes it; fault: a key of FAULTS."""
+    bf = prec == "bf16"
+    lw = layer_ref.layer_weights(weights, prec)
+    target = FAULTS[fault][0] if fault else None
+    T = {}
+    info = {}
+
+    def f32(a):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32))
+
+    def store(name, v, f32_out=False):
+        if bf and not f32_out:
+            v = _trunc_bf16(v) if (fault == "truncate" and name == target) else _rne_bf16(v)
+        T[name] = v
+
+    def same(x, k, stride, top=None):
+        def lohi(n):
+            total = max((-(-n // stride) - 1) * stride + k - n, 0)
+            return total // 2, total - total // 2
+        (t, b), (l, r) = lohi(x.shape[2]), lohi(x.shape[3])
+        if top is not None:
+            t, b = top, t + b - top
+        return F.pad(x, (l, r, t, b))
+
+    for name, (op, ins, p) in TABLE.items():
+        if op == "input":
+            x = f32(batch).permute(0, 3, 1, 2)
+            T[name] = _rne_bf16(x) if bf else x
+        elif op == "pool":
+            T[name] = layer_ref.maxpool_same(T[ins[0]])
+        elif op in ("conv", "head"):
+            x = T[ins[0]]
+            if op == "head":
+                w, b, k, stride, relu = lw["res5c_branch2c/kernel"], np.zeros(84, np.float32), 1, 1, False
+            else:
+                w, b = lw[p["scope"] + "/weights"], np.array(lw[p["scope"] + "/biases"], np.float32)
+                k, stride, relu = p["k"], p["stride"], p["relu"]
+            if fault == "bias" and name == target:
+                b = b.copy()
+                b[:4] = 0
+            wt = f32(w).permute(3, 2, 0, 1)
+            acc = F.conv2d(same(x, k, stride) if k > 1 else x, wt, stride=stride)
+            if fault == "kchunk" and name == target:   # the last tile's rows without K chunk 0 (tap (0,0), channels 0..63)
+                wc = wt.clone()
+                wc[:, :64, 0, 0] = 0
+                tail = F.conv2d(same(x, k, stride), wc, stride=stride)
+                S, C, H, W = acc.shape
+                a2 = acc.permute(0, 2, 3, 1).reshape(-1, C).clone()
+                a2[-64:] = tail.permute(0, 2, 3, 1).reshape(-1, C)[-64:]
+                acc = a2.reshape(S, H, W, C).permute(0, 3, 1, 2)
+            if fault == "pad_row" and name == target:  # output row 0 with no padding row above the image (both below it)
+                acc = acc.clone()
+                acc[:, :, 0] = F.conv2d(same(x, k, stride, top=0), wt, stride=stride)[:, :, 0]
+            v = acc + f32(b).view(1, -1, 1, 1)
+            if len(ins) > 1:
+                if fault == "double_round" and name == target:
+                    v = _rne_bf16(v)
+                v = v + T[ins[1]]
+            if relu:
+                v = F.relu(v)
+            if fault == "channel" and name == target:
+                ch = _low_channel(v)
+                info.update(channel=ch, ch_max=float(v[:, ch].abs().max()), layer_max=float(v.abs().max()))
+                v = v.clone()
+                v[:, ch] *= 1.001
+            store(name, v, f32_out=op == "head")
+        elif op == "feat":
+            x = T[ins[0]]
+            d2 = F.conv_transpose2d(x, f32(lw["res5c_branch2a/kernel"]).permute(3, 2, 0, 1), stride=2, padding=1)
+            d1 = F.conv_transpose2d(x, f32(lw["res5c_branch1a/kernel"]).permute(3, 2, 0, 1), stride=2, padding=1)
+            bias, scale, shift = (f32(v).view(1, -1, 1, 1) for v in layer_ref.fold_bn(lw))
+            bn = F.relu((d2 + bias) * scale + shift)
+            deltas = _rne_bf16(d1) if bf else d1
+            dx, dy, dz = deltas[:, 0:21], deltas[:, 21:42], deltas[:, 42:63]
+            bone = torch.sqrt((dx * dx + dy * dy) + dz * dz)
+            store(name, torch.cat([bn, d1, bone], 1))
+    return {k: v.permute(0, 2, 3, 1).contiguous().numpy() for k, v in T.items()}, info
+
+
+@pytest.fixture(scope="module")
+def batch():
+    frame = helpers.synth_frame(1234, smooth=True).astype(np.float32)
+    return (frame / 255.0 - 0.4)[None]
+
+
+def _failing(rows):
+    return sorted(r["tensor"] for r in rows if not r["ok"])
+
+
+def _report(tag, rows):
+    worst = max(rows, key=lambda r: r["cal"])
+    m = [r["match"] for r in rows if r["match"] is not None]
+    print("%-24s worst calibrated %.3g (%s), worst rigorous %.3g, lowest bf16 match %s" % (
+        tag, worst["cal"], worst["tensor"], max(r["rig"] for r in rows), ("%.5f" % min(m)) if m else "-"))
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_clean_stand_in_passes_every_tensor(weights, batch, prec):
+    acts, _ = device_forward(weights, batch, prec)
+    rows = layer_ref.check_all(acts, weights, prec, batch)
+    _report(prec, rows)
+    assert len(rows) == len(TABLE)
+    assert _failing(rows) == [], [r for r in rows if not r["ok"]][:3]
+
+
+@pytest.mark.parametrize("fault", sorted(FAULTS))
+def test_planted_fault_fails_the_gate_on_its_tensor(weights, batch, fault):
+    target, prec = FAULTS[fault]
+    acts, info = device_forward(weights, batch, prec, fault)
+    rows = layer_ref.check_all(acts, weights, prec, batch)
+    _report(fault, rows)
+    assert _failing(rows) == [target]
+    row = next(r for r in rows if r["tensor"] == target)
+    if fault == "truncate":
+        assert row["match"] < 0.75  # the sharpness gate alone catches a truncating store
+    if fault == "channel":
+        # invisible to the layer-maximum gate of test_conv_stack_every_layer, caught by the calibrated tier only
+        assert 1e-3 * info["ch_max"] <= 1e-4 * info["layer_max"], info
+        assert row["cal"] > 1.0 and row["rig"] <= 1.0, row
+
+
+def test_table_wiring_matches_the_float64_graph(weights, batch):
+    """The input table is the graph of tests/torch_net.py: each tensor's reference, fed torch_net's own float64 activations (as
+    float32), reproduces torch_net's activation of that name (a wrong input, scope, stride, padding, ReLU or BN fold would not)."""
+    from tests import torch_net
+    taps = {}
+    torch_net.forward(weights, batch, taps=taps)
+    acts = {k: v.numpy().astype(np.float32) for k, v in taps.items()}
+    acts["input"] = batch
+    for name, (op, _, _) in TABLE.items():
+        if op == "input":
+            continue
+        r = layer_ref.reference(name, acts, weights)
+        y = r["exact"] if "exact" in r else r["y"]
+        want = taps[name].numpy()
+        assert y.shape == want.shape, name
+        assert float(np.abs(y - want).max()) <= 1e-5 * float(np.abs(want).max()), name
+
+
+def test_every_launch_form_maps_to_a_checked_tensor():
+    """launch_tensors: the launch names of keep_activations plans (rt_plan.cpp) map to table tensors; fused launches and unknown
+    names raise, so that the GPU test's coverage assertion fails on a launch form it does not know."""
+    lt = layer_ref.launch_tensors
+    assert lt("res2a_branch2a+branch1") == ["res2a_branch2a", "res2a_branch1"]
+    assert lt("res2b_branch2b+res2c_branch2b") == ["res2b_branch2b", "res2c_branch2b"]
+    assert lt("res5a_branch2a_new[:256]") == ["res5a_branch2a_new"]
+    assert lt("res5a_branch2a_new+branch1_new") == ["res5a_branch2a_new", "res5a_branch1_new"]
+    assert lt("res3b_branch2c") == ["res3b"] and lt("res5a_branch2c_new") == ["res5a"]
+    assert lt("res5c_deconv") == lt("res5c_bone_length") == ["res5c_branch2a_feat"]
+    assert lt("res5c_branch2c") == ["res5c_branch2c"] and lt("res5b_branch2c_new") == ["res5b_branch2c_new"]
+    assert lt("conv1", stem=True) == ["pool1"]
+    for bad in ("res2a_branch2b>res2a_branch2c", "res3a_branch2b>res3a_branch2c>res3b_branch2a", "res2c_branch2a", "res6a"):
+        with pytest.raises(KeyError):
+            lt(bad)
