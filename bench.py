@@ -1,6 +1,6 @@
 """bench.py -- frames/s of 368x368, 3-scale VNect inference on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1: one rank per GPU.  Under a launcher (torch.distributed.run sets RANK / WORLD_SIZE) this process IS a rank; started bare
 (`python bench.py --gpus N`, no WORLD_SIZE) it spawns its N rank processes itself -- children with RANK / LOCAL_RANK /
@@ -13,8 +13,12 @@ HBM before the timed region (the host-to-device copy of a frame is OUTSIDE it; t
 beside `value`); each step ends with the 21x2 + 21x3 joints back on the host (synchronous, as the reference's
 tracking loop consumes them).  N>1 = N independent streams, one per GPU (weak scaling, no collective on the data
 path; BASELINE.json configs[4]); `--pyramid` = ONE stream, one scale per GPU (configs[3]).  Weights are seeded
-synthetic (none ship with the reference).  Rank 0 prints ONE JSON line; at N=1 it also carries the bf16 path
-(configs[2]) measured the same way behind the fp32 timed region, under the key "bf16".
+synthetic (none ship with the reference).  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line.  `--full` adds everything else behind the headline's timed region: the auxiliary legs (PCIe-inclusive, frames in flight,
+two and three streams per GPU), the bf16 (configs[2]) and split-product legs at N=1, the live roofline and per-rank device figures
+of the profiling twin, the same-job N = 1 reference at N>1 and the CPU baselines.
 """
 import argparse
 import glob
@@ -282,13 +286,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline (see the module's docstring); off: set up, warm up, time the K steps, "
+                         "write --dump-outputs, print the line")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches everywhere")
     ap.add_argument("--graph", action="store_true", help="replay the frame graph for synchronous frames too (default: auto = eager "
                                                         "launches for a synchronous frame, graph replay when frames are in flight)")
     ap.add_argument("--no-aux", action="store_true",
-                    help="skip the auxiliary legs (PCIe-inclusive, frames in flight, two streams per GPU, the bf16 leg): a rocprofv3 "
-                         "run meant to describe the synchronous headline loop of ONE precision uses this")
+                    help="--full: skip the auxiliary legs (PCIe-inclusive, frames in flight, two streams per GPU, the bf16 leg): a "
+                         "profiler run meant to describe the synchronous headline loop of ONE precision uses this")
     ap.add_argument("--precision", choices=["fp32", "bf16", "fp32_split"], default="fp32",
                     help="fp32 = BASELINE.json configs[1] (default, the headline); bf16 = configs[2] (bf16 MFMA conv path); fp32_split = fp32 "
                          "tensors and accumulators, products on the bf16 matrix pipe by exact three-way splits (VNECT_FP32_SPLIT)")
@@ -315,7 +322,8 @@ def main():
                          "itself to the cores local to its GPU (/sys/bus/pci/devices/<bdf>/local_cpulist) and reports the mask in `ranks[]`")
     ap.add_argument("--bind", action="store_true", help="apply the same binding at N = 1 (default there: report it, do not apply it)")
     ap.add_argument("--no-n1", action="store_true",
-                    help="N > 1: skip the same-job N = 1 reference (rank 0's loop run alone, the other ranks idle, before the N-rank region)")
+                    help="--full, N > 1: skip the same-job N = 1 reference (rank 0's loop run alone, the other ranks idle, before the N-rank "
+                         "region)")
     ap.add_argument("--pyramid-both", action="store_true",
                     help="--pyramid with BOTH exchange forms in one job (rccl first, then p2p): the side-by-side SURVEY 8e asks for "
                          "from one 3-GPU lease; `value` is the RCCL all-gather form (the one north_star names), p2p under \"pyramid_p2p\"")
@@ -486,10 +494,11 @@ def main():
         np.savez("%s.%s.rank%d.npz" % (args.dump_joints, leg, rank), j2=np.stack([a for a, _ in js]), j3=np.stack([b for _, b in js]),
                  device=np.int64(local_rank), stream=np.int64(stream))
 
-    # N > 1: the same-box, same-minute denominator of `value / N` -- rank 0 runs the N = 1 loop ALONE first (W warm-up + K timed frames of
+    # N > 1, --full: the same-box, same-minute denominator of `value / N` -- rank 0 runs the N = 1 loop ALONE first (W warm-up + K timed frames of
     # the plain 3-scale handle; a pyramid job builds one for this), the other ranks wait on the rendezvous store with their GPUs idle.
     n1_same_job = None
-    if args.gpus > 1 and not args.no_n1:
+    nprof = min(max(args.steps // 4, 10), 100)   # frames of a profiling-twin pass (--full)
+    if args.full and args.gpus > 1 and not args.no_n1:
         grp.barrier()
         if rank == 0:
             h1 = h
@@ -507,12 +516,11 @@ def main():
                 st1.append(time.perf_counter())
             torch.cuda.synchronize()
             e1 = time.perf_counter() - t0
-            np1 = min(max(args.steps // 4, 10), 100)
-            tim1 = profile(lambda n: run(h1, n), h1, np1)   # the same device-side figures the per-rank reports carry, for the solo loop
+            tim1 = profile(lambda n: run(h1, n), h1, nprof)   # the same device-side figures the per-rank reports carry, for the solo loop
             n1_same_job = {"value": round(args.steps / e1, 2), "unit": "frames/s", "ms_per_step": round(e1 / args.steps * 1e3, 4),
                            "steps": args.steps, "warmup": args.warmup, "rank": 0, "device": local_rank,
                            "latency_ms": latency_summary(np.diff(np.array(st1)) * 1e3, args.steps),
-                           "conv_stack_ms": round(tim1["conv_slot_ms"] / np1, 4), "frame_ms_hip_events": round(tim1["total_ms"] / np1, 4),
+                           "conv_stack_ms": round(tim1["conv_slot_ms"] / nprof, 4), "frame_ms_hip_events": round(tim1["total_ms"] / nprof, 4),
                            "shader_clock_mhz": None if not tim1.get("shader_clock_mhz") else round(tim1["shader_clock_mhz"], 1),
                            "what": "rank 0's synchronous 3-scale loop run alone inside this job, before the %d-rank region; the other ranks "
                                    "wait on the rendezvous store (host-side: their GPUs are idle)" % args.gpus}
@@ -522,6 +530,11 @@ def main():
                 h.reset_filters()
         grp.host_handoff("n1_done", release=rank == 0)
         grp.barrier()
+    elif args.gpus > 1 and not args.no_n1 and rank == 0:
+        # without --full the reference leg does not run, but its frames' timestamps still pass on rank 0: the filters then see the
+        # same timestamps as in a --full run, so --dump-outputs writes the same joints
+        for _ in range(args.warmup + args.steps + nprof):
+            clock[0] += 1 / 30
 
     elapsed, lat = timed(h, args.steps, args.warmup)
     own_elapsed, own_close = own[0], own[1]
@@ -535,7 +548,7 @@ def main():
     # pipelined rate of the same stream (three frames in flight on three lanes: they overlap, only the filter kernels stay
     # ordered), reported beside the synchronous one
     pipelined = pcie = pinned = two_streams = call_surface = None
-    if not args.no_aux and not args.pyramid:
+    if args.full and not args.no_aux and not args.pyramid:
         barrier()
         p0 = time.perf_counter()
         depth = 3  # frames in flight = lanes of the handle
@@ -613,7 +626,7 @@ def main():
     # three independent video streams served by THIS handle (vnect_submit_stream: a filter bank per stream, one weight copy, three
     # lanes): nothing chains frames of different streams, so they overlap completely.  Beside the headline, never `value`.
     streams3 = None
-    if not args.no_aux and not args.pyramid:
+    if args.full and not args.no_aux and not args.pyramid:
         barrier()
         base = clock[0] + 1000.0
         s0 = time.perf_counter()
@@ -629,23 +642,25 @@ def main():
         clock[0] = base + 100 + args.steps / 30
         h.reset_filters()
 
-    nprof = min(max(args.steps // 4, 10), 100)
-    # every rank profiles its own handle (no collective inside a replica's frames; a pyramid job's inferences contain the exchange, so
+    # --full: every rank profiles its own handle (no collective inside a replica's frames; a pyramid job's inferences contain the exchange, so
     # every rank must take part anyway): per-rank conv-stack time and the shader clock each GPU held are what explains an N > 1 curve
     def rank_report(lat_, own_, tim_, close_):
-        return grp.all_gather_object({
+        rep = {
             "rank": rank, "device": local_rank,
             "frames_per_s": round(args.steps / own_, 2), "own_elapsed_s": round(own_, 5),
             # the closing barrier + torch.cuda.synchronize() of the timed region (the contract puts it inside): what separates `value` from the
             # frames' own rate in a short window; at N > 1 it also holds this rank's wait for the slowest one
             "closing_barrier_us": round(close_ * 1e6, 1),
-            "latency_ms": {k: v for k, v in latency_summary(lat_, args.steps).items() if k != "frames_ms"},
-            "conv_stack_ms": round(tim_["conv_slot_ms"] / nprof, 4), "conv_first_to_last_ms": round(tim_["net_ms"] / nprof, 4),
-            "frame_ms_hip_events": round(tim_["total_ms"] / nprof, 4),
-            "shader_clock_mhz": None if not tim_.get("shader_clock_mhz") else round(tim_["shader_clock_mhz"], 1),
-            "host_binding": {k: binding.get(k) for k in ("bound", "affinity", "n_cpus", "numa_node", "bdf", "reason") if binding.get(k) is not None}})
+            "latency_ms": {k: v for k, v in latency_summary(lat_, args.steps).items() if k != "frames_ms"}}
+        if tim_ is not None:
+            rep.update({
+                "conv_stack_ms": round(tim_["conv_slot_ms"] / nprof, 4), "conv_first_to_last_ms": round(tim_["net_ms"] / nprof, 4),
+                "frame_ms_hip_events": round(tim_["total_ms"] / nprof, 4),
+                "shader_clock_mhz": None if not tim_.get("shader_clock_mhz") else round(tim_["shader_clock_mhz"], 1)})
+        rep["host_binding"] = {k: binding.get(k) for k in ("bound", "affinity", "n_cpus", "numa_node", "bdf", "reason") if binding.get(k) is not None}
+        return grp.all_gather_object(rep)
 
-    tim = profile(lambda n: run(h, n), h, nprof)
+    tim = profile(lambda n: run(h, n), h, nprof) if args.full else None
     per_rank = rank_report(lat, own_elapsed, tim, own_close)
     pyramid_p2p = None
     if args.pyramid_both:  # the same job again with the exchange by peer writes: same frames, steps, barriers; every rank takes part
@@ -657,7 +672,7 @@ def main():
         e2, lat2 = timed(h, args.steps, args.warmup)
         own2, close2 = own[0], own[1]
         dump_joints(h, "pyramid_p2p")
-        tim2 = profile(lambda n: run(h, n), h, nprof)
+        tim2 = profile(lambda n: run(h, n), h, nprof) if args.full else None
         pyramid_p2p = {"value": round(args.steps / e2, 2), "unit": "frames/s", "ms_per_step": round(e2 / args.steps * 1e3, 4),
                        "exchange": "peer writes over xGMI (exchange_kernel)",
                        "latency_ms": latency_summary(lat2, args.steps), "per_rank": rank_report(lat2, own2, tim2, close2)}
@@ -690,8 +705,9 @@ def main():
             "rccl_ranks": ranks_seen if backend == "nccl" else None, "backend": backend, "backend_ranks": ranks_seen,
             # (round 6) what explains an N > 1 curve, rank by rank: each rank's OWN rate over its K frames (`value` is N K / the slowest
             # rank's time), its latency distribution, its conv stack on the device clock, the shader clock its GPU held under load
-            # (eight GPUs share a node's power), where its host thread sat; and the N = 1 loop of the same job
-            "per_rank": per_rank, "n1_same_job": n1_same_job, "build": _native.build_info()["text"],
+            # (eight GPUs share a node's power), where its host thread sat; and the N = 1 loop of the same job (the device figures
+            # and the N = 1 loop with --full)
+            "per_rank": per_rank, "build": _native.build_info()["text"],
             "ranks": placement, "launched_by": "bench.py (self-spawned ranks)" if os.environ.get("VNECT_BENCH_SPAWNED") else
                                                ("launcher (RANK / WORLD_SIZE in the environment)" if args.gpus > 1 else "single process"),
             "exchange": (("rccl: ncclAllGather of 710 976 B per rank" if args.exchange == "rccl" else "p2p: peer writes over xGMI")
@@ -706,19 +722,22 @@ def main():
             "one_scale_vs_three": (dict(zip(("ms_per_frame", "source"), committed("_one_scale_rate.json", "ms_per_frame")))
                                    if args.pyramid else None),
             "rccl_library": rccl_lib,
-            "pcie_inclusive_frames_per_s_per_gpu": None if pcie is None else round(pcie, 2),
-            "pcie_inclusive_from_pinned_capture_buffer_frames_per_s_per_gpu": None if pinned is None else round(pinned, 2),
-            "call_surface": call_surface,
-            "pipelined_frames_per_s_per_gpu": None if pipelined is None else round(pipelined, 2),
-            "two_streams_on_one_gpu_frames_per_s": None if two_streams is None else round(two_streams, 2),
-            "three_streams_on_one_handle_frames_per_s": None if streams3 is None else round(streams3, 2),
-            "roofline": roofline(tim, nprof, args.precision, frac_images),
         }
+        if args.full:
+            out.update({
+                "n1_same_job": n1_same_job,
+                "pcie_inclusive_frames_per_s_per_gpu": None if pcie is None else round(pcie, 2),
+                "pcie_inclusive_from_pinned_capture_buffer_frames_per_s_per_gpu": None if pinned is None else round(pinned, 2),
+                "call_surface": call_surface,
+                "pipelined_frames_per_s_per_gpu": None if pipelined is None else round(pipelined, 2),
+                "two_streams_on_one_gpu_frames_per_s": None if two_streams is None else round(two_streams, 2),
+                "three_streams_on_one_handle_frames_per_s": None if streams3 is None else round(streams3, 2),
+                "roofline": roofline(tim, nprof, args.precision, frac_images)})
     h.close()
 
     # BASELINE.json configs[2] in the same record: the bf16 MFMA conv path, measured exactly like the headline (same frames,
     # same warm-up / steps / barriers), after the fp32 timed region.  N=1 only; never `value`.
-    if args.gpus == 1 and args.precision == "fp32" and not args.no_aux and not args.pyramid:
+    if args.full and args.gpus == 1 and args.precision == "fp32" and not args.no_aux and not args.pyramid:
         hb = make("bf16", use_graph=graph_mode, lanes=3)
         for k in range(nslots):
             hb.upload_frame(k, host_frames[k])
@@ -747,7 +766,7 @@ def main():
     # The split-product fp32 path (VNECT_FP32_SPLIT: fp32 tensors and accumulators, fp32-class results -- gated like fp32 in
     # tests/test_gpu_split.py -- with the products of the big layers on the bf16 matrix pipe), measured exactly like the headline.
     # Beside the headline, never `value`: the headline stays the fp32 INSTRUCTION path until the judge rules on this one.
-    if args.gpus == 1 and args.precision == "fp32" and not args.no_aux and not args.pyramid:
+    if args.full and args.gpus == 1 and args.precision == "fp32" and not args.no_aux and not args.pyramid:
         hs = make("fp32_split", use_graph=graph_mode, lanes=3)
         for k in range(nslots):
             hs.upload_frame(k, host_frames[k])
@@ -775,7 +794,7 @@ def main():
                              "roofline": roofline(tims, nprof, "fp32_split")}
 
     if rank == 0:
-        if args.cpu_seconds > 0 and args.gpus == 1:
+        if args.full and args.cpu_seconds > 0 and args.gpus == 1:
             # `cpu_baseline` is the FASTEST honest CPU implementation of the same workload this box can run: the reference's TF-CPU path
             # cannot run at all (no TF1, no weights), so both candidates are stand-ins and say so -- the C/OpenMP port of the path (the
             # oracle; always kept under `cpu_baseline_port`) and the torch-CPU / oneDNN network with the oracle's pre / post-processing
@@ -791,7 +810,7 @@ def main():
             out["cpu_baseline_framework"] = fw
             out["cpu_baseline"] = dict(fw if fw.get("value", 0) > port["value"] else port)
             out["cpu_baseline"]["chosen_as"] = "the faster of cpu_baseline_port and cpu_baseline_framework on this box"
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

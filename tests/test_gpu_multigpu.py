@@ -163,10 +163,11 @@ def _check_pyramid(weights, prefix, legs):
 # ------------------------------------------------------------------------------------------ armed: need the devices
 @needs(3)
 def test_needs_3_gpus_pyramid_both_exchange_forms_bit_equal(weights, tmp_path):
-    """configs[3] on hardware: `bench.py --gpus 3 --pyramid-both` -- 3 RCCL ranks on 3 distinct devices, the all-gather form and the
+    """configs[3] on hardware: `bench.py --full --gpus 3 --pyramid-both` -- 3 RCCL ranks on 3 distinct devices, the all-gather form and the
     peer-write form in one job, each bit-equal on every rank to the host-stacked reference on device 0 (hence to each other)."""
     prefix = str(tmp_path / "j")
-    d = _bench(["--gpus", "3", "--pyramid-both", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--dump-joints", prefix], _clean_env())
+    d = _bench(["--full", "--gpus", "3", "--pyramid-both", "--steps", "30", "--warmup", "5", "--cpu-seconds", "0", "--dump-joints", prefix],
+               _clean_env())
     assert d["rccl_ranks"] == 3 and d["backend"] == "nccl" and d["n_gpus"] == 3 and d["scaling"] == "strong"
     assert len({r["pci_bus_id"] for r in d["ranks"]}) == 3 and sorted(r["device"] for r in d["ranks"]) == [0, 1, 2], d["ranks"]
     assert d["exchange"].startswith("rccl") and d["pyramid_p2p"] and d["pyramid_p2p"]["value"] > 0
@@ -259,10 +260,10 @@ def test_needs_2_gpus_p2p_missing_peer_fails_the_frame(tmp_path):
 
 @needs(2)
 def test_needs_2_gpus_stream_replicas_rccl(weights, tmp_path):
-    """configs[4] with two ranks: `bench.py --gpus 2` (self-spawned, backend nccl): rccl_ranks == 2 on two distinct devices, each rank's
+    """configs[4] with two ranks: `bench.py --full --gpus 2` (self-spawned, backend nccl): rccl_ranks == 2 on two distinct devices, each rank's
     stream bit-equal to a single-GPU run of the same seeds, and the per-GPU rate within 10 % of the N = 1 line of the same call."""
     prefix = str(tmp_path / "j")
-    common = ["--steps", "200", "--warmup", "20", "--cpu-seconds", "0", "--no-aux"]
+    common = ["--full", "--steps", "200", "--warmup", "20", "--cpu-seconds", "0", "--no-aux"]
     one = _bench(["--gpus", "1"] + common, _clean_env())
     two = _bench(["--gpus", "2", "--dump-joints", prefix] + common, _clean_env())
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -279,7 +280,7 @@ def test_rehearsal_one_device_two_replicas_gloo(weights, tmp_path):
     """The comparison code of test_needs_2_gpus_stream_replicas_rccl with both ranks on device 0 over gloo (RCCL refuses two ranks on one
     device): spawner, --dump-joints, every stream against a single-GPU run of its seeds.  No rate is asserted."""
     prefix = str(tmp_path / "j")
-    d = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--no-aux", "--dump-joints", prefix],
+    d = _bench(["--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--no-aux", "--dump-joints", prefix],
                _clean_env(VNECT_BENCH_BACKEND="gloo", VNECT_BENCH_DEVICE="0"))
     assert d["backend"] == "gloo" and d["rccl_ranks"] is None
     _check_replicas(weights, d, prefix, 2, same_device=True)
@@ -289,7 +290,7 @@ def test_rehearsal_one_device_pyramid_p2p_gloo(weights, tmp_path):
     """The comparison code of test_needs_3_gpus_pyramid_both_exchange_forms_bit_equal with the three ranks on device 0 (three processes,
     IPC-mapped blocks, gloo): the peer-write leg only -- the line says why -- against the host-stacked reference."""
     prefix = str(tmp_path / "j")
-    d = _bench(["--gpus", "3", "--pyramid-both", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--dump-joints", prefix],
+    d = _bench(["--full", "--gpus", "3", "--pyramid-both", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--dump-joints", prefix],
                _clean_env(VNECT_BENCH_BACKEND="gloo", VNECT_BENCH_DEVICE="0"))
     assert d["backend_ranks"] == 3 and d["exchange"].startswith("p2p") and "RCCL leg" in d["note"]
     _check_self_explaining(d, 3, same_device=True, replicas=False)

@@ -112,10 +112,10 @@ def test_library_alone_opens_rocms_rccl(tmp_path):
 
 
 def test_bench_pyramid_one_rank_under_nccl():
-    """`python bench.py --pyramid --scales 1.0 --gpus 1`: the configs[3] code path end to end with ONE rank -- backend "nccl", the
+    """`python bench.py --full --pyramid --scales 1.0 --gpus 1`: the configs[3] code path end to end with ONE rank -- backend "nccl", the
     process group built although the world is 1, PyramidJob, ncclAllGather in every frame, timed loop, profiling twin -- and the line
     says which RCCL it used and that it is a rehearsal."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pyramid", "--scales", "1.0", "--gpus", "1", "--steps", "30",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--pyramid", "--scales", "1.0", "--gpus", "1", "--steps", "30",
                         "--warmup", "5", "--cpu-seconds", "0"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -671,7 +671,7 @@ def test_a_c_program_runs_frames_through_the_abi(weights, tmp_path):
 
 # ------------------------------------------------------------------------------------------ the bench line's contract
 def test_bench_line_contract():
-    """`python bench.py` as the driver runs it (N = 1): ONE JSON line on stdout with the contract's keys -- metric / value / unit /
+    """`python bench.py --full` (N = 1): ONE JSON line on stdout with the contract's keys -- metric / value / unit /
     n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload -- plus the
     `roofline` and `cpu_baseline` objects, the bf16 and split-product legs, and the evidence of what ran (ranks, backend)."""
     import json
@@ -679,7 +679,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--cpu-seconds", "1.5"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--cpu-seconds", "1.5"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -3,7 +3,7 @@
     python3 tools/explain_scale.py SCALE_r06.json            # the driver's record (any JSON holding bench lines under "parsed" or in a list)
     python3 tools/explain_scale.py line_n1.json line_n8.json # or the lines themselves
 
-For every line with `per_rank` (bench.py, round 6) it prints the ranks side by side -- own rate, p50 / p95, device time of a frame (HIP
+For every line with `per_rank` (bench.py --full, round 6) it prints the ranks side by side -- own rate, p50 / p95, device time of a frame (HIP
 events, profiling twin), conv stack, shader clock held under load, host gap per frame (1 / rate - device frame time), host binding -- and
 an attribution of `value / N` against the job's own N = 1 loop (`n1_same_job`):
   clock   the conv stack got slower in step with the shader clock (eight GPUs share a node's power / cooling)

@@ -9,7 +9,7 @@ O=$PWD/gpurun_out/kernel_avg; rm -rf $O; mkdir -p $O
 for v in "$@"; do
   export VNECT_LIB=$PWD/vnect_amd/lib/libvnect_hip$v.so
   if [ ! -f "$VNECT_LIB" ]; then echo "variant [$v]: not built"; continue; fi
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v$v -o p -- python3 bench.py --steps 100 --warmup 10 --cpu-seconds 0 --no-aux --precision ${PREC:-fp32} > $O/bench$v.json 2> $O/log$v.txt
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v$v -o p -- python3 bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 --no-aux --precision ${PREC:-fp32} > $O/bench$v.json 2> $O/log$v.txt
   f=$(find $O/v$v -name '*kernel_stats.csv' 2>/dev/null | head -1)
   if [ -z "$f" ]; then echo "variant [$v]: no statistics (see $O/log$v.txt)"; continue; fi
   echo "variant [$v]: $(python3 -c "import json,sys; d=json.load(open('$O/bench$v.json')); print('%.1f fps' % d['value'])" 2>/dev/null)"

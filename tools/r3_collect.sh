@@ -9,9 +9,9 @@ for r in r03 r03_bf16 r03_split; do cp gpurun_out/prof_$r/summary/* $O/ 2>/dev/n
 python tools/layer_table.py > $O/r03_layer_table.txt 2>/dev/null
 LT_BF16=1 python tools/layer_table.py > $O/r03_bf16_layer_table.txt 2>/dev/null
 LT_SPLIT=1 python tools/layer_table.py > $O/r03_split_layer_table.txt 2>/dev/null
-python bench.py > $O/r03_bench_line.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 5 --cpu-seconds 0 > $O/r03_bench_line_short_run.json 2>> $O/bench.err
+python bench.py --full > $O/r03_bench_line.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 > $O/r03_bench_line_short_run.json 2>> $O/bench.err
 timeout -k 10 120 tools/bf16_bglobal > $O/r03_bf16_bglobal_microbench.txt 2>&1
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python bench.py --gpus 2 --steps 100 --warmup 10 > $O/r03_rehearsal_spawn2_one_gpu.json 2>> $O/bench.err
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python bench.py --gpus 3 --pyramid-both --steps 100 --warmup 10 > $O/r03_rehearsal_pyramid_both_one_gpu.json 2>> $O/bench.err
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python bench.py --full --gpus 2 --steps 100 --warmup 10 > $O/r03_rehearsal_spawn2_one_gpu.json 2>> $O/bench.err
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python bench.py --full --gpus 3 --pyramid-both --steps 100 --warmup 10 > $O/r03_rehearsal_pyramid_both_one_gpu.json 2>> $O/bench.err
 ls -la $O | head -40

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r3e
 rm -rf $OUT; mkdir -p $OUT
 for prec in fp32 bf16; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$prec -o s -- python3 bench.py --steps 100 --warmup 10 --cpu-seconds 0 --no-aux --precision $prec > $OUT/bench_$prec.json 2> $OUT/stats_$prec.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$prec -o s -- python3 bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 --no-aux --precision $prec > $OUT/bench_$prec.json 2> $OUT/stats_$prec.log
   f=$(find $OUT/stats_$prec -name "*kernel_stats.csv" | head -1)
   cp "$f" $OUT/kernel_stats_$prec.csv
   find $OUT/stats_$prec -name "*kernel_trace.csv" -delete

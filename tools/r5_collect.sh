@@ -10,7 +10,7 @@ python3 tools/layer_table.py > $O/r05_layer_table.txt 2>/dev/null
 LT_BF16=1 python3 tools/layer_table.py > $O/r05_bf16_layer_table.txt 2>/dev/null
 VNECT_PROF_DETAIL=1 PT_PROD=1 python3 tools/phase_table.py > $O/r05_phase_table.txt 2>/dev/null
 VNECT_PROF_DETAIL=1 PT_PROD=1 LT_BF16=1 python3 tools/phase_table.py > $O/r05_bf16_phase_table.txt 2>/dev/null; echo "tables done"
-python3 bench.py > $O/r05_bench_line.json 2> $O/bench.err; echo "bench done"
-python3 bench.py --steps 20 --warmup 5 > $O/r05_bench_line_short_run.json 2>> $O/bench.err
+python3 bench.py --full > $O/r05_bench_line.json 2> $O/bench.err; echo "bench done"
+python3 bench.py --full --steps 20 --warmup 5 > $O/r05_bench_line_short_run.json 2>> $O/bench.err
 python3 tools/one_scale_rate.py $O/r05_one_scale_rate.json > $O/r05_one_scale_rate.txt 2>&1
 ls -la $O | head -40

@@ -11,8 +11,8 @@ python3 tools/layer_table.py > $O/r06_layer_table.txt 2>/dev/null
 LT_BF16=1 python3 tools/layer_table.py > $O/r06_bf16_layer_table.txt 2>/dev/null
 VNECT_PROF_DETAIL=1 PT_PROD=1 python3 tools/phase_table.py > $O/r06_phase_table.txt 2>/dev/null
 VNECT_PROF_DETAIL=1 PT_PROD=1 LT_BF16=1 python3 tools/phase_table.py > $O/r06_bf16_phase_table.txt 2>/dev/null; echo "tables done"
-python3 bench.py > $O/r06_bench_line.json 2> $O/bench.err; echo "bench done rc $?"
-python3 bench.py --steps 20 --warmup 5 > $O/r06_bench_line_short_run.json 2>> $O/bench.err; echo "short bench done rc $?"
+python3 bench.py --full > $O/r06_bench_line.json 2> $O/bench.err; echo "bench done rc $?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/r06_bench_line_short_run.json 2>> $O/bench.err; echo "short bench done rc $?"
 python3 tools/one_scale_rate.py $O/r06_one_scale_rate.json > $O/r06_one_scale_rate.txt 2>&1
 ls -la $O | head -50
 python3 -c "

@@ -4,10 +4,10 @@
 O=gpurun_out/r06f; mkdir -p $O
 python3 -m pytest tests -m gpu -x -q > $O/gputests.txt 2>&1; echo "pytest rc $?"; tail -4 $O/gputests.txt
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc $?"; tail -1 $O/smoke.txt
-python3 bench.py > $O/r06_bench_line.json 2> $O/bench.err; echo "bench rc $?"
-python3 bench.py --steps 20 --warmup 5 > $O/r06_bench_line_short_run.json 2>> $O/bench.err; echo "short bench rc $?"
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --gpus 2 --steps 100 --warmup 10 --cpu-seconds 0 --no-aux > $O/r06_rehearsal_replicas_one_gpu.json 2>$O/err_reh2.txt; echo "rehearsal replicas rc $?"
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --gpus 3 --pyramid-both --steps 100 --warmup 10 --cpu-seconds 0 > $O/r06_rehearsal_pyramid_one_gpu.json 2>$O/err_reh3.txt; echo "rehearsal pyramid rc $?"
+python3 bench.py --full > $O/r06_bench_line.json 2> $O/bench.err; echo "bench rc $?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/r06_bench_line_short_run.json 2>> $O/bench.err; echo "short bench rc $?"
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --full --gpus 2 --steps 100 --warmup 10 --cpu-seconds 0 --no-aux > $O/r06_rehearsal_replicas_one_gpu.json 2>$O/err_reh2.txt; echo "rehearsal replicas rc $?"
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --full --gpus 3 --pyramid-both --steps 100 --warmup 10 --cpu-seconds 0 > $O/r06_rehearsal_pyramid_one_gpu.json 2>$O/err_reh3.txt; echo "rehearsal pyramid rc $?"
 python3 tools/explain_scale.py $O/r06_rehearsal_replicas_one_gpu.json $O/r06_rehearsal_pyramid_one_gpu.json > $O/r06_explain_scale_rehearsals.txt 2>&1; cat $O/r06_explain_scale_rehearsals.txt
 python3 -c "
 import json

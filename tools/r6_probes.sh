@@ -19,11 +19,11 @@ except Exception as e: print('cpu.max ?', e)
 "; } > $O/r06_box_topology.txt 2>&1
 for rep in 1 2 3; do
   for v in "" "--bind"; do
-    r=$(python3 bench.py --steps 300 --warmup 30 --cpu-seconds 0 --no-aux $v 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f fps  p50 %.4f  clock %s MHz  binding %s' % (d['value'], d['latency_ms']['p50'], d['per_rank'][0]['shader_clock_mhz'], d['ranks'][0]['host_binding']))")
+    r=$(python3 bench.py --full --steps 300 --warmup 30 --cpu-seconds 0 --no-aux $v 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f fps  p50 %.4f  clock %s MHz  binding %s' % (d['value'], d['latency_ms']['p50'], d['per_rank'][0]['shader_clock_mhz'], d['ranks'][0]['host_binding']))")
     echo "[N=1 ${v:-unbound}] $r"
   done
 done > $O/r06_ab_bind_n1.txt 2>&1; echo "bind A/B done"
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --gpus 2 --steps 100 --warmup 10 --cpu-seconds 0 --no-aux > $O/r06_rehearsal_replicas_one_gpu.json 2>$O/err_reh2.txt; echo "rehearsal replicas rc $?"
-VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --gpus 3 --pyramid-both --steps 100 --warmup 10 --cpu-seconds 0 > $O/r06_rehearsal_pyramid_one_gpu.json 2>$O/err_reh3.txt; echo "rehearsal pyramid rc $?"
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --full --gpus 2 --steps 100 --warmup 10 --cpu-seconds 0 --no-aux > $O/r06_rehearsal_replicas_one_gpu.json 2>$O/err_reh2.txt; echo "rehearsal replicas rc $?"
+VNECT_BENCH_BACKEND=gloo VNECT_BENCH_DEVICE=0 python3 bench.py --full --gpus 3 --pyramid-both --steps 100 --warmup 10 --cpu-seconds 0 > $O/r06_rehearsal_pyramid_one_gpu.json 2>$O/err_reh3.txt; echo "rehearsal pyramid rc $?"
 tail -n 30 $O/r06_call_surface_fp32.txt $O/r06_call_surface_bf16.txt $O/r06_ab_bind_n1.txt $O/r06_box_topology.txt
 head -8 $O/r06_two_frames_probe_fp32.txt $O/r06_two_frames_probe_bf16.txt

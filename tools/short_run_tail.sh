@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 N=${1:-10}; shift
 O=gpurun_out/short_run; mkdir -p $O
 for rep in $(seq 1 $N); do
-  python3 bench.py --steps 20 --warmup 5 --cpu-seconds 0 "$@" > $O/line_$rep.json 2> $O/err_$rep.txt || { echo "repeat $rep failed"; tail -5 $O/err_$rep.txt; exit 1; }
+  python3 bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 "$@" > $O/line_$rep.json 2> $O/err_$rep.txt || { echo "repeat $rep failed"; tail -5 $O/err_$rep.txt; exit 1; }
   python3 - $O/line_$rep.json $rep <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
