@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VNECT_ABI_VERSION 6
+#define VNECT_ABI_VERSION 7
 #define VNECT_MAX_SCALES 8
 #define VNECT_MAX_STREAMS 4 /* independent video streams one handle can serve (vnect_submit_stream) */
 #define VNECT_BOX 368      /* src/estimator.py:19 box_size   */
@@ -164,6 +164,22 @@ int vnect_submit_stream(vnect_handle* h, int stream, int slot, double t2d, doubl
 int vnect_collect_stream(vnect_handle* h, int32_t* stream_out, double* joints_2d, float* joints_3d);
 /* New filters for ONE stream (vnect_reset_filters resets all of them). */
 int vnect_reset_filters_stream(vnect_handle* h, int stream);
+/* ABI v7.  Two videos' frames through ONE conv stack per launch.  The reference runs one estimator per video (run_estimator_ps.py:120-129)
+ * over a batch whose images are independent (src/estimator.py:75-80, the batch that sess.run takes at :100-104); here two streams' frames
+ * form one batch of 2 S images: image i is scale i % S of the i / S-th frame.  Called before vnect_finalize: n = 1 is the default (no
+ * batched plan); n = 2 makes finalize build a second launch plan for 2 S images -- the S-image plan's layers, tiles, K splits and fused
+ * forms with M doubled, the same packed weights -- and gives every lane an activation arena for it.  VNECT_E_STATE after finalize or on a
+ * preprocess_only handle; VNECT_E_ARG on a pyramid-sharded handle, for n outside 1 .. 2, or when 2 S > VNECT_MAX_SCALES.
+ * Pays with two or more videos per GPU, where a frame is bound by launch count (bf16); a stream's latency becomes its batch's.         */
+int vnect_set_stream_batch(vnect_handle* h, int n);
+/* n frames of DISTINCT streams from resident slots as one batch (src/estimator.py:97-142 once per stream, as the reference's per-video
+ * processes call it, run_estimator_ps.py:120-129).  n == 2 runs the batched plan; n == 1 is vnect_submit_stream.  Results come back through
+ * vnect_collect_stream, one per frame, in array order.  A batch takes one lane and counts once against the in-flight limit.  Atomic: slots,
+ * distinct streams, the in-flight limit and both streams' timestamps (VNECT_E_TIMESTAMP / VNECT_E_TIMEORDER as vnect_infer reports them)
+ * are all checked before anything changes, so a refused batch leaves every filter bank and timestamp as it was.  Each stream's joints
+ * are bit-identical to a handle of its own fed the same frames.  (vnect_forward on such a handle also takes num_images == 2 S and
+ * runs the batched plan: a parity aid.) */
+int vnect_submit_streams(vnect_handle* h, int n, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
@@ -216,6 +232,9 @@ typedef struct vnect_layer_info {
     double last_ms;            /* kernel duration in the last profiled frame, device clock (0 if none) */
 } vnect_layer_info;
 int vnect_get_layer_info(vnect_handle* h, int idx, vnect_layer_info* out);
+/* ABI v7.  The same for the batched plan of vnect_set_stream_batch(h, 2) (VNECT_E_STATE without one); last_ms is from the last batch
+ * submitted while profiling.  Its counterpart in the reference is the batch dimension of the one graph (src/estimator.py:100-104). */
+int vnect_get_batch_layer_info(vnect_handle* h, int idx, vnect_layer_info* out);
 /* Raw 100 MHz device-clock stamps of layer idx in the last profiled frame (tuning aid): [0] earliest workgroup start,
  * [1..8] latest workgroup ends, [9..13] workgroup 0: start, operands requested, first chunk in LDS, K loop done,
  * stores done; [15] start of the last-dispatched workgroups; [16..18] shader-clock cycles producer wave 0 of workgroup

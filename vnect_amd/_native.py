@@ -15,7 +15,7 @@ _lib = None
 
 MAX_SCALES = 8
 OK, E_ARG, E_STATE, E_HIP, E_NODEVICE, E_TIMESTAMP, E_COMM, E_TIMEORDER, E_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7, -8
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_STREAMS = 4
 XCHG_RCCL, XCHG_P2P = 0, 1
 FP32, BF16, FP32_SPLIT = 0, 1, 2
@@ -72,6 +72,9 @@ SYMBOLS = {
     "vnect_submit_stream": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_double]),
     "vnect_collect_stream": (C.c_int, [_H, _i32p, _f64p, _f32p]),
     "vnect_reset_filters_stream": (C.c_int, [_H, C.c_int]),
+    "vnect_set_stream_batch": (C.c_int, [_H, C.c_int]),
+    "vnect_submit_streams": (C.c_int, [_H, C.c_int, _i32p, _i32p, _f64p, _f64p]),
+    "vnect_get_batch_layer_info": (C.c_int, [_H, C.c_int, C.POINTER(LayerInfo)]),
     "vnect_joint_filter": (C.c_int, [_H, C.c_int, _f64p, C.c_int, C.c_double, _f64p]),
     "vnect_reset_filters": (C.c_int, [_H]),
     "vnect_read_activation": (C.c_int, [_H, C.c_char_p, _f32p, C.c_int64, _i32p]),
@@ -141,7 +144,7 @@ class Handle:
 
     def __init__(self, scales, device=0, precision=FP32, paper_res2c=False, use_graph="auto", numpy_promotion=0,
                  max_frame_bytes=0, num_frame_slots=0, pyramid=None, keep_activations=False, lanes=1,
-                 preprocess_only=False, exchange=XCHG_RCCL):
+                 preprocess_only=False, exchange=XCHG_RCCL, stream_batch=1):
         L = lib()
         cfg = Config()
         cfg.struct_size = C.sizeof(Config)
@@ -168,6 +171,14 @@ class Handle:
             msg = L.vnect_last_error(self._h).decode()
             self.close()
             raise VnectError(rc, msg)
+        self.stream_batch = int(stream_batch)  # 2: finalize also builds the batched plan of two streams (submit_streams)
+        if self.stream_batch != 1:
+            self.set_stream_batch(self.stream_batch)
+
+    def set_stream_batch(self, n):
+        """vnect_set_stream_batch: 2 = two video streams' frames per launch (before finalize)."""
+        self._ck(lib().vnect_set_stream_batch(self._h, int(n)))
+        self.stream_batch = int(n)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -194,11 +205,13 @@ class Handle:
         self._ck(lib().vnect_set_scales(self._h, _ptr(sc, _f64p), len(sc)))
 
     def forward(self, batch):
+        """(S,368,368,3) -> (S,46,46,84); on a stream_batch=2 handle also (2S,368,368,3), run on the batched plan."""
         batch = np.ascontiguousarray(batch, dtype=np.float32)
-        if batch.shape != (self.net_images, 368, 368, 3):
+        n = batch.shape[0] if batch.ndim == 4 else -1
+        if batch.shape[1:] != (368, 368, 3) or (n != self.net_images and not (self.stream_batch == 2 and n == 2 * self.net_images)):
             raise ValueError("batch must be (%d,368,368,3)" % self.net_images)
-        out = np.empty((self.net_images, 46, 46, 84), np.float32)
-        self._ck(lib().vnect_forward(self._h, _ptr(batch, _f32p), self.net_images, _ptr(out, _f32p)))
+        out = np.empty((n, 46, 46, 84), np.float32)
+        self._ck(lib().vnect_forward(self._h, _ptr(batch, _f32p), n, _ptr(out, _f32p)))
         return out
 
     def preprocess(self, img, want_batch=True):
@@ -279,6 +292,28 @@ class Handle:
             self._ck(rc)
         return s.value, j2.copy(), j3.copy()
 
+    def submit_streams(self, streams, slots, t2d, t3d):
+        """Frames of DISTINCT streams from resident slots as one batch (two: the batched plan; one: submit_stream).  Their results come
+        back through collect_stream, one per frame, in this order.  Refused as a whole, with no state changed, if any check fails."""
+        n = len(streams)
+        if not (len(slots) == len(t2d) == len(t3d) == n):
+            raise ValueError("streams, slots, t2d and t3d must have the same length")
+        st, sl = np.asarray(streams, np.int32), np.asarray(slots, np.int32)
+        a2, a3 = np.asarray(t2d, np.float64), np.asarray(t3d, np.float64)
+        self._ck(lib().vnect_submit_streams(self._h, n, _ptr(st, _i32p), _ptr(sl, _i32p), _ptr(a2, _f64p), _ptr(a3, _f64p)))
+
+    def infer_streams(self, frames, t2d, t3d, streams=(0, 1), slots=(0, 1)):
+        """Synchronous convenience: uploads frames[k] into slots[k], submits them as one batch of `streams` and collects
+        -> [(joints_2d, joints_3d) per frame]."""
+        for slot, img in zip(slots, frames):
+            self.upload_frame(slot, img)
+        self.submit_streams(list(streams)[:len(frames)], list(slots)[:len(frames)], t2d, t3d)
+        return [self.collect_stream()[1:] for _ in frames]
+
+    def batch_layers(self):
+        """The batched plan's layers (vnect_get_batch_layer_info), in the layout of layers()."""
+        return self._layer_list(lib().vnect_get_batch_layer_info)
+
     @staticmethod
     def comm_unique_id():
         buf = (C.c_char * 128)()
@@ -357,10 +392,16 @@ class Handle:
         return list(buf)
 
     def layers(self):
+        return self._layer_list(lib().vnect_get_layer_info)
+
+    def _layer_list(self, fn):
         out, i = [], 0
         while True:
             li = LayerInfo()
-            if lib().vnect_get_layer_info(self._h, i, C.byref(li)):
+            rc = fn(self._h, i, C.byref(li))
+            if rc == E_STATE:
+                self._ck(rc)
+            if rc:
                 return out
             out.append({k: (getattr(li, k).decode() if k == "name" else getattr(li, k)) for k, _ in LayerInfo._fields_})
             i += 1

@@ -1717,7 +1717,12 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     const bool plain64 = KG == 1 && BN <= 64 && maxwg_env <= 0 && !no_big && !a.x3 && !a.pixmode;
     const bool big_grid = plain64 && (a.bf16 ? a.items <= 4 * cus : (a.ntaps * a.cpt <= 8 && a.items <= 8 * cus));
     const bool one = a.ksplit == 1 && !no_one && (a.items <= maxwg || big_grid);
-    dim3 grid(one ? a.items : (a.items < maxwg ? a.items : maxwg));
+    // The fused forms (tail GEMM, bone features) are one-item kernels by construction (FUSE != 0 implies SINGLE): workgroup i takes item i,
+    // so their grid is the item count at ANY size.  A handle's own plan picks them only where that is one round over the CUs; the
+    // batched plan of two video streams (vnect_set_stream_batch) keeps them at twice the items, and the later workgroups start as the
+    // earlier ones retire (profiles/stream_batch_rate.txt has the per-layer times).
+    const bool fused = a.tail_n > 0 || a.bone;
+    dim3 grid((one || fused) ? a.items : (a.items < maxwg ? a.items : maxwg));
     const size_t lds = stream_lds<BM, BN, KG, NS>();
     // profiling twin: start / end stamps only, or (VNECT_PROF_DETAIL=1, tools/phase_table.py) the per-phase stamps too
     static const bool detail = getenv("VNECT_PROF_DETAIL") && atoi(getenv("VNECT_PROF_DETAIL")) != 0;
@@ -1731,8 +1736,8 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     if constexpr (BM == 64 && BN == 64 && KG == 1) {
         if (a.x3) {  // split-product form (plain, with the tail GEMM or with the bone features behind it); start / end stamps at most
             if (a.bf16 || a.pixmode || a.K % 32) return hipErrorInvalidValue;
-            if (a.bone && (a.items > maxwg || a.ksplit != 1 || a.Npad != 192 || a.ldc < 212 || a.tail_n > 0)) return hipErrorInvalidValue;
-            if (a.tail_n > 0 && (a.items > maxwg || a.ksplit != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias))
+            if (a.bone && (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212 || a.tail_n > 0)) return hipErrorInvalidValue;
+            if (a.tail_n > 0 && (a.ksplit != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias))
                 return hipErrorInvalidValue;
             // (Measured, A/B in one call each: a 7-stage ring for launches with one workgroup per CU 1 162 vs 1 174 frames/s without; the
             // hi plane's bytes only -- 12 KiB per chunk instead of 20 -- +1.6 %; no split arithmetic +13 %; 3 MFMAs instead of 6 +9 %:
@@ -1752,7 +1757,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
             return hipGetLastError();
         }
         if (a.tail_n > 0) {  // tail GEMM variant: one tile per workgroup, start / end stamps at most
-            if (a.items > maxwg || a.ksplit != 1 || a.nphase != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias)
+            if (a.ksplit != 1 || a.nphase != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias)
                 return hipErrorInvalidValue;
             // the 64-wide chain: bf16, behind a tail with shortcut + ReLU and bf16 output only
             if (a.chain_n != 0 && (!a.bf16 || a.chain_n != 64 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 64 || !a.resid ||
@@ -1787,7 +1792,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     if constexpr (BN == 96) {
         // three accumulators per wave (fp32): no shortcut, one output tensor, no K slabs, no tail; plain or with the bone features
         if (a.bf16 || a.x3 || a.tail_n > 0 || a.resid || a.out2 || a.ksplit != 1 || a.pixmode || (a.relu_cols & 31)) return hipErrorInvalidValue;
-        if (a.bone && (a.items > maxwg || a.Npad != 192 || a.ldc < 212)) return hipErrorInvalidValue;
+        if (a.bone && (a.Npad != 192 || a.ldc < 212)) return hipErrorInvalidValue;
 #define LAUNCH_96(PR, FU) hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, false, PR, FU>), grid, dim3(512), lds, st, a)
 #define LAUNCH_96_ONE(PR) hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, false, PR, 0, false, false, true>), grid, dim3(512), lds, st, a)
         if (a.bone) {
@@ -1806,7 +1811,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     }
     if constexpr (BM == 32 && BN == 128 && KG == 1) {
         if (a.tail_n > 0) {  // the wide tail (tail_wide): one 32x128 tile per workgroup, K = 128, at most 16 column blocks
-            if (a.x3 || a.bone || a.items > maxwg || a.ksplit != 1 || a.nphase != 1 || a.Npad != 128 || a.os != 1 || a.tail_n > 512 || !a.tail_w || !a.tail_bias ||
+            if (a.x3 || a.bone || a.ksplit != 1 || a.nphase != 1 || a.Npad != 128 || a.os != 1 || a.tail_n > 512 || !a.tail_w || !a.tail_bias ||
                 (a.chain_n != 0 && (a.chain_n != 128 || a.tail_n != 512 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 128)))
                 return hipErrorInvalidValue;
 #define LAUNCH_WTAIL(BF, PR)                                                                                                              \
@@ -1828,7 +1833,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     if (a.tail_n > 0 || a.x3) return hipErrorInvalidValue;
     if constexpr (BM == 64 && BN == 64 && KG == 1) {
         if (a.bone) {  // bone-length features inside the transposed conv's launch: one tile per workgroup again
-            if (a.items > maxwg || a.ksplit != 1 || a.Npad != 192 || a.ldc < 212) return hipErrorInvalidValue;
+            if (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212) return hipErrorInvalidValue;
 #define LAUNCH_BONE(BF, PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, BF, PR, 2>), grid, dim3(512), lds, st, a)
             if (a.bf16) {
                 if (prof == 0) LAUNCH_BONE(true, 0);

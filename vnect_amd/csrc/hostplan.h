@@ -458,10 +458,13 @@ inline int stem_groups(int S, unsigned char* row0)
 // The from-the-frame form of the stem lands, per tile, the rectangle of the square its input patch is made from in LDS (stem.hip, phase
 // B): at most STEM_REG_ROWS rows of STEM_REG_PITCH bytes.  True if that holds for EVERY tile of every image at these scales -- the same
 // bounds arithmetic as the kernel's, on the host's copy of the tables (scales below ~0.48 need more and take the batch-tensor form).
-inline bool stem_frame_fits(const ScaleTabs& st, int S, int scale_base, int groups, const unsigned char* row0, bool bf16)
+// per_stream > 0: a batch of two frames (vnect_submit_streams), S = 2 per_stream images, image sI at scale sI % per_stream -- the row groups
+// are those of 2 per_stream images (stem_groups), so a batch can need more frame rows per tile than one frame at the same scales.
+inline bool stem_frame_fits(const ScaleTabs& st, int S, int scale_base, int groups, const unsigned char* row0, bool bf16, int per_stream = 0)
 {
+    if (per_stream > 0 && (S != 2 * per_stream || scale_base != 0)) return false;
     for (int sI = 0; sI < S; sI++) {
-        const int s = sI + scale_base;
+        const int s = per_stream > 0 ? sI % per_stream : sI + scale_base;
         if (s < 0 || s >= 8) return false;
         const ResizeTab& t = st.t[s];
         const bool scaled = st.scaled[s] != 0, resize = scaled && !t.copy;

@@ -236,6 +236,18 @@ void hp_choose_tile96(int M, int Nreal, int ntaps, int cpt, int K, int nphase, i
 }
 int hp_pair_head_cols(int M, int cout_a, int cout_b, int K, int bf16) { return plan::pair_head_cols(M, cout_a, cout_b, K, bf16 != 0); }
 int hp_stem_groups(int S, uint8_t* row0) { return plan::stem_groups(S, row0); }
+// the frame form of the stem for a batch of two frames at these S scales (2 S images, their row groups)
+int hp_stem_frame_fits_streams(const double* scales, int S, int bf16)
+{
+    if (S < 1 || 2 * S > 8) return -1;
+    std::vector<ScaleTabs> st(1);
+    memset(&st[0], 0, sizeof(ScaleTabs));
+    for (int i = 0; i < S; i++)
+        if (plan::build_scale_tab(scales[i], &st[0], i)) return -1;
+    uint8_t row0[STEM_MAXGROUPS + 1];
+    const int G = plan::stem_groups(2 * S, row0);
+    return plan::stem_frame_fits(st[0], 2 * S, 0, G, row0, bf16 != 0, S) ? 1 : 0;
+}
 int hp_stem_frame_fits(const double* scales, int S, int scale_base, int bf16)
 {
     std::vector<ScaleTabs> st(1);

@@ -137,6 +137,10 @@ struct FrameDyn {     // what does change every frame: passed to the two kernels
 };
 
 hipError_t launch_pyramid(const FrameParams* fp, FrameDyn dyn, const ScaleTabs* tabs, void* batch4, int S, int scale_base, int bf16, hipStream_t st);
+// two streams' frames into one (2 S)-image batch: images 0 .. S-1 from (fp0, dyn0), S .. 2 S-1 from (fp1, dyn1) (vnect_submit_streams)
+constexpr int VNECT_MAX_IMAGES = 8;  // images of one batch at most (= VNECT_MAX_SCALES: the batched plan needs 2 S <= it)
+hipError_t launch_pyramid_streams(const FrameParams* fp0, const FrameParams* fp1, FrameDyn dyn0, FrameDyn dyn1, const ScaleTabs* tabs,
+                                  void* batch4, int S, int bf16, hipStream_t st);
 
 // vnect_infer: H rows of `row` bytes from device-mapped pinned host memory (`stride` bytes apart) into a resident frame slot, as a kernel
 hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int row, long long stride, const uint8_t* src_end, hipStream_t st);
@@ -161,6 +165,12 @@ struct StemArgs {
     unsigned long long* prof_end;  // ... and every workgroup's end stamp, like ConvArgs
     int S, groups;         // images; row groups per image (grid = S * groups * 4 tiles)
     int scale_base;        // from_frame: image 0 of the batch is scale `scale_base` (a pyramid-sharded rank)
+    // from_frame with TWO frames (a batch of two video streams, vnect_submit_streams): images 0 .. per_stream-1 come from (fp, dyn) at
+    // scales 0 .. per_stream-1, images per_stream .. S-1 from (fp2, frame2, stride2) at the same scales.  per_stream = 0: one frame.
+    int per_stream;
+    const FrameParams* fp2;
+    const uint8_t* frame2;
+    long long stride2;
     int bf16, from_frame;
     int dbg;               // tuning only (VNECT_STEM_DBG): 1 = no conv blocks, 2 = no pooling, 4 = no patch (timing breakdowns; wrong results)
     unsigned char row0[STEM_MAXGROUPS + 1];  // first pooled row of every group; row0[groups] = 92

@@ -37,6 +37,33 @@ hipError_t launch_pyramid(const FrameParams* fp, FrameDyn dyn, const ScaleTabs* 
     return hipGetLastError();
 }
 
+// Two video streams' frames as ONE batch (vnect_submit_streams): image z of the (2 S)-image batch is scale z % S of stream z / S.  Each
+// stream brings its own frame, row stride and squarify geometry (the two frames may differ in size and crop); the per-pixel arithmetic
+// is pyramid_pixel's, so every image is bit-identical to what pyramid_kernel writes for that stream alone.
+template <typename T>
+__global__ void pyramid_streams_kernel(const FrameParams* __restrict__ fp0, const FrameParams* __restrict__ fp1, const FrameDyn dyn0,
+                                       const FrameDyn dyn1, const ScaleTabs* __restrict__ tabs, T* __restrict__ batch4, int S)
+{
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, z = blockIdx.z;
+    if (x >= BOX) return;
+    const bool second = z >= S;  // (uniform over the workgroup)
+    int v[3];
+    pyramid_pixel(second ? fp1 : fp0, second ? dyn1 : dyn0, tabs, second ? z - S : z, y, x, v);
+    f32x4 o = {tabs->lut[v[0]], tabs->lut[v[1]], tabs->lut[v[2]], 0.f};
+    store_wt((tx4*)(batch4 + (((long long)z * BOX + y) * BOX + x) * 4), __builtin_convertvector(o, tx4));
+}
+
+hipError_t launch_pyramid_streams(const FrameParams* fp0, const FrameParams* fp1, FrameDyn dyn0, FrameDyn dyn1, const ScaleTabs* tabs,
+                                  void* batch4, int S, int bf16, hipStream_t st)
+{
+    if (S < 1 || 2 * S > VNECT_MAX_IMAGES) return hipErrorInvalidValue;
+    dim3 g((BOX + 127) / 128, BOX, 2 * S);
+    if (bf16) hipLaunchKernelGGL(pyramid_streams_kernel<__bf16>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (__bf16*)batch4, S);
+    else hipLaunchKernelGGL(pyramid_streams_kernel<float>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (float*)batch4, S);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // vnect_infer's host-to-device copy as a KERNEL on the frame's own stream: rows of `row` bytes from device-mapped PINNED host memory
 // (src, stride bytes apart) to the resident frame slot (dst, rows packed).  hipMemcpyAsync of the same 406 KB costs ~21 us of a

@@ -45,7 +45,7 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: num_scales out of range");
         if (cfg->precision != VNECT_FP32 && cfg->precision != VNECT_BF16 && cfg->precision != VNECT_FP32_SPLIT)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: precision must be VNECT_FP32, VNECT_BF16 or VNECT_FP32_SPLIT");
-        if (cfg->lanes < 0 || cfg->lanes > RING - 1)
+        if (cfg->lanes < 0 || cfg->lanes > MAX_LANES)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: lanes must be 0 .. 3");
         if (cfg->exchange != VNECT_XCHG_RCCL && cfg->exchange != VNECT_XCHG_P2P)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: exchange must be VNECT_XCHG_RCCL or VNECT_XCHG_P2P");
@@ -159,6 +159,7 @@ void vnect_destroy(vnect_handle* h)
     if (!h) return;
     hipSetDevice(h->cfg.device);
     if (h->st) hipStreamSynchronize(h->st);
+    destroy_batch_lanes(h);  // (they run on the lanes' streams)
     destroy_twins(h);
     comm_destroy(h);
     if (h->gexec) hipGraphExecDestroy(h->gexec);
@@ -220,6 +221,8 @@ int vnect_finalize(vnect_handle* h)
         if (rc) return rc;
         rc = build_twins(h);
         if (rc) return rc;
+        rc = build_batch_lanes(h);
+        if (rc) return rc;
         HIPCK(h, hipStreamSynchronize(h->st));
         h->finalized = true;
         h->weights.clear();
@@ -262,9 +265,12 @@ int vnect_forward(vnect_handle* h, const float* batch, int num_images, float* ou
         if (!h || !batch || !out) return VNECT_E_ARG;
         if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_forward before vnect_finalize");
         if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        if (num_images != h->Snet)
-            return fail(h, VNECT_E_ARG, "vnect_forward: num_images must equal num_scales (1 on a pyramid-sharded handle)");
+        const bool batched = !h->blanes.empty() && num_images == 2 * h->Snet;
+        if (num_images != h->Snet && !batched)
+            return fail(h, VNECT_E_ARG, "vnect_forward: num_images must equal num_scales (1 on a pyramid-sharded handle; "
+                                        "or 2 x num_scales after vnect_set_stream_batch(h, 2))");
         HIPCK(h, hipSetDevice(h->cfg.device));
+        if (batched) return forward_batch(h, batch, out);
         const long long npix = (long long)h->Snet * BOX * BOX;
         HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
         HIPCK(h, launch_pad3to4(h->in3, h->tensors[h->t_input4].d, npix, h->bf16, h->st));
@@ -551,21 +557,62 @@ int vnect_reset_timings(vnect_handle* h)
     });
 }
 
+static int layer_info(const std::vector<Layer>& layers, int idx, vnect_layer_info* out)
+{
+    if (!out || idx < 0 || idx >= (int)layers.size()) return VNECT_E_ARG;
+    const Layer& L = layers[idx];
+    memset(out, 0, sizeof *out);
+    snprintf(out->name, sizeof out->name, "%s", L.name.c_str());
+    if (L.op == OP_CONV) {
+        out->M = L.a.M * L.a.nphase, out->N = L.Nreal, out->K = L.Kreal;
+        out->tile_m = L.BM, out->tile_n = L.BN, out->split_k = L.a.ksplit;
+        out->workgroups = ((L.a.M + L.BM - 1) / L.BM) * (L.a.Npad / L.BN) * L.a.nphase * L.a.ksplit;
+        out->flops = L.flops;
+    }
+    out->last_ms = L.last_ms;
+    return VNECT_OK;
+}
+
 int vnect_get_layer_info(vnect_handle* h, int idx, vnect_layer_info* out)
 {
+    return guarded(&h, [&]() -> int { return h ? layer_info(h->layers, idx, out) : VNECT_E_ARG; });
+}
+
+int vnect_get_batch_layer_info(vnect_handle* h, int idx, vnect_layer_info* out)
+{
     return guarded(&h, [&]() -> int {
-        if (!h || !out || idx < 0 || idx >= (int)h->layers.size()) return VNECT_E_ARG;
-        const Layer& L = h->layers[idx];
-        memset(out, 0, sizeof *out);
-        snprintf(out->name, sizeof out->name, "%s", L.name.c_str());
-        if (L.op == OP_CONV) {
-            out->M = L.a.M * L.a.nphase, out->N = L.Nreal, out->K = L.Kreal;
-            out->tile_m = L.BM, out->tile_n = L.BN, out->split_k = L.a.ksplit;
-            out->workgroups = ((L.a.M + L.BM - 1) / L.BM) * (L.a.Npad / L.BN) * L.a.nphase * L.a.ksplit;
-            out->flops = L.flops;
-        }
-        out->last_ms = L.last_ms;
+        if (!h) return VNECT_E_ARG;
+        if (h->blanes.empty()) return fail(h, VNECT_E_STATE, "vnect_get_batch_layer_info: no batched plan (vnect_set_stream_batch(h, 2), then vnect_finalize)");
+        return layer_info(h->blanes[0]->layers, idx, out);
+    });
+}
+
+int vnect_set_stream_batch(vnect_handle* h, int n)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (h->finalized || h->pre_only) return fail(h, VNECT_E_STATE, "vnect_set_stream_batch after vnect_finalize or on a preprocess_only handle");
+        if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: a pyramid-sharded handle serves one stream");
+        if (n < 1 || n > 2) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: n must be 1 or 2");
+        if (2 * h->Snet > VNECT_MAX_SCALES && n == 2) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: 2 x num_scales exceeds VNECT_MAX_SCALES");
+        h->stream_batch = n;
         return VNECT_OK;
+    });
+}
+
+int vnect_submit_streams(vnect_handle* h, int n, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (!streams || !slots || !t2d || !t3d) return fail(h, VNECT_E_ARG, "vnect_submit_streams: bad argument");
+        if (!h->finalized) return fail(h, VNECT_E_STATE, "inference before vnect_finalize");
+        if (n != 1 && n != 2) return fail(h, VNECT_E_ARG, "vnect_submit_streams: n must be 1 or 2");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        if (n == 1) {
+            int ring;
+            return enqueue_frame(h, slots[0], t2d[0], t3d[0], &ring, streams[0]);
+        }
+        return enqueue_batch(h, streams, slots, t2d, t3d);
     });
 }
 

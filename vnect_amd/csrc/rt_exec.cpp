@@ -42,13 +42,15 @@ int run_network(vnect_handle* h, bool timed, bool stem_done)
 
 // Crop geometry -> d_fp, only if it differs from what the device holds (a stream of equally sized crops never uploads).
 // In-stream, so frames still in flight keep the geometry they were launched with.
-int sync_geometry(vnect_handle* h, const FrameParams& fp)
+int sync_geometry(vnect_handle* h, const FrameParams& fp, int which)
 {
-    if (h->fp_dev_valid && memcmp(&h->fp_dev, &fp, sizeof fp) == 0) return VNECT_OK;
+    FrameParams& held = which ? h->fp_dev2 : h->fp_dev;
+    bool& valid = which ? h->fp_dev2_valid : h->fp_dev_valid;
+    if (valid && memcmp(&held, &fp, sizeof fp) == 0) return VNECT_OK;
     const int r = h->fp_ring = (h->fp_ring + 1) % RING;  // a staging slot of its own: earlier copies may still be queued
     *h->h_fp[r] = fp;
-    HIPCK(h, hipMemcpyAsync(h->d_fp, h->h_fp[r], sizeof(FrameParams), hipMemcpyHostToDevice, h->st));
-    h->fp_dev = fp, h->fp_dev_valid = true;
+    HIPCK(h, hipMemcpyAsync(which ? h->d_fp2 : h->d_fp, h->h_fp[r], sizeof(FrameParams), hipMemcpyHostToDevice, h->st));
+    held = fp, valid = true;
     return VNECT_OK;
 }
 
@@ -283,6 +285,22 @@ int build_twins(vnect_handle* h)
     return VNECT_OK;
 }
 
+// Frames (or batches of two streams' frames) in flight, and how many may be: one lane queues two on its stream, more lanes one each
+static unsigned long long units_in_flight(const vnect_handle* h)
+{
+    return h->seq_submit == h->seq_collect ? 0 : h->unit_submit - h->ring_unit[h->seq_collect % RING];
+}
+static unsigned long long max_in_flight(const vnect_handle* h) { return h->twins.empty() ? 2 : h->twins.size() + 1; }
+
+// the lane a frame (or batch) submitted now runs on: the first whose last frame has been collected (lane 0 when nothing is in flight)
+static vnect_handle* pick_lane(vnect_handle* h, bool timed)
+{
+    if (!h->twins.empty() && !timed && h->lane_seq >= (long long)h->seq_collect)
+        for (vnect_handle* t : h->twins)
+            if (t->lane_seq < (long long)h->seq_collect) return t;
+    return h;
+}
+
 // enqueue one frame from a resident slot; results land in h_out[ring]
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream)
 {
@@ -290,8 +308,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     if (stream != 0 && h->sharded) return fail(h, VNECT_E_ARG, "a pyramid-sharded handle serves one stream");
     if (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0)
         return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
-    const unsigned long long max_in_flight = h->twins.empty() ? 2 : h->twins.size() + 1;  // one lane: two frames queue on its stream
-    if (h->seq_submit - h->seq_collect >= max_in_flight) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
+    if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
     if (h->sharded && !comm_ready(h))  // refuse before any filter / timestamp state changes
         return fail(h, VNECT_E_STATE, "pyramid-sharded handle: call vnect_comm_init / vnect_comm_p2p_init before inference");
     const auto& si = h->slots[slot];
@@ -311,13 +328,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // (post_kernel: merge + arg-max + joints; with VNECT_NO_POST_MERGE=1 only the joints kernel) waits for the SAME video's previous
     // frame.  Measured (round 3, A/B in one call): 1 388-1 390 frames/s three deep with the merged launch, 1 388-1 389 with the two
     // launches -- ordering the 17-us merged launch instead of the 11-us joints kernel costs nothing measurable.
-    vnect_handle* L = h;
-    if (!h->twins.empty() && !timed && h->lane_seq >= (long long)h->seq_collect)
-        for (vnect_handle* t : h->twins)
-            if (t->lane_seq < (long long)h->seq_collect) {
-                L = t;
-                break;
-            }
+    vnect_handle* L = pick_lane(h, timed);
     if ((rc = sync_geometry(L, fp))) return fail(h, rc, L->err);
     if (timed) HIPCK(h, hipEventRecord(h->ev[0], L->st));
     {
@@ -354,12 +365,27 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     HIPCK(h, hipEventRecord(h->done[ring], L->st));
     commit_time(h, t2d, t3d, stream);  // only now: every launch of the frame has been accepted
     h->stream_seq[stream] = (long long)h->seq_submit, h->stream_lane[stream] = L, h->ring_stream[ring] = stream;
+    h->ring_unit[ring] = h->unit_submit++, h->ring_batch[ring] = false, h->ring_prof[ring] = nullptr;
     h->last_lane = L;
     L->lane_seq = (long long)h->seq_submit;
     h->slots[slot].last_use = (long long)h->seq_submit;
     h->seq_submit++;
     *ring_out = ring;
     return VNECT_OK;
+}
+
+// a profiled batch's per-layer times (vnect_get_batch_layer_info): first workgroup start to last workgroup end of every conv launch
+static void read_layer_ms(vnect_handle* b)
+{
+    for (size_t i = 0; i < b->layers.size(); i++) {
+        Layer& L = b->layers[i];
+        const unsigned long long t0 = b->h_prof[PROF_SLOTS * i];
+        unsigned long long t1 = 0;
+        const unsigned long long* e = b->h_prof_end + (size_t)PROF_WGS * i;
+        if (L.op == OP_CONV)
+            for (int k = 0; k < PROF_WGS; k++) t1 = std::max(t1, e[k]);
+        L.last_ms = (L.op == OP_CONV && t1 > t0) ? (float)((double)(t1 - t0) * 1e-5) : 0.f;
+    }
 }
 
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out)
@@ -383,7 +409,8 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out)
     if (j2) memcpy(j2, h->h_out[ring]->j2d, sizeof(double) * NJ * 2);
     if (j3) memcpy(j3, h->h_out[ring]->j3d, sizeof(float) * NJ * 3);
     if (stream_out) *stream_out = h->ring_stream[ring];
-    if (h->profiling) {
+    if (h->ring_prof[ring]) read_layer_ms(h->ring_prof[ring]), h->ring_prof[ring] = nullptr;
+    if (h->profiling && !h->ring_batch[ring]) {
         float frame_ms = 0;
         hipEventElapsedTime(&frame_ms, h->ev[0], h->ev[3]);
         unsigned long long first = ~0ull, last = 0;
@@ -564,6 +591,17 @@ int prime(vnect_handle* h)
         for (int i = 0; i < depth && !rc; i++, t += 1.0) rc = enqueue_frame(h, ps, t, t, &ring);
         for (int i = 0; i < depth && !rc; i++) rc = collect_impl(h, nullptr, nullptr);
     }
+    // the batched plan of two streams (vnect_set_stream_batch): synchronous batches, then as many in flight as there are lanes
+    for (int i = 0; i < 8 && !rc && !h->blanes.empty(); i++) {
+        const int32_t st2[2] = {0, 1}, sl[2] = {ps, ps};
+        const int depth = i < 6 ? 1 : (int)h->blanes.size();
+        for (int d = 0; d < depth && !rc; d++, t += 1.0) {
+            const double tt[2] = {t, t};
+            rc = enqueue_batch(h, st2, sl, tt, tt);
+        }
+        for (int d = 0; d < 2 * depth && !rc; d++) rc = collect_impl(h, nullptr, nullptr);
+    }
+    for (vnect_handle* b : h->blanes) b->fp_dev_valid = b->fp_dev2_valid = false;
     // A fresh handle's state comes back UNCONDITIONALLY: whatever is still in flight is drained and dropped, the slot is emptied, the
     // filter banks are rebuilt.  What the failure means for vnect_finalize depends on its kind (advisor, round 4):
     //  * VNECT_E_HIP / VNECT_E_INTERNAL / VNECT_E_COMM -- a launch was refused or the device faulted on the launch plan this handle
@@ -595,6 +633,107 @@ int prime(vnect_handle* h)
     return VNECT_OK;
 }
 
+// ---- two video streams per launch (vnect_submit_streams) ----------------------------------------------------------------------------
+// Frames of two DIFFERENT streams from resident slots as ONE batch on the batched plan: one pyramid launch for both frames, the conv
+// stack once for 2 S images, then each stream's merge + arg-max + joints on its own S images (post_kernel with the maps of its half,
+// its filter bank, its geometry).  One batch takes one lane and counts once against the in-flight limit; its two results come back
+// through collect_impl in array order.  Every check comes before any state changes: a refused batch leaves every filter bank, every
+// timestamp and every slot as it was.
+int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d)
+{
+    if (h->blanes.empty()) return fail(h, VNECT_E_STATE, "vnect_submit_streams of two frames needs vnect_set_stream_batch(h, 2) before vnect_finalize");
+    FrameParams fp[2];
+    FrameDyn dyn[2] = {};
+    for (int k = 0; k < 2; k++) {
+        if (streams[k] < 0 || streams[k] >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+        if (slots[k] < 0 || slots[k] >= (int)h->slots.size() || h->slots[slots[k]].H == 0)
+            return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+    }
+    if (streams[0] == streams[1]) return fail(h, VNECT_E_ARG, "a batch takes frames of two DIFFERENT streams (a stream's frames are a chain)");
+    if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
+    int rc;
+    for (int k = 0; k < 2; k++) {
+        const auto& si = h->slots[slots[k]];
+        if ((rc = squarify_params(h, si.H, si.W, &fp[k]))) return rc;
+        if ((rc = check_time(h, t2d[k], t3d[k], streams[k]))) return rc;
+        dyn[k].t2d = t2d[k], dyn[k].t3d = t3d[k];
+        dyn[k].row_stride = si.stride;
+        dyn[k].frame = h->frames + (size_t)slots[k] * h->cfg.max_frame_bytes;
+    }
+    const bool timed = h->profiling;
+    vnect_handle* L = pick_lane(h, timed);
+    vnect_handle* b = h->blanes[L == h ? 0 : 1 + (std::find(h->twins.begin(), h->twins.end(), L) - h->twins.begin())];
+    if ((rc = sync_geometry(b, fp[0], 0)) || (rc = sync_geometry(b, fp[1], 1))) return fail(h, rc, b->err);
+    // gen_input_batch of both frames inside the stem launch (as run_pre does for one frame), or the batch tensor first
+    const bool frame_stem = b->stem_mode == 2 && b->stem_frame_ok && fp[0].sq.copy && fp[1].sq.copy;
+    if (!frame_stem)
+        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], b->d_stabs, b->tensors[b->t_input4].d, b->S, b->bf16, b->st));
+    if (b->stem_mode == 2) {
+        StemArgs a = b->stem;
+        a.prof = timed ? b->d_prof + PROF_SLOTS * b->l_conv1 : nullptr;
+        a.prof_end = timed ? b->d_prof_end + (size_t)PROF_WGS * b->l_conv1 : nullptr;
+        a.from_frame = frame_stem;
+        a.dyn = dyn[0], a.frame2 = dyn[1].frame, a.stride2 = dyn[1].row_stride;
+        HIPCK(h, launch_stem(a, b->st));
+    }
+    const bool replay = b->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect);
+    if (replay && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
+    else if ((rc = run_frame_kernels(b, timed))) return fail(h, rc, b->err);
+    const size_t half = (size_t)b->S * HM * HM * MAPC;
+    const float* maps = b->tensors[b->t_out].d;
+    for (int k = 0; k < 2; k++) {
+        const int s = streams[k], ring = (int)((h->seq_submit + k) % RING);
+        // the filters are a chain within a stream: wait for its previous frame if that one ran on another lane and may be in flight
+        if (h->stream_seq[s] >= (long long)h->seq_collect && h->stream_lane[s] && h->stream_lane[s] != L)
+            HIPCK(h, hipStreamWaitEvent(b->st, h->done[h->stream_seq[s] % RING], 0));
+        HIPCK(h, launch_post(maps + k * half, b->mgeo, b->d_part, b->d_ticket, h->d_fb + s, k ? b->d_fp2 : b->d_fp, dyn[k], h->cfg.numpy_promotion,
+                             h->h_out_dev[ring], b->st));
+        HIPCK(h, hipEventRecord(h->done[ring], b->st));
+    }
+    for (int k = 0; k < 2; k++) {  // every launch of the batch has been accepted: commit
+        const int s = streams[k], ring = (int)(h->seq_submit % RING);
+        commit_time(h, t2d[k], t3d[k], s);
+        h->stream_seq[s] = (long long)h->seq_submit, h->stream_lane[s] = L, h->ring_stream[ring] = s;
+        h->ring_unit[ring] = h->unit_submit, h->ring_batch[ring] = true, h->ring_prof[ring] = (timed && k == 1) ? b : nullptr;
+        h->slots[slots[k]].last_use = (long long)h->seq_submit;
+        L->lane_seq = (long long)h->seq_submit;
+        h->seq_submit++;
+    }
+    h->unit_submit++;
+    h->last_lane = L;
+    return VNECT_OK;
+}
+
+// vnect_forward of 2 S images on the batched plan (parity / debug aid): the first lane's batched plan on the handle's stream
+int forward_batch(vnect_handle* h, const float* batch, float* out)
+{
+    vnect_handle* b = h->blanes[0];
+    const long long npix = (long long)b->Snet * BOX * BOX;
+    HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
+    HIPCK(h, launch_pad3to4(h->in3, b->tensors[b->t_input4].d, npix, b->bf16, h->st));
+    int rc = run_network(b, false);
+    if (rc) return fail(h, rc, b->err);
+    const Tensor& t = b->tensors[b->t_out];
+    HIPCK(h, hipMemcpyAsync(out, t.d, t.bytes(), hipMemcpyDeviceToHost, h->st));
+    HIPCK(h, hipStreamSynchronize(h->st));
+    return VNECT_OK;
+}
+
+void destroy_batch_lanes(vnect_handle* h)
+{
+    for (vnect_handle* b : h->blanes) {
+        if (b->st) hipStreamSynchronize(b->st);  // (the lane's stream: its owner destroys it)
+        if (b->gexec) hipGraphExecDestroy(b->gexec);
+        if (b->graph) hipGraphDestroy(b->graph);
+        for (int i = 0; i < RING; i++)
+            if (b->h_fp[i]) hipHostFree(b->h_fp[i]);
+        if (b->h_prof) hipHostFree(b->h_prof);
+        if (b->h_prof_end) hipHostFree(b->h_prof_end);
+        for (void* p : b->dev_allocs) hipFree(p);
+        delete b;
+    }
+    h->blanes.clear();
+}
 
 }  // namespace rt
 }  // namespace vnect

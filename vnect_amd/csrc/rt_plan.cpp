@@ -55,6 +55,10 @@ int build_scale_tables(vnect_handle* h)
     // the stem's from-the-frame form: do all tiles' frame rectangles still fit its LDS scratch at these scales?  (lanes share the tables)
     if (h->stem_mode == 2) h->stem_frame_ok = plan::stem_frame_fits(st, h->stem.S, h->stem.scale_base, h->stem.groups, h->stem.row0, h->bf16);
     for (vnect_handle* tw : h->twins) tw->stabs_host = st, tw->mgeo = mg, tw->stem_frame_ok = h->stem_frame_ok;
+    for (vnect_handle* b : h->blanes) {
+        b->stabs_host = st, b->mgeo = mg;
+        b->stem_frame_ok = b->stem_mode == 2 && plan::stem_frame_fits(st, b->stem.S, 0, b->stem.groups, b->stem.row0, b->bf16, b->stem.per_stream);
+    }
     return VNECT_OK;
 }
 
@@ -402,10 +406,12 @@ void setup_stem(vnect_handle* h)
     a.batch = tin.d, a.w = C.w, a.bias = C.bias, a.out = tp.d;
     a.fp = h->d_fp, a.tabs = h->d_stabs;
     a.S = h->Snet, a.scale_base = h->sharded ? h->cfg.pyramid_rank : 0, a.bf16 = h->bf16;
+    // a batched plan's stem reads two frames: images 0 .. S-1 from the first stream's, S .. 2 S-1 from the second's (d_fp2)
+    a.per_stream = h->batched ? h->S : 0, a.fp2 = h->batched ? h->d_fp2 : nullptr;
     // row groups of 4 and 5 pooled rows (hostplan.h)
     a.groups = plan::stem_groups(a.S, a.row0);
-    // (a lane's tables are lane 0's: build_twin copies stabs_host before calling this)
-    h->stem_frame_ok = h->stem_mode == 2 && plan::stem_frame_fits(h->stabs_host, a.S, a.scale_base, a.groups, a.row0, h->bf16);
+    // (a lane's tables are lane 0's: build_twin / build_batch_lane copy stabs_host before calling this)
+    h->stem_frame_ok = h->stem_mode == 2 && plan::stem_frame_fits(h->stabs_host, a.S, a.scale_base, a.groups, a.row0, h->bf16, a.per_stream);
     // PAIR form: the launch behind pool1 is res2a_branch2a + res2a_branch1 (1x1 on pool1's 64 channels) and nothing else reads pool1:
     // the stem runs it on the pooled tile and pool1 is never written.  Not with per-layer read-back (pool1 must exist there).
     // VNECT_NO_STEM_PAIR=1: A/B runs.
@@ -419,6 +425,61 @@ void setup_stem(vnect_handle* h)
             h->stem_pair = true;
         }
     }
+}
+
+// + 64 pixels of slack per tensor: the streaming conv kernel's epilogue reads shortcut rows and writes output rows of
+// its last 64-row tile without a per-row bound check (rows >= M land in the slack and are never read)
+static size_t padded(const Tensor& t) { return (t.bytes() + (size_t)64 * t.Cs * t.esz + 255) & ~(size_t)255; }
+
+// Activation arena: a tensor lives from the layer that writes it to the last layer that reads it, and tensors with
+// disjoint lifetimes share addresses (first fit over the live intervals).  The per-frame working set is then the
+// peak live set (~0.1 GB at S = 3) instead of one buffer per layer output (~0.35 GB), so weights + activations stay
+// inside the 256 MiB Infinity Cache from frame to frame.
+static int alloc_arena(vnect_handle* h)
+{
+    const int nt = (int)h->tensors.size(), nl = (int)h->layers.size();
+    std::vector<int> first(nt, nl + 1), last(nt, -2);
+    auto touch = [&](int t, int l) {
+        if (t < 0) return;
+        first[t] = std::min(first[t], l), last[t] = std::max(last[t], l);
+    };
+    touch(h->t_input4, -1);  // written by the pre-processing
+    for (int l = 0; l < nl; l++) {
+        const Layer& L = h->layers[l];
+        touch(L.in, l), touch(L.resid, l), touch(L.out, l), touch(L.out2, l), touch(L.out3, l);
+        // the stem may run this pair itself (setup_stem, PAIR form) and then writes its outputs while it still reads the batch tensor:
+        // they must not share addresses with anything alive from conv1 on
+        if (L.frag_w && l == h->l_pool1 + 1) touch(L.out, h->l_conv1), touch(L.out2, h->l_conv1);
+    }
+    touch(h->t_out, nl);  // read by the post-processing
+    std::vector<size_t> need(nt), off;
+    for (int t = 0; t < nt; t++) {
+        if (last[t] < first[t]) first[t] = -1, last[t] = nl;  // never touched by a layer: keep it private
+        need[t] = padded(h->tensors[t]);
+    }
+    const size_t total = plan::arena_first_fit(first, last, need, off);
+    char* base = nullptr;
+    int rc = dev_alloc(h, &base, total);
+    if (rc) return rc;
+    HIPCK(h, hipMemset(base, 0, total));
+    for (int t = 0; t < nt; t++) h->tensors[t].d = (float*)(base + off[t]);
+    h->arena_bytes = total, h->arena_off = off;
+    return VNECT_OK;
+}
+
+// the split-K slabs of the largest K-split launch
+static int alloc_workspace(vnect_handle* h)
+{
+    size_t ws = 0;
+    for (Layer& L : h->layers)
+        if (L.op == OP_CONV && L.a.ksplit > 1)
+            ws = std::max(ws, (size_t)L.a.ksplit * ((size_t)L.a.S * L.a.OH * L.a.OW + 64) * L.a.Npad);
+    h->ws_floats = ws;
+    if (ws) {
+        int rc = dev_alloc(h, &h->ws, ws);
+        if (rc) return rc;
+    }
+    return VNECT_OK;
 }
 
 int finalize_impl(vnect_handle* h)
@@ -639,41 +700,9 @@ int finalize_impl(vnect_handle* h)
     }
 #undef NEED
     // buffers
-    // + 64 pixels of slack per tensor: the streaming conv kernel's epilogue reads shortcut rows and writes output rows of
-    // its last 64-row tile without a per-row bound check (rows >= M land in the slack and are never read)
-    auto padded = [](const Tensor& t) { return (t.bytes() + (size_t)64 * t.Cs * t.esz + 255) & ~(size_t)255; };
     if (!h->keep_activations) {
-        // Activation arena: a tensor lives from the layer that writes it to the last layer that reads it, and tensors with
-        // disjoint lifetimes share addresses (first fit over the live intervals).  The per-frame working set is then the
-        // peak live set (~0.1 GB at S = 3) instead of one buffer per layer output (~0.35 GB), so weights + activations stay
-        // inside the 256 MiB Infinity Cache from frame to frame.
-        const int nt = (int)h->tensors.size(), nl = (int)h->layers.size();
-        std::vector<int> first(nt, nl + 1), last(nt, -2);
-        auto touch = [&](int t, int l) {
-            if (t < 0) return;
-            first[t] = std::min(first[t], l), last[t] = std::max(last[t], l);
-        };
-        touch(h->t_input4, -1);  // written by the pre-processing
-        for (int l = 0; l < nl; l++) {
-            const Layer& L = h->layers[l];
-            touch(L.in, l), touch(L.resid, l), touch(L.out, l), touch(L.out2, l), touch(L.out3, l);
-            // the stem may run this pair itself (setup_stem, PAIR form) and then writes its outputs while it still reads the batch tensor:
-            // they must not share addresses with anything alive from conv1 on
-            if (L.frag_w && l == h->l_pool1 + 1) touch(L.out, h->l_conv1), touch(L.out2, h->l_conv1);
-        }
-        touch(h->t_out, nl);  // read by the post-processing
-        std::vector<size_t> need(nt), off;
-        for (int t = 0; t < nt; t++) {
-            if (last[t] < first[t]) first[t] = -1, last[t] = nl;  // never touched by a layer: keep it private
-            need[t] = padded(h->tensors[t]);
-        }
-        const size_t total = plan::arena_first_fit(first, last, need, off);
-        char* base = nullptr;
-        int rc = dev_alloc(h, &base, total);
+        int rc = alloc_arena(h);
         if (rc) return rc;
-        HIPCK(h, hipMemset(base, 0, total));
-        for (int t = 0; t < nt; t++) h->tensors[t].d = (float*)(base + off[t]);
-        h->arena_bytes = total, h->arena_off = off;
     } else {
         for (Tensor& t : h->tensors) {
             char* p = nullptr;
@@ -683,15 +712,8 @@ int finalize_impl(vnect_handle* h)
             HIPCK(h, hipMemset(t.d, 0, padded(t)));
         }
     }
-    size_t ws = 0;
-    for (Layer& L : h->layers)
-        if (L.op == OP_CONV && L.a.ksplit > 1)
-            ws = std::max(ws, (size_t)L.a.ksplit * ((size_t)L.a.S * L.a.OH * L.a.OW + 64) * L.a.Npad);
-    h->ws_floats = ws;
-    if (ws) {
-        int rc = dev_alloc(h, &h->ws, ws);
-        if (rc) return rc;
-    }
+    int rcw = alloc_workspace(h);
+    if (rcw) return rcw;
     HIPCK(h, hipDeviceSynchronize());
     h->conv_flops = 0, h->conv_launches = 0;
     for (Layer& L : h->layers) {
@@ -733,6 +755,66 @@ int finalize_impl(vnect_handle* h)
     setup_stem(h);
     if (h->stem_pair) h->conv_launches -= 1;
     return VNECT_OK;
+}
+
+// ---- the batched plan of two video streams (vnect_set_stream_batch) ------------------------------------------------------------------
+// Image i of a batch is scale i % S of stream i / S, and the conv stack treats the images of a batch independently
+// (the reference builds the same kind of batch per video, src/estimator.py:75-80).  So the batched plan is the S-image plan with every
+// M doubled and NOTHING else changed: each layer keeps its MFMA instruction, tile, K decomposition, split-K count, fused form, split-product
+// weights (the same device pointers: one weight copy) and K order, so every output element sees the same products summed in the same
+// order as on a handle of its own -- bit-identical by construction.  The fused forms then have twice their items: they run beyond one
+// round of resident workgroups (conv.hip, launch_stream: one item per workgroup at any grid).  Only the arena, the split-K workspace and the
+// geometry blocks are new, once per lane.  The stem builds both frames' pyramids itself (stem.hip, per_stream) where every tile's frame
+// rectangle fits its LDS scratch and both frames' squarify step is a copy; otherwise pyramid_streams_kernel writes the batch tensor first.
+static int build_batch_lane(vnect_handle* h, vnect_handle* lane)
+{
+    vnect_handle* b = new vnect_handle();
+    h->blanes.push_back(b);
+    b->is_twin = true, b->batched = true, b->st = lane->st;
+    b->cfg = h->cfg, b->S = h->S, b->Snet = 2 * h->Snet, b->bf16 = h->bf16, b->x3 = h->x3, b->keep_activations = false;
+    b->frames = h->frames, b->d_stabs = h->d_stabs, b->mgeo = h->mgeo, b->d_fb = h->d_fb, b->stabs_host = h->stabs_host;
+    b->post_merged = true;  // each stream's merge + arg-max + joints as one post_kernel launch (its maps, bank and geometry)
+    int rc;
+    if ((rc = dev_alloc(b, &b->d_fp, 1)) || (rc = dev_alloc(b, &b->d_fp2, 1))) return fail(h, rc, b->err);
+    if ((rc = dev_alloc(b, &b->d_part, (size_t)NJ * ARG_SLABS_MAX))) return fail(h, rc, b->err);
+    if ((rc = dev_alloc(b, &b->d_ticket, 4))) return fail(h, rc, b->err);
+    HIPCK(h, hipMemset(b->d_ticket, 0, 4 * sizeof(unsigned)));
+    for (int i = 0; i < RING; i++) HIPCK(h, hipHostMalloc((void**)&b->h_fp[i], sizeof(FrameParams), hipHostMallocDefault));
+    b->tensors = h->tensors, b->layers = h->layers, b->tensor_by_name = h->tensor_by_name;
+    b->t_input4 = h->t_input4, b->t_out = h->t_out, b->l_conv1 = h->l_conv1, b->l_pool1 = h->l_pool1;
+    for (Tensor& t : b->tensors) t.S *= 2;
+    for (Layer& L : b->layers) {
+        L.flops *= 2, L.last_ms = 0;
+        if (L.op != OP_CONV) continue;
+        ConvArgs& a = L.a;
+        a.S *= 2, a.M *= 2;
+        if (a.ksplit > 1) a.slab_pix = (long long)a.S * a.OH * a.OW + 64, L.r.slab_pix = a.slab_pix, L.r.npix = (long long)a.S * a.OH * a.OW;
+    }
+    if ((rc = alloc_arena(b)) || (rc = alloc_workspace(b))) return fail(h, rc, b->err);
+    b->conv_flops = 0, b->conv_launches = 0;
+    for (Layer& L : b->layers)
+        if (L.op == OP_CONV) bind_activations(b, L), b->conv_flops += L.flops, b->conv_launches += 1;
+    setup_stem(b);  // the two-frame form of the stem (StemArgs::per_stream) where it fits, else pyramid_streams_kernel + the batch-tensor form
+    if (b->stem_pair) b->conv_launches -= 1;
+    // profiled batches (vnect_set_profiling) stamp into buffers of their own
+    if ((rc = dev_alloc(b, &b->d_prof, PROF_SLOTS * 128)) || (rc = dev_alloc(b, &b->d_prof_end, (size_t)PROF_WGS * 128))) return fail(h, rc, b->err);
+    HIPCK(h, hipMemset(b->d_prof_end, 0, (size_t)PROF_WGS * 128 * sizeof(unsigned long long)));
+    HIPCK(h, hipHostMalloc((void**)&b->h_prof_end, (size_t)PROF_WGS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCK(h, hipHostMalloc((void**)&b->h_prof, PROF_SLOTS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
+    b->finalized = true;
+    if ((rc = build_graph(b))) return fail(h, rc, b->err);
+    HIPCK(h, hipStreamSynchronize(b->st));
+    return VNECT_OK;
+}
+
+int build_batch_lanes(vnect_handle* h)
+{
+    destroy_batch_lanes(h);
+    if (h->stream_batch < 2) return VNECT_OK;
+    if (h->layers.size() > 128) return fail(h, VNECT_E_STATE, "internal: more layers than the profiling buffers hold");
+    int rc = build_batch_lane(h, h);
+    for (size_t i = 0; i < h->twins.size() && !rc; i++) rc = build_batch_lane(h, h->twins[i]);
+    return rc;
 }
 
 }  // namespace rt

@@ -61,7 +61,9 @@ struct Layer {
     float last_ms = 0;
 };
 
-constexpr int RING = 4;
+// result ring: one entry per frame in flight -- up to three lanes of two-frame batches (vnect_submit_streams)
+constexpr int RING = 8;
+constexpr int MAX_LANES = 3;
 
 }  // namespace rt
 }  // namespace vnect
@@ -144,6 +146,20 @@ struct vnect_handle {
     long long stream_seq[VNECT_MAX_STREAMS] = {-1, -1, -1, -1};
     vnect_handle* stream_lane[VNECT_MAX_STREAMS] = {};
     int ring_stream[RING] = {};
+    // in-flight limit in UNITS (a frame, or a batch of two streams' frames): unit_submit counts them, ring_unit[r] is the unit of ring entry r
+    unsigned long long unit_submit = 0;
+    unsigned long long ring_unit[RING] = {};
+    bool ring_batch[RING] = {};          // the entry is a frame of a batch (the handle's own profiling figures skip it)
+    vnect_handle* ring_prof[RING] = {};  // a profiled batch's plan, on the ring entry of its last frame (collect reads its layer times)
+    // Two video streams per launch (vnect_set_stream_batch): the batched plan for 2 S images -- the S-image plan's layers, tiles, K splits and
+    // fused forms with M doubled, the same packed weights -- once per lane: blanes[i] runs on lane i's stream (0: this handle) with an arena
+    // of its own.  A batch's second stream keeps its geometry in d_fp2.
+    int stream_batch = 1;
+    std::vector<vnect_handle*> blanes;
+    bool batched = false;  // this is a batched plan (its `st` is its lane's; its stem takes two frames: StemArgs::per_stream)
+    FrameParams* d_fp2 = nullptr;
+    FrameParams fp_dev2{};
+    bool fp_dev2_valid = false;
     // cached squarify table
     int sq_H = -1, sq_W = -1;
     FrameParams sq_cache{};
@@ -262,10 +278,11 @@ int add_tensor(vnect_handle* h, const std::string& name, int S, int H, int W, in
 void bind_activations(vnect_handle* h, Layer& L);
 void setup_stem(vnect_handle* h);
 int finalize_impl(vnect_handle* h);
+int build_batch_lanes(vnect_handle* h);
 
 // ---- rt_exec.cpp ---------------------------------------------------------------------------------------------------------------
 int run_network(vnect_handle* h, bool timed, bool stem_done = false);
-int sync_geometry(vnect_handle* h, const FrameParams& fp);
+int sync_geometry(vnect_handle* h, const FrameParams& fp, int which = 0);  // which 1: a batch's second stream (d_fp2)
 int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed = false, bool want_batch = false);
 int run_argmax(vnect_handle* h);
 int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0);
@@ -283,6 +300,9 @@ int ensure_stage(vnect_handle* h, int i, size_t bytes);
 int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
 int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
 int prime(vnect_handle* h);
+int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
+int forward_batch(vnect_handle* h, const float* batch, float* out);
+void destroy_batch_lanes(vnect_handle* h);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);

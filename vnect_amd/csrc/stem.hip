@@ -169,13 +169,18 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
         StemCol* cols = (StemCol*)(scr + STEM_SCR_COLS);
         int* rowmis = (int*)(scr + STEM_SCR_MIS);
         unsigned char* reg = (unsigned char*)(scr + STEM_SCR_REG);
-        const int s = sI + a.scale_base;
+        // image sI of a batch of two frames: scale sI % per_stream of frame sI / per_stream (uniform over the workgroup)
+        const bool second = a.per_stream > 0 && sI >= a.per_stream;
+        const int s = second ? sI - a.per_stream : sI + a.scale_base;
+        const FrameParams* fp = second ? a.fp2 : a.fp;
+        const unsigned long long fbase = second ? (unsigned long long)a.frame2 : (unsigned long long)a.dyn.frame;
+        const unsigned long long fstride = second ? (unsigned long long)a.stride2 : (unsigned long long)a.dyn.row_stride;
         const ResizeTab& t = a.tabs->t[s];
         const int scaled = a.tabs->scaled[s];
         const bool resize = scaled && !t.copy;       // (a scale whose size rounds to 368 is a plain copy of the square)
         const int off = scaled ? a.tabs->pad[s] : 0;  // origin and size of the scaled image on the canvas
         const int dh = scaled ? t.dh : BOX, dw = scaled ? t.dw : BOX;
-        const int offy = a.fp->offy, offx = a.fp->offx, FH = a.fp->sq.dh, FW = a.fp->sq.dw;  // the frame inside the square
+        const int offy = fp->offy, offx = fp->offx, FH = fp->sq.dh, FW = fp->sq.dw;  // the frame inside the square
         // -- A + B in ONE memory round trip and one barrier (round 5; they used to be two of each: the rectangle was computed from the
         //    row / column descriptors in LDS, i.e. behind the barrier that published them):
         //    (A) tables -> LDS: the `/255 - 0.4` table, one descriptor per patch row / column;
@@ -229,7 +234,6 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
             const int fx0 = qx0 - offx;                             // frame column of square column qx0 (may be negative)
             const int fxL = fx0 > 0 ? fx0 : 0, fxR = (fx0 + RW - 1 < FW - 1 ? fx0 + RW - 1 : FW - 1);
             const int lead = fxL - fx0, cnt = fxR - fxL + 1;        // clipped-away pixels on the left; pixels inside the frame
-            const unsigned long long fbase = (unsigned long long)a.dyn.frame;
             unsigned v[PER], msk[PER];
 #pragma unroll
             for (int k = 0; k < PER; k++) {
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
                     const int i = tid + k * STEM_THREADS, r = (int)(((float)i + 0.5f) * rpw_inv), j = i - r * RPW;
                     const int fy = qy0 + r - offy;
                     const bool rv = i < total && (unsigned)fy < (unsigned)FH && cnt > 0;
-                    const unsigned long long G = fbase + (unsigned long long)(rv ? fy : 0) * (unsigned long long)a.dyn.row_stride + 3ull * fxL;
+                    const unsigned long long G = fbase + (unsigned long long)(rv ? fy : 0) * fstride + 3ull * fxL;
                     const int m = (int)((G - 3ull * lead) & 3ull);
                     const int lo = 3 * lead + m, hi = lo + 3 * cnt;       // the row's valid bytes in LDS
                     int first = lo - 4 * j, last = hi - 4 * j;
@@ -541,6 +545,7 @@ hipError_t launch_stem(const StemArgs& a_in, hipStream_t st)
         if (hgt < 1 || hgt > STEM_MAXH) return hipErrorInvalidValue;
     }
     if (!a.w || !a.bias || !a.out || (a.from_frame ? (!a.fp || !a.tabs || !a.dyn.frame) : !a.batch)) return hipErrorInvalidValue;
+    if (a.per_stream && (a.S != 2 * a.per_stream || a.scale_base != 0 || (a.from_frame && (!a.fp2 || !a.frame2)))) return hipErrorInvalidValue;
     if (a.pair_w && (!a.pair_bias || !a.pair_out_a || !a.pair_out_b)) return hipErrorInvalidValue;
     const dim3 grid(a.S * a.groups * 4), block(STEM_THREADS);
     const bool prof = a.prof != nullptr;
