@@ -44,9 +44,13 @@ enum {
 
 enum { VNECT_FP32 = 0,        /* fp32 tensors, v_mfma_f32_32x32x2_f32 (BASELINE.json configs[1])                                      */
        VNECT_BF16 = 1,        /* bf16 tensors and weights, fp32 accumulate (configs[2])                                               */
-       VNECT_FP32_SPLIT = 2   /* fp32 tensors, fp32 accumulate; the PRODUCTS of the 64x64-tile layers run on the bf16 matrix pipe as
+       VNECT_FP32_SPLIT = 2,  /* fp32 tensors, fp32 accumulate; the PRODUCTS of the 64x64-tile layers run on the bf16 matrix pipe as
                                  exact three-way splits (x = xh + xm + xl, 6 of the 9 piece products; conv.hip, X3): fp32-class
-                                 results -- gated like VNECT_FP32 -- at 2.7x the matrix rate of the fp32 instruction                  */ };
+                                 results -- gated like VNECT_FP32 -- at 2.7x the matrix rate of the fp32 instruction                  */
+       VNECT_FP16 = 3         /* fp16 (IEEE binary16, round to nearest even) tensors and weights, fp32 accumulate, bias, BN and split-K
+                                 slabs; final maps and post-processing fp32/f64 -- VNECT_BF16's plan launch for launch on
+                                 v_mfma_f32_32x32x16_f16 (the same cycles), with 11 significant bits against 8.  vnect_finalize refuses a conv
+                                 weight that rounds to infinity in fp16 (|w| >= 65520) with VNECT_E_ARG and the tensor's name                */ };
 
 typedef struct vnect_handle vnect_handle;
 
@@ -55,7 +59,7 @@ typedef struct vnect_config {
     int32_t device;                   /* HIP device ordinal                                       */
     int32_t num_scales;               /* len(self.scales), src/estimator.py:32                    */
     double scales[VNECT_MAX_SCALES];  /* each in (0, 1]                                           */
-    int32_t precision;                /* VNECT_FP32 | VNECT_BF16 | VNECT_FP32_SPLIT               */
+    int32_t precision;                /* VNECT_FP32 | VNECT_BF16 | VNECT_FP32_SPLIT | VNECT_FP16  */
     int32_t paper_res2c;              /* 0 = reference wiring src/vnect_model.py:56 (default)     */
     int32_t use_graph;                /* 0 = eager launches; 1 = replay the frame as one hipGraph;
                                          2 = auto: eager for a frame submitted while none is in flight

@@ -31,6 +31,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------
 // The LDS image of a chunk is lane-linear per LDS-DMA instruction (8 rows x 128 B).  Bank conflicts are removed by
@@ -79,14 +81,38 @@ __device__ __forceinline__ void put_f32(gfloat* p, float v)
     __hip_atomic_store((float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store_dword ... sc1
 #endif
 }
-__device__ __forceinline__ void put_bf16(gbf16* p, float v)
+// The 16-bit element formats, the kernels' BF template parameter: 0 = fp32, 1 = bf16, 2 = fp16 (VNECT_FP16).  Both 16-bit formats share
+// every layout, tile and fused form (`if constexpr (BF)` means "16-bit elements"); they differ only in the conversions, the matrix
+// instruction and the widening of a raw 16-bit value, all of which go through the helpers below.
+template <int BF>
+using h16 = typename std::conditional<BF == 2, _Float16, __bf16>::type;
+// round to nearest even in the handle's 16-bit format, back to fp32 (exact): what a layer that reads the value back from HBM sees
+template <int BF>
+__device__ __forceinline__ float round16(float x) { return (float)(h16<BF>)x; }
+// a value as loaded (fp32 bits, or a zero-extended 16-bit element) -> fp32
+template <int BF>
+__device__ __forceinline__ float widen(unsigned u)
+{
+    if constexpr (BF == 2) return (float)__builtin_bit_cast(_Float16, (unsigned short)u);  // v_cvt_f32_f16
+    else if constexpr (BF == 1) return __builtin_bit_cast(float, u << 16);
+    else return __builtin_bit_cast(float, u);
+}
+// one 32x32x16 matrix instruction, eight 16-bit elements per lane and operand (16 bytes)
+template <int BF>
+__device__ __forceinline__ f32x16 mfma16(f32x4 a, f32x4 b, f32x16 acc)
+{
+    if constexpr (BF == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+}
+template <int BF>
+__device__ __forceinline__ void put16(gbf16* p, float v)
 {
 #if BF16_NOSTORE  // timing probe (make VARIANT=_ns EXTRA=-DBF16_NOSTORE=1; wrong results): what the 2-byte stores of the bf16 epilogues cost
     return;           // -- up to 31 of 260 us of kernel time per frame (profiles/r05_bf16_store_cost.txt)
 #endif
-    const __bf16 b = (__bf16)v;  // round to nearest even
+    const h16<BF> b = (h16<BF>)v;  // round to nearest even
 #if VNECT_AB
-    *p = b;
+    *(__attribute__((address_space(1))) h16<BF>*)p = b;
 #else
     __hip_atomic_store((unsigned short*)p, __builtin_bit_cast(unsigned short, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
@@ -122,7 +148,7 @@ __device__ __forceinline__ float bone_len(float x, float y, float z)
 #pragma clang fp contract(off)
     return sqrtf((x * x + y * y) + z * z);  // one rounding per operation, in both the fused and the stand-alone form
 }
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void bone_features(const ConvArgs& a, const float* t, int m0, int phase, int tid, int M, int Wo, int Ho,
                                               unsigned mg_wo, unsigned mg_ho)
 {
@@ -143,10 +169,10 @@ __device__ __forceinline__ void bone_features(const ConvArgs& a, const float* t,
         float v = 0.f;
         if (j < 21) {
             float x = tr[j], y = tr[21 + j], z = tr[42 + j];
-            if constexpr (BF) x = (float)(__bf16)x, y = (float)(__bf16)y, z = (float)(__bf16)z;  // what the stand-alone kernel reads back
+            if constexpr (BF) x = round16<BF>(x), y = round16<BF>(y), z = round16<BF>(z);  // what the stand-alone kernel reads back
             v = bone_len(x, y, z);
         }
-        if constexpr (BF) put_bf16((gbf16*)a.out + base + j, v);
+        if constexpr (BF) put16<BF>((gbf16*)a.out + base + j, v);
         else put_f32((gfloat*)a.out + base + j, v);
     }
 }
@@ -159,16 +185,16 @@ __device__ __forceinline__ void bone_features(const ConvArgs& a, const float* t,
 // blocks 2 + g, 4 + g, ... -- three times as many, because a producer wave has registers to spare while the first GEMM runs: it
 // requests the shortcut values of its first two blocks and the weight fragments of its first block BEFORE the K loop, so the
 // shortcut read (half of this layer's bytes) overlaps the first GEMM's MFMA phase instead of following it.
-template <bool BF>
+template <int BF>
 constexpr int TAIL_MS = BF ? 72 : 68;  // mid row stride in elements: 144 B (bf16) / 272 B (fp32), conflict-free 16-byte reads
-template <bool BF>
+template <int BF>
 struct TailRegs {
     static constexpr int NQ = BF ? 4 : 8;  // MFMA groups over K = 64: 4 x (k = 16) bf16 / 8 x 4 x (k = 2) fp32
     unsigned rw[2][16];                    // shortcut values of two blocks, as loaded (fp32 bits or a zero-extended bf16)
     f32x4 Bf[NQ];                          // weight fragments of one block
 };
 // shortcut values of column block cb for the lane's 16 rows (mb = first row of the lane's C/D map)
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void tail_load_resid(const ConvArgs& a, int mb, int cb, int lane, unsigned (&rw)[16])
 {
     const unsigned off = (unsigned)(mb * a.ldr + cb * 32 + (lane & 31));
@@ -184,7 +210,7 @@ __device__ __forceinline__ void tail_load_resid(const ConvArgs& a, int mb, int c
         for (int r = 0; r < 16; r++) rw[r] = rp[off], rp += ((r & 3) == 3 ? 5 : 1) * a.ldr;
     }
 }
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void tail_load_b(const ConvArgs& a, int cb, int lane, f32x4 (&Bf)[TailRegs<BF>::NQ])
 {
     // tail_w is packed in fragment order (hostplan.h: pack_tail): [block][q][lane] x 16 bytes -- one contiguous KiB per instruction
@@ -201,7 +227,7 @@ constexpr int NCHAIN_OS = 264;
 constexpr int NCHAIN_OFF = 64 * TAIL_MS<true>;  // bf16 elements from the start of the LDS
 // bf16 64-wide tail: does the launch take the staged form (its output through the LDS tile)?  Uniform, decided by the arguments alone, so
 // every wave of the workgroup agrees and meets at the barrier in front of tail_write_out.
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ bool tail_staged(const ConvArgs& a)
 {
     return BF && a.resid != nullptr && a.relu_cols >= 256 && !a.out_f32 && a.Nvalid == 256 && a.tail_n == 256 && (a.ldc & 7) == 0;
@@ -218,7 +244,7 @@ __device__ __forceinline__ void tail_write_out(const ConvArgs& a, const float* s
     }
 }
 // NBLK blocks cb0, cb0 + cbs, ...; PRE: T.rw[0], T.rw[1] (blocks 0, 1) and T.Bf (block 0) were requested by the caller
-template <bool BF, int NBLK, bool PRE, bool CH = false>
+template <int BF, int NBLK, bool PRE, bool CH = false>
 __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, int m0, int wm, int cb0, int cbs, int lane, TailRegs<BF>& T)
 {
     static_assert(!CH || BF, "the 64-wide chain exists in bf16 only");
@@ -251,7 +277,7 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             if constexpr (BF) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Af[q]), __builtin_bit_cast(bf16x8, T.Bf[q]), acc, 0, 0, 0);
+                acc = mfma16<BF>(Af[q], T.Bf[q], acc);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Af[q][e], T.Bf[q][e], acc, 0, 0, 0);
@@ -269,19 +295,19 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
             // cost ~3 us of a 10-us launch (profiles/r05_bf16_store_cost.txt).  The chain GEMM (CH) reads the same tile.
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const float o = __builtin_fmaxf(acc[r] + bias2 + __builtin_bit_cast(float, rw[r] << 16), 0.f);
-                ((__bf16*)smem)[NCHAIN_OFF + (wm * 32 + 4 * hh + (r & 3) + 8 * (r >> 2)) * NCHAIN_OS + n2] = (__bf16)o;
+                const float o = __builtin_fmaxf(acc[r] + bias2 + widen<BF>(rw[r]), 0.f);
+                ((h16<BF>*)smem)[NCHAIN_OFF + (wm * 32 + 4 * hh + (r & 3) + 8 * (r >> 2)) * NCHAIN_OS + n2] = (h16<BF>)o;
             }
         } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 float o = acc[r] + bias2;
-                if (a.resid) o = o + __builtin_bit_cast(float, BF ? rw[r] << 16 : rw[r]);
+                if (a.resid) o = o + widen<BF>(rw[r]);
                 if (relu2) o = __builtin_fmaxf(o, 0.f);
                 const unsigned oo = off0 + (unsigned)(((r & 3) + 8 * (r >> 2)) * a.ldc);
                 if (n2 < a.Nvalid) {
                     if (t_of32) put_f32(op + oo, o);
-                    else put_bf16((gbf16*)op + oo, o);
+                    else put16<BF>((gbf16*)op + oo, o);
                 }
             }
         }
@@ -303,21 +329,21 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
 #ifndef WT_DBG
 #define WT_DBG 0  // timing probes of the wide tail (wrong results): 1 = 1 / NQ of the MFMAs, 2 = no stores, 3 = one weight load per block
 #endif
-template <bool BF>
+template <int BF>
 constexpr int WIDE_MS = BF ? 136 : 132;  // mid row stride in elements: 272 B (bf16) / 528 B (fp32), conflict-free 16-byte reads
 // The chain GEMM's A operand: the tail's OUTPUT tile (32 pixels x 512 channels, what the block writes to HBM) kept in LDS behind the
 // mid tile; row stride 516 / 520 elements (conflict-free 16-byte reads, like the mid tile's)
-template <bool BF>
+template <int BF>
 constexpr int CHAIN_OS = BF ? 520 : 516;
-template <bool BF>
+template <int BF>
 constexpr int CHAIN_OFF = 32 * WIDE_MS<BF>;  // elements from the start of the LDS
-template <bool BF>
+template <int BF>
 struct WideRegs {
     static constexpr int NQ = BF ? 8 : 16;  // MFMA groups over K = 128
     unsigned rw[2][16];                      // shortcut values of this wave's two blocks, as loaded
     f32x4 Bf[2][NQ];                         // weight fragments of both blocks
 };
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void wide_load_b(const ConvArgs& a, int cb, int lane, f32x4 (&Bf)[WideRegs<BF>::NQ])
 {
     // tail_w is packed in fragment order (hostplan.h: pack_tail): [block][q][lane] x 16 bytes -- one contiguous KiB per instruction
@@ -328,7 +354,7 @@ __device__ __forceinline__ void wide_load_b(const ConvArgs& a, int cb, int lane,
     for (int q = 0; q < NQ; q++) Bf[q] = bp[(WT_DBG == 3 ? 0 : q) * 64];
 }
 // the shortcut values of a tail wave's blocks (any wave can request them before the K loop: 32 registers) ...
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void wide_load_resid(const ConvArgs& a, int m0, int tw, int lane, WideRegs<BF>& T)
 {
     const int nb = (a.tail_n + 31) >> 5, mb = m0 + 4 * (lane >> 5);
@@ -337,7 +363,7 @@ __device__ __forceinline__ void wide_load_resid(const ConvArgs& a, int m0, int t
     if (tw + 8 < nb) tail_load_resid<BF>(a, mb, tw + 8, lane, T.rw[1]);
 }
 // ... and the weight fragments (a producer wave before the K loop -- it has the registers --, a consumer wave behind it)
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void wide_load_weights(const ConvArgs& a, int tw, int lane, WideRegs<BF>& T)
 {
     const int nb = (a.tail_n + 31) >> 5;
@@ -348,12 +374,12 @@ __device__ __forceinline__ void wide_load_weights(const ConvArgs& a, int tw, int
 // interleaved, every A fragment (one 16-byte LDS read) feeding both.  The two tail waves of a SIMD -- one producer, one consumer
 // wave -- share its matrix pipe: the producer's operands are in registers when the K loop ends, so its MFMAs cover the consumer's
 // wait for its weight fragments.
-template <bool BF>
+template <int BF>
 constexpr int CHAIN_DEPTH = BF ? 16 : 8;  // weight groups of the chain GEMM in flight ahead of its MFMAs (registers the tail's own weights free)
 // bf16 wide tail whose output is a block output (shortcut + ReLU, bf16, all 512 columns valid): staged like the 64-wide tail's (tail_staged /
 // tail_write_out) -- the blocks go to the LDS output tile only (32 rows x 512 channels behind the mid tile, where the chain GEMM reads them
 // anyway) and leave in whole 1-KiB rows, 16 bytes per thread and store, behind the barrier all eight tail waves meet at.
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ bool wide_staged(const ConvArgs& a)
 {
     return BF && a.resid != nullptr && a.relu_cols >= 512 && !a.out_f32 && a.Nvalid == 512 && a.tail_n == 512 && (a.ldc & 7) == 0;
@@ -372,7 +398,7 @@ __device__ __forceinline__ void wide_write_out(const ConvArgs& a, const float* s
 // wave that runs a chain block (cq != nullptr: tail waves 0..3) requests that block's first weight groups BEFORE its stores -- vmcnt
 // counts loads and stores alike on this chip, so loads issued behind the 32 write-through stores could only be waited for together
 // with them.
-template <bool BF, bool CH>
+template <int BF, bool CH>
 __device__ __forceinline__ void tail_wide(const ConvArgs& a, const float* smem, int m0, int tw, int lane, WideRegs<BF>& T, f32x4* cq = nullptr)
 {
     constexpr int MS = WIDE_MS<BF>, NQ = WideRegs<BF>::NQ;
@@ -397,9 +423,9 @@ __device__ __forceinline__ void tail_wide(const ConvArgs& a, const float* smem, 
             const f32x4 Af = An;
             if (q + 1 < NQ) An = afrag(q + 1);
             if constexpr (BF) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Af), __builtin_bit_cast(bf16x8, T.Bf[0][q]), acc0, 0, 0, 0);
+                acc0 = mfma16<BF>(Af, T.Bf[0][q], acc0);
                 if constexpr (decltype(TWO)::value)
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Af), __builtin_bit_cast(bf16x8, T.Bf[1][q]), acc1, 0, 0, 0);
+                    acc1 = mfma16<BF>(Af, T.Bf[1][q], acc1);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
@@ -447,8 +473,8 @@ __device__ __forceinline__ void tail_wide(const ConvArgs& a, const float* smem, 
             if (wide_staged<BF>(a)) {  // (uniform) the block output: to the LDS tile only, wide_write_out stores it
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    const float o = __builtin_fmaxf(acc[r] + bias2 + __builtin_bit_cast(float, rw[r] << 16), 0.f);
-                    ((__bf16*)smem)[CHAIN_OFF<BF> + (4 * hh + (r & 3) + 8 * (r >> 2)) * CHAIN_OS<BF> + n2] = (__bf16)o;
+                    const float o = __builtin_fmaxf(acc[r] + bias2 + widen<BF>(rw[r]), 0.f);
+                    ((h16<BF>*)smem)[CHAIN_OFF<BF> + (4 * hh + (r & 3) + 8 * (r >> 2)) * CHAIN_OS<BF> + n2] = (h16<BF>)o;
                 }
                 return;
             }
@@ -459,16 +485,16 @@ __device__ __forceinline__ void tail_wide(const ConvArgs& a, const float* smem, 
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 float o = acc[r] + bias2;
-                if constexpr (decltype(RESID)::value) o = o + __builtin_bit_cast(float, BF ? rw[r] << 16 : rw[r]);
+                if constexpr (decltype(RESID)::value) o = o + widen<BF>(rw[r]);
                 if constexpr (decltype(RELU)::value) o = __builtin_fmaxf(o, 0.f);
                 if (WT_DBG != 2 || a.ldc < 0) {
                     if constexpr (decltype(OUTF32)::value) put_f32((gfloat*)op + off0, o);
-                    else put_bf16((gbf16*)op + off0, o);
+                    else put16<BF>((gbf16*)op + off0, o);
                 }
                 op += ((r & 3) == 3 ? 5 : 1) * a.ldc;
                 if constexpr (CH) {  // the same value, in the precision it has in HBM, for the chain GEMM
                     const int row = 4 * hh + (r & 3) + 8 * (r >> 2);
-                    if constexpr (BF) ((__bf16*)smem)[CHAIN_OFF<BF> + row * CHAIN_OS<BF> + n2] = (__bf16)o;
+                    if constexpr (BF) ((h16<BF>*)smem)[CHAIN_OFF<BF> + row * CHAIN_OS<BF> + n2] = (h16<BF>)o;
                     else const_cast<float*>(smem)[CHAIN_OFF<BF> + row * CHAIN_OS<BF> + n2] = o;
                 }
             }
@@ -502,7 +528,7 @@ __device__ __forceinline__ void tail_wide(const ConvArgs& a, const float* smem, 
 // runs its block's whole K = 512 in one accumulator, chunk by chunk like the stand-alone layer: bit-identical).  The weights stream
 // from global memory in fragment order (one KiB per instruction) through a ring of registers, CHAIN_DEPTH groups ahead of the MFMAs
 // (the first of them requested inside tail_wide, in front of its stores).
-template <bool BF>
+template <int BF>
 __device__ __forceinline__ void chain_gemm(const ConvArgs& a, const float* smem, int m0, int cb, int lane, f32x4 (&Bq)[CHAIN_DEPTH<BF>])
 {
     typedef __attribute__((address_space(1))) const f32x4 cgf4;
@@ -527,7 +553,7 @@ __device__ __forceinline__ void chain_gemm(const ConvArgs& a, const float* smem,
         if (q + 1 < NQ) An = afrag(q + 1);
         if (CH_DBG == 1 && q > 0) continue;
         if constexpr (BF) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Af), __builtin_bit_cast(bf16x8, Bf), acc, 0, 0, 0);
+            acc = mfma16<BF>(Af, Bf, acc);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Af[e], Bf[e], acc, 0, 0, 0);
@@ -536,12 +562,12 @@ __device__ __forceinline__ void chain_gemm(const ConvArgs& a, const float* smem,
     }
     const int n3 = cb * 32 + col;
     const unsigned off0 = (unsigned)(mb * a.chain_ld + n3);
-    typedef typename std::conditional<BF, gbf16, gfloat>::type OT;
+    typedef typename std::conditional<BF != 0, gbf16, gfloat>::type OT;
     OT* op = (OT*)a.chain_out;  // scalar row base stepped by additions, one lane offset
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const float o = __builtin_fmaxf(acc[r] + bias3, 0.f);
-        if constexpr (BF) put_bf16(op + off0, o);
+        if constexpr (BF) put16<BF>(op + off0, o);
         else put_f32(op + off0, o);
         op += ((r & 3) == 3 ? 5 : 1) * a.chain_ld;
     }
@@ -549,6 +575,7 @@ __device__ __forceinline__ void chain_gemm(const ConvArgs& a, const float* smem,
 
 // [64 x 256] x [256 x 64]: 2 row halves x 2 column blocks, one per producer wave (rh = wave & 1, cb = wave >> 1), K = 256 in one
 // accumulator (16 MFMAs: the stand-alone layer's order), weights in fragment order from L2.
+template <int BF>
 __device__ __forceinline__ void chain_narrow(const ConvArgs& a, const float* smem, int m0, int wave, int lane)
 {
     typedef __attribute__((address_space(1))) const f32x4 cgf4;
@@ -567,12 +594,12 @@ __device__ __forceinline__ void chain_narrow(const ConvArgs& a, const float* sme
     for (int r = 0; r < 16; r++) acc[r] = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; q++)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, *(const f32x4*)(at + 16 * q)), __builtin_bit_cast(bf16x8, Bq[q]), acc, 0, 0, 0);
+        acc = mfma16<BF>(*(const f32x4*)(at + 16 * q), Bq[q], acc);
     const unsigned off0 = (unsigned)((m0 + rh * 32 + 4 * hh) * a.chain_ld + cb * 32 + col);
     gbf16* op = (gbf16*)a.chain_out;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        put_bf16(op + off0, __builtin_fmaxf(acc[r] + bias3, 0.f));
+        put16<BF>(op + off0, __builtin_fmaxf(acc[r] + bias3, 0.f));
         op += ((r & 3) == 3 ? 5 : 1) * a.chain_ld;
     }
 }
@@ -619,7 +646,7 @@ __device__ __forceinline__ void chain_narrow(const ConvArgs& a, const float* sme
 // the issue path, K slices) is compiled OUT of such a launch's kernel.  A launch's cold start is ~750 one-off instructions in front of the
 // first DMA, issued at one per ~4 cycles by a single wave (profiles/r04_phase_producer_start.txt): what is not there is not issued.  Every
 // fused form (FUSE != 0) is a one-item launch by construction.
-template <int BM, int BN, int KG, int NS, bool BF, int PROF, int FUSE = 0, bool SPAN = false, bool X3 = false, bool ONE = false>
+template <int BM, int BN, int KG, int NS, int BF, int PROF, int FUSE = 0, bool SPAN = false, bool X3 = false, bool ONE = false>
 __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_stream_kernel(const ConvArgs a)
 {
     constexpr bool TAIL = FUSE == 1 || FUSE == 3, BONE = FUSE == 2, CHAIN = FUSE == 3;  // 3: the wide tail with a chain GEMM behind it
@@ -1021,7 +1048,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                 }
             } else {
                 tail_gemm<BF, 3, true, CHAIN>(a, smem, decode(0).m0, wm2, 2 + g2, 2, lane, T);
-                if constexpr (CHAIN) chain_narrow(a, smem, decode(0).m0, wave, lane);
+                if constexpr (CHAIN) chain_narrow<BF>(a, smem, decode(0).m0, wave, lane);
                 else if constexpr (BF) {
                     if (tail_staged<BF>(a)) {  // (uniform) the block output leaves from the LDS tile: all eight waves, behind one barrier
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1078,7 +1105,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
     };
     auto mma = [&](const f32x4& af, const f32x4& bf) __attribute__((always_inline)) {
         if constexpr (BF) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf), acc, 0, 0, 0);
+            acc = mfma16<BF>(af, bf, acc);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
@@ -1457,7 +1484,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                 for (int r = 0; r < 16; r++) {
                     const int row = wm * 32 + rhalf + (r & 3) + 8 * (r >> 2);
                     const float v = __builtin_fmaxf(acc[r] + bias, 0.f);
-                    if constexpr (BF) ((__bf16*)smem)[row * MS + k1] = (__bf16)v;
+                    if constexpr (BF) ((h16<BF>*)smem)[row * MS + k1] = (h16<BF>)v;
                     else smem[row * MS + k1] = v;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1535,7 +1562,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                        "+v"(rsw[14]), "+v"(rsw[15]));
         float rs[16];
 #pragma unroll
-        for (int r = 0; r < 16; r++) rs[r] = __builtin_bit_cast(float, BF ? rsw[r] << 16 : rsw[r]);
+        for (int r = 0; r < 16; r++) rs[r] = widen<BF>(rsw[r]);
         const int py = it.phase >> 1, px = it.phase & 1;
         const bool second = fused && c.out2 != nullptr && it.n0 >= c.split_n;  // two layers sharing one input run as one GEMM: columns [0, split_n) -> out, the rest -> out2 (split_n is a multiple of the tile width)
         gfloat* outp = (gfloat*)(!fused ? c.ws + (long long)it.ks * c.slab_pix * c.Npad : (second ? c.out2 : c.out));
@@ -1558,7 +1585,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                     o = o + rs[r];
                     if constexpr (decltype(RELU)::value) o = __builtin_fmaxf(o, 0.f);
                     if constexpr (decltype(OUTF32)::value) put_f32((gfloat*)op + off0, o);
-                    else put_bf16((gbf16*)op + off0, o);
+                    else put16<BF>((gbf16*)op + off0, o);
                     op += ((r & 3) == 3 ? 5 : 1) * ldo;
                 }
             };
@@ -1586,7 +1613,7 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                 if (m < h.M && n < nlim) {
                     const unsigned off = (unsigned)(op * ldo + (n - ncol0));  // tensors are far below 2^32 elements
                     if (of32) put_f32(outp + off, o);
-                    else put_bf16((gbf16*)outp + off, o);
+                    else put16<BF>((gbf16*)outp + off, o);
                 }
             }
         }
@@ -1617,8 +1644,11 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
 // split-K second pass: slabs summed in slice order (deterministic), then the same epilogue.  One thread = 4 consecutive channels of one pixel:
 // the slab loads, the bias / BN vectors and the shortcut are requested together, the result leaves as ONE 16-byte (fp32) or 8-byte (bf16)
 // write-through store where all four channels are valid (round 4: the scalar per-channel form took 7.7 us for 19 MB).
+template <bool F16>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs a)
 {
+    typedef typename std::conditional<F16, _Float16, __bf16>::type H;  // the 16-bit element format (a.bf16: 16-bit elements at all)
+    typedef H hx4 __attribute__((ext_vector_type(4)));
     const int n4 = a.Npad >> 2;
     const long long total = a.npix * n4;
     // vector loads / stores of the shortcut and the output need 4-element pixel strides AND 16-byte (bf16: 8-byte) aligned bases -- checked once
@@ -1639,7 +1669,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs a)
             bv = *(const f32x4*)(a.bias + n);
             if (a.scale) scv = *(const f32x4*)(a.scale + n), shv = *(const f32x4*)(a.shift + n);
             if (a.resid) {
-                if (a.bf16) rv = __builtin_convertvector(*(const bf16x4*)((const __bf16*)a.resid + pix * a.ldr + n), f32x4);
+                if (a.bf16) rv = __builtin_convertvector(*(const hx4*)((const H*)a.resid + pix * a.ldr + n), f32x4);
                 else rv = *(const f32x4*)(a.resid + pix * a.ldr + n);
             }
         }
@@ -1657,7 +1687,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs a)
                 if (n + e < a.relu_cols) t = t > 0.f ? t : 0.f;
                 v[e] = t;
             }
-            if (a.bf16 && !a.out_f32) store_wt((bf16x4*)((__bf16*)a.out + pix * a.ldc + n), __builtin_convertvector(v, bf16x4));
+            if (a.bf16 && !a.out_f32) store_wt((hx4*)((H*)a.out + pix * a.ldc + n), __builtin_convertvector(v, hx4));
             else store_wt((f32x4*)(a.out + pix * a.ldc + n), v);
             continue;
         }
@@ -1667,9 +1697,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs a)
             if (c >= a.Nvalid) continue;
             float v = s[e] + a.bias[c];
             if (a.scale) v = v * a.scale[c] + a.shift[c];
-            if (a.resid) v = v + (a.bf16 ? (float)((const __bf16*)a.resid)[pix * a.ldr + c] : a.resid[pix * a.ldr + c]);
+            if (a.resid) v = v + (a.bf16 ? (float)((const H*)a.resid)[pix * a.ldr + c] : a.resid[pix * a.ldr + c]);
             if (c < a.relu_cols) v = v > 0.f ? v : 0.f;
-            if (a.bf16 && !a.out_f32) ((__bf16*)a.out)[pix * a.ldc + c] = (__bf16)v;
+            if (a.bf16 && !a.out_f32) ((H*)a.out)[pix * a.ldc + c] = (H)v;
             else a.out[pix * a.ldc + c] = v;
         }
     }
@@ -1766,9 +1796,15 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
                                                        // staged form (tail_staged: whole 16-byte units per row, ldc % 8 == 0; advisor, round 5)
                 return hipErrorInvalidValue;
 #define LAUNCH_TAIL(BF, PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, BF, PR, 1>), grid, dim3(512), lds, st, a)
-            if (a.bf16 && a.chain_n) {
+            if (a.f16 && a.chain_n) {
+                if (prof == 0) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, 2, 0, 3>), grid, dim3(512), lds, st, a);
+                else hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, 2, 1, 3>), grid, dim3(512), lds, st, a);
+            } else if (a.bf16 && a.chain_n) {
                 if (prof == 0) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, true, 0, 3>), grid, dim3(512), lds, st, a);
                 else hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, true, 1, 3>), grid, dim3(512), lds, st, a);
+            } else if (a.f16) {
+                if (prof == 0) LAUNCH_TAIL(2, 0);
+                else LAUNCH_TAIL(2, 1);
             } else if (a.bf16) {
                 if (prof == 0) LAUNCH_TAIL(true, 0);
                 else LAUNCH_TAIL(true, 1);
@@ -1819,7 +1855,10 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
         if (a.chain_n) hipLaunchKernelGGL((conv_stream_kernel<32, 128, 1, NS, BF, PR, 3>), grid, dim3(512), lds, st, a);                     \
         else hipLaunchKernelGGL((conv_stream_kernel<32, 128, 1, NS, BF, PR, 1>), grid, dim3(512), lds, st, a);                               \
     } while (0)
-            if (a.bf16) {
+            if (a.f16) {
+                if (prof == 0) LAUNCH_WTAIL(2, 0);
+                else LAUNCH_WTAIL(2, 1);
+            } else if (a.bf16) {
                 if (prof == 0) LAUNCH_WTAIL(true, 0);
                 else LAUNCH_WTAIL(true, 1);
             } else {
@@ -1835,7 +1874,10 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
         if (a.bone) {  // bone-length features inside the transposed conv's launch: one tile per workgroup again
             if (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212) return hipErrorInvalidValue;
 #define LAUNCH_BONE(BF, PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, BF, PR, 2>), grid, dim3(512), lds, st, a)
-            if (a.bf16) {
+            if (a.f16) {
+                if (prof == 0) LAUNCH_BONE(2, 0);
+                else LAUNCH_BONE(2, 1);
+            } else if (a.bf16) {
                 if (prof == 0) LAUNCH_BONE(true, 0);
                 else LAUNCH_BONE(true, 1);
             } else {
@@ -1859,7 +1901,11 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
         }
     }
     if constexpr (BN != 96) {
-        if (a.bf16) {
+        if (a.f16) {
+            if (prof == 0) LAUNCH_STREAM(2, 0);
+            else if (prof == 1) LAUNCH_STREAM(2, 1);
+            else LAUNCH_STREAM(2, 2);
+        } else if (a.bf16) {
             if (prof == 0) LAUNCH_STREAM(true, 0);
             else if (prof == 1) LAUNCH_STREAM(true, 1);
             else LAUNCH_STREAM(true, 2);
@@ -1906,11 +1952,15 @@ static hipError_t setup_stream_rest()
     hipFuncAttributes fa;
     std::vector<const void*> fns = {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 0>,
                                     (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 1>,
-                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2>};
-    const void* twins_one[2] = {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2, 0, false, false, true>};
+                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2>,
+                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 0>, (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 1>,
+                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2>};
+    const void* twins_one[3] = {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2, 0, false, false, true>,
+                                (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2, 0, false, false, true>};
     for (const void* f : {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 0, 0, false, false, true>,
                           (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 1, 0, false, false, true>,
-                          twins_one[0], twins_one[1]})
+                          (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 0, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 1, 0, false, false, true>,
+                          twins_one[0], twins_one[1], twins_one[2]})
         fns.push_back(f);
     if constexpr (BM == 64 && BN == 64 && KG == 1) {
         fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 0, 1>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 1>);
@@ -1919,6 +1969,10 @@ static hipError_t setup_stream_rest()
         fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 3>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 1, 3>);
         fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 0, 2>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 2>);
         fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 1, 2>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 1, 2>);
+        for (const void* f : {(const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 1>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 1>,
+                              (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 3>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 3>,
+                              (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 2>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 2>})
+            fns.push_back(f);
         static_assert(x3_lds() <= stream_lds<64, 64, 1, 5>(), "the split-product ring fits the same LDS allowance");
     }
     if constexpr (BM == 64 && BN == 64 && KG == 1) {  // the split-product instantiations have LDS sizes of their own
@@ -1939,6 +1993,9 @@ static hipError_t setup_stream_rest()
         fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 1, 1>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 1, 1>);
         fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 0, 3>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 0, 3>);
         fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 1, 3>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 1, 3>);
+        for (const void* f : {(const void*)conv_stream_kernel<32, 128, 1, NS, 2, 0, 1>, (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 1, 1>,
+                              (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 0, 3>, (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 1, 3>})
+            fns.push_back(f);
     }
     if constexpr (BM == 64 && BN == 32 && KG == 2) {
         for (const void* f : {(const void*)conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 0, 0, false, true>, (const void*)conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 1, 0, false, true>}) {
@@ -1959,7 +2016,8 @@ static hipError_t setup_stream_rest()
         // the launch plan assumes two workgroups per CU (one for the K-group shapes): refuse a build that needs more registers
         // or scratch (the per-phase tuning twins, PROF = 2, may spill a few bytes)
         const bool twin = f == (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2> || f == (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2> ||
-                          f == twins_one[0] || f == twins_one[1] || f == span_twin;
+                          f == (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2> || f == twins_one[0] || f == twins_one[1] || f == twins_one[2] ||
+                          f == span_twin;
         if (fa.numRegs > (KG == 1 && BN <= 64 ? 128 : 256) || (fa.localSizeBytes != 0 && !twin && !F32_NOSTORE)) return hipErrorLaunchOutOfResources;  // (the probe build may spill)
     }
     return hipSuccess;
@@ -1991,7 +2049,7 @@ hipError_t conv_setup()
 hipError_t launch_conv(const ConvArgs& a, int BM, int BN, int KG, hipStream_t st)
 {
     const int epr = a.bf16 ? 64 : 32;
-    if (a.Npad % BN != 0 || a.K != a.ntaps * a.cpt * epr || a.nphase * a.ntaps > MAX_TAPS ||
+    if ((a.f16 && !a.bf16) || a.Npad % BN != 0 || a.K != a.ntaps * a.cpt * epr || a.nphase * a.ntaps > MAX_TAPS ||
         a.ksplit < 1 || (a.ksplit > 1 && !a.ws) || (a.Cs & 3) || (a.bf16 && a.out2 && a.split_n % 64))
         return hipErrorInvalidValue;
     // range of the multiply-high divisions in the kernel (x / d exact while x * d < 2^32)
@@ -2009,11 +2067,12 @@ hipError_t launch_reduce(const ReduceArgs& a, hipStream_t st)
     long long total = a.npix * (a.Npad >> 2);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a);
+    if (a.f16) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-// ---- layout helpers (T = float or __bf16 activations) ------------------------------------------------
+// ---- layout helpers (T = float, __bf16 or _Float16 activations) ------------------------------------------------
 template <typename T>
 __global__ void pad3to4_kernel(const float* __restrict__ in3, T* __restrict__ out4, long long npix)
 {
@@ -2028,17 +2087,19 @@ __global__ void strip4to3_kernel(const T* __restrict__ in4, float* __restrict__ 
     if (p >= npix) return;
     out3[p * 3] = (float)in4[p * 4], out3[p * 3 + 1] = (float)in4[p * 4 + 1], out3[p * 3 + 2] = (float)in4[p * 4 + 2];
 }
-hipError_t launch_pad3to4(const float* in3, void* out4, long long npix, int bf16, hipStream_t st)
+hipError_t launch_pad3to4(const float* in3, void* out4, long long npix, int el, hipStream_t st)
 {
     dim3 g((unsigned)((npix + 255) / 256));
-    if (bf16) hipLaunchKernelGGL(pad3to4_kernel<__bf16>, g, dim3(256), 0, st, in3, (__bf16*)out4, npix);
+    if (el == EL_F16) hipLaunchKernelGGL(pad3to4_kernel<_Float16>, g, dim3(256), 0, st, in3, (_Float16*)out4, npix);
+    else if (el) hipLaunchKernelGGL(pad3to4_kernel<__bf16>, g, dim3(256), 0, st, in3, (__bf16*)out4, npix);
     else hipLaunchKernelGGL(pad3to4_kernel<float>, g, dim3(256), 0, st, in3, (float*)out4, npix);
     return hipGetLastError();
 }
-hipError_t launch_strip4to3(const void* in4, float* out3, long long npix, int bf16, hipStream_t st)
+hipError_t launch_strip4to3(const void* in4, float* out3, long long npix, int el, hipStream_t st)
 {
     dim3 g((unsigned)((npix + 255) / 256));
-    if (bf16) hipLaunchKernelGGL(strip4to3_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in4, out3, npix);
+    if (el == EL_F16) hipLaunchKernelGGL(strip4to3_kernel<_Float16>, g, dim3(256), 0, st, (const _Float16*)in4, out3, npix);
+    else if (el) hipLaunchKernelGGL(strip4to3_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in4, out3, npix);
     else hipLaunchKernelGGL(strip4to3_kernel<float>, g, dim3(256), 0, st, (const float*)in4, out3, npix);
     return hipGetLastError();
 }
@@ -2073,11 +2134,12 @@ __global__ void maxpool_kernel(const T* __restrict__ in, T* __restrict__ out, in
     }
     store_wt((tx4*)(out + p * C + c), __builtin_convertvector(m, tx4));  // exact: the maximum is one of the inputs
 }
-hipError_t launch_maxpool(const void* in, void* out, int S, int H, int W, int C, int Ho, int Wo, int bf16, hipStream_t st)
+hipError_t launch_maxpool(const void* in, void* out, int S, int H, int W, int C, int Ho, int Wo, int el, hipStream_t st)
 {
     long long total = (long long)S * Ho * Wo * (C >> 2);
     dim3 g((unsigned)((total + 255) / 256));
-    if (bf16) hipLaunchKernelGGL(maxpool_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in, (__bf16*)out, S, H, W, C, Ho, Wo);
+    if (el == EL_F16) hipLaunchKernelGGL(maxpool_kernel<_Float16>, g, dim3(256), 0, st, (const _Float16*)in, (_Float16*)out, S, H, W, C, Ho, Wo);
+    else if (el) hipLaunchKernelGGL(maxpool_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in, (__bf16*)out, S, H, W, C, Ho, Wo);
     else hipLaunchKernelGGL(maxpool_kernel<float>, g, dim3(256), 0, st, (const float*)in, (float*)out, S, H, W, C, Ho, Wo);
     return hipGetLastError();
 }
@@ -2114,11 +2176,12 @@ bool conv_probes_off()
     return X3_DBG == 0 && WT_DBG == 0 && CH_DBG == 0 && F32_NOSTORE == 0 && BF16_NOSTORE == 0 && VNECT_AB == 0 && NS_6432 == 5 && NS_32128 == 5;
 }
 
-hipError_t launch_bone(void* feat, long long npix, int ld, int bf16, hipStream_t st)
+hipError_t launch_bone(void* feat, long long npix, int ld, int el, hipStream_t st)
 {
     long long total = npix * (ld - 191);
     dim3 g((unsigned)((total + 255) / 256));
-    if (bf16) hipLaunchKernelGGL(bone_kernel<__bf16>, g, dim3(256), 0, st, (__bf16*)feat, npix, ld);
+    if (el == EL_F16) hipLaunchKernelGGL(bone_kernel<_Float16>, g, dim3(256), 0, st, (_Float16*)feat, npix, ld);
+    else if (el) hipLaunchKernelGGL(bone_kernel<__bf16>, g, dim3(256), 0, st, (__bf16*)feat, npix, ld);
     else hipLaunchKernelGGL(bone_kernel<float>, g, dim3(256), 0, st, (float*)feat, npix, ld);
     return hipGetLastError();
 }

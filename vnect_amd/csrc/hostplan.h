@@ -213,6 +213,51 @@ inline float from_bf16(uint16_t b)
     memcpy(&f, &u, 4);
     return f;
 }
+// fp32 -> fp16 (IEEE binary16, VNECT_FP16), round to nearest even: subnormals below 2^-14, infinity from 65520 on (the midpoint above
+// 65504 rounds to even), NaN stays a quiet NaN
+inline uint16_t to_f16(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // |f| >= 65520 (and infinity)
+    if (a >= 0x38800000u) {                                      // |f| >= 2^-14: a normal fp16 (a carry out of the mantissa is the next binade)
+        const uint32_t r = a + 0xFFFu + ((a >> 13) & 1u);
+        return (uint16_t)(sign | ((r - 0x38000000u) >> 13));
+    }
+    float m;  // subnormal: |f| / 2^-24 is exact in fp32, nearbyintf rounds it half to even (1024 is the smallest normal's encoding)
+    memcpy(&m, &a, 4);
+    return (uint16_t)(sign | (uint32_t)nearbyintf(m * 16777216.f));
+}
+inline float from_f16(uint16_t hb)
+{
+    const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 0x1Fu, m = hb & 0x3FFu;
+    uint32_t u;
+    if (e == 0x1F) u = sign | 0x7F800000u | (m << 13);
+    else if (e) u = sign | ((e + 112u) << 23) | (m << 13);
+    else {
+        const float v = (float)m * 5.9604644775390625e-8f;  // m 2^-24, exact
+        memcpy(&u, &v, 4);
+        u |= sign;
+    }
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// packed fp32 weights -> the 16-bit elements of a bf16 or an fp16 handle (same positions: the layouts key on "16-bit", not on the format)
+inline void to_16(const std::vector<float>& v, bool f16, std::vector<uint16_t>& out)
+{
+    out.resize(v.size());
+    for (size_t i = 0; i < v.size(); i++) out[i] = f16 ? to_f16(v[i]) : to_bf16(v[i]);
+}
+// the first finite element of a weight tensor that fp16 cannot hold (it rounds to infinity), or -1
+inline long long first_f16_overflow(const float* d, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (fabsf(d[i]) >= 65520.f && fabsf(d[i]) < INFINITY) return (long long)i;  // (to_f16's threshold)
+    return -1;
+}
 
 // fp32 -> three bf16 pieces, hi + mid + lo ~= x to 24 bits (each piece rounded to nearest even from what the previous ones left: the
 // pieces may differ in sign).  The split-product conv path (VNECT_FP32_SPLIT) stores its WEIGHTS this way; the kernel splits the

@@ -211,6 +211,20 @@ void hp_pack_split3(const float* wp, int Npad, int K, uint16_t* out)
 }
 uint16_t hp_to_bf16(float f) { return plan::to_bf16(f); }
 float hp_from_bf16(uint16_t b) { return plan::from_bf16(b); }
+uint16_t hp_to_f16(float f) { return plan::to_f16(f); }
+float hp_from_f16(uint16_t b) { return plan::from_f16(b); }
+// whole arrays: packed weights -> the 16-bit elements the runtime uploads (f16 = 0: bf16, 1: fp16), and fp16 -> fp32
+void hp_to_16(const float* v, int64_t n, int f16, uint16_t* out)
+{
+    std::vector<uint16_t> o;
+    plan::to_16(std::vector<float>(v, v + n), f16 != 0, o);
+    memcpy(out, o.data(), o.size() * 2);
+}
+void hp_from_f16_array(const uint16_t* b, int64_t n, float* out)
+{
+    for (int64_t i = 0; i < n; i++) out[i] = plan::from_f16(b[i]);
+}
+long long hp_first_f16_overflow(const float* d, int64_t n) { return plan::first_f16_overflow(d, (size_t)n); }
 
 // ---- arena, tiles, stem ----
 uint64_t hp_arena(const int* first, const int* last, const uint64_t* need, int n, uint64_t* off)

@@ -7,6 +7,10 @@
 
 namespace vnect {
 
+// element format of the activations and the packed weights: what the small launchers' `el` argument takes (the conv and stem launches
+// say it as bf16 = "16-bit elements" plus f16 = "they are fp16")
+enum { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2 };
+
 constexpr int MAX_TAPS = 16;
 constexpr int ARG_SLABS_MAX = 32;  // upper bound of the arg-max workgroups per joint (post.hip: ARG_SLABS): what the partials' buffer is sized for
 constexpr int PROF_WGS = 512;   // end-stamp slots per launch (two workgroups per CU; a power of two: larger grids wrap around)
@@ -44,6 +48,7 @@ struct ConvArgs {
     int pixmode;          // conv1: a chunk row is 8 consecutive NHWC4 pixels of one input row (bf16: of two rows)
     int bf16;             // operands and activations are bf16 (accumulators, bias, slabs stay fp32)
     int out_f32;          // bf16 path: this layer writes fp32 (the final maps feed the f64 post-processing)
+    int f16;              // with bf16: the 16-bit elements are fp16 (VNECT_FP16), not bf16 -- the same plan, layouts and fused forms
     int tiles_m, tiles_n; // filled by the launcher
     int items;            // work items = tiles_m * tiles_n * nphase * ksplit (launcher; streaming kernel)
     unsigned mg_ks, mg_cpt;  // same for d = ksplit, cpt
@@ -87,7 +92,7 @@ struct ReduceArgs {  // split-K second pass: out = epilogue(sum_ks ws[ks])
     float* out;
     long long npix;
     int Npad, Nvalid, ldc, ldr, ksplit, relu_cols;
-    int bf16, out_f32;
+    int bf16, out_f32, f16;  // (as in ConvArgs)
 };
 
 // Write-through (`sc1`) vector stores for the small kernels between the conv launches: like the conv epilogue's, their output
@@ -119,10 +124,10 @@ bool conv_probes_off();
 const char* post_build_probes();
 bool post_probes_off();
 
-hipError_t launch_pad3to4(const float* in3, void* out4, long long npix, int bf16, hipStream_t st);
-hipError_t launch_strip4to3(const void* in4, float* out3, long long npix, int bf16, hipStream_t st);
-hipError_t launch_maxpool(const void* in, void* out, int S, int H, int W, int C, int Ho, int Wo, int bf16, hipStream_t st);
-hipError_t launch_bone(void* feat, long long npix, int ld, int bf16, hipStream_t st);
+hipError_t launch_pad3to4(const float* in3, void* out4, long long npix, int el, hipStream_t st);  // el: EL_F32 / EL_BF16 / EL_F16
+hipError_t launch_strip4to3(const void* in4, float* out3, long long npix, int el, hipStream_t st);
+hipError_t launch_maxpool(const void* in, void* out, int S, int H, int W, int C, int Ho, int Wo, int el, hipStream_t st);
+hipError_t launch_bone(void* feat, long long npix, int ld, int el, hipStream_t st);
 
 // ---- pre-processing (the table structs live in tables.h) -------------------------------
 struct FrameDyn {     // what does change every frame: passed to the two kernels that need it BY VALUE (kernel arguments),
@@ -136,11 +141,11 @@ struct FrameDyn {     // what does change every frame: passed to the two kernels
     unsigned xseq;
 };
 
-hipError_t launch_pyramid(const FrameParams* fp, FrameDyn dyn, const ScaleTabs* tabs, void* batch4, int S, int scale_base, int bf16, hipStream_t st);
+hipError_t launch_pyramid(const FrameParams* fp, FrameDyn dyn, const ScaleTabs* tabs, void* batch4, int S, int scale_base, int el, hipStream_t st);
 // two streams' frames into one (2 S)-image batch: images 0 .. S-1 from (fp0, dyn0), S .. 2 S-1 from (fp1, dyn1) (vnect_submit_streams)
 constexpr int VNECT_MAX_IMAGES = 8;  // images of one batch at most (= VNECT_MAX_SCALES: the batched plan needs 2 S <= it)
 hipError_t launch_pyramid_streams(const FrameParams* fp0, const FrameParams* fp1, FrameDyn dyn0, FrameDyn dyn1, const ScaleTabs* tabs,
-                                  void* batch4, int S, int bf16, hipStream_t st);
+                                  void* batch4, int S, int el, hipStream_t st);
 
 // vnect_infer: H rows of `row` bytes from device-mapped pinned host memory (`stride` bytes apart) into a resident frame slot, as a kernel
 hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int row, long long stride, const uint8_t* src_end, hipStream_t st);
@@ -171,7 +176,7 @@ struct StemArgs {
     const FrameParams* fp2;
     const uint8_t* frame2;
     long long stride2;
-    int bf16, from_frame;
+    int bf16, f16, from_frame;  // (bf16, f16 as in ConvArgs)
     int dbg;               // tuning only (VNECT_STEM_DBG): 1 = no conv blocks, 2 = no pooling, 4 = no patch (timing breakdowns; wrong results)
     unsigned char row0[STEM_MAXGROUPS + 1];  // first pooled row of every group; row0[groups] = 92
 };

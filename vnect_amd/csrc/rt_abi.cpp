@@ -43,8 +43,8 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: bad config (struct_size mismatch)");
         if (cfg->num_scales < 1 || cfg->num_scales > VNECT_MAX_SCALES)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: num_scales out of range");
-        if (cfg->precision != VNECT_FP32 && cfg->precision != VNECT_BF16 && cfg->precision != VNECT_FP32_SPLIT)
-            return fail(nullptr, VNECT_E_ARG, "vnect_create: precision must be VNECT_FP32, VNECT_BF16 or VNECT_FP32_SPLIT");
+        if (cfg->precision != VNECT_FP32 && cfg->precision != VNECT_BF16 && cfg->precision != VNECT_FP32_SPLIT && cfg->precision != VNECT_FP16)
+            return fail(nullptr, VNECT_E_ARG, "vnect_create: precision must be VNECT_FP32, VNECT_BF16, VNECT_FP32_SPLIT or VNECT_FP16");
         if (cfg->lanes < 0 || cfg->lanes > MAX_LANES)
             return fail(nullptr, VNECT_E_ARG, "vnect_create: lanes must be 0 .. 3");
         if (cfg->exchange != VNECT_XCHG_RCCL && cfg->exchange != VNECT_XCHG_P2P)
@@ -65,7 +65,8 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
         h->cfg = *cfg;
         h->S = cfg->num_scales;
         h->Snet = sharded ? 1 : cfg->num_scales;
-        h->bf16 = cfg->precision == VNECT_BF16;
+        h->bf16 = cfg->precision == VNECT_BF16 || cfg->precision == VNECT_FP16;  // 16-bit elements: the bf16 plan
+        h->f16 = cfg->precision == VNECT_FP16;
         h->x3 = cfg->precision == VNECT_FP32_SPLIT;
         h->sharded = sharded;
         h->keep_activations = cfg->keep_activations != 0;
@@ -211,6 +212,16 @@ int vnect_finalize(vnect_handle* h)
         if (!h) return VNECT_E_ARG;
         if (h->finalized) return fail(h, VNECT_E_STATE, "already finalized");
         if (h->pre_only) return fail(h, VNECT_E_STATE, "vnect_finalize on a preprocess_only handle");
+        if (h->f16) {  // an fp16 handle holds its conv weights as fp16: one that rounds to infinity would poison every frame
+            for (const auto& kv : h->weights) {
+                const std::string& n = kv.first;
+                const bool conv_w = n.size() > 8 && (n.compare(n.size() - 8, 8, "/weights") == 0 || n.compare(n.size() - 7, 7, "/kernel") == 0);
+                const long long i = conv_w ? plan::first_f16_overflow(kv.second.d.data(), kv.second.d.size()) : -1;
+                if (i >= 0)
+                    return fail(h, VNECT_E_ARG, "vnect_finalize: weight " + n + " element " + std::to_string(i) + " = " +
+                                                    std::to_string(kv.second.d[i]) + " is outside the fp16 range (|w| < 65520) of a VNECT_FP16 handle");
+            }
+        }
         HIPCK(h, hipSetDevice(h->cfg.device));
         int rc = finalize_impl(h);
         if (rc) {
@@ -273,7 +284,7 @@ int vnect_forward(vnect_handle* h, const float* batch, int num_images, float* ou
         if (batched) return forward_batch(h, batch, out);
         const long long npix = (long long)h->Snet * BOX * BOX;
         HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
-        HIPCK(h, launch_pad3to4(h->in3, h->tensors[h->t_input4].d, npix, h->bf16, h->st));
+        HIPCK(h, launch_pad3to4(h->in3, h->tensors[h->t_input4].d, npix, h->el(), h->st));
         int rc = run_network(h, false);
         if (rc) return rc;
         const Tensor& t = h->tensors[h->t_out];
@@ -301,7 +312,7 @@ int vnect_preprocess(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t 
         if ((rc = run_pre(h, dyn, false, true))) return rc;
         if (batch_out) {
             const long long npix = (long long)h->Snet * BOX * BOX;
-            HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->bf16, h->st));
+            HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
             HIPCK(h, hipMemcpyAsync(batch_out, h->in3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, h->st));
         }
         HIPCK(h, hipStreamSynchronize(h->st));
@@ -504,10 +515,10 @@ int vnect_read_activation(vnect_handle* h, const char* name, float* out, int64_t
         if (t.esz == 4) {
             HIPCK(h, hipMemcpy2D(out, (size_t)t.C * sizeof(float), t.d, (size_t)t.Cs * sizeof(float), (size_t)t.C * sizeof(float),
                                  npix, hipMemcpyDeviceToHost));
-        } else {  // bf16 activations: fetch raw, widen on the host
+        } else {  // 16-bit activations: fetch raw, widen on the host
             std::vector<uint16_t> raw(npix * t.C);
             HIPCK(h, hipMemcpy2D(raw.data(), (size_t)t.C * 2, t.d, (size_t)t.Cs * 2, (size_t)t.C * 2, npix, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < raw.size(); i++) out[i] = plan::from_bf16(raw[i]);
+            for (size_t i = 0; i < raw.size(); i++) out[i] = h->f16 ? plan::from_f16(raw[i]) : plan::from_bf16(raw[i]);
         }
         return VNECT_OK;
     });

@@ -31,10 +31,10 @@ int run_network(vnect_handle* h, bool timed, bool stem_done)
             if (L.a.ksplit > 1) HIPCK(h, launch_reduce(L.r, h->st));
         } else if (L.op == OP_POOL) {
             const Tensor &i = h->tensors[L.in], &o = h->tensors[L.out];
-            HIPCK(h, launch_maxpool(i.d, o.d, i.S, i.H, i.W, i.Cs, o.H, o.W, h->bf16, h->st));
+            HIPCK(h, launch_maxpool(i.d, o.d, i.S, i.H, i.W, i.Cs, o.H, o.W, h->el(), h->st));
         } else {
             const Tensor& t = h->tensors[L.out];
-            HIPCK(h, launch_bone(t.d, (long long)t.S * t.H * t.W, t.Cs, h->bf16, h->st));
+            HIPCK(h, launch_bone(t.d, (long long)t.S * t.H * t.W, t.Cs, h->el(), h->st));
         }
     }
     return VNECT_OK;
@@ -69,13 +69,13 @@ int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed, bool want_batch)
             return VNECT_OK;
         }
         HIPCK(h, launch_pyramid(h->d_fp, dyn, h->d_stabs, h->tensors[h->t_input4].d, h->Snet,
-                                h->sharded ? h->cfg.pyramid_rank : 0, h->bf16, h->st));
+                                h->sharded ? h->cfg.pyramid_rank : 0, h->el(), h->st));
         a.from_frame = 0;
         HIPCK(h, launch_stem(a, h->st));
         return VNECT_OK;
     }
     HIPCK(h, launch_pyramid(h->d_fp, dyn, h->d_stabs, h->tensors[h->t_input4].d, h->Snet,
-                            h->sharded ? h->cfg.pyramid_rank : 0, h->bf16, h->st));
+                            h->sharded ? h->cfg.pyramid_rank : 0, h->el(), h->st));
     return VNECT_OK;
 }
 
@@ -243,7 +243,7 @@ static int build_twin(vnect_handle* h)
     vnect_handle* t = new vnect_handle();
     h->twins.push_back(t);
     t->is_twin = true;
-    t->cfg = h->cfg, t->S = h->S, t->Snet = h->Snet, t->bf16 = h->bf16, t->keep_activations = false;
+    t->cfg = h->cfg, t->S = h->S, t->Snet = h->Snet, t->bf16 = h->bf16, t->f16 = h->f16, t->keep_activations = false;
     HIPCK(h, hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
     // shared: read-only tables and frames; the filter bank (its users are chained by events)
     t->frames = h->frames, t->d_stabs = h->d_stabs, t->mgeo = h->mgeo, t->d_fb = h->d_fb;
@@ -667,7 +667,7 @@ int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots,
     // gen_input_batch of both frames inside the stem launch (as run_pre does for one frame), or the batch tensor first
     const bool frame_stem = b->stem_mode == 2 && b->stem_frame_ok && fp[0].sq.copy && fp[1].sq.copy;
     if (!frame_stem)
-        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], b->d_stabs, b->tensors[b->t_input4].d, b->S, b->bf16, b->st));
+        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], b->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
     if (b->stem_mode == 2) {
         StemArgs a = b->stem;
         a.prof = timed ? b->d_prof + PROF_SLOTS * b->l_conv1 : nullptr;
@@ -710,7 +710,7 @@ int forward_batch(vnect_handle* h, const float* batch, float* out)
     vnect_handle* b = h->blanes[0];
     const long long npix = (long long)b->Snet * BOX * BOX;
     HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
-    HIPCK(h, launch_pad3to4(h->in3, b->tensors[b->t_input4].d, npix, b->bf16, h->st));
+    HIPCK(h, launch_pad3to4(h->in3, b->tensors[b->t_input4].d, npix, b->el(), h->st));
     int rc = run_network(b, false);
     if (rc) return fail(h, rc, b->err);
     const Tensor& t = b->tensors[b->t_out];

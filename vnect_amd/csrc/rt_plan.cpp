@@ -6,14 +6,12 @@
 namespace vnect {
 namespace rt {
 
-using plan::from_bf16;
-using plan::to_bf16;
-// packed weights: fp32 as is, or converted to bf16 (the device pointer is typed float* either way)
+// packed weights: fp32 as is, or converted to the handle's 16-bit format, bf16 or fp16 (the device pointer is typed float* either way)
 static int upload_weights(vnect_handle* h, float** dst, const std::vector<float>& v)
 {
     if (!h->bf16) return upload(h, dst, v);
-    std::vector<uint16_t> b(v.size());
-    for (size_t i = 0; i < v.size(); i++) b[i] = to_bf16(v[i]);
+    std::vector<uint16_t> b;
+    plan::to_16(v, h->f16, b);
     uint16_t* p = nullptr;
     int rc = upload(h, &p, b);
     *dst = (float*)p;
@@ -405,7 +403,7 @@ void setup_stem(vnect_handle* h)
     memset(&a, 0, sizeof a);
     a.batch = tin.d, a.w = C.w, a.bias = C.bias, a.out = tp.d;
     a.fp = h->d_fp, a.tabs = h->d_stabs;
-    a.S = h->Snet, a.scale_base = h->sharded ? h->cfg.pyramid_rank : 0, a.bf16 = h->bf16;
+    a.S = h->Snet, a.scale_base = h->sharded ? h->cfg.pyramid_rank : 0, a.bf16 = h->bf16, a.f16 = h->f16;
     // a batched plan's stem reads two frames: images 0 .. S-1 from the first stream's, S .. 2 S-1 from the second's (d_fp2)
     a.per_stream = h->batched ? h->S : 0, a.fp2 = h->batched ? h->d_fp2 : nullptr;
     // row groups of 4 and 5 pooled rows (hostplan.h)
@@ -719,6 +717,7 @@ int finalize_impl(vnect_handle* h)
     for (Layer& L : h->layers) {
         if (L.op != OP_CONV) continue;
         ConvArgs& a = L.a;
+        a.f16 = a.bf16 && h->f16;  // (every 16-bit launch of an fp16 handle; its fp32 final maps stay what they are)
         bind_activations(h, L);
         {   // tap byte offsets for the buffer-addressed loads (kernels.h)
             const int esz = a.bf16 ? 2 : 4, nt = a.nphase * a.ntaps;
@@ -747,7 +746,7 @@ int finalize_impl(vnect_handle* h)
             a.slab_pix = (long long)a.S * a.OH * a.OW + 64, q.slab_pix = a.slab_pix;
             q.npix = (long long)a.S * a.OH * a.OW, q.Npad = a.Npad, q.Nvalid = a.Nvalid, q.ldc = a.ldc, q.ldr = a.ldr;
             q.ksplit = a.ksplit, q.relu_cols = a.relu_cols;
-            q.bf16 = a.bf16, q.out_f32 = a.out_f32;
+            q.bf16 = a.bf16, q.out_f32 = a.out_f32, q.f16 = a.f16;
         }
         h->conv_flops += L.flops;
         h->conv_launches += 1;
@@ -771,7 +770,7 @@ static int build_batch_lane(vnect_handle* h, vnect_handle* lane)
     vnect_handle* b = new vnect_handle();
     h->blanes.push_back(b);
     b->is_twin = true, b->batched = true, b->st = lane->st;
-    b->cfg = h->cfg, b->S = h->S, b->Snet = 2 * h->Snet, b->bf16 = h->bf16, b->x3 = h->x3, b->keep_activations = false;
+    b->cfg = h->cfg, b->S = h->S, b->Snet = 2 * h->Snet, b->bf16 = h->bf16, b->f16 = h->f16, b->x3 = h->x3, b->keep_activations = false;
     b->frames = h->frames, b->d_stabs = h->d_stabs, b->mgeo = h->mgeo, b->d_fb = h->d_fb, b->stabs_host = h->stabs_host;
     b->post_merged = true;  // each stream's merge + arg-max + joints as one post_kernel launch (its maps, bank and geometry)
     int rc;

@@ -80,6 +80,9 @@ struct vnect_handle {
     bool pre_only = false;  // vnect_config::preprocess_only: the input batch buffer and the resize tables, nothing else
     bool x3 = false;    // VNECT_FP32_SPLIT: fp32 tensors; the 64x64-tile layers multiply on the bf16 pipe by three-way splits (conv.hip, X3)
     bool bf16 = false;  // VNECT_BF16: bf16 activations + weights, fp32 accumulate; final maps and post-processing stay fp32/f64
+                        // (VNECT_FP16 too: this flag means "16-bit elements" -- the plan, layouts and fused forms key on it alone)
+    bool f16 = false;   // VNECT_FP16: the 16-bit elements are fp16 (IEEE binary16) instead of bf16; everything else is the bf16 handle's
+    int el() const { return bf16 ? (f16 ? EL_F16 : EL_BF16) : EL_F32; }  // the element format the kernel launchers take
     hipStream_t st = nullptr;
     std::map<std::string, HostArray> weights;
     std::vector<Tensor> tensors;

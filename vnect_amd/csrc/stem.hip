@@ -39,6 +39,15 @@ typedef float f32x3 __attribute__((ext_vector_type(3)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// BF: 0 = fp32, 1 = bf16, 2 = fp16 (VNECT_FP16; conv.hip: h16).  One 32x32x16 matrix instruction of the 16-bit forms.
+template <int BF>
+__device__ __forceinline__ f32x16 stem_mfma16(f32x4 a, f32x4 b, f32x16 acc)
+{
+    if constexpr (BF == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+}
 
 constexpr int STEM_CW = 2 * STEM_TW + 1;             // conv columns per tile (47)
 constexpr int STEM_LW = 48;                          // row stride of the tile's conv pixels in M (47 + one dummy): a lane's groups of four
@@ -61,7 +70,7 @@ constexpr int STEM_SCR_LUT = 0, STEM_SCR_ROWS = 1024, STEM_SCR_COLS = STEM_SCR_R
               STEM_SCR_REG = STEM_SCR_MIS + 4 * STEM_REG_ROWS, STEM_SCR_BYTES = STEM_SCR_REG + STEM_REG_ROWS * STEM_REG_PITCH;
 static_assert(STEM_SCR_REG % 16 == 0 && STEM_PH <= 32 && STEM_PW <= 104, "scratch layout");
 
-template <bool BF, bool FRAME = false>
+template <int BF, bool FRAME = false>
 constexpr size_t stem_lds()
 {
     // patch, pooled tile, (FRAME) scratch, and 512 bytes for the PAIR form's table of output-pixel offsets
@@ -90,10 +99,10 @@ __device__ __forceinline__ void stem_prof_end(const StemArgs& a)
     a.prof_end[blockIdx.x] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
 }
 
-template <bool BF, bool FRAME, bool PROF, bool PAIR = false>
+template <int BF, bool FRAME, bool PROF, bool PAIR = false>
 __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
 {
-    typedef typename std::conditional<BF, __bf16, float>::type T;
+    typedef typename std::conditional<BF == 2, _Float16, typename std::conditional<BF == 1, __bf16, float>::type>::type T;
     typedef T tx4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
     T* patch = (T*)smem;                                                     // [PH][PW][4]
@@ -339,7 +348,7 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 if (k + 1 < 16) nxt = rd(k + 1);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cur), __builtin_bit_cast(bf16x8, Bb[k >> 2][k & 3]), acc, 0, 0, 0);
+                acc = stem_mfma16<BF>(cur, Bb[k >> 2][k & 3], acc);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read ...
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // ... then this step's MFMA
                 cur = nxt;
@@ -373,7 +382,7 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 v[e] = __builtin_fmaxf(acc[4 * g4 + e] + bias, 0.f);
-                if constexpr (BF) v[e] = (float)(__bf16)v[e];  // what the stand-alone conv1 stores (round to nearest even), then pools
+                if constexpr (BF) v[e] = (float)(T)v[e];  // what the stand-alone conv1 stores (round to nearest even), then pools
                 if (x0 + e >= STEM_CW || cx0 + x0 + e >= 2 * 92) v[e] = 0.f;  // the dummy column; conv column 184 (the pool's padding)
             }
             if (y < nrow && cy0 + y < 2 * 92 && !(a.dbg & 2)) {
@@ -414,7 +423,8 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
         for (int q = 0; q < NQ; q++) {
             if constexpr (BF) {  // the pooled values are bf16 numbers held as fp32 (rounded before the max): the conversion is exact
                 const f32x4 lo = *(const f32x4*)(pooled + ia * 64 + 16 * q + 8 * hh), hi = *(const f32x4*)(pooled + ia * 64 + 16 * q + 8 * hh + 4);
-                const bf16x8 v = {(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+                typedef T tx8 __attribute__((ext_vector_type(8)));
+                const tx8 v = {(T)lo[0], (T)lo[1], (T)lo[2], (T)lo[3], (T)hi[0], (T)hi[1], (T)hi[2], (T)hi[3]};
                 Af[q] = __builtin_bit_cast(f32x4, v);
             } else
                 Af[q] = *(const f32x4*)(pooled + ia * 64 + 8 * q + 4 * hh);
@@ -436,7 +446,7 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
             // bf16: this wave's output tile in LDS, over the patch / pooled / scratch areas -- every wave has its A fragments in registers,
             // but waves still READING theirs must be past that point before anyone writes here: the barrier below
             constexpr int WT_LD = 168;  // row stride in elements: 336 B, 16-byte aligned, rows 4 banks apart
-            __bf16* const wtile = (__bf16*)smem + wave * (32 * WT_LD);
+            T* const wtile = (T*)smem + wave * (32 * WT_LD);
             f32x4 Bc[NQ], Bn[NQ];
 #pragma unroll
             for (int q = 0; q < NQ; q++) Bc[q] = bp[(cb0 * NQ + q) * 64], Bn[q] = Bc[q];
@@ -457,7 +467,7 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
                     if constexpr (BF) {
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Af[q]), __builtin_bit_cast(bf16x8, Bc[q]), acc, 0, 0, 0);
+                        acc = stem_mfma16<BF>(Af[q], Bc[q], acc);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; e++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Af[q][e], Bc[q][e], acc, 0, 0, 0);
@@ -470,11 +480,11 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
                     // bf16: the block goes to this wave's LDS tile [32 rows][160 columns + pad] and leaves in whole rows below (round 5: as
                     // 16 two-byte stores per lane and block -- 64-byte half lines -- the 16 MB of this GEMM's output took 8.6 us of a
                     // 26-us launch, tools/stem_breakdown.sh; lane pairs exchanging values by DPP for 4-byte stores did not change that)
-                    __bf16* const tl = wtile + (cb - cb0) * 32 + col;
+                    T* const tl = wtile + (cb - cb0) * 32 + col;
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
                         const float v = acc[r] + bias2;
-                        tl[((r & 3) + 8 * (r >> 2) + 4 * hh) * WT_LD] = (__bf16)(first ? __builtin_fmaxf(v, 0.f) : v);
+                        tl[((r & 3) + 8 * (r >> 2) + 4 * hh) * WT_LD] = (T)(first ? __builtin_fmaxf(v, 0.f) : v);
                     }
                 } else {
 #pragma unroll
@@ -529,6 +539,7 @@ hipError_t stem_setup()
         return e;
     STEM_ATTR(false, false, false) STEM_ATTR(false, false, true) STEM_ATTR(false, true, false) STEM_ATTR(false, true, true)
     STEM_ATTR(true, false, false) STEM_ATTR(true, false, true) STEM_ATTR(true, true, false) STEM_ATTR(true, true, true)
+    STEM_ATTR(2, false, false) STEM_ATTR(2, false, true) STEM_ATTR(2, true, false) STEM_ATTR(2, true, true)
 #undef STEM_ATTR
     return hipSuccess;
 }
@@ -554,7 +565,11 @@ hipError_t launch_stem(const StemArgs& a_in, hipStream_t st)
         if (a.pair_w) hipLaunchKernelGGL((stem_kernel<BF, FR, PR, true>), grid, block, (stem_lds<BF, FR>()), st, a);       \
         else hipLaunchKernelGGL((stem_kernel<BF, FR, PR>), grid, block, (stem_lds<BF, FR>()), st, a);                    \
     } while (0)
-    if (a.bf16) {
+    if (a.f16 && !a.bf16) return hipErrorInvalidValue;
+    if (a.f16) {
+        if (a.from_frame) { if (prof) STEM_GO(2, true, true); else STEM_GO(2, true, false); }
+        else { if (prof) STEM_GO(2, false, true); else STEM_GO(2, false, false); }
+    } else if (a.bf16) {
         if (a.from_frame) { if (prof) STEM_GO(true, true, true); else STEM_GO(true, true, false); }
         else { if (prof) STEM_GO(true, false, true); else STEM_GO(true, false, false); }
     } else {

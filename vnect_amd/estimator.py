@@ -16,6 +16,9 @@ import numpy as np
 from . import _native
 from .weights import MASTER_SEED, check_schema, load_weights, synthetic_weights
 
+# VNectEstimator(precision=...) -> vnect_config::precision
+PRECISIONS = {"fp32": _native.FP32, "bf16": _native.BF16, "fp32_split": _native.FP32_SPLIT, "fp16": _native.FP16}
+
 
 class VNectEstimator:
     # class attributes of src/estimator.py:18-25
@@ -37,7 +40,7 @@ class VNectEstimator:
             weights = synthetic_weights(seed)
         else:
             check_schema(weights)
-        self._cfg = dict(device=device, precision={"fp32": _native.FP32, "bf16": _native.BF16, "fp32_split": _native.FP32_SPLIT}[precision],
+        self._cfg = dict(device=device, precision=PRECISIONS[precision],
                          paper_res2c=paper_res2c, use_graph=use_graph,
                          numpy_promotion={"legacy": 0, "nep50": 1}[numpy_promotion], lanes=lanes)
         self._submitted = 0
