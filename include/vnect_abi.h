@@ -185,6 +185,33 @@ int vnect_set_stream_batch(vnect_handle* h, int n);
  * runs the batched plan: a parity aid.) */
 int vnect_submit_streams(vnect_handle* h, int n, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 
+/* ABI v7, additive.  The tracking loop on the device.  The reference's tracking script (run_estimator_ps.py:80-109) crops every frame with
+ * the current box (:88), runs the estimator (src/estimator.py:97-142), shifts the 2-D joints back into frame coordinates (:92-93) and grows
+ * their bounding box into the next crop (:96-107), all on the host: frame t+1's crop waits for frame t's joints.  Here the box lives on the
+ * device: a small kernel behind the joints stage writes the stream's next rect and its crop geometry, so frames of a tracked stream can be
+ * submitted ahead and the host never waits for joints to feed the next frame.  Results are bit-identical to that loop over vnect_infer.
+ *
+ * vnect_track_begin: stream `stream` tracks (H, W) frames from now on, starting at rect4 = (x, y, w, h) -- NULL: the whole frame.  A rect
+ * narrower or lower than one pixel stands for the whole frame (:85-86's fallback); any other rect must start inside the frame (VNECT_E_ARG
+ * otherwise), and one that runs past its far edges crops what the loop's numpy slicing crops (:88) and is reported as given.
+ * The stream's filters are not reset.  VNECT_E_STATE while frames of the stream are in flight; VNECT_E_ARG on a pyramid-sharded handle
+ * or one with vnect_set_stream_batch(h, 2).
+ * vnect_submit_tracked: the next frame, the WHOLE (H, W) frame in a resident slot (vnect_upload_frame); the device crops it.
+ * vnect_submit_tracked_pinned: the same from pinned buffer buffer_index (vnect_frame_buffer; rows row_stride bytes apart): only the crop's
+ * rows cross PCIe.  The buffer is read when the frame runs: rewrite it only after that frame has been collected.
+ * vnect_collect_tracked: the oldest frame in flight, as vnect_collect_stream, with joints_2d in FRAME coordinates and the rect the frame was
+ * cropped with; an untracked frame gives its usual joints and rect4 = (-1, -1, -1, -1).  vnect_collect / vnect_collect_stream return a
+ * tracked frame's joints in frame coordinates too.  A crop squarify refuses (src/utils.py:82-120 raises for it) fails its frame with
+ * VNECT_E_ARG and vnect_infer's message; the frame's filters do not advance and its timestamps do not count (as a refusal of vnect_infer
+ * commits none), later frames of the stream already in flight fail with VNECT_E_STATE, and so does every submit on the stream until the
+ * next vnect_track_begin.
+ * vnect_track_box: the rect of the stream's next tracked frame (waits for the stream's frames in flight). */
+int vnect_track_begin(vnect_handle* h, int stream, int H, int W, const int32_t* rect4);
+int vnect_submit_tracked(vnect_handle* h, int stream, int slot, double t2d, double t3d);
+int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, int64_t row_stride, double t2d, double t3d);
+int vnect_collect_tracked(vnect_handle* h, int32_t* stream_out, double* joints_2d, float* joints_3d, int32_t* rect4);
+int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4);
+
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
  * per call, :84).  Values travel as float64; values_are_f32 = 1 says they are numpy float32 scalars -- what the reference

@@ -88,6 +88,11 @@ SYMBOLS = {
     "vnect_comm_library": (C.c_int, [C.c_char_p, C.c_int, _i32p]),
     "vnect_comm_p2p_export": (C.c_int, [_H, C.c_void_p]),
     "vnect_comm_p2p_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "vnect_track_begin": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _i32p]),
+    "vnect_submit_tracked": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "vnect_submit_tracked_pinned": (C.c_int, [_H, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double]),
+    "vnect_collect_tracked": (C.c_int, [_H, _i32p, _f64p, _f32p, _i32p]),
+    "vnect_track_box": (C.c_int, [_H, C.c_int, _i32p]),
 }
 
 
@@ -309,6 +314,35 @@ class Handle:
             self.upload_frame(slot, img)
         self.submit_streams(list(streams)[:len(frames)], list(slots)[:len(frames)], t2d, t3d)
         return [self.collect_stream()[1:] for _ in frames]
+
+    # -- tracking on the device (vnect_track_begin ...): runner.track's crop box kept on the GPU -------------------------------------
+    def track_begin(self, stream, H, W, rect=None):
+        """Stream `stream` tracks (H, W) frames from now on, starting at rect (x, y, w, h); None: the whole frame."""
+        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
+        self._ck(lib().vnect_track_begin(self._h, stream, int(H), int(W), None if r is None else _ptr(r, _i32p)))
+
+    def submit_tracked(self, stream, slot, t2d, t3d):
+        """The stream's next frame, the whole frame in resident slot `slot`; the device crops it with the stream's box."""
+        self._ck(lib().vnect_submit_tracked(self._h, stream, slot, t2d, t3d))
+
+    def submit_tracked_pinned(self, stream, index, row_stride, t2d, t3d):
+        """The stream's next frame, the whole frame in pinned buffer `index` (frame_buffer): only the crop's rows cross PCIe."""
+        self._ck(lib().vnect_submit_tracked_pinned(self._h, stream, index, int(row_stride), t2d, t3d))
+
+    def collect_tracked(self):
+        """(stream, joints_2d in frame coordinates, joints_3d, rect_used) of the oldest frame in flight (rect_used [-1] * 4: untracked)."""
+        j2, j3, p2, p3, _, _ = self._results()
+        s, r = C.c_int32(-1), (C.c_int32 * 4)()
+        rc = lib().vnect_collect_tracked(self._h, C.byref(s), p2, p3, r)
+        if rc:
+            self._ck(rc)
+        return s.value, j2.copy(), j3.copy(), list(r)
+
+    def track_box(self, stream):
+        """The rect (x, y, w, h) the stream's next tracked frame will be cropped with."""
+        r = (C.c_int32 * 4)()
+        self._ck(lib().vnect_track_box(self._h, stream, r))
+        return list(r)
 
     def batch_layers(self):
         """The batched plan's layers (vnect_get_batch_layer_info), in the layout of layers()."""

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "axis.h"
+#include "crop.h"
 #include "hostplan.h"
 
 using namespace vnect;
@@ -271,6 +272,40 @@ int hp_stem_frame_fits(const double* scales, int S, int scale_base, int bf16)
     uint8_t row0[STEM_MAXGROUPS + 1];
     const int G = plan::stem_groups(S, row0);
     return plan::stem_frame_fits(st[0], S, scale_base, G, row0, bf16 != 0) ? 1 : 0;
+}
+
+// ---- the tracking loop's crop arithmetic (crop.h), shared with the device (track.hip) ----
+int hp_frame_params_size(void) { return (int)sizeof(FrameParams); }
+// hostplan.h's squarify: the FrameParams bytes the host uploads for an untracked frame.  Returns 0, or -1 with the message in err.
+int hp_squarify_bytes(int H, int W, uint8_t* out, char* err, int errlen)
+{
+    std::vector<FrameParams> fp(1);
+    memset(&fp[0], 0, sizeof(FrameParams));
+    if (const char* why = plan::squarify(H, W, &fp[0])) {
+        snprintf(err, errlen, "%s", why);
+        return -1;
+    }
+    memcpy(out, &fp[0], sizeof(FrameParams));
+    return 0;
+}
+// crop.h's entry-by-entry builder (what the device runs): the status code, its message, and the bytes
+int hp_crop_squarify_bytes(int H, int W, uint8_t* out, char* err, int errlen)
+{
+    std::vector<FrameParams> fp(1);
+    const int status = crop_squarify(H, W, &fp[0]);
+    if (status) snprintf(err, errlen, "%s", crop_refusal(status));
+    memcpy(out, &fp[0], sizeof(FrameParams));
+    return status;
+}
+// runner.bbox_update on n joint sets (n x 21 x 2 doubles [row, col]) -> n x 4 ints (x, y, w, h); fallback != 0: then runner.track's fallback
+void hp_box_update(const double* j2, int n, int W, int H, int fallback, int32_t* rects)
+{
+    for (int i = 0; i < n; i++) {
+        int r[4];
+        box_update(j2 + (size_t)i * NJ * 2, W, H, r);
+        if (fallback) box_fallback(W, H, r);
+        for (int k = 0; k < 4; k++) rects[(size_t)i * 4 + k] = r[k];
+    }
 }
 
 }  // extern "C"

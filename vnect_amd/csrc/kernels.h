@@ -240,6 +240,36 @@ struct XchgArgs {
 };
 hipError_t launch_exchange(const XchgArgs& a, hipStream_t st);
 
+// ---- the tracking loop on the device (track.hip; vnect_track_begin / vnect_submit_tracked) ------------------------------------
+// run_estimator_ps.py:80-109 (runner.track) keeps the crop box on the host: frame t+1's crop comes from frame t's joints.  Here it stays
+// on the device: a box kernel behind the joints stage turns a frame's joints into the next crop and its squarify geometry (crop.h).
+struct TrackState {   // per video stream, device memory: the crop of the stream's NEXT tracked frame
+    int x, y, w, h;   // the crop (after the fallback to the whole frame, clipped to the frame)
+    int uw, uh;       // the rect's extent as reported (rect_used): an initial rect past the frame's far edges is cropped the way numpy
+                      // slicing crops it (runner.track), but reported as given
+    int H, W;         // the frame's size
+    int status;       // SQ_OK, or why squarify refuses the crop (crop.h); sticky until vnect_track_begin
+    unsigned fail;    // FrameDyn::xfail word: the number of the tracked frame whose joints stage is to be skipped
+    FrameParams fp;   // the crop's squarify geometry
+};
+struct TrackOut {     // per result-ring slot, device-mapped pinned host memory
+    int rect[4];      // the rect the frame was cropped with
+    int status;       // SQ_OK, or the refusal of that crop (the frame's joints stage was skipped)
+    int pad_;
+};
+// the pyramid of a tracked frame: the crop origin (and, `packed`, the row stride of a crop copied out of a pinned buffer) from the
+// stream's state instead of FrameDyn::frame; geometry ts->fp
+hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, const ScaleTabs* tabs, void* batch4, int S, int el, hipStream_t st);
+// the crop's rows (rect from the stream's state) out of a pinned frame of H rows into `dst`, packed; grid sized for the whole frame
+hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev, uint8_t* dst, int H, int W, long long stride, const uint8_t* src_end,
+                                   hipStream_t st);
+// behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
+// its geometry to `ts`
+hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st);
+// post_kernel with the same box stage as its tail (the last arriver's joints stage hands its frame-coordinate joints over in LDS)
+hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st);
+
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);
 

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "pyramid.h"
 #include "axis.h"  // axis_x_at / axis_y_at: one entry of cv2.resize's per-axis tables, computed where it is used
+#include "trackbox.h"  // the box stage of a tracked frame (post_kernel<.., true>)
 
 #include <stddef.h>
 
@@ -94,10 +95,11 @@ __global__ __launch_bounds__(256) void frame_copy_kernel(const uint8_t* __restri
 // assembles the destination dword; a wave writes 63 destination dwords.  The destination rows are packed (row bytes apart), so a row
 // starts at byte (y * row) & 3 of the destination's dword grid: interior dwords are whole stores, the first / last dword of a row is
 // shared with its neighbours and written byte by byte.  grid = (ceil(dwords per row / 252), H), 256 threads.
-__global__ __launch_bounds__(256) void frame_copy_rows_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int row, long long stride,
-                                                              const uint8_t* src_end)
+// (the body is shared with frame_copy_track_kernel below: row y of src -> row y of dst)
+__device__ __forceinline__ void copy_row_any_align(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int y, int row, long long stride,
+                                                   const uint8_t* src_end)
 {
-    const int y = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uintptr_t s = (uintptr_t)src + (unsigned long long)y * (unsigned long long)stride;  // first source byte of the row
     const uintptr_t d = (uintptr_t)dst + (unsigned long long)y * (unsigned long long)row;      // first destination byte
     const uintptr_t d0 = d & ~(uintptr_t)3;                                                    // the destination's dword grid
@@ -126,6 +128,29 @@ __global__ __launch_bounds__(256) void frame_copy_rows_kernel(const uint8_t* __r
         for (int j = 0; j < 4; j++)
             if (b0 + j >= 0 && b0 + j < row) ((uint8_t*)d0)[4 * k + j] = (uint8_t)(v >> (8 * j));
     }
+}
+__global__ __launch_bounds__(256) void frame_copy_rows_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int row, long long stride,
+                                                              const uint8_t* src_end)
+{
+    copy_row_any_align(src, dst, blockIdx.y, row, stride, src_end);
+}
+// A tracked frame from a pinned buffer (vnect_submit_tracked_pinned): only the crop's rows cross PCIe, as when the host cuts the crop
+// itself -- but the crop (x, y, w, h) is the stream's state on the device, written by the previous frame's box kernel (track.hip).  The
+// grid covers the largest crop, the whole frame; workgroups past the crop leave at once.
+__global__ __launch_bounds__(256) void frame_copy_track_kernel(const TrackState* __restrict__ ts, const uint8_t* __restrict__ src,
+                                                               uint8_t* __restrict__ dst, long long stride, const uint8_t* src_end)
+{
+    const int x0 = ts->x, y0 = ts->y, w = ts->w, h = ts->h;
+    if ((int)blockIdx.y >= h || (int)blockIdx.x * 252 >= ((3 + 3 * w + 3) >> 2)) return;
+    copy_row_any_align(src + (long long)y0 * stride + 3LL * x0, dst, blockIdx.y, 3 * w, stride, src_end);
+}
+hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev, uint8_t* dst, int H, int W, long long stride, const uint8_t* src_end,
+                                   hipStream_t st)
+{
+    if (H < 1 || H > 65535 || W < 1) return hipErrorInvalidValue;
+    const int ndw_max = (3 + 3 * W + 3) >> 2;
+    hipLaunchKernelGGL(frame_copy_track_kernel, dim3((unsigned)((ndw_max + 251) / 252), (unsigned)H), dim3(256), 0, st, ts, src_dev, dst, stride, src_end);
+    return hipGetLastError();
 }
 // `src_end`: end of the pinned buffer `src_dev` lies in (device address; only the any-alignment form reads it)
 hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int row, long long stride, const uint8_t* src_end, hipStream_t st)
@@ -501,10 +526,13 @@ __device__ __forceinline__ WideRole wide_role()
     r.j3 = (u >= 0 && u < NJ * 3) ? u / 3 : 0, r.k3 = (u >= 0 && u < NJ * 3) ? u - 3 * r.j3 : 0;
     return r;
 }
-template <int SMAX>
+// TRACK: a tracked frame -- the 2-D joints are written in FRAME coordinates (+ the crop origin `shift`, [row, col]; run_estimator_ps.py:92-93)
+// and also left in LDS (`jf`) for the box stage behind this one
+template <int SMAX, bool TRACK = false>
 __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const float* __restrict__ maps, const MergeGeo& geo, FilterBank* fb,
                                                   Filt& f2, Filt& f3, const OefPrep& pr2, const OefPrep& pr3, double scaler, double off,
-                                                  const FrameDyn& dyn, int nep50, JointsOut* __restrict__ out)
+                                                  const FrameDyn& dyn, int nep50, JointsOut* __restrict__ out, const int* shift = nullptr,
+                                                  double* jf = nullptr)
 {
     __shared__ double c2[NJ * 2];
     __shared__ double mc[NJ * 3 * 4];
@@ -564,7 +592,15 @@ __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const 
         out->j3d[u] = oef_f32_fin(f3, pr3, d, dyn.t3d, nep50);
         fb->f3[ro.j3][ro.k3] = f3;
     }
-    if (t < NJ * 2) out->j2d[t] = (c2[t] - off) / scaler;
+    if (t < NJ * 2) {
+        if constexpr (TRACK) {
+            const double v = (c2[t] - off) / scaler + (double)shift[t & 1];
+            out->j2d[t] = v;
+            jf[t] = v;
+        } else {
+            out->j2d[t] = (c2[t] - off) / scaler;
+        }
+    }
     if (t == 0) out->status = 0;
 }
 
@@ -583,10 +619,13 @@ __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const 
 // joints stage -- the filter banks do not advance on stale maps -- and reports status 1.
 // Round 5: the joints stage runs on all six waves of the last arriver (joints_stage_wide), and the value-independent half of the filter
 // steps is computed here, in every workgroup, between the partial's store and the wait for it.
-template <int SMAX>
+// TRACK (a tracked frame, launch_post_track): fp is the stream's TrackState's, and the last arriver runs the box stage (trackbox.h) behind the
+// joints stage -- the joints it needs are in its LDS, not in the result ring slot in host memory.
+template <int SMAX, bool TRACK = false>
 __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restrict__ maps, const MergeGeo geo, ArgPartial* part, unsigned* ticket,
                                                            FilterBank* fb, const FrameParams* __restrict__ fp, const FrameDyn dyn,
-                                                           int nep50, JointsOut* __restrict__ out)
+                                                           int nep50, JointsOut* __restrict__ out, TrackState* ts = nullptr,
+                                                           TrackOut* tout = nullptr)
 {
     __shared__ int last;
     if (POST_DBG == 4) return;
@@ -594,6 +633,9 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
     const WideRole ro = wide_role();
     Filt f2 = fb->f2[ro.j2][ro.k2], f3 = fb->f3[ro.j3][ro.k3];
     const double scaler = fp->scaler, off = ro.k2 == 0 ? (double)fp->offy : (double)fp->offx;
+    TrackNow c{};
+    if constexpr (TRACK) c = track_now(ts);  // (with the filters: the last arriver starts no round trip for it; the box stage writes the
+                                             // state only behind the barriers of its own workgroup, and no other workgroup uses it)
     argmax_body<SMAX>(maps, geo, part);
     const OefPrep pr2 = oef_prep(f2, dyn.t2d), pr3 = oef_prep(f3, dyn.t3d);  // (thread 0: behind its partial's stores, in front of the wait for them)
     if (threadIdx.x == 0) {
@@ -604,17 +646,38 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
     }
     __syncthreads();  // the other waves of the last arriver load the partials (sc1) only behind this barrier
     if (!last || (POST_DBG >= 1 && POST_DBG <= 3)) return;
-    if (dyn.xfail && __hip_atomic_load(dyn.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == dyn.xseq) {
-        if (threadIdx.x == 0) out->status = 1;  // the exchange of THIS frame timed out: stale maps, leave the filters alone
-        return;
+    if constexpr (TRACK) {
+        if (c.status != SQ_OK) {  // this frame's crop was refused (dyn.xfail names it): no joints stage, the stream stays stopped
+            if (threadIdx.x == 0) out->status = 1;
+            track_refused(ts, c, tout, dyn.xseq);
+            return;
+        }
+        __shared__ double jf[NJ * 2];
+        const int shift[2] = {c.y, c.x};
+        joints_stage_wide<SMAX, true>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out, shift, jf);
+        __syncthreads();
+        track_box_stage(ts, c, jf, tout, dyn.xseq);
+    } else {
+        if (dyn.xfail && __hip_atomic_load(dyn.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == dyn.xseq) {
+            if (threadIdx.x == 0) out->status = 1;  // the exchange of THIS frame timed out: stale maps, leave the filters alone
+            return;
+        }
+        joints_stage_wide<SMAX>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out);
     }
-    joints_stage_wide<SMAX>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out);
 }
 hipError_t launch_post(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, const FrameParams* fp,
                        FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st)
 {
     if (geo.S <= 3) hipLaunchKernelGGL(post_kernel<3>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out);
     else hipLaunchKernelGGL(post_kernel<VNECT_MAX_S>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out);
+    return hipGetLastError();
+}
+hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st)
+{
+    const FrameParams* fp = &ts->fp;
+    if (geo.S <= 3) hipLaunchKernelGGL((post_kernel<3, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, ts, tout);
+    else hipLaunchKernelGGL((post_kernel<VNECT_MAX_S, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, ts, tout);
     return hipGetLastError();
 }
 hipError_t launch_joints(const ArgPartial* part, const float* maps, MergeGeo geo, FilterBank* fb, const FrameParams* fp, FrameDyn dyn,

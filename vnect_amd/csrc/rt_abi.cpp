@@ -94,6 +94,12 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
         HIPCK(h, hipMemset(h->d_ticket, 0, 4 * sizeof(unsigned)));
         h->post_merged = getenv("VNECT_NO_POST_MERGE") == nullptr;
         if (!pre && (rc = dev_alloc(h, &h->d_fb, VNECT_MAX_STREAMS))) return rc;
+        if (!pre && (rc = dev_alloc(h, &h->d_track, VNECT_MAX_STREAMS))) return rc;
+        if (!pre) {
+            HIPCK(h, hipHostMalloc((void**)&h->h_tout, RING * sizeof(TrackOut), hipHostMallocMapped | hipHostMallocCoherent));
+            memset(h->h_tout, 0, RING * sizeof(TrackOut));
+            HIPCK(h, hipHostGetDevicePointer((void**)&h->h_tout_dev, h->h_tout, 0));
+        }
         if ((rc = dev_alloc(h, &h->in3, (size_t)(pre ? h->Snet : VNECT_MAX_SCALES) * BOX * BOX * 3))) return rc;
         if (!pre && (rc = dev_alloc(h, &h->gather, (size_t)VNECT_MAX_SCALES * HM * HM * MAPC))) return rc;
         for (int i = 0; i < RING; i++) {
@@ -177,6 +183,7 @@ void vnect_destroy(vnect_handle* h)
     for (int r = 0; r < VNECT_MAX_SCALES; r++)
         if (h->xopened[r] && h->xpeer[r]) hipIpcCloseMemHandle(h->xpeer[r]);
     if (h->h_xstatus) hipHostFree(h->h_xstatus);
+    if (h->h_tout) hipHostFree(h->h_tout);
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
@@ -624,6 +631,84 @@ int vnect_submit_streams(vnect_handle* h, int n, const int32_t* streams, const i
             return enqueue_frame(h, slots[0], t2d[0], t3d[0], &ring, streams[0]);
         }
         return enqueue_batch(h, streams, slots, t2d, t3d);
+    });
+}
+
+// ---- tracking on the device (ABI v7, additive) ---------------------------------------------------------------------------------------
+int vnect_track_begin(vnect_handle* h, int stream, int H, int W, const int32_t* rect4)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a pyramid-sharded handle is not supported");
+        if (h->stream_batch == 2 || !h->blanes.empty())
+            return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
+        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_track_begin before vnect_finalize");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return track_begin_impl(h, stream, H, W, rect4);
+    });
+}
+
+static int tracked_ok(vnect_handle* h, int stream)
+{
+    if (!h->finalized) return fail(h, VNECT_E_STATE, "inference before vnect_finalize");
+    if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+    if (!h->track_on[stream]) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
+    if (h->track_stopped[stream]) return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
+    return VNECT_OK;
+}
+
+int vnect_submit_tracked(vnect_handle* h, int stream, int slot, double t2d, double t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = tracked_ok(h, stream);
+        if (rc) return rc;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        TrackedSrc tk;
+        int ring;
+        return enqueue_frame(h, slot, t2d, t3d, &ring, stream, &tk);
+    });
+}
+
+int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, int64_t row_stride, double t2d, double t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = tracked_ok(h, stream);
+        if (rc) return rc;
+        if (buffer_index < 0 || buffer_index > 1 || !h->stage[buffer_index]) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: no such pinned buffer (vnect_frame_buffer)");
+        const int H = h->track_H[stream], W = h->track_W[stream];
+        if (row_stride < (int64_t)W * 3 || (size_t)(H - 1) * (size_t)row_stride + (size_t)W * 3 > h->stage_cap[buffer_index])
+            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: the frame does not fit the pinned buffer at this row stride");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        TrackedSrc tk;
+        tk.pinned_dev = h->stage_dev[buffer_index], tk.pinned_end = h->stage_dev[buffer_index] + h->stage_cap[buffer_index], tk.stride = row_stride;
+        int ring;
+        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+    });
+}
+
+int vnect_collect_tracked(vnect_handle* h, int32_t* stream_out, double* j2, float* j3, int32_t* rect4)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return collect_impl(h, j2, j3, stream_out, rect4);
+    });
+}
+
+int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !rect4) return VNECT_E_ARG;
+        if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+        if (!h->track_on[stream]) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        if (h->stream_seq[stream] >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->done[h->stream_seq[stream] % RING]));
+        std::vector<TrackState> ts(1);
+        HIPCK(h, hipMemcpy(&ts[0], h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
+        rect4[0] = ts[0].x, rect4[1] = ts[0].y, rect4[2] = ts[0].uw, rect4[3] = ts[0].uh;
+        return VNECT_OK;
     });
 }
 

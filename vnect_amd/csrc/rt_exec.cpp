@@ -88,18 +88,37 @@ int run_argmax(vnect_handle* h)
 }
 
 // filters + read-off; results go straight to `out` (a device-mapped pinned host slot)
-int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream)
+int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
 {
     const float* maps = h->sharded ? h->gather : h->tensors[h->t_out].d;
-    HIPCK(h, launch_joints(h->d_part, maps, h->mgeo, h->d_fb + stream, h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
+    HIPCK(h, launch_joints(h->d_part, maps, h->mgeo, h->d_fb + stream, fp ? fp : h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
     return VNECT_OK;
 }
 
 // both in one launch (post.hip: post_kernel): takes the frame's arguments by value, so it runs behind the graph, not inside it
-int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream)
+int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
 {
     const float* maps = h->sharded ? h->gather : h->tensors[h->t_out].d;
-    HIPCK(h, launch_post(maps, h->mgeo, h->d_part, h->d_ticket, h->d_fb + stream, h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
+    HIPCK(h, launch_post(maps, h->mgeo, h->d_part, h->d_ticket, h->d_fb + stream, fp ? fp : h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
+    return VNECT_OK;
+}
+
+// gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the pinned frame when
+// the frame lies in one), the pyramid from it, and on a stem_mode 2 lane the stem from the batch tensor (the host does not know whether
+// the crop's squarify step is a copy, which the stem's frame form needs; the results are the same bit for bit)
+static int run_pre_tracked(vnect_handle* h, vnect_handle* L, int stream, const FrameDyn& dyn, const TrackedSrc& tk, bool timed)
+{
+    TrackState* ts = h->d_track + stream;
+    if (tk.pinned_dev)
+        HIPCK(h, launch_frame_copy_track(ts, tk.pinned_dev, h->track_buf[stream], h->track_H[stream], h->track_W[stream], tk.stride, tk.pinned_end, L->st));
+    HIPCK(h, launch_pyramid_track(ts, dyn, tk.pinned_dev != nullptr, L->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
+    if (L->stem_mode == 2) {
+        StemArgs a = L->stem;
+        a.prof = timed ? L->d_prof + PROF_SLOTS * L->l_conv1 : nullptr;
+        a.prof_end = timed ? L->d_prof_end + (size_t)PROF_WGS * L->l_conv1 : nullptr;
+        a.from_frame = 0;
+        HIPCK(h, launch_stem(a, L->st));
+    }
     return VNECT_OK;
 }
 
@@ -301,27 +320,34 @@ static vnect_handle* pick_lane(vnect_handle* h, bool timed)
     return h;
 }
 
-// enqueue one frame from a resident slot; results land in h_out[ring]
-int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream)
+// enqueue one frame from a resident slot; results land in h_out[ring].  `tk`: a tracked frame (vnect_submit_tracked*) -- its crop and
+// geometry are the stream's state on the device, the frame is the whole one (in `slot`, or in a pinned buffer: then slot is -1)
+int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream, const TrackedSrc* tk)
 {
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
     if (stream != 0 && h->sharded) return fail(h, VNECT_E_ARG, "a pyramid-sharded handle serves one stream");
-    if (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0)
+    if (!(tk && tk->pinned_dev) && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0))
         return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+    if (tk && !tk->pinned_dev && (h->slots[slot].H != h->track_H[stream] || h->slots[slot].W != h->track_W[stream]))
+        return fail(h, VNECT_E_ARG, "the slot's frame is not of the size vnect_track_begin gave for this stream");
     if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
     if (h->sharded && !comm_ready(h))  // refuse before any filter / timestamp state changes
         return fail(h, VNECT_E_STATE, "pyramid-sharded handle: call vnect_comm_init / vnect_comm_p2p_init before inference");
-    const auto& si = h->slots[slot];
     FrameParams fp;
-    int rc = squarify_params(h, si.H, si.W, &fp);
+    int rc = tk ? VNECT_OK : squarify_params(h, h->slots[slot].H, h->slots[slot].W, &fp);
     if (rc) return rc;
     rc = check_time(h, t2d, t3d, stream);
     if (rc) return rc;
     const int ring = (int)(h->seq_submit % RING);
     FrameDyn dyn{};
     dyn.t2d = t2d, dyn.t3d = t3d;
-    dyn.row_stride = si.stride;
-    dyn.frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+    if (tk && tk->pinned_dev) {
+        dyn.frame = h->track_buf[stream];  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
+    } else {
+        dyn.row_stride = h->slots[slot].stride;
+        dyn.frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+    }
+    if (tk) dyn.xfail = &h->d_track[stream].fail, dyn.xseq = h->track_seq[stream];  // a refused crop skips the joints stage
     const bool timed = h->profiling;
     // Lane: the first whose last frame has been collected (lane 0 when nothing is in flight).  Frames on different lanes
     // overlap -- the idle CUs between one frame's launches are the other frames' -- and only the post-processing launch of a frame
@@ -329,11 +355,15 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // frame.  Measured (round 3, A/B in one call): 1 388-1 390 frames/s three deep with the merged launch, 1 388-1 389 with the two
     // launches -- ordering the 17-us merged launch instead of the 11-us joints kernel costs nothing measurable.
     vnect_handle* L = pick_lane(h, timed);
-    if ((rc = sync_geometry(L, fp))) return fail(h, rc, L->err);
+    // the stream's previous frame ran on another lane and may still be in flight: the filters are a chain (its post-processing waits
+    // for it), and a tracked frame's crop is that frame's box kernel's output (everything of it waits)
+    const bool after_prev = h->stream_seq[stream] >= (long long)h->seq_collect && h->stream_lane[stream] && h->stream_lane[stream] != L;
+    if (!tk && (rc = sync_geometry(L, fp))) return fail(h, rc, L->err);
+    if (tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->done[h->stream_seq[stream] % RING], 0));
     if (timed) HIPCK(h, hipEventRecord(h->ev[0], L->st));
     {
         RoctxRange r("vnect:gen_input_batch");
-        if ((rc = run_pre(L, dyn, timed))) return fail(h, rc, L->err);
+        if ((rc = tk ? run_pre_tracked(h, L, stream, dyn, *tk, timed) : run_pre(L, dyn, timed))) return fail(h, rc, tk ? h->err : L->err);
     }
     RoctxRange r_net("vnect:conv_stack+merge+argmax");
     // use_graph 2 (auto): a frame submitted while nothing is in flight -- the synchronous pattern -- is launched eagerly (median
@@ -357,18 +387,33 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     if (g_roctx.pop) g_roctx.pop(), g_roctx.push(L->post_merged ? "vnect:merge+argmax+filters+readoff" : "vnect:filters+readoff");  // r_net's pop now closes this range
     // the filters are a chain WITHIN a video stream: this frame's post-processing waits for the stream's previous frame if that one
     // ran on another lane and may still be in flight (frames of other streams are no concern of it)
-    if (h->stream_seq[stream] >= (long long)h->seq_collect && h->stream_lane[stream] && h->stream_lane[stream] != L)
-        HIPCK(h, hipStreamWaitEvent(L->st, h->done[h->stream_seq[stream] % RING], 0));
+    if (!tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->done[h->stream_seq[stream] % RING], 0));
     // writes the ring slot in pinned host memory
-    if ((rc = L->post_merged ? run_post(L, dyn, h->h_out_dev[ring], stream) : run_joints(L, dyn, h->h_out_dev[ring], stream))) return fail(h, rc, L->err);
+    // A tracked frame also turns its joints into frame coordinates and grows the next crop and its geometry (trackbox.h): as the tail of
+    // post_kernel (the default: measured faster, TRACKING.md), or -- the two-launch post-processing, VNECT_TRACK_BOX_LAUNCH=1 (A/B, read per
+    // frame) -- as a launch of its own behind it, which reads the joints back from the result ring slot
+    const bool box_tail = tk && L->post_merged && !getenv("VNECT_TRACK_BOX_LAUNCH");
+    if (box_tail) {
+        const float* maps = L->sharded ? L->gather : L->tensors[L->t_out].d;
+        HIPCK(h, launch_post_track(maps, L->mgeo, L->d_part, L->d_ticket, L->d_fb + stream, h->d_track + stream, dyn, h->cfg.numpy_promotion,
+                                   h->h_out_dev[ring], h->h_tout_dev + ring, L->st));
+    } else {
+        const FrameParams* tfp = tk ? &h->d_track[stream].fp : nullptr;
+        if ((rc = L->post_merged ? run_post(L, dyn, h->h_out_dev[ring], stream, tfp) : run_joints(L, dyn, h->h_out_dev[ring], stream, tfp)))
+            return fail(h, rc, L->err);
+        if (tk) HIPCK(h, launch_track_box(h->d_track + stream, h->h_out_dev[ring], h->h_tout_dev + ring, dyn.xseq, L->st));
+    }
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
     HIPCK(h, hipEventRecord(h->done[ring], L->st));
+    if (tk) h->ring_time[ring] = {h->have2[stream], h->have3[stream], h->last2[stream], h->last3[stream]};  // (a refused crop rolls back)
     commit_time(h, t2d, t3d, stream);  // only now: every launch of the frame has been accepted
     h->stream_seq[stream] = (long long)h->seq_submit, h->stream_lane[stream] = L, h->ring_stream[ring] = stream;
     h->ring_unit[ring] = h->unit_submit++, h->ring_batch[ring] = false, h->ring_prof[ring] = nullptr;
+    h->ring_track[ring] = tk != nullptr;
+    if (tk) h->track_seq[stream]++;
     h->last_lane = L;
     L->lane_seq = (long long)h->seq_submit;
-    h->slots[slot].last_use = (long long)h->seq_submit;
+    if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
     h->seq_submit++;
     *ring_out = ring;
     return VNECT_OK;
@@ -388,7 +433,7 @@ static void read_layer_ms(vnect_handle* b)
     }
 }
 
-int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out)
+int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, int32_t* rect_out)
 {
     if (h->seq_collect == h->seq_submit) return fail(h, VNECT_E_STATE, "nothing in flight");
     const int ring = (int)(h->seq_collect % RING);
@@ -406,9 +451,22 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out)
         return fail(h, VNECT_E_COMM, "pyramid exchange: a peer's maps did not arrive within the bound (ranks out of step?); "
                                      "destroy the handles of every rank and reconnect");
     }
+    if (stream_out) *stream_out = h->ring_stream[ring];
+    if (rect_out)
+        for (int k = 0; k < 4; k++) rect_out[k] = h->ring_track[ring] ? h->h_tout[ring].rect[k] : -1;
+    if (h->ring_track[ring] && h->h_tout[ring].status != SQ_OK) {  // the frame's crop was refused: its joints stage was skipped
+        const int s = h->ring_stream[ring];
+        if (h->track_stopped[s])
+            return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
+        h->track_stopped[s] = true;
+        // vnect_infer's refusal commits no timestamp, and the device's filters did not see this frame (nor the stream's later ones, which
+        // are refused too): the host's last timestamps go back to what they were before it
+        const auto& tb = h->ring_time[ring];
+        h->have2[s] = tb.have2, h->have3[s] = tb.have3, h->last2[s] = tb.last2, h->last3[s] = tb.last3;
+        return fail(h, VNECT_E_ARG, crop_refusal(h->h_tout[ring].status));
+    }
     if (j2) memcpy(j2, h->h_out[ring]->j2d, sizeof(double) * NJ * 2);
     if (j3) memcpy(j3, h->h_out[ring]->j3d, sizeof(float) * NJ * 3);
-    if (stream_out) *stream_out = h->ring_stream[ring];
     if (h->ring_prof[ring]) read_layer_ms(h->ring_prof[ring]), h->ring_prof[ring] = nullptr;
     if (h->profiling && !h->ring_batch[ring]) {
         float frame_ms = 0;
@@ -733,6 +791,51 @@ void destroy_batch_lanes(vnect_handle* h)
         delete b;
     }
     h->blanes.clear();
+}
+
+// ---- tracking on the device (vnect_track_begin) --------------------------------------------------------------------------------------
+// The stream's first crop and its geometry, built here with crop.h (what the box kernel runs on the device for every later frame).
+int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4)
+{
+    if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+    if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a pyramid-sharded handle is not supported");
+    if (!h->blanes.empty()) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
+    if (H < 1 || W < 1 || H > 65532 || (size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes)
+        return fail(h, VNECT_E_ARG, "vnect_track_begin: frame size out of range (1 .. 65532 rows, at most max_frame_bytes)");
+    if (h->stream_seq[stream] >= (long long)h->seq_collect) return fail(h, VNECT_E_STATE, "vnect_track_begin: frames of this stream in flight");
+    int r[4] = {0, 0, W, H};
+    if (rect4) {
+        for (int k = 0; k < 4; k++) r[k] = rect4[k];
+        box_fallback(W, H, r);  // runner.track applies its fallback to the initial rect as well
+        if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H)
+            return fail(h, VNECT_E_ARG, "vnect_track_begin: the rect's origin must lie inside the frame");
+    }
+    // a rect past the frame's far edges crops what numpy slicing crops (frame[y:y + h, x:x + w]) and is reported as given
+    std::vector<TrackState> ts(1);
+    memset(&ts[0], 0, sizeof(TrackState));
+    TrackState& t = ts[0];
+    t.x = r[0], t.y = r[1], t.w = std::min(r[2], W - r[0]), t.h = std::min(r[3], H - r[1]), t.uw = r[2], t.uh = r[3], t.H = H, t.W = W;
+    t.status = crop_squarify(t.h, t.w, &t.fp);
+    t.fail = t.status != SQ_OK ? 1u : 0u;  // (the first tracked frame is number 1)
+    const size_t need = (size_t)H * W * 3 + 16;
+    if (h->track_cap[stream] < need) {  // the crop buffer of pinned frames (the largest crop is the frame)
+        for (vnect_handle* tw : h->twins) HIPCK(h, hipStreamSynchronize(tw->st));
+        HIPCK(h, hipStreamSynchronize(h->st));
+        if (h->track_buf[stream]) {
+            HIPCK(h, hipFree(h->track_buf[stream]));
+            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->track_buf[stream]));
+            h->track_buf[stream] = nullptr, h->track_cap[stream] = 0;
+        }
+        int rc = dev_alloc(h, &h->track_buf[stream], need);
+        if (rc) return rc;
+        h->track_cap[stream] = need;
+    }
+    HIPCK(h, hipMemcpyAsync(h->d_track + stream, &t, sizeof(TrackState), hipMemcpyHostToDevice, h->st));
+    HIPCK(h, hipStreamSynchronize(h->st));
+    h->track_on[stream] = true, h->track_stopped[stream] = false;
+    h->track_H[stream] = H, h->track_W[stream] = W;
+    h->track_seq[stream] = 1;
+    return VNECT_OK;
 }
 
 }  // namespace rt

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/vnect_abi.h"
+#include "crop.h"
 #include "hostplan.h"
 #include "kernels.h"
 
@@ -163,6 +164,19 @@ struct vnect_handle {
     FrameParams* d_fp2 = nullptr;
     FrameParams fp_dev2{};
     bool fp_dev2_valid = false;
+    // tracking on the device (vnect_track_begin; track.hip): per stream the next crop and its geometry on the device, the frame size,
+    // the number the next tracked frame gets (FrameDyn::xseq against TrackState::fail), and whether a refused crop has stopped the stream
+    TrackState* d_track = nullptr;  // [VNECT_MAX_STREAMS]
+    TrackOut* h_tout = nullptr;     // pinned, device-mapped, [RING]: rect_used + status of every tracked frame in flight
+    TrackOut* h_tout_dev = nullptr;
+    bool track_on[VNECT_MAX_STREAMS] = {}, track_stopped[VNECT_MAX_STREAMS] = {};
+    int track_H[VNECT_MAX_STREAMS] = {}, track_W[VNECT_MAX_STREAMS] = {};
+    unsigned track_seq[VNECT_MAX_STREAMS] = {};
+    uint8_t* track_buf[VNECT_MAX_STREAMS] = {};  // a stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
+    size_t track_cap[VNECT_MAX_STREAMS] = {};    // waits for this frame's box kernel, which runs after everything that reads the crop)
+    bool ring_track[RING] = {};
+    struct TimeState { bool have2, have3; double last2, last3; };
+    TimeState ring_time[RING] = {};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
     // cached squarify table
     int sq_H = -1, sq_W = -1;
     FrameParams sq_cache{};
@@ -288,8 +302,8 @@ int run_network(vnect_handle* h, bool timed, bool stem_done = false);
 int sync_geometry(vnect_handle* h, const FrameParams& fp, int which = 0);  // which 1: a batch's second stream (d_fp2)
 int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed = false, bool want_batch = false);
 int run_argmax(vnect_handle* h);
-int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0);
-int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0);
+int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);  // fp: d_fp
+int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);
 int check_time(vnect_handle* h, double t2d, double t3d, int s = 0);
 void commit_time(vnect_handle* h, double t2d, double t3d, int s = 0);
 int reset_filters_impl(vnect_handle* h, int stream = -1);  // -1: every stream
@@ -297,8 +311,15 @@ void roctx_load();
 int build_graph(vnect_handle* h);
 void destroy_twins(vnect_handle* h);
 int build_twins(vnect_handle* h);
-int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0);
-int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr);
+// a tracked frame (vnect_submit_tracked*): the whole frame in a resident slot (pinned_dev == nullptr) or in a pinned buffer
+struct TrackedSrc {
+    const uint8_t* pinned_dev = nullptr;  // the frame as the device addresses it
+    const uint8_t* pinned_end = nullptr;  // end of its pinned buffer
+    long long stride = 0;                 // its row stride
+};
+int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const TrackedSrc* tk = nullptr);
+int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
+int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4);
 int ensure_stage(vnect_handle* h, int i, size_t bytes);
 int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
 int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);

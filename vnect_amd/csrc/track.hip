@@ -1,0 +1,72 @@
+// track.hip -- the tracking loop of run_estimator_ps.py:80-109 (runner.track) on the device: per tracked frame, the pyramid reads the
+// crop the stream's state names, and a box kernel behind the joints stage shifts the 2-D joints into frame coordinates (:92-93), grows
+// their bounding box into the next crop (:96-107) and builds that crop's squarify geometry (utils.img_scale_squarify), so the host never
+// waits for a frame's joints to submit the next frame.  Built with -ffp-contract=off: crop.h's double / float arithmetic rounds like
+// the host's (tests/test_track_cpu.py holds its host build to hostplan.h and runner.bbox_update; tests/test_gpu_track.py holds the
+// device to runner.track, frame by frame, bit for bit).
+#include "kernels.h"
+#include "pyramid.h"
+#include "crop.h"
+#include "trackbox.h"
+
+namespace vnect {
+
+typedef float f32x4t __attribute__((ext_vector_type(4)));
+
+// pyramid_kernel (post.hip) for a tracked frame: the same pixels, the crop taken from the stream's state -- at (x, y) of the whole frame
+// in a resident slot, or (packed) the crop's own rows, 3 w bytes apart, as frame_copy_track_kernel left them
+template <typename T>
+__global__ void pyramid_track_kernel(const TrackState* __restrict__ ts, const FrameDyn dyn, int packed, const ScaleTabs* __restrict__ tabs,
+                                     T* __restrict__ batch4)
+{
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, s = blockIdx.z;
+    if (x >= BOX) return;
+    FrameDyn d = dyn;
+    if (packed) d.row_stride = 3LL * ts->w;
+    else d.frame = dyn.frame + (long long)ts->y * dyn.row_stride + 3LL * ts->x;
+    int v[3];
+    pyramid_pixel(&ts->fp, d, tabs, s, y, x, v);
+    f32x4t o = {tabs->lut[v[0]], tabs->lut[v[1]], tabs->lut[v[2]], 0.f};
+    store_wt((tx4*)(batch4 + (((long long)s * BOX + y) * BOX + x) * 4), __builtin_convertvector(o, tx4));
+}
+
+hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, const ScaleTabs* tabs, void* batch4, int S, int el, hipStream_t st)
+{
+    dim3 g((BOX + 127) / 128, BOX, S);
+    if (el == EL_F16) hipLaunchKernelGGL(pyramid_track_kernel<_Float16>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (_Float16*)batch4);
+    else if (el) hipLaunchKernelGGL(pyramid_track_kernel<__bf16>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (__bf16*)batch4);
+    else hipLaunchKernelGGL(pyramid_track_kernel<float>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (float*)batch4);
+    return hipGetLastError();
+}
+
+// The box stage as its own launch, behind post_kernel (or joints_kernel): the joints come back from the result ring slot.  One workgroup, one
+// thread per table entry.  A frame whose own crop was refused (its joints stage skipped, post_kernel's xfail test) keeps the stream
+// stopped: the next frame is refused too, until vnect_track_begin.
+constexpr int BOX_THREADS = 384;
+__global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __restrict__ ts, JointsOut* out, TrackOut* tout, unsigned xseq)
+{
+    __shared__ double j2[NJ * 2];
+    const int t = threadIdx.x;
+    const TrackNow c = track_now(ts);
+    __syncthreads();  // (every thread has read the state before thread 0 overwrites it)
+    if (c.status != SQ_OK) {
+        track_refused(ts, c, tout, xseq);
+        return;
+    }
+    if (t < NJ * 2) {  // run_estimator_ps.py:92-93: joints_2d[:, 0] += y; joints_2d[:, 1] += x  (float64)
+        const double v = out->j2d[t] + (double)((t & 1) ? c.x : c.y);
+        out->j2d[t] = v;
+        j2[t] = v;
+    }
+    __syncthreads();
+    track_box_stage(ts, c, j2, tout, xseq);
+}
+
+hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st)
+{
+    hipLaunchKernelGGL(track_box_kernel, dim3(1), dim3(BOX_THREADS), 0, st, ts, out, tout, xseq);
+    return hipGetLastError();
+}
+
+}  // namespace vnect

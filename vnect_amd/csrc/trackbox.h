@@ -1,0 +1,52 @@
+// trackbox.h -- the box stage of a tracked frame (run_estimator_ps.py:96-107 and the loop's fallback, then the next crop's squarify
+// geometry), as a device function of ONE workgroup of at least BOX threads: the body of track_box_kernel (track.hip, its own launch) and
+// of post_kernel's tracked form (post.hip, the tail of the joints stage).  Arithmetic in crop.h.
+#pragma once
+#include "crop.h"
+#include "kernels.h"
+
+namespace vnect {
+
+struct TrackNow {  // what a frame's box stage reads of the stream's state before it overwrites it
+    int x, y, w, h, uw, uh, H, W, status;
+};
+__device__ __forceinline__ TrackNow track_now(const TrackState* ts)
+{
+    return TrackNow{ts->x, ts->y, ts->w, ts->h, ts->uw, ts->uh, ts->H, ts->W, ts->status};
+}
+// the frame's crop was refused (its joints stage skipped): report it, and keep the stream stopped -- the next frame is skipped too
+__device__ __forceinline__ void track_refused(TrackState* ts, const TrackNow& c, TrackOut* tout, unsigned xseq)
+{
+    if (threadIdx.x == 0) {
+        tout->rect[0] = c.x, tout->rect[1] = c.y, tout->rect[2] = c.uw, tout->rect[3] = c.uh, tout->status = c.status;
+        ts->fail = xseq + 1;
+    }
+}
+// j2: the frame's 21 x 2 joints in FRAME coordinates, in LDS (every thread's write of them behind a barrier).  Every thread calls this.
+__device__ __forceinline__ void track_box_stage(TrackState* ts, const TrackNow& c, const double* j2, TrackOut* tout, unsigned xseq)
+{
+    __shared__ int rect[4];
+    const int t = threadIdx.x;
+    if (t == 0) {
+        int r[4];
+        box_update(j2, c.W, c.H, r);
+        box_fallback(c.W, c.H, r);
+        rect[0] = r[0], rect[1] = r[1], rect[2] = r[2], rect[3] = r[3];
+        tout->rect[0] = c.x, tout->rect[1] = c.y, tout->rect[2] = c.uw, tout->rect[3] = c.uh, tout->status = SQ_OK;
+    }
+    __syncthreads();
+    const int cw = rect[2], ch = rect[3];
+    SqHead g = {};
+    const int status = crop_head(ch, cw, &g);
+    if (status != SQ_OK) g = SqHead{};  // zero tables: the pyramid reads nothing of a refused crop
+    const int inner = t < BOX ? crop_entry(g, cw, ch, t, &ts->fp.sq) : 0;
+    const int xmax = __syncthreads_count(inner);
+    if (t == 0) {
+        crop_fill_head(g, status, ch, cw, xmax, &ts->fp);
+        ts->x = rect[0], ts->y = rect[1], ts->w = cw, ts->h = ch, ts->uw = cw, ts->uh = ch;
+        ts->status = status;
+        ts->fail = status != SQ_OK ? xseq + 1 : 0u;
+    }
+}
+
+}  // namespace vnect

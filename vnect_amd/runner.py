@@ -93,6 +93,116 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None):
         yield joints_2d, joints_3d, used
 
 
+def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0):
+    """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
+
+    Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
+    frame t+1 without waiting for frame t.  ``ahead``: frames submitted before the oldest is collected (0: one at a time; at most
+    ``max(lanes, 2) - 1``).  ``source``: "pinned" -- the frame is written into the handle's pinned buffers and only the crop's rows cross
+    PCIe -- or "resident" (vnect_upload_frame of the whole frame).  ``stream``: which of the handle's video streams (its filter bank).
+    ``rect`` must start inside the frame (``track`` would slice from outside it); one that runs past the far edges is cropped as
+    ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight."""
+    for _, j2, j3, used in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
+                                                None if timestamps is None else [timestamps], ahead, source, [stream]):
+        yield j2, j3, used
+
+
+def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None):
+    """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
+    overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
+    ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None)."""
+    from collections import deque
+
+    from . import _native
+    h = estimator.handle
+    n = len(videos)
+    streams = list(range(n)) if streams is None else [int(s) for s in streams]
+    its = [iter(v) for v in videos]
+    tss = [iter(t) if t is not None else None for t in (timestamps if timestamps is not None else [None] * n)]
+    rects = rects if rects is not None else [None] * n
+    limit = max(int(estimator._cfg.get("lanes", 1)), 2)
+    window = max(0, min(int(ahead), limit - 1)) + 1
+    if source not in ("pinned", "resident"):
+        raise ValueError("source must be 'pinned' or 'resident'")
+
+    def prep(f):
+        f = np.rot90(f, 3) if transpose else f
+        return np.ascontiguousarray(f, dtype=np.uint8)
+
+    pending = [None] * n
+    for i in range(n):                         # the first frame of every video: its size starts the stream's track
+        f = next(its[i], None)
+        if f is not None:
+            pending[i] = prep(f)
+            H, W = pending[i].shape[:2]
+            h.track_begin(streams[i], H, W, rects[i])
+    flat = []
+    if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
+        nbytes = max([p.size for p in pending if p is not None] + [3])
+        flat = [h.frame_buffer(b, 1, (nbytes + 2) // 3).reshape(-1) for b in range(2)]
+    nslots = int(getattr(h, "num_frame_slots", 0) or 4)
+    inflight = deque()                         # (video, submission number)
+    video_of = {s: i for i, s in enumerate(streams)}
+    count = 0
+
+    def collect():
+        inflight.popleft()
+        try:
+            s, j2, j3, used = h.collect_tracked()
+        except _native.VnectError as e:
+            estimator._raise_like_reference(e)
+        return video_of[s], j2, j3, used
+
+    # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
+    # collected and dropped, so the estimator is usable at once afterwards (runner.track leaves nothing in flight either)
+    try:
+        live = [p is not None for p in pending]
+        while any(live):
+            for i in range(n):
+                if not live[i]:
+                    continue
+                frame = pending[i]
+                t2d, t3d = estimator._stamps(next(tss[i]) if tss[i] is not None else None)
+                H, W = frame.shape[:2]
+                try:
+                    if source == "pinned":
+                        b = count % 2                  # a frame captured into this buffer already (the view itself) is not copied
+                        view = flat[b][:H * W * 3].reshape(H, W, 3)
+                        if frame.ctypes.data != view.ctypes.data:
+                            while any(k == count - 2 for _, k in inflight):   # the buffer's last frame must have been copied: collected
+                                yield collect()
+                            view[...] = frame
+                        h.submit_tracked_pinned(streams[i], b, W * 3, t2d, t3d)
+                    else:
+                        slot = count % nslots
+                        h.upload_frame(slot, frame)
+                        h.submit_tracked(streams[i], slot, t2d, t3d)
+                except _native.VnectError as e:           # as in track: every earlier frame's results first
+                    while inflight:
+                        yield collect()
+                    estimator._raise_like_reference(e)
+                inflight.append((i, count))
+                count += 1
+                while len(inflight) >= window:
+                    yield collect()
+                f = next(its[i], None)
+                if f is None:
+                    live[i] = False
+                else:
+                    pending[i] = prep(f)
+                    if pending[i].shape[:2] != (H, W):
+                        raise ValueError("frames of one video must have one size")
+        while inflight:
+            yield collect()
+    finally:
+        while inflight:
+            inflight.popleft()
+            try:
+                h.collect_tracked()
+            except _native.VnectError:
+                pass
+
+
 def synthetic_stream(stream, n_frames, height=368, width=368, smooth=True):
     """Deterministic synthetic video: frame k of stream s has seed 1234 + 1000*s + k."""
     from .parallel import stream_seed
