@@ -178,11 +178,11 @@ def test_two_tracked_streams_and_an_untracked_one_interleaved():
 def test_refused_crop_stops_the_stream_until_track_begin():
     """A crop squarify refuses fails its frame with VNECT_E_ARG and the host path's message; the frame behind it, already in flight, and
     every later submit fail with VNECT_E_STATE until vnect_track_begin.  The refused crop here is the initial rect, whose geometry
-    vnect_track_begin builds on the host: the box stage's own refusal branch (a refused NEXT crop, trackbox.h: status, zero tables,
-    `fail` for the next frame) is NOT covered on the GPU -- the box rule reaches such a crop from a valid frame (joints within about
-    1.5 rows of a crop more than 736 pixels wide, or about 0.67 columns of one more than 736 tall, or an extent clamped to 1 pixel at the
-    frame's edge), but no planted scene steers the joints there reliably.  The geometry's refusals are covered on the CPU
-    (tests/test_track_cpu.py), the propagation to the next frame by this test."""
+    vnect_track_begin builds on the host.  The box stage's own refusal branch (a refused NEXT crop, trackbox.h: status, zero tables,
+    `fail` for the next frame) is reached from a valid frame by joints within about 1.5 rows of a crop more than 736 pixels wide, or about
+    0.67 columns of one more than 736 tall, or an extent clamped to 1 pixel at the frame's edge; no planted scene steers the joints there
+    reliably, so it is covered with chosen maps (tests/test_gpu_track_maps.py::test_box_stage_refuses_a_crop) and chosen joints
+    (tests/test_gpu_track_kernels.py).  This test holds the propagation from a refused INITIAL rect."""
     from vnect_amd import _native, runner
     w = _planted()
     frames, times = _video(6, H=480, W=1000, seed=1100), _times(6, 7)

@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import track_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vnect_amd", "csrc")
 SO = os.environ.get("VNECT_HOSTPLAN_SO") or os.path.join(ROOT, "vnect_amd", "lib", "libvnect_hostplan.so")
@@ -50,22 +52,14 @@ def _check(hp, H, W):
 def test_shared_geometry_equals_host_squarify_up_to_1024(hp):
     """Every crop size up to 1024 x 1024 on a dense subsample: all sizes up to 96 on both sides, every size paired with the
     sizes around 368 and with a stride-7 grid, the bytes of the whole FrameParams equal."""
-    small = range(1, 97)
-    pairs = {(h, w) for h in small for w in small}
-    ring = list(range(360, 377)) + [1, 2, 3, 735, 736, 737, 738, 1024]
-    pairs |= {(h, w) for h in range(1, 1025) for w in ring} | {(w, h) for h in range(1, 1025) for w in ring}
-    pairs |= {(h, w) for h in range(1, 1025, 7) for w in range(3, 1025, 7)}
-    refused = sum(_check(hp, h, w) for h, w in sorted(pairs))
+    pairs = track_cases.dense_sizes()   # (shared with the device twin, tests/test_gpu_track_kernels.py)
+    refused = sum(_check(hp, h, w) for h, w in pairs)
     assert refused > 0   # (h, w) = (1, 737): 368 / 737 scales the short side to 0 pixels
 
 
 def test_shared_geometry_equals_host_squarify_random_sizes(hp):
     """Random sizes up to 8192 (and past it: "frame size out of range"), skinny ones included so that refusals occur."""
-    rng = np.random.default_rng(7)
-    sizes = [(int(h), int(w)) for h, w in rng.integers(1, 8193, (3000, 2))]
-    sizes += [(int(h), int(w)) for h, w in zip(rng.integers(1, 12, 1500), rng.integers(700, 8193, 1500))]
-    sizes += [(int(w), int(h)) for h, w in zip(rng.integers(1, 12, 1500), rng.integers(700, 8193, 1500))]
-    sizes += [(0, 5), (5, 0), (8193, 10), (10, 8193), (-1, 4), (8192, 8192)]
+    sizes = track_cases.random_sizes()
     refused = sum(_check(hp, h, w) for h, w in sizes)
     assert refused > 100
 

@@ -99,13 +99,19 @@ SYMBOLS = {
 TESTHOOKS_LIB = os.path.join(_HERE, "lib", "libvnect_hip_testhooks.so")   # the host runtime with -DVNECT_TEST_HOOKS=1 (tests only)
 
 
+TRACKPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_trackprobe.so")     # track.o + post.o behind csrc/track_probe.cpp (tests only)
+
+
 def build(force=False):
-    """hipcc --offload-arch=gfx950 build of the library (works without a GPU), and of its test twin: the same kernel objects under a
-    host runtime compiled with the warm start's failure injection (`make testhooks`; only tests/test_gpu_surface.py loads it)."""
+    """hipcc --offload-arch=gfx950 build of the library (works without a GPU), and of its test twins: the same kernel objects under a
+    host runtime compiled with the test hooks (`make testhooks`; tests/test_gpu_surface.py, tests/test_gpu_track_maps.py), and the
+    tracking kernels' objects behind a probe shim (`make trackprobe`; tests/test_gpu_track_kernels.py).  The product loads neither."""
     src = os.path.join(_HERE, "csrc")
     cmd = ["make", "-C", src] + (["-B"] if force else [])
     subprocess.check_call(cmd, stdout=subprocess.DEVNULL)
     subprocess.check_call(["make", "-C", src, "testhooks"], stdout=subprocess.DEVNULL)
+    # the tracking kernels' probe (tests/test_gpu_track_kernels.py): the same track.o / post.o behind a test shim
+    subprocess.check_call(["make", "-C", src, "trackprobe"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 

@@ -297,6 +297,8 @@ int hp_crop_squarify_bytes(int H, int W, uint8_t* out, char* err, int errlen)
     memcpy(out, &fp[0], sizeof(FrameParams));
     return status;
 }
+// crop.h's message for a refusal code (TrackState::status as the device writes it); nullptr for SQ_OK and unknown codes
+const char* hp_crop_refusal(int code) { return crop_refusal(code); }
 // runner.bbox_update on n joint sets (n x 21 x 2 doubles [row, col]) -> n x 4 ints (x, y, w, h); fallback != 0: then runner.track's fallback
 void hp_box_update(const double* j2, int n, int W, int H, int fallback, int32_t* rects)
 {

@@ -190,6 +190,9 @@ void vnect_destroy(vnect_handle* h)
     if (h->h_prof) hipHostFree(h->h_prof);
     if (h->h_prof_end) hipHostFree(h->h_prof_end);
     for (void* p : h->dev_allocs) hipFree(p);
+#if VNECT_TEST_HOOKS
+    if (h->test_st) hipStreamDestroy(h->test_st);
+#endif
     if (h->st) hipStreamDestroy(h->st);
     delete h;
 }
@@ -711,5 +714,49 @@ int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4)
         return VNECT_OK;
     });
 }
+
+#if VNECT_TEST_HOOKS
+// ---- test build only (`make testhooks`): NOT in the shipped library, NOT declared in include/vnect_abi.h --------------------------------
+// While set, every enqueued frame's conv-stack output is overwritten with these (S, 46, 46, 84) maps before its post-processing launch
+// (rt_exec.cpp: enqueue_frame), so a test chooses the joints -- and through them the next crop -- of a tracked frame, while lane choice,
+// cross-lane waits, xfail / xseq, ring slots, collect, error propagation and the timestamps' rollback stay the product's.  The maps
+// are copied to the device here: the caller's buffer is free on return, and a frame in flight keeps the maps it was enqueued with.
+// maps == nullptr ends the override.
+int vnect_test_maps_override(vnect_handle* h, const float* maps)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (!h->finalized || h->sharded) return fail(h, VNECT_E_STATE, "vnect_test_maps_override: needs a finalized, unsharded handle");
+        if (!maps) {
+            h->test_maps_cur = -1;
+            return VNECT_OK;
+        }
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        const size_t n = (size_t)h->S * HM * HM * MAPC;
+        if (!h->test_st) HIPCK(h, hipStreamCreateWithFlags(&h->test_st, hipStreamNonBlocking));
+        const int k = (h->test_maps_cur + 1) % (RING + 1);
+        int rc;
+        if (!h->test_maps[k] && (rc = dev_alloc(h, &h->test_maps[k], n))) return rc;
+        HIPCK(h, hipMemcpyAsync(h->test_maps[k], maps, n * sizeof(float), hipMemcpyHostToDevice, h->test_st));
+        HIPCK(h, hipStreamSynchronize(h->test_st));
+        h->test_maps_cur = k;
+        return VNECT_OK;
+    });
+}
+// the stream's TrackState as the device holds it once the stream's last frame has finished: sizeof(TrackState) bytes (returned in *size)
+int vnect_test_track_state(vnect_handle* h, int stream, uint8_t* out, int32_t cap, int32_t* size)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !out || !size) return VNECT_E_ARG;
+        if (stream < 0 || stream >= VNECT_MAX_STREAMS || !h->track_on[stream]) return fail(h, VNECT_E_STATE, "vnect_test_track_state: stream is not tracking");
+        *size = (int32_t)sizeof(TrackState);
+        if (cap < *size) return fail(h, VNECT_E_ARG, "vnect_test_track_state: buffer too small");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        if (h->stream_seq[stream] >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->done[h->stream_seq[stream] % RING]));
+        HIPCK(h, hipMemcpy(out, h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
+        return VNECT_OK;
+    });
+}
+#endif
 
 }  // extern "C"

@@ -378,6 +378,13 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
         rc = run_frame_kernels(L, timed);
         if (rc) return fail(h, rc, L->err);
     }
+#if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
+    // test build only (vnect_test_maps_override): the conv stack's output replaced by the caller's maps, on the frame's own lane stream --
+    // everything behind it (post-processing, box stage, ring slot, collect) is the product's path on chosen maps
+    if (h->test_maps_cur >= 0 && !L->sharded)
+        HIPCK(h, hipMemcpyAsync(L->tensors[L->t_out].d, h->test_maps[h->test_maps_cur], (size_t)h->S * HM * HM * MAPC * sizeof(float),
+                                hipMemcpyDeviceToDevice, L->st));
+#endif
     if (L->sharded) {  // the one exchange of the pyramid path, then the merge + arg-max over everybody's maps
         if (g_roctx.pop) g_roctx.pop(), g_roctx.push("vnect:exchange+merge+argmax");
         if ((rc = exchange_maps(L, h->seq_submit, ring))) return fail(h, rc, L->err);

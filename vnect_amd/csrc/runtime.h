@@ -175,6 +175,13 @@ struct vnect_handle {
     uint8_t* track_buf[VNECT_MAX_STREAMS] = {};  // a stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
     size_t track_cap[VNECT_MAX_STREAMS] = {};    // waits for this frame's box kernel, which runs after everything that reads the crop)
     bool ring_track[RING] = {};
+#if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
+    // test build only (make testhooks; tests/test_gpu_track_maps.py): vnect_test_maps_override's maps on the device, RING + 1 buffers taken in
+    // turn (a frame in flight keeps reading the one it was enqueued with), and the stream the uploads run on
+    float* test_maps[RING + 1] = {};
+    int test_maps_cur = -1;  // -1: no override
+    hipStream_t test_st = nullptr;
+#endif
     struct TimeState { bool have2, have3; double last2, last3; };
     TimeState ring_time[RING] = {};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
     // cached squarify table

@@ -1,0 +1,249 @@
+// track_probe.cpp -- C shim over the tracking kernels' launchers for tests/test_gpu_track_kernels.py.  TEST INFRASTRUCTURE: it is NOT part
+// of libvnect_hip.so, and the product never loads it.  `make trackprobe` links this file with the SAME track.o and post.o the shipped
+// library links (nothing of the kernels is recompiled), so the device compile of crop.h / trackbox.h / pyramid.h that the product runs
+// is what the tests hold to the host's references, case by case: batches of cases in arrays, one launch per case on one stream, one
+// copy back per batch.
+// Every case is validated on the host BEFORE anything is launched (check_frame, check_frame_state, tp_box's own loop): a case that could make a kernel read or write outside
+// its buffers gets an error code and no launch.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "crop.h"
+#include "hostplan.h"
+#include "kernels.h"
+
+using namespace vnect;
+
+namespace {
+
+enum { TP_OK = 0, TP_E_CROP = 1, TP_E_SIZE = 2, TP_E_STATE = 3, TP_E_JOINTS = 4, TP_E_ROOM = 5 };
+constexpr uint8_t GARBAGE = 0xA5;   // what ts->fp holds before a box launch: an entry no thread writes keeps it
+constexpr uint8_t DST_FILL = 0xCD;  // what a crop copy's destination holds before the launch
+constexpr int DST_GUARD = 64;       // bytes in front of (and at least as many behind) a crop copy's destination
+
+struct BoxCase {  // one case of tp_box on the device
+    TrackState ts;
+    JointsOut jo;
+    TrackOut to;
+};
+
+#define TP_HIP(x)                           \
+    do {                                    \
+        const hipError_t e_ = (x);          \
+        if (e_ != hipSuccess) return -(int)e_ - 1000; \
+    } while (0)
+
+struct Dev {  // device / pinned allocations of one call, freed however it ends
+    std::vector<void*> dev, host;
+    hipStream_t st = nullptr;
+    ~Dev()
+    {
+        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
+        for (void* p : dev) (void)hipFree(p);
+        for (void* p : host) (void)hipHostFree(p);
+    }
+    hipError_t alloc(void** p, size_t n)
+    {
+        const hipError_t e = hipMalloc(p, n ? n : 1);
+        if (e == hipSuccess) dev.push_back(*p);
+        return e;
+    }
+    hipError_t pinned(void** p, size_t n)
+    {
+        const hipError_t e = hipHostMalloc(p, n ? n : 4, hipHostMallocMapped);
+        if (e == hipSuccess) host.push_back(*p);
+        return e;
+    }
+};
+
+// A state that a frame-reading kernel (crop copy, tracked pyramid) may be launched with, over an (H, W) frame `stride` bytes a row:
+// the frame's size is the allocation's, the crop lies inside it, and the geometry is hostplan.h's for the crop's size -- or, for a
+// refused crop, all zero (the pyramid reads nothing of it).
+int check_frame_state(const TrackState& s, int H, int W)
+{
+    if (s.H != H || s.W != W) return TP_E_SIZE;
+    if (s.x < 0 || s.y < 0 || s.w < 1 || s.h < 1 || (long long)s.x + s.w > W || (long long)s.y + s.h > H) return TP_E_CROP;
+    std::vector<FrameParams> want(1);
+    memset(&want[0], 0, sizeof(FrameParams));
+    const char* why = plan::squarify(s.h, s.w, &want[0]);
+    if (why) memset(&want[0], 0, sizeof(FrameParams));
+    if ((s.status != SQ_OK) != (why != nullptr)) return TP_E_STATE;
+    if (memcmp(&s.fp, &want[0], sizeof(FrameParams)) != 0) return TP_E_STATE;
+    return TP_OK;
+}
+int check_frame(int H, int W, long long stride, long long cap)
+{
+    if (H < 1 || W < 1 || H > 65535 || W > 65535 || stride < 3LL * W || stride > (1LL << 20)) return TP_E_SIZE;
+    if ((long long)(H - 1) * stride + 3LL * W > cap) return TP_E_SIZE;
+    return TP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// [0] sizeof(TrackState), [1] offset of its fp, [2] sizeof(FrameParams), [3] sizeof(TrackOut), [4] the garbage byte, [5] the
+// destination fill byte, [6] the destination guard
+void tp_layout(int32_t* out)
+{
+    out[0] = (int)sizeof(TrackState), out[1] = (int)offsetof(TrackState, fp), out[2] = (int)sizeof(FrameParams), out[3] = (int)sizeof(TrackOut);
+    out[4] = GARBAGE, out[5] = DST_FILL, out[6] = DST_GUARD;
+}
+
+// The box stage (launch_track_box) over n cases: states (n x sizeof(TrackState) bytes), joints (n x 21 x 2 doubles in CROP coordinates),
+// xseq (n).  ts->fp of every case is filled with the garbage byte before its launch.  Out: the states after the launch, tout
+// (n x 6 ints: rect, status, pad) and the joints as the kernel left them.  err (n): TP_OK or why the case was not launched; returns 0,
+// the number of refused cases (nothing at all is launched then), or < -1000 for a HIP error.
+int tp_box(int n, const uint8_t* states, const double* joints, const uint32_t* xseq, uint8_t* states_out, int32_t* tout, double* joints_out,
+           int32_t* err)
+{
+    if (n < 1) return 0;
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        TrackState s;
+        memcpy(&s, states + (size_t)i * sizeof(TrackState), sizeof s);
+        err[i] = TP_OK;
+        if (s.status < SQ_OK || s.status > SQ_LONG) err[i] = TP_E_STATE;
+        for (int k = 0; k < NJ * 2; k++) {
+            const double v = joints[(size_t)i * NJ * 2 + k];
+            if (!(fabs(v) < 1e9)) err[i] = TP_E_JOINTS;   // (NaN and infinities too: the C casts of box_axis need a finite value in range)
+        }
+        bad += err[i] != TP_OK;
+    }
+    if (bad) return bad;
+    Dev D;
+    TP_HIP(hipStreamCreate(&D.st));
+    const int CH = 4096;
+    std::vector<BoxCase> hb(n < CH ? n : CH);
+    BoxCase* db = nullptr;
+    TP_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int m = n - c0 < CH ? n - c0 : CH;
+        memset(hb.data(), 0, (size_t)m * sizeof(BoxCase));
+        for (int i = 0; i < m; i++) {
+            memcpy(&hb[i].ts, states + (size_t)(c0 + i) * sizeof(TrackState), sizeof(TrackState));
+            memset(&hb[i].ts.fp, GARBAGE, sizeof(FrameParams));
+            memcpy(hb[i].jo.j2d, joints + (size_t)(c0 + i) * NJ * 2, sizeof hb[i].jo.j2d);
+            memset(&hb[i].to, GARBAGE, sizeof(TrackOut));
+        }
+        TP_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
+        for (int i = 0; i < m; i++) TP_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st));
+        TP_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
+        TP_HIP(hipStreamSynchronize(D.st));
+        for (int i = 0; i < m; i++) {
+            memcpy(states_out + (size_t)(c0 + i) * sizeof(TrackState), &hb[i].ts, sizeof(TrackState));
+            memcpy(tout + (size_t)(c0 + i) * 6, &hb[i].to, sizeof(TrackOut));
+            memcpy(joints_out + (size_t)(c0 + i) * NJ * 2, hb[i].jo.j2d, sizeof hb[i].jo.j2d);
+        }
+    }
+    return 0;
+}
+
+// The crop copy (launch_frame_copy_track) of n states' crops out of ONE pinned (H, W, 3) frame whose rows are `stride` bytes apart
+// (frame: (H - 1) * stride + 3 W bytes).  The pinned buffer's capacity is that size rounded up to 4, and its end is the kernel's
+// src_end.  Every case has its own destination of dst_cap bytes, pre-filled, with a pre-filled guard on both sides: dst_out gets
+// n x (DST_GUARD + dst_cap + DST_GUARD) bytes.
+int tp_copy(const uint8_t* frame, int H, int W, int64_t stride, int n, const uint8_t* states, int64_t dst_cap, uint8_t* dst_out, int32_t* err)
+{
+    if (n < 1) return 0;
+    const long long used = H > 0 ? (long long)(H - 1) * stride + 3LL * W : 0;
+    const long long cap = (used + 3) & ~3LL;
+    const int fe = check_frame(H, W, stride, cap);
+    int bad = 0;
+    std::vector<TrackState> hs(n);
+    for (int i = 0; i < n; i++) {
+        memcpy(&hs[i], states + (size_t)i * sizeof(TrackState), sizeof(TrackState));
+        err[i] = fe ? fe : check_frame_state(hs[i], H, W);
+        if (!err[i] && (dst_cap < 0 || dst_cap % 64 != 0 || 3LL * hs[i].w * hs[i].h > dst_cap)) err[i] = TP_E_ROOM;
+        bad += err[i] != TP_OK;
+    }
+    if (bad) return bad;
+    Dev D;
+    TP_HIP(hipStreamCreate(&D.st));
+    uint8_t *pin = nullptr, *pin_dev = nullptr, *dst = nullptr;
+    TrackState* ds = nullptr;
+    const size_t region = (size_t)dst_cap + 2 * DST_GUARD;
+    TP_HIP(D.pinned((void**)&pin, (size_t)cap));
+    TP_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
+    memset(pin, 0, (size_t)cap);
+    memcpy(pin, frame, (size_t)used);
+    TP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    TP_HIP(D.alloc((void**)&dst, (size_t)n * region));
+    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
+    for (int i = 0; i < n; i++)
+        TP_HIP(launch_frame_copy_track(&ds[i], pin_dev, dst + (size_t)i * region + DST_GUARD, H, W, stride, pin_dev + cap, D.st));
+    TP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
+    TP_HIP(hipStreamSynchronize(D.st));
+    return 0;
+}
+
+// The tracked pyramid (launch_pyramid_track) of n states over ONE (H, W, 3) frame: packed[i] = 0 reads the crop at (x, y) of the whole
+// frame in device memory, rows `stride` bytes apart; packed[i] = 1 reads the crop's own rows, 3 w bytes apart, from a buffer of exactly
+// 3 w h bytes that the host packed.  ScaleTabs from hostplan.h (build_scale_tab, fill_lut).  el: EL_F32 / EL_BF16 / EL_F16.
+// out: n x (S, 368, 368, 4) elements.
+int tp_pyramid(const uint8_t* frame, int H, int W, int64_t stride, int n, const uint8_t* states, const int32_t* packed, const double* scales, int S,
+               int el, void* out, int32_t* err)
+{
+    if (n < 1) return 0;
+    if (S < 1 || S > 8 || el < EL_F32 || el > EL_F16) return -1;
+    std::vector<ScaleTabs> tabs(1);
+    memset(&tabs[0], 0, sizeof(ScaleTabs));
+    tabs[0].S = S;
+    plan::fill_lut(tabs[0].lut);
+    for (int i = 0; i < S; i++)
+        if (plan::build_scale_tab(scales[i], &tabs[0], i)) return -1;
+    const long long used = H > 0 ? (long long)(H - 1) * stride + 3LL * W : 0;
+    const int fe = check_frame(H, W, stride, used);
+    int bad = 0;
+    std::vector<TrackState> hs(n);
+    std::vector<size_t> off(n + 1, 0);  // of every packed crop in the packed buffer (16-byte aligned, as hipMalloc'd buffers are)
+    for (int i = 0; i < n; i++) {
+        memcpy(&hs[i], states + (size_t)i * sizeof(TrackState), sizeof(TrackState));
+        err[i] = fe ? fe : check_frame_state(hs[i], H, W);
+        bad += err[i] != TP_OK;
+        // (room for rows 3 uw bytes apart, not only 3 w: a kernel that took the stride from the REPORTED extent of an initial rect past the
+        // frame's edge must read wrong pixels, not memory outside the buffer; what lies between the rows' ends is noise, not zeros)
+        const size_t wide = (size_t)(hs[i].uw > hs[i].w ? hs[i].uw : hs[i].w);
+        if (!err[i] && (hs[i].uw < hs[i].w || hs[i].uh < hs[i].h || hs[i].uw > 65535 || hs[i].uh > 65535)) err[i] = TP_E_STATE, bad++;
+        off[i + 1] = off[i] + (err[i] || !packed[i] ? 0 : ((3 * wide * hs[i].h + 255) & ~(size_t)255));
+    }
+    if (bad) return bad;
+    std::vector<uint8_t> pk(off[n] ? off[n] : 1, 0);
+    for (size_t k = 0; k < pk.size(); k++) pk[k] = (uint8_t)(k * 2654435761u >> 24);
+    for (int i = 0; i < n; i++)
+        if (packed[i])
+            for (int r = 0; r < hs[i].h; r++)
+                memcpy(&pk[off[i] + (size_t)r * 3 * hs[i].w], frame + (size_t)(hs[i].y + r) * stride + (size_t)3 * hs[i].x, (size_t)3 * hs[i].w);
+    Dev D;
+    TP_HIP(hipStreamCreate(&D.st));
+    uint8_t *dframe = nullptr, *dpk = nullptr, *dout = nullptr;
+    TrackState* ds = nullptr;
+    ScaleTabs* dt = nullptr;
+    const size_t per = (size_t)S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
+    TP_HIP(D.alloc((void**)&dframe, (size_t)used));
+    TP_HIP(D.alloc((void**)&dpk, pk.size()));
+    TP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    TP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    TP_HIP(D.alloc((void**)&dout, (size_t)n * per));
+    TP_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemsetAsync(dout, 0xFF, (size_t)n * per, D.st));
+    for (int i = 0; i < n; i++) {
+        FrameDyn dyn = {};
+        dyn.frame = packed[i] ? dpk + off[i] : dframe;
+        dyn.row_stride = stride;
+        TP_HIP(launch_pyramid_track(&ds[i], dyn, packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
+    }
+    TP_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
+    TP_HIP(hipStreamSynchronize(D.st));
+    return 0;
+}
+
+}  // extern "C"
