@@ -21,9 +21,10 @@
 #define BF16_NOSTORE 0  // tuning builds only (wrong results): no bf16 epilogue stores
 #endif
 
+#include <array>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
+#include <utility>
 
 namespace vnect {
 
@@ -1721,9 +1722,95 @@ static int g_cus = 256;  // compute units of the device the handles run on (conv
 #endif
 constexpr int X3_NS_6432 = 5;  // the split-product form of 64x32x2: 5 stages of 28 KiB
 static_assert(stream_lds<64, 32, 2, NS_6432>() <= 160 * 1024 && stream_lds<32, 128, 1, NS_32128>() <= 160 * 1024 && x3_stream_lds<64, 32, 2, X3_NS_6432>() <= 160 * 1024, "one workgroup's ring fits a CU's LDS");
-constexpr size_t x3_lds() { return x3_stream_lds<64, 64, 1, X3_NS>(); }
+// ---- which instantiations of conv_stream_kernel exist ---------------------------------------------------------------------------
+// ONE rule, asked at compile time.  conv_setup prepares every variant it admits (raised LDS limit, register and scratch check) and
+// launch_stream launches out of the table the same enumeration fills: a variant is in both or in neither.
+struct Variant {
+    int el, prof, fuse;  // EL_*; 0 / 1 = start + end stamps / 2 = per-phase stamps too; 0 / 1 = tail GEMM / 2 = bone features / 3 = tail + chain GEMM
+    bool span, x3, one;  // conv1's span form; split-product form; one item per workgroup without the streaming machinery
+};
+constexpr int N_VARIANTS = 3 * 3 * 4 * 2 * 2 * 2;
+constexpr int variant_index(Variant v) { return ((((v.el * 3 + v.prof) * 4 + v.fuse) * 2 + v.span) * 2 + v.x3) * 2 + v.one; }
+constexpr Variant variant_at(int i) { return {i / 96, i / 32 % 3, i / 8 % 4, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0}; }
 
-template <int BM, int BN, int KG, int NS>
+template <int BM, int BN, int KG>
+constexpr bool variant_exists(Variant v)
+{
+    constexpr bool t6464 = BM == 64 && BN == 64 && KG == 1, t6432 = BM == 64 && BN == 32 && KG == 2, t32128 = BM == 32 && BN == 128 && KG == 1;
+    if (BN == 96)  // three accumulators per wave: fp32 only; streaming, one-item or with the bone features; start / end stamps at most
+        return v.el == EL_F32 && v.prof < 2 && !v.span && !v.x3 && (v.fuse == 0 || (v.fuse == 2 && !v.one));
+    if (v.x3)  // split-product form: fp32 layers on 64x64 tiles (plain, with the tail GEMM or the bone features) and on 64x32x2 tiles (plain)
+        return v.el == EL_F32 && v.prof < 2 && !v.span && !v.one && (t6464 ? v.fuse <= 2 : t6432 && v.fuse == 0);
+    if (v.span)  // conv1, fp32
+        return t6464 && v.el == EL_F32 && v.prof < 2 && v.fuse == 0 && !v.one;
+    if (v.fuse != 0)  // one-item kernels by construction (FUSE != 0 implies SINGLE); the 64-wide chain exists in the 16-bit formats only
+        return v.prof < 2 && !v.one && (t6464 ? (v.fuse != 3 || v.el != EL_F32) : t32128 && (v.fuse == 1 || v.fuse == 3));
+    return true;  // the plain form: every element type, every PROF, streaming or one-item
+}
+template <int BM, int BN, int KG>
+constexpr int variant_count()
+{
+    int n = 0;
+    for (int i = 0; i < N_VARIANTS; i++) n += variant_exists<BM, BN, KG>(variant_at(i));
+    return n;
+}
+static_assert(variant_count<64, 64, 1>() == 42 && variant_count<64, 32, 2>() == 20 && variant_count<32, 32, 4>() == 18 && variant_count<32, 128, 1>() == 30 &&
+                  variant_count<64, 96, 2>() == 6,
+              "116 instantiations: a new variant is a decision (compile time, library size), not a side effect of editing the rule");
+
+// Ring depths: 5 x 16 KiB leaves room for two 64x64 workgroups per CU (measured faster than one deeper ring on every
+// layer); the K-group shapes run one workgroup per CU.
+template <int BM, int BN, int KG>
+constexpr int ring_depth(bool x3)
+{
+    if (BN == 96) return 3;  // 3 stages of 40 KiB + 24 KiB of partial sums: one workgroup per CU
+    if (BN == 128) return NS_32128;
+    if (KG == 4) return 4;
+    if (KG == 2) return x3 ? X3_NS_6432 : NS_6432;
+    return x3 ? X3_NS : 5;
+}
+template <int BM, int BN, int KG>
+constexpr size_t variant_lds(bool x3)
+{
+    return x3 ? x3_stream_lds<BM, BN, KG, ring_depth<BM, BN, KG>(true)>() : stream_lds<BM, BN, KG, ring_depth<BM, BN, KG>(false)>();
+}
+static_assert(variant_lds<64, 64, 1>(true) <= variant_lds<64, 64, 1>(false), "the split-product ring fits the two-workgroups-per-CU LDS allowance");
+// the bytes every launch asks for, written out: a change of a ring depth or of a formula above shows here, not first on the device
+static_assert(variant_lds<64, 64, 1>(false) == 81920 && variant_lds<64, 64, 1>(true) == 81920 && variant_lds<64, 32, 2>(false) == 131136 &&
+                  variant_lds<64, 32, 2>(true) == 151616 && variant_lds<32, 32, 4>(false) == 143424 && variant_lds<32, 128, 1>(false) == 102400 &&
+                  variant_lds<64, 96, 2>(false) == 147520,
+              "dynamic LDS per shape and form");
+// the launch plan assumes two workgroups per CU (one for the K-group and the wide shapes): conv_setup refuses a build that needs more
+// registers than that leaves ...
+template <int BM, int BN, int KG>
+constexpr int variant_reg_cap() { return (KG == 1 && BN <= 64) ? 128 : 256; }
+// ... or scratch.  The per-phase tuning twins (PROF = 2) may spill a few bytes, conv1's span form with start / end stamps (VNECT_NO_STEM=1
+// under the profiling twin) may spill 8, and so may the F32_NOSTORE probe build.
+constexpr bool variant_may_spill(Variant v) { return v.prof == 2 || (v.span && v.prof == 1) || F32_NOSTORE; }
+
+struct StreamKernel {
+    void (*fn)(const ConvArgs);  // nullptr: no such instantiation
+    size_t lds;
+};
+template <int BM, int BN, int KG, int I>
+constexpr StreamKernel stream_kernel_at()
+{
+    constexpr Variant v = variant_at(I);
+    static_assert(variant_index(v) == I, "variant_at is the inverse of variant_index: slot I holds the kernel the launcher looks up there");
+    if constexpr (variant_exists<BM, BN, KG>(v))
+        return {conv_stream_kernel<BM, BN, KG, ring_depth<BM, BN, KG>(v.x3), v.el, v.prof, v.fuse, v.span, v.x3, v.one>, variant_lds<BM, BN, KG>(v.x3)};
+    else
+        return {nullptr, 0};
+}
+template <int BM, int BN, int KG, int... I>
+constexpr std::array<StreamKernel, sizeof...(I)> stream_kernels(std::integer_sequence<int, I...>)
+{
+    return {{stream_kernel_at<BM, BN, KG, I>()...}};
+}
+template <int BM, int BN, int KG>
+constexpr auto STREAM_KERNELS = stream_kernels<BM, BN, KG>(std::make_integer_sequence<int, N_VARIANTS>{});  // indexed by variant_index
+
+template <int BM, int BN, int KG>
 static hipError_t launch_stream(ConvArgs a, hipStream_t st)
 {
     if (a.cpt % KG != 0 || a.Npad % BN != 0) return hipErrorInvalidValue;
@@ -1753,169 +1840,60 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     // earlier ones retire (profiles/stream_batch_rate.txt has the per-layer times).
     const bool fused = a.tail_n > 0 || a.bone;
     dim3 grid((one || fused) ? a.items : (a.items < maxwg ? a.items : maxwg));
-    const size_t lds = stream_lds<BM, BN, KG, NS>();
     // profiling twin: start / end stamps only, or (VNECT_PROF_DETAIL=1, tools/phase_table.py) the per-phase stamps too
     static const bool detail = getenv("VNECT_PROF_DETAIL") && atoi(getenv("VNECT_PROF_DETAIL")) != 0;
     const int prof = a.prof ? (detail ? 2 : 1) : 0;
-    // one item per workgroup and no K slabs (`one`, above): the kernel without the streaming machinery (conv_stream_kernel, ONE)
-#define LAUNCH_STREAM(BF, PR)                                                                                                        \
-    do {                                                                                                                             \
-        if (one) hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, BF, PR, 0, false, false, true>), grid, dim3(512), lds, st, a); \
-        else hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, BF, PR>), grid, dim3(512), lds, st, a);                          \
-    } while (0)
-    if constexpr (BM == 64 && BN == 64 && KG == 1) {
-        if (a.x3) {  // split-product form (plain, with the tail GEMM or with the bone features behind it); start / end stamps at most
-            if (a.bf16 || a.pixmode || a.K % 32) return hipErrorInvalidValue;
-            if (a.bone && (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212 || a.tail_n > 0)) return hipErrorInvalidValue;
-            if (a.tail_n > 0 && (a.ksplit != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias))
+
+    // ---- argument checks, by form: what keeps a wrong plan from reading or writing out of bounds.  That a shape has no such form at all
+    // (a tail on 64x32x2 tiles, bf16 on 64x96 ...) is the rule's answer below, not repeated here.
+    if (a.x3) {
+        // split-product form (plain, with the tail GEMM or with the bone features behind it): fp32 activations, K in whole 32-element chunks
+        // (Measured, A/B in one call each: a 7-stage ring for launches with one workgroup per CU 1 162 vs 1 174 frames/s without; the
+        // hi plane's bytes only -- 12 KiB per chunk instead of 20 -- +1.6 %; no split arithmetic +13 %; 3 MFMAs instead of 6 +9 %:
+        // the loop is bound by the VALU + MFMA issue of the consumer waves, not by bytes into the LDS.  DESIGN 4.1d.)
+        if (a.bf16 || a.pixmode || a.K % 32) return hipErrorInvalidValue;
+        if (a.chain_n != 0) return hipErrorInvalidValue;  // no split-product kernel runs the chain GEMM: refuse it rather than drop it
+    }
+    if (a.tail_n > 0) {
+        // tail GEMM: ONE tile per workgroup that holds all of the layer's channels, one phase, no K slabs, never with the bone features
+        if (a.bone || a.ksplit != 1 || a.nphase != 1 || a.os != 1 || !a.tail_w || !a.tail_bias) return hipErrorInvalidValue;
+        if constexpr (BN == 128) {  // the wide tail (tail_wide): one 32x128 tile per workgroup, K = 128, at most 16 column blocks
+            if (a.Npad != 128 || a.tail_n > 512 ||
+                (a.chain_n != 0 && (a.chain_n != 128 || a.tail_n != 512 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 128)))
                 return hipErrorInvalidValue;
-            // (Measured, A/B in one call each: a 7-stage ring for launches with one workgroup per CU 1 162 vs 1 174 frames/s without; the
-            // hi plane's bytes only -- 12 KiB per chunk instead of 20 -- +1.6 %; no split arithmetic +13 %; 3 MFMAs instead of 6 +9 %:
-            // the loop is bound by the VALU + MFMA issue of the consumer waves, not by bytes into the LDS.  DESIGN 4.1d.)
-            const int fu = a.bone ? 2 : (a.tail_n > 0 ? 1 : 0);
-#define LAUNCH_X3(NSX, PR, FU) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NSX, false, PR, FU, false, true>), grid, dim3(512), (x3_stream_lds<64, 64, 1, NSX>()), st, a)
-#define LAUNCH_X3_FU(NSX, PR)                 \
-    do {                                      \
-        if (fu == 0) LAUNCH_X3(NSX, PR, 0);   \
-        else if (fu == 1) LAUNCH_X3(NSX, PR, 1); \
-        else LAUNCH_X3(NSX, PR, 2);           \
-    } while (0)
-            if (prof == 0) LAUNCH_X3_FU(X3_NS, 0);
-            else LAUNCH_X3_FU(X3_NS, 1);
-#undef LAUNCH_X3_FU
-#undef LAUNCH_X3
-            return hipGetLastError();
-        }
-        if (a.tail_n > 0) {  // tail GEMM variant: one tile per workgroup, start / end stamps at most
-            if (a.ksplit != 1 || a.nphase != 1 || a.Npad != 64 || a.os != 1 || a.tail_n != 256 || !a.tail_w || !a.tail_bias)
-                return hipErrorInvalidValue;
+        } else {
+            if (a.Npad != 64 || a.tail_n != 256) return hipErrorInvalidValue;
             // the 64-wide chain: bf16, behind a tail with shortcut + ReLU and bf16 output only
             if (a.chain_n != 0 && (!a.bf16 || a.chain_n != 64 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 64 || !a.resid ||
                                    a.relu_cols < 256 || a.out_f32 || a.Nvalid != 256 ||
                                    (a.ldc & 7) != 0))  // the chain stores the block output from the LDS tile, which tail_gemm fills only in its
                                                        // staged form (tail_staged: whole 16-byte units per row, ldc % 8 == 0; advisor, round 5)
                 return hipErrorInvalidValue;
-#define LAUNCH_TAIL(BF, PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, BF, PR, 1>), grid, dim3(512), lds, st, a)
-            if (a.f16 && a.chain_n) {
-                if (prof == 0) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, 2, 0, 3>), grid, dim3(512), lds, st, a);
-                else hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, 2, 1, 3>), grid, dim3(512), lds, st, a);
-            } else if (a.bf16 && a.chain_n) {
-                if (prof == 0) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, true, 0, 3>), grid, dim3(512), lds, st, a);
-                else hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, true, 1, 3>), grid, dim3(512), lds, st, a);
-            } else if (a.f16) {
-                if (prof == 0) LAUNCH_TAIL(2, 0);
-                else LAUNCH_TAIL(2, 1);
-            } else if (a.bf16) {
-                if (prof == 0) LAUNCH_TAIL(true, 0);
-                else LAUNCH_TAIL(true, 1);
-            } else {
-                if (prof == 0) LAUNCH_TAIL(false, 0);
-                else LAUNCH_TAIL(false, 1);
-            }
-#undef LAUNCH_TAIL
-            return hipGetLastError();
         }
     }
-    if constexpr (BM == 64 && BN == 32 && KG == 2) {
-        if (a.x3) {  // split-product form of the in-workgroup K-group shape (one workgroup per CU; 5 stages of 28 KiB)
-            if (a.bf16 || a.pixmode || a.K % 32 || a.tail_n > 0 || a.bone) return hipErrorInvalidValue;
-            const size_t l3 = x3_stream_lds<64, 32, 2, X3_NS_6432>();
-            if (prof == 0) hipLaunchKernelGGL((conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 0, 0, false, true>), grid, dim3(512), l3, st, a);
-            else hipLaunchKernelGGL((conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 1, 0, false, true>), grid, dim3(512), l3, st, a);
-            return hipGetLastError();
-        }
-    }
+    // bone-length features inside the transposed conv's launch: one tile per workgroup again, all 192 columns, room for channels 191 .. 211
+    if (a.bone && (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212)) return hipErrorInvalidValue;
     if constexpr (BN == 96) {
         // three accumulators per wave (fp32): no shortcut, one output tensor, no K slabs, no tail; plain or with the bone features
         if (a.bf16 || a.x3 || a.tail_n > 0 || a.resid || a.out2 || a.ksplit != 1 || a.pixmode || (a.relu_cols & 31)) return hipErrorInvalidValue;
-        if (a.bone && (a.Npad != 192 || a.ldc < 212)) return hipErrorInvalidValue;
-#define LAUNCH_96(PR, FU) hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, false, PR, FU>), grid, dim3(512), lds, st, a)
-#define LAUNCH_96_ONE(PR) hipLaunchKernelGGL((conv_stream_kernel<BM, BN, KG, NS, false, PR, 0, false, false, true>), grid, dim3(512), lds, st, a)
-        if (a.bone) {
-            if (prof == 0) LAUNCH_96(0, 2);
-            else LAUNCH_96(1, 2);
-        } else if (one) {
-            if (prof == 0) LAUNCH_96_ONE(0);
-            else LAUNCH_96_ONE(1);
-        } else {
-            if (prof == 0) LAUNCH_96(0, 0);
-            else LAUNCH_96(1, 0);
-        }
-#undef LAUNCH_96_ONE
-#undef LAUNCH_96
-        return hipGetLastError();
     }
-    if constexpr (BM == 32 && BN == 128 && KG == 1) {
-        if (a.tail_n > 0) {  // the wide tail (tail_wide): one 32x128 tile per workgroup, K = 128, at most 16 column blocks
-            if (a.x3 || a.bone || a.ksplit != 1 || a.nphase != 1 || a.Npad != 128 || a.os != 1 || a.tail_n > 512 || !a.tail_w || !a.tail_bias ||
-                (a.chain_n != 0 && (a.chain_n != 128 || a.tail_n != 512 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 128)))
-                return hipErrorInvalidValue;
-#define LAUNCH_WTAIL(BF, PR)                                                                                                              \
-    do {                                                                                                                                  \
-        if (a.chain_n) hipLaunchKernelGGL((conv_stream_kernel<32, 128, 1, NS, BF, PR, 3>), grid, dim3(512), lds, st, a);                     \
-        else hipLaunchKernelGGL((conv_stream_kernel<32, 128, 1, NS, BF, PR, 1>), grid, dim3(512), lds, st, a);                               \
-    } while (0)
-            if (a.f16) {
-                if (prof == 0) LAUNCH_WTAIL(2, 0);
-                else LAUNCH_WTAIL(2, 1);
-            } else if (a.bf16) {
-                if (prof == 0) LAUNCH_WTAIL(true, 0);
-                else LAUNCH_WTAIL(true, 1);
-            } else {
-                if (prof == 0) LAUNCH_WTAIL(false, 0);
-                else LAUNCH_WTAIL(false, 1);
-            }
-#undef LAUNCH_WTAIL
-            return hipGetLastError();
-        }
-    }
-    if (a.tail_n > 0 || a.x3) return hipErrorInvalidValue;
-    if constexpr (BM == 64 && BN == 64 && KG == 1) {
-        if (a.bone) {  // bone-length features inside the transposed conv's launch: one tile per workgroup again
-            if (a.ksplit != 1 || a.Npad != 192 || a.ldc < 212) return hipErrorInvalidValue;
-#define LAUNCH_BONE(BF, PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, BF, PR, 2>), grid, dim3(512), lds, st, a)
-            if (a.f16) {
-                if (prof == 0) LAUNCH_BONE(2, 0);
-                else LAUNCH_BONE(2, 1);
-            } else if (a.bf16) {
-                if (prof == 0) LAUNCH_BONE(true, 0);
-                else LAUNCH_BONE(true, 1);
-            } else {
-                if (prof == 0) LAUNCH_BONE(false, 0);
-                else LAUNCH_BONE(false, 1);
-            }
-#undef LAUNCH_BONE
-            return hipGetLastError();
-        }
-    }
-    if (a.bone) return hipErrorInvalidValue;
-    if constexpr (BM == 64 && BN == 64 && KG == 1) {
-        // conv1, fp32: the span form (VNECT_NO_SPAN=1: the gathered-window form, for A/B runs)
-        const bool no_span = getenv("VNECT_NO_SPAN") != nullptr;  // read per launch: a test flips it inside one process
-        if (a.pixmode && !a.bf16 && !no_span && a.ksplit == 1 && a.cpt == 1 && a.Wo >= 64 && a.stride == 2) {
-#define LAUNCH_SPAN(PR) hipLaunchKernelGGL((conv_stream_kernel<64, 64, 1, NS, false, PR, 0, true>), grid, dim3(512), lds, st, a)
-            if (prof == 0) LAUNCH_SPAN(0);
-            else LAUNCH_SPAN(1);
-#undef LAUNCH_SPAN
-            return hipGetLastError();
-        }
-    }
-    if constexpr (BN != 96) {
-        if (a.f16) {
-            if (prof == 0) LAUNCH_STREAM(2, 0);
-            else if (prof == 1) LAUNCH_STREAM(2, 1);
-            else LAUNCH_STREAM(2, 2);
-        } else if (a.bf16) {
-            if (prof == 0) LAUNCH_STREAM(true, 0);
-            else if (prof == 1) LAUNCH_STREAM(true, 1);
-            else LAUNCH_STREAM(true, 2);
-        } else {
-            if (prof == 0) LAUNCH_STREAM(false, 0);
-            else if (prof == 1) LAUNCH_STREAM(false, 1);
-            else LAUNCH_STREAM(false, 2);
-        }
-    }
-#undef LAUNCH_STREAM
+
+    // ---- the request as a variant, and the one launch
+    Variant v{};
+    v.el = a.f16 ? EL_F16 : a.bf16 ? EL_BF16 : EL_F32;
+    v.fuse = a.tail_n > 0 ? (a.chain_n ? 3 : 1) : a.bone ? 2 : 0;
+    v.x3 = a.x3 != 0;
+    // conv1, fp32: the span form (VNECT_NO_SPAN=1: the gathered-window form, for A/B runs; read per launch: a test flips it inside one process)
+    v.span = variant_exists<BM, BN, KG>({EL_F32, 0, 0, true, false, false}) && !v.x3 && v.fuse == 0 && a.pixmode && !a.bf16 && a.ksplit == 1 &&
+             a.cpt == 1 && a.Wo >= 64 && a.stride == 2 && getenv("VNECT_NO_SPAN") == nullptr;
+    // one item per workgroup and no K slabs (`one`, above): the kernel without the streaming machinery (conv_stream_kernel, ONE)
+    v.one = one && v.fuse == 0 && !v.x3 && !v.span;
+    v.prof = prof;
+    if (prof == 2 && !variant_exists<BM, BN, KG>(v)) v.prof = 1;  // per-phase stamps exist for the plain form only: start / end stamps elsewhere
+    if (!variant_exists<BM, BN, KG>(v)) return hipErrorInvalidValue;
+    const StreamKernel& k = STREAM_KERNELS<BM, BN, KG>[variant_index(v)];
+    void* args[] = {&a};
+    hipLaunchKernel((const void*)k.fn, grid, dim3(512), args, k.lds, st);
     return hipGetLastError();
 }
 
@@ -1924,107 +1902,22 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
 static bool g_deconv96 = false;
 bool conv_deconv96_available() { return g_deconv96; }
 
-template <int BM, int BN, int KG, int NS>
-static hipError_t setup_stream_rest();
-template <int BM, int BN, int KG, int NS>
+template <int BM, int BN, int KG>
 static hipError_t setup_stream()
 {
-    hipFuncAttributes fa;
-    if constexpr (BN == 96) {
-        for (const void* f : {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0, 0>, (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1, 0>,
-                              (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0, 2>, (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1, 2>,
-                              (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0, 0, false, false, true>,
-                              (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1, 0, false, false, true>}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stream_lds<BM, BN, KG, NS>());
-            if (e != hipSuccess) return e;
-            e = hipFuncGetAttributes(&fa, f);
-            if (e != hipSuccess) return e;
-            if (fa.numRegs > 256 || fa.localSizeBytes != 0) return hipErrorLaunchOutOfResources;
-        }
-        return hipSuccess;
-    } else {
-        return setup_stream_rest<BM, BN, KG, NS>();
-    }
-}
-template <int BM, int BN, int KG, int NS>
-static hipError_t setup_stream_rest()
-{
-    hipFuncAttributes fa;
-    std::vector<const void*> fns = {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 0>,
-                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 1>,
-                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2>,
-                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 0>, (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 1>,
-                                    (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2>};
-    const void* twins_one[3] = {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2, 0, false, false, true>,
-                                (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2, 0, false, false, true>};
-    for (const void* f : {(const void*)conv_stream_kernel<BM, BN, KG, NS, false, 0, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 0, 0, false, false, true>,
-                          (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 1, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 1, 0, false, false, true>,
-                          (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 0, 0, false, false, true>, (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 1, 0, false, false, true>,
-                          twins_one[0], twins_one[1], twins_one[2]})
-        fns.push_back(f);
-    if constexpr (BM == 64 && BN == 64 && KG == 1) {
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 0, 1>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 1>);
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 1, 1>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 1, 1>);
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 0, 0, true>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 1, 0, true>);
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 3>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 1, 3>);
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 0, 2>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 0, 2>);
-        fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, false, 1, 2>), fns.push_back((const void*)conv_stream_kernel<64, 64, 1, NS, true, 1, 2>);
-        for (const void* f : {(const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 1>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 1>,
-                              (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 3>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 3>,
-                              (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 0, 2>, (const void*)conv_stream_kernel<64, 64, 1, NS, 2, 1, 2>})
-            fns.push_back(f);
-        static_assert(x3_lds() <= stream_lds<64, 64, 1, 5>(), "the split-product ring fits the same LDS allowance");
-    }
-    if constexpr (BM == 64 && BN == 64 && KG == 1) {  // the split-product instantiations have LDS sizes of their own
-        static_assert(x3_lds() <= stream_lds<64, 64, 1, 5>(), "the split-product ring fits the two-workgroups-per-CU LDS allowance");
-        const void* x3s[] = {(const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 0, 0, false, true>, (const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 1, 0, false, true>,
-                             (const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 0, 1, false, true>, (const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 1, 1, false, true>,
-                             (const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 0, 2, false, true>, (const void*)conv_stream_kernel<64, 64, 1, X3_NS, false, 1, 2, false, true>};
-        for (int i = 0; i < 6; i++) {
-            hipError_t e = hipFuncSetAttribute(x3s[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)x3_stream_lds<64, 64, 1, X3_NS>());
-            if (e != hipSuccess) return e;
-            e = hipFuncGetAttributes(&fa, x3s[i]);
-            if (e != hipSuccess) return e;
-            if (fa.numRegs > 128 || fa.localSizeBytes != 0) return hipErrorLaunchOutOfResources;
-        }
-    }
-    if constexpr (BM == 32 && BN == 128 && KG == 1) {
-        fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 0, 1>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 0, 1>);
-        fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 1, 1>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 1, 1>);
-        fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 0, 3>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 0, 3>);
-        fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, false, 1, 3>), fns.push_back((const void*)conv_stream_kernel<32, 128, 1, NS, true, 1, 3>);
-        for (const void* f : {(const void*)conv_stream_kernel<32, 128, 1, NS, 2, 0, 1>, (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 1, 1>,
-                              (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 0, 3>, (const void*)conv_stream_kernel<32, 128, 1, NS, 2, 1, 3>})
-            fns.push_back(f);
-    }
-    if constexpr (BM == 64 && BN == 32 && KG == 2) {
-        for (const void* f : {(const void*)conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 0, 0, false, true>, (const void*)conv_stream_kernel<64, 32, 2, X3_NS_6432, false, 1, 0, false, true>}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x3_stream_lds<64, 32, 2, X3_NS_6432>());
-            if (e != hipSuccess) return e;
-            e = hipFuncGetAttributes(&fa, f);
-            if (e != hipSuccess) return e;
-            if (fa.numRegs > 256 || fa.localSizeBytes != 0) return hipErrorLaunchOutOfResources;
-        }
-    }
-    const void* span_twin = nullptr;  // conv1's span form with start / end stamps (VNECT_NO_STEM=1 under the profiling twin): may spill 8 bytes
-    if constexpr (BM == 64 && BN == 64 && KG == 1) span_twin = (const void*)conv_stream_kernel<64, 64, 1, NS, false, 1, 0, true>;
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stream_lds<BM, BN, KG, NS>());
+    for (int i = 0; i < N_VARIANTS; i++) {
+        const StreamKernel& k = STREAM_KERNELS<BM, BN, KG>[i];
+        if (!k.fn) continue;
+        hipFuncAttributes fa;
+        hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
         if (e != hipSuccess) return e;
-        e = hipFuncGetAttributes(&fa, f);
+        e = hipFuncGetAttributes(&fa, (const void*)k.fn);
         if (e != hipSuccess) return e;
-        // the launch plan assumes two workgroups per CU (one for the K-group shapes): refuse a build that needs more registers
-        // or scratch (the per-phase tuning twins, PROF = 2, may spill a few bytes)
-        const bool twin = f == (const void*)conv_stream_kernel<BM, BN, KG, NS, false, 2> || f == (const void*)conv_stream_kernel<BM, BN, KG, NS, true, 2> ||
-                          f == (const void*)conv_stream_kernel<BM, BN, KG, NS, 2, 2> || f == twins_one[0] || f == twins_one[1] || f == twins_one[2] ||
-                          f == span_twin;
-        if (fa.numRegs > (KG == 1 && BN <= 64 ? 128 : 256) || (fa.localSizeBytes != 0 && !twin && !F32_NOSTORE)) return hipErrorLaunchOutOfResources;  // (the probe build may spill)
+        if (fa.numRegs > variant_reg_cap<BM, BN, KG>() || (fa.localSizeBytes != 0 && !variant_may_spill(variant_at(i)))) return hipErrorLaunchOutOfResources;
     }
     return hipSuccess;
 }
 
-// Ring depths: 5 x 16 KiB leaves room for two 64x64 workgroups per CU (measured faster than one deeper ring on every
-// layer); the K-group shapes run one workgroup per CU.
 int conv_cu_count() { return g_cus; }
 
 hipError_t conv_setup()
@@ -2036,11 +1929,11 @@ hipError_t conv_setup()
         if ((e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
         if (n >= 8) g_cus = n;
     }
-    if ((e = setup_stream<64, 64, 1, 5>()) != hipSuccess) return e;
-    if ((e = setup_stream<64, 32, 2, NS_6432>()) != hipSuccess) return e;
-    if ((e = setup_stream<32, 32, 4, 4>()) != hipSuccess) return e;
-    if ((e = setup_stream<32, 128, 1, NS_32128>()) != hipSuccess) return e;
-    e = setup_stream<64, 96, 2, 3>();
+    if ((e = setup_stream<64, 64, 1>()) != hipSuccess) return e;
+    if ((e = setup_stream<64, 32, 2>()) != hipSuccess) return e;
+    if ((e = setup_stream<32, 32, 4>()) != hipSuccess) return e;
+    if ((e = setup_stream<32, 128, 1>()) != hipSuccess) return e;
+    e = setup_stream<64, 96, 2>();
     g_deconv96 = e == hipSuccess;
     if (e != hipSuccess && e != hipErrorLaunchOutOfResources) return e;  // out of registers: deconv96 unavailable, not an error
     return hipSuccess;
@@ -2054,11 +1947,11 @@ hipError_t launch_conv(const ConvArgs& a, int BM, int BN, int KG, hipStream_t st
         return hipErrorInvalidValue;
     // range of the multiply-high divisions in the kernel (x / d exact while x * d < 2^32)
     if ((long long)a.M * (a.Wo > a.Ho ? a.Wo : a.Ho) >= (1ll << 32) || a.M >= (1 << 24)) return hipErrorInvalidValue;
-    if (KG == 2 && BM == 64 && BN == 32) return launch_stream<64, 32, 2, NS_6432>(a, st);
-    if (KG == 4 && BM == 32 && BN == 32) return launch_stream<32, 32, 4, 4>(a, st);
-    if (KG == 1 && BM == 64 && BN == 64) return launch_stream<64, 64, 1, 5>(a, st);
-    if (KG == 1 && BM == 32 && BN == 128) return launch_stream<32, 128, 1, NS_32128>(a, st);
-    if (KG == 2 && BM == 64 && BN == 96) return g_deconv96 ? launch_stream<64, 96, 2, 3>(a, st) : hipErrorInvalidValue;  // 3 stages of 40 KiB + 24 KiB of partial sums: one workgroup per CU
+    if (KG == 2 && BM == 64 && BN == 32) return launch_stream<64, 32, 2>(a, st);
+    if (KG == 4 && BM == 32 && BN == 32) return launch_stream<32, 32, 4>(a, st);
+    if (KG == 1 && BM == 64 && BN == 64) return launch_stream<64, 64, 1>(a, st);
+    if (KG == 1 && BM == 32 && BN == 128) return launch_stream<32, 128, 1>(a, st);
+    if (KG == 2 && BM == 64 && BN == 96) return g_deconv96 ? launch_stream<64, 96, 2>(a, st) : hipErrorInvalidValue;
     return hipErrorInvalidValue;
 }
 
@@ -2090,17 +1983,19 @@ __global__ void strip4to3_kernel(const T* __restrict__ in4, float* __restrict__ 
 hipError_t launch_pad3to4(const float* in3, void* out4, long long npix, int el, hipStream_t st)
 {
     dim3 g((unsigned)((npix + 255) / 256));
-    if (el == EL_F16) hipLaunchKernelGGL(pad3to4_kernel<_Float16>, g, dim3(256), 0, st, in3, (_Float16*)out4, npix);
-    else if (el) hipLaunchKernelGGL(pad3to4_kernel<__bf16>, g, dim3(256), 0, st, in3, (__bf16*)out4, npix);
-    else hipLaunchKernelGGL(pad3to4_kernel<float>, g, dim3(256), 0, st, in3, (float*)out4, npix);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pad3to4_kernel<T>, g, dim3(256), 0, st, in3, (T*)out4, npix);
+    });
     return hipGetLastError();
 }
 hipError_t launch_strip4to3(const void* in4, float* out3, long long npix, int el, hipStream_t st)
 {
     dim3 g((unsigned)((npix + 255) / 256));
-    if (el == EL_F16) hipLaunchKernelGGL(strip4to3_kernel<_Float16>, g, dim3(256), 0, st, (const _Float16*)in4, out3, npix);
-    else if (el) hipLaunchKernelGGL(strip4to3_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in4, out3, npix);
-    else hipLaunchKernelGGL(strip4to3_kernel<float>, g, dim3(256), 0, st, (const float*)in4, out3, npix);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(strip4to3_kernel<T>, g, dim3(256), 0, st, (const T*)in4, out3, npix);
+    });
     return hipGetLastError();
 }
 
@@ -2138,9 +2033,10 @@ hipError_t launch_maxpool(const void* in, void* out, int S, int H, int W, int C,
 {
     long long total = (long long)S * Ho * Wo * (C >> 2);
     dim3 g((unsigned)((total + 255) / 256));
-    if (el == EL_F16) hipLaunchKernelGGL(maxpool_kernel<_Float16>, g, dim3(256), 0, st, (const _Float16*)in, (_Float16*)out, S, H, W, C, Ho, Wo);
-    else if (el) hipLaunchKernelGGL(maxpool_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)in, (__bf16*)out, S, H, W, C, Ho, Wo);
-    else hipLaunchKernelGGL(maxpool_kernel<float>, g, dim3(256), 0, st, (const float*)in, (float*)out, S, H, W, C, Ho, Wo);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(maxpool_kernel<T>, g, dim3(256), 0, st, (const T*)in, (T*)out, S, H, W, C, Ho, Wo);
+    });
     return hipGetLastError();
 }
 
@@ -2180,9 +2076,10 @@ hipError_t launch_bone(void* feat, long long npix, int ld, int el, hipStream_t s
 {
     long long total = npix * (ld - 191);
     dim3 g((unsigned)((total + 255) / 256));
-    if (el == EL_F16) hipLaunchKernelGGL(bone_kernel<_Float16>, g, dim3(256), 0, st, (_Float16*)feat, npix, ld);
-    else if (el) hipLaunchKernelGGL(bone_kernel<__bf16>, g, dim3(256), 0, st, (__bf16*)feat, npix, ld);
-    else hipLaunchKernelGGL(bone_kernel<float>, g, dim3(256), 0, st, (float*)feat, npix, ld);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(bone_kernel<T>, g, dim3(256), 0, st, (T*)feat, npix, ld);
+    });
     return hipGetLastError();
 }
 

@@ -11,6 +11,18 @@ namespace vnect {
 // say it as bf16 = "16-bit elements" plus f16 = "they are fp16")
 enum { EL_F32 = 0, EL_BF16 = 1, EL_F16 = 2 };
 
+// The one place where a launcher's run-time `el` becomes a C++ element type: f is called with an ElType<T> tag (host code only; any
+// value other than EL_F32 / EL_F16 means bf16, as the launchers always took it).
+template <typename T>
+struct ElType {
+    using type = T;
+};
+template <typename F>
+inline auto with_el(int el, F&& f)
+{
+    return el == EL_F16 ? f(ElType<_Float16>{}) : el != EL_F32 ? f(ElType<__bf16>{}) : f(ElType<float>{});
+}
+
 constexpr int MAX_TAPS = 16;
 constexpr int ARG_SLABS_MAX = 32;  // upper bound of the arg-max workgroups per joint (post.hip: ARG_SLABS): what the partials' buffer is sized for
 constexpr int PROF_WGS = 512;   // end-stamp slots per launch (two workgroups per CU; a power of two: larger grids wrap around)

@@ -33,9 +33,10 @@ __global__ void pyramid_kernel(const FrameParams* __restrict__ fp, const FrameDy
 hipError_t launch_pyramid(const FrameParams* fp, FrameDyn dyn, const ScaleTabs* tabs, void* batch4, int S, int scale_base, int el, hipStream_t st)
 {
     dim3 g((BOX + 127) / 128, BOX, S);
-    if (el == EL_F16) hipLaunchKernelGGL(pyramid_kernel<_Float16>, g, dim3(128), 0, st, fp, dyn, tabs, (_Float16*)batch4, scale_base);
-    else if (el) hipLaunchKernelGGL(pyramid_kernel<__bf16>, g, dim3(128), 0, st, fp, dyn, tabs, (__bf16*)batch4, scale_base);
-    else hipLaunchKernelGGL(pyramid_kernel<float>, g, dim3(128), 0, st, fp, dyn, tabs, (float*)batch4, scale_base);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pyramid_kernel<T>, g, dim3(128), 0, st, fp, dyn, tabs, (T*)batch4, scale_base);
+    });
     return hipGetLastError();
 }
 
@@ -61,9 +62,10 @@ hipError_t launch_pyramid_streams(const FrameParams* fp0, const FrameParams* fp1
 {
     if (S < 1 || 2 * S > VNECT_MAX_IMAGES) return hipErrorInvalidValue;
     dim3 g((BOX + 127) / 128, BOX, 2 * S);
-    if (el == EL_F16) hipLaunchKernelGGL(pyramid_streams_kernel<_Float16>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (_Float16*)batch4, S);
-    else if (el) hipLaunchKernelGGL(pyramid_streams_kernel<__bf16>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (__bf16*)batch4, S);
-    else hipLaunchKernelGGL(pyramid_streams_kernel<float>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (float*)batch4, S);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pyramid_streams_kernel<T>, g, dim3(128), 0, st, fp0, fp1, dyn0, dyn1, tabs, (T*)batch4, S);
+    });
     return hipGetLastError();
 }
 

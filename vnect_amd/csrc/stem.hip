@@ -28,8 +28,10 @@
 #include "kernels.h"
 #include "pyramid.h"
 
+#include <array>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace vnect {
 
@@ -527,20 +529,31 @@ __global__ __launch_bounds__(STEM_THREADS, 2) void stem_kernel(const StemArgs a)
     if (PROF && tid == 0 && blockIdx.x < PROF_WGS) stem_prof_end(a);
 }
 
+// Every instantiation of stem_kernel, (EL, FRAME, PROF, PAIR), with its LDS size: stem_setup raises the limit of each and launch_stem
+// launches out of the same table.
+struct StemKernel {
+    void (*fn)(const StemArgs);
+    size_t lds;
+};
+constexpr int stem_index(int el, bool frame, bool prof, bool pair) { return ((el * 2 + frame) * 2 + prof) * 2 + pair; }
+template <int I>
+constexpr StemKernel stem_kernel_at()
+{
+    constexpr int el = I / 8;
+    constexpr bool frame = (I & 4) != 0, prof = (I & 2) != 0, pair = (I & 1) != 0;
+    static_assert(stem_index(el, frame, prof, pair) == I, "slot I holds the kernel launch_stem looks up there");
+    return {stem_kernel<el, frame, prof, pair>, stem_lds<el, frame>()};
+}
+template <int... I>
+constexpr std::array<StemKernel, sizeof...(I)> stem_kernels(std::integer_sequence<int, I...>) { return {{stem_kernel_at<I>()...}}; }
+constexpr auto STEM_KERNELS = stem_kernels(std::make_integer_sequence<int, 3 * 2 * 2 * 2>{});
+
 hipError_t stem_setup()
 {
-    hipError_t e;
-#define STEM_ATTR(BF, FR, PR)                                                                                                        \
-    if ((e = hipFuncSetAttribute((const void*)stem_kernel<BF, FR, PR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_lds<BF, FR>())) != \
-        hipSuccess)                                                                                                                  \
-        return e;                                                                                                                    \
-    if ((e = hipFuncSetAttribute((const void*)stem_kernel<BF, FR, PR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_lds<BF, FR>())) != \
-        hipSuccess)                                                                                                                  \
-        return e;
-    STEM_ATTR(false, false, false) STEM_ATTR(false, false, true) STEM_ATTR(false, true, false) STEM_ATTR(false, true, true)
-    STEM_ATTR(true, false, false) STEM_ATTR(true, false, true) STEM_ATTR(true, true, false) STEM_ATTR(true, true, true)
-    STEM_ATTR(2, false, false) STEM_ATTR(2, false, true) STEM_ATTR(2, true, false) STEM_ATTR(2, true, true)
-#undef STEM_ATTR
+    for (const StemKernel& k : STEM_KERNELS) {
+        hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -559,24 +572,10 @@ hipError_t launch_stem(const StemArgs& a_in, hipStream_t st)
     if (a.per_stream && (a.S != 2 * a.per_stream || a.scale_base != 0 || (a.from_frame && (!a.fp2 || !a.frame2)))) return hipErrorInvalidValue;
     if (a.pair_w && (!a.pair_bias || !a.pair_out_a || !a.pair_out_b)) return hipErrorInvalidValue;
     const dim3 grid(a.S * a.groups * 4), block(STEM_THREADS);
-    const bool prof = a.prof != nullptr;
-#define STEM_GO(BF, FR, PR)                                                                                              \
-    do {                                                                                                                 \
-        if (a.pair_w) hipLaunchKernelGGL((stem_kernel<BF, FR, PR, true>), grid, block, (stem_lds<BF, FR>()), st, a);       \
-        else hipLaunchKernelGGL((stem_kernel<BF, FR, PR>), grid, block, (stem_lds<BF, FR>()), st, a);                    \
-    } while (0)
     if (a.f16 && !a.bf16) return hipErrorInvalidValue;
-    if (a.f16) {
-        if (a.from_frame) { if (prof) STEM_GO(2, true, true); else STEM_GO(2, true, false); }
-        else { if (prof) STEM_GO(2, false, true); else STEM_GO(2, false, false); }
-    } else if (a.bf16) {
-        if (a.from_frame) { if (prof) STEM_GO(true, true, true); else STEM_GO(true, true, false); }
-        else { if (prof) STEM_GO(true, false, true); else STEM_GO(true, false, false); }
-    } else {
-        if (a.from_frame) { if (prof) STEM_GO(false, true, true); else STEM_GO(false, true, false); }
-        else { if (prof) STEM_GO(false, false, true); else STEM_GO(false, false, false); }
-    }
-#undef STEM_GO
+    const StemKernel& k = STEM_KERNELS[stem_index(a.f16 ? EL_F16 : a.bf16 ? EL_BF16 : EL_F32, a.from_frame != 0, a.prof != nullptr, a.pair_w != nullptr)];
+    void* args[] = {&a};
+    hipLaunchKernel((const void*)k.fn, grid, block, args, k.lds, st);
     return hipGetLastError();
 }
 

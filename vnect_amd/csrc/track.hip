@@ -34,9 +34,10 @@ __global__ void pyramid_track_kernel(const TrackState* __restrict__ ts, const Fr
 hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, const ScaleTabs* tabs, void* batch4, int S, int el, hipStream_t st)
 {
     dim3 g((BOX + 127) / 128, BOX, S);
-    if (el == EL_F16) hipLaunchKernelGGL(pyramid_track_kernel<_Float16>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (_Float16*)batch4);
-    else if (el) hipLaunchKernelGGL(pyramid_track_kernel<__bf16>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (__bf16*)batch4);
-    else hipLaunchKernelGGL(pyramid_track_kernel<float>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (float*)batch4);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pyramid_track_kernel<T>, g, dim3(128), 0, st, ts, dyn, packed, tabs, (T*)batch4);
+    });
     return hipGetLastError();
 }
 
