@@ -329,15 +329,23 @@ def test_no_exception_crosses_the_abi(weights):
 
 
 # ------------------------------------------------------------------------------------------ several streams on one handle
-@pytest.mark.parametrize("two_launches", [False, True])
-def test_reassigned_scales_equal_a_fresh_estimator(weights, monkeypatch, two_launches):
+@pytest.mark.parametrize("two_launches,how", [(False, "sync"), (True, "sync"), (False, "lanes3"), (True, "lanes3"), (False, "batch2")],
+                         ids=["False", "True", "lanes3", "lanes3-two_launches", "batch2"])
+def test_reassigned_scales_equal_a_fresh_estimator(weights, monkeypatch, two_launches, how):
     """`estimator.scales = [...]` (a plain attribute in the reference, estimator.py:32) re-plans pyramid and merge on a live
     handle: the frames after it are bit-identical to a new estimator made with those scales.  The merge geometry is a by-value
     kernel argument, so the two-launch form of the post-processing (VNECT_NO_POST_MERGE=1), whose arg-max launch sits inside the
-    captured graph, has to capture again -- both forms are run."""
+    captured graph, has to capture again -- both forms are run.
+    lanes3 / batch2: the same on a handle with more than one plan -- three lanes with three frames in flight (in both forms of the
+    post-processing: every lane captures again), and the two-stream batch through submit_streams -- on frames whose long side is
+    368, which take the stem's from-the-frame form where every plan's rectangles fit its LDS scratch.  They fit at the old scales
+    and do not at the new ones (tests/test_hostplan.py: fits([1.0, 0.15]) == 0), so a plan whose stem_frame_ok the reassignment
+    left behind would go on reading rectangles that do not fit.  The fresh handle is a plain one, run frame by frame."""
     from tests import helpers
     if two_launches:
         monkeypatch.setenv("VNECT_NO_POST_MERGE", "1")
+    if how != "sync":
+        return _reassigned_scales_on_plans(weights, how)
     frames = [np.ascontiguousarray(helpers.synth_frame(300 + k, 300, 420, smooth=True)) for k in range(4)]
     live = _est(weights, scales=[1.0, 0.85, 0.7])
     for k in range(2):
@@ -349,6 +357,53 @@ def test_reassigned_scales_equal_a_fresh_estimator(weights, monkeypatch, two_lau
         a2, a3 = live(f, timestamp=T0 + 10 + k / 30)
         b2, b3 = fresh(f, timestamp=T0 + 10 + k / 30)
         assert np.array_equal(a2, b2) and np.array_equal(a3, b3), k
+    live.close(), fresh.close()
+
+
+def _reassigned_scales_on_plans(weights, how):
+    from vnect_amd import _native
+    from tests import helpers
+    old, new = [1.0, 0.7], [1.0, 0.15]
+    shapes = [(368, 200), (240, 368)] if how == "batch2" else [(368, 200)]
+    frames = [np.ascontiguousarray(helpers.synth_frame(340 + k, *shapes[k % len(shapes)], smooth=True)) for k in range(4)]
+
+    def make(scales, **kw):
+        h = _native.Handle(scales, num_frame_slots=4, **kw)
+        h.set_weights(weights)
+        h.finalize()
+        for k, f in enumerate(frames):
+            h.upload_frame(k, f)
+        return h
+
+    def run(h, t0, batched, depth):
+        """-> [(stream, j2, j3)] of the four frames: as two batches of streams (0, 1), or stream 0's, `depth` in flight"""
+        got = []
+        if how == "batch2":
+            for k in range(2):
+                t = [t0 + k / 30, t0 + 5 + k / 30]
+                if batched:
+                    h.submit_streams([0, 1], [2 * k, 2 * k + 1], t, t)
+                else:
+                    for s in (0, 1):
+                        h.submit_stream(s, 2 * k + s, t[s], t[s])
+                got += [h.collect_stream() for _ in range(2)]
+            return got
+        for k0 in range(0, 4, depth):
+            ks = range(k0, min(k0 + depth, 4))
+            for k in ks:
+                h.submit_resident(k, t0 + k / 30, t0 + k / 30)
+            got += [h.collect_stream() for _ in ks]
+        return got
+
+    live = make(old, **({"stream_batch": 2} if how == "batch2" else {"lanes": 3}))
+    run(live, T0, True, 3)
+    live.set_scales(new)
+    live.reset_filters()
+    a = run(live, T0 + 10, True, 3)
+    fresh = make(new)
+    b = run(fresh, T0 + 10, False, 1)
+    for k in range(4):
+        assert a[k][0] == b[k][0] and np.array_equal(a[k][1], b[k][1]) and np.array_equal(a[k][2], b[k][2]), k
     live.close(), fresh.close()
 
 

@@ -62,6 +62,7 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
         if (sharded && (cfg->pyramid_nranks != cfg->num_scales || cfg->pyramid_rank < 0 || cfg->pyramid_rank >= cfg->pyramid_nranks))
             return fail(nullptr, VNECT_E_ARG, "vnect_create: pyramid sharding needs pyramid_nranks == num_scales and 0 <= pyramid_rank < nranks");
         vnect_handle* h = new vnect_handle();
+        h->owner = h, h->lanes = {h}, h->owns_stream = true, h->prof_graph = true;  // lane 0
         h->cfg = *cfg;
         h->S = cfg->num_scales;
         h->Snet = sharded ? 1 : cfg->num_scales;
@@ -104,9 +105,9 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
         if (!pre && (rc = dev_alloc(h, &h->gather, (size_t)VNECT_MAX_SCALES * HM * HM * MAPC))) return rc;
         for (int i = 0; i < RING; i++) {
             HIPCK(h, hipHostMalloc((void**)&h->h_fp[i], sizeof(FrameParams), hipHostMallocDefault));
-            HIPCK(h, hipHostMalloc((void**)&h->h_out[i], sizeof(JointsOut), hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCK(h, hipHostGetDevicePointer((void**)&h->h_out_dev[i], h->h_out[i], 0));
-            HIPCK(h, hipEventCreateWithFlags(&h->done[i], hipEventDisableTiming));
+            HIPCK(h, hipHostMalloc((void**)&h->ring[i].out, sizeof(JointsOut), hipHostMallocMapped | hipHostMallocCoherent));
+            HIPCK(h, hipHostGetDevicePointer((void**)&h->ring[i].out_dev, h->ring[i].out, 0));
+            HIPCK(h, hipEventCreateWithFlags(&h->ring[i].done, hipEventDisableTiming));
         }
         if (sharded && cfg->exchange == VNECT_XCHG_P2P) {
             // fine-grained device memory: peers' stores and the system-scope loads of this device bypass its L2, so a slot is
@@ -166,17 +167,11 @@ void vnect_destroy(vnect_handle* h)
     if (!h) return;
     hipSetDevice(h->cfg.device);
     if (h->st) hipStreamSynchronize(h->st);
-    destroy_batch_lanes(h);  // (they run on the lanes' streams)
-    destroy_twins(h);
+    destroy_plans(h);  // (batched plans first: they run on the lanes' streams)
     comm_destroy(h);
-    if (h->gexec) hipGraphExecDestroy(h->gexec);
-    if (h->graph) hipGraphDestroy(h->graph);
-    if (h->pgexec) hipGraphExecDestroy(h->pgexec);
-    if (h->pgraph) hipGraphDestroy(h->pgraph);
-    for (int i = 0; i < RING; i++) {
-        if (h->h_fp[i]) hipHostFree(h->h_fp[i]);
-        if (h->h_out[i]) hipHostFree(h->h_out[i]);
-        if (h->done[i]) hipEventDestroy(h->done[i]);
+    for (InFlight& e : h->ring) {
+        if (e.out) hipHostFree(e.out);
+        if (e.done) hipEventDestroy(e.done);
     }
     for (auto& e : h->ev)
         if (e) hipEventDestroy(e);
@@ -187,13 +182,10 @@ void vnect_destroy(vnect_handle* h)
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
-    if (h->h_prof) hipHostFree(h->h_prof);
-    if (h->h_prof_end) hipHostFree(h->h_prof_end);
-    for (void* p : h->dev_allocs) hipFree(p);
 #if VNECT_TEST_HOOKS
     if (h->test_st) hipStreamDestroy(h->test_st);
 #endif
-    if (h->st) hipStreamDestroy(h->st);
+    destroy_plan(h);  // lane 0: its graphs, buffers (every device allocation of the handle is on its list) and stream
     delete h;
 }
 
@@ -240,9 +232,7 @@ int vnect_finalize(vnect_handle* h)
         }
         rc = build_graph(h);
         if (rc) return rc;
-        rc = build_twins(h);
-        if (rc) return rc;
-        rc = build_batch_lanes(h);
+        rc = build_plans(h);
         if (rc) return rc;
         HIPCK(h, hipStreamSynchronize(h->st));
         h->finalized = true;
@@ -258,8 +248,7 @@ int vnect_set_scales(vnect_handle* h, const double* scales, int n)
         if (n != h->S) return fail(h, VNECT_E_ARG, "vnect_set_scales: the number of scales is fixed at create time");
         if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
         HIPCK(h, hipSetDevice(h->cfg.device));
-        HIPCK(h, hipStreamSynchronize(h->st));
-        for (vnect_handle* t : h->twins) HIPCK(h, hipStreamSynchronize(t->st));
+        for (Plan* l : h->lanes) HIPCK(h, hipStreamSynchronize(l->st));
         double old[VNECT_MAX_SCALES];
         memcpy(old, h->cfg.scales, sizeof old);
         for (int i = 0; i < n; i++) h->cfg.scales[i] = scales[i];
@@ -271,9 +260,8 @@ int vnect_set_scales(vnect_handle* h, const double* scales, int n)
         // the two-launch form of the post-processing (VNECT_NO_POST_MERGE=1) has its arg-max launch -- and with it the merge geometry,
         // a by-value kernel argument -- inside the captured graph: capture again (the default form launches post_kernel eagerly)
         if (h->finalized && !h->sharded && !h->post_merged && h->gexec) {
-            int rg = build_graph(h);
-            for (vnect_handle* t : h->twins)
-                if (!rg && (rg = build_graph(t))) fail(h, rg, t->err);
+            int rg = VNECT_OK;
+            for (size_t i = 0; i < h->lanes.size() && !rg; i++) rg = build_graph(h->lanes[i]);
             if (rg) return rg;
         }
         return rc;
@@ -286,12 +274,12 @@ int vnect_forward(vnect_handle* h, const float* batch, int num_images, float* ou
         if (!h || !batch || !out) return VNECT_E_ARG;
         if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_forward before vnect_finalize");
         if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        const bool batched = !h->blanes.empty() && num_images == 2 * h->Snet;
-        if (num_images != h->Snet && !batched)
+        const bool doubled = !h->bplans.empty() && num_images == 2 * h->Snet;
+        if (num_images != h->Snet && !doubled)
             return fail(h, VNECT_E_ARG, "vnect_forward: num_images must equal num_scales (1 on a pyramid-sharded handle; "
                                         "or 2 x num_scales after vnect_set_stream_batch(h, 2))");
         HIPCK(h, hipSetDevice(h->cfg.device));
-        if (batched) return forward_batch(h, batch, out);
+        if (doubled) return forward_batch(h, batch, out);
         const long long npix = (long long)h->Snet * BOX * BOX;
         HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
         HIPCK(h, launch_pad3to4(h->in3, h->tensors[h->t_input4].d, npix, h->el(), h->st));
@@ -342,7 +330,7 @@ int vnect_postprocess(vnect_handle* h, const float* maps, double t2d, double t3d
         if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
         if (!(scaler > 0)) return fail(h, VNECT_E_ARG, "scaler must be positive");
         HIPCK(h, hipSetDevice(h->cfg.device));
-        int rc = check_time(h, t2d, t3d);
+        int rc = check_time(h, h->streams[0], t2d, t3d);
         if (rc) return rc;
         float* dst = h->sharded ? h->gather : h->tensors[h->t_out].d;
         HIPCK(h, hipMemcpyAsync(dst, maps, (size_t)h->S * HM * HM * MAPC * sizeof(float), hipMemcpyHostToDevice, h->st));
@@ -353,15 +341,15 @@ int vnect_postprocess(vnect_handle* h, const float* maps, double t2d, double t3d
         dyn.t2d = t2d, dyn.t3d = t3d;
         if ((rc = sync_geometry(h, fp))) return rc;
         if (h->post_merged) {
-            if ((rc = run_post(h, dyn, h->h_out_dev[0]))) return rc;
+            if ((rc = run_post(h, dyn, h->ring[0].out_dev))) return rc;
         } else {
             if ((rc = run_argmax(h))) return rc;
-            if ((rc = run_joints(h, dyn, h->h_out_dev[0]))) return rc;
+            if ((rc = run_joints(h, dyn, h->ring[0].out_dev))) return rc;
         }
-        commit_time(h, t2d, t3d);
+        commit_time(h->streams[0], t2d, t3d);
         HIPCK(h, hipStreamSynchronize(h->st));
-        memcpy(j2, h->h_out[0]->j2d, sizeof(double) * NJ * 2);
-        memcpy(j3, h->h_out[0]->j3d, sizeof(float) * NJ * 3);
+        memcpy(j2, h->ring[0].out->j2d, sizeof(double) * NJ * 2);
+        memcpy(j3, h->ring[0].out->j3d, sizeof(float) * NJ * 3);
         return VNECT_OK;
     });
 }
@@ -478,8 +466,9 @@ int vnect_joint_filter(vnect_handle* h, int dim, const double* joints_in, int va
         if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
         HIPCK(h, hipSetDevice(h->cfg.device));
         // the timestamp rules of check_time, for the one bank this call advances
-        const bool have = dim == 2 ? h->have2[0] : h->have3[0];   // (stream 0: the bank vnect_infer advances)
-        const double last = dim == 2 ? h->last2[0] : h->last3[0];
+        TimeState& ts = h->streams[0].t;  // (stream 0: the bank vnect_infer advances)
+        const bool have = dim == 2 ? ts.have2 : ts.have3;
+        const double last = dim == 2 ? ts.last2 : ts.last3;
         if (have && last != 0.0 && t != 0.0) {
             if (t == last) return fail(h, VNECT_E_TIMESTAMP, "timestamp equals the previous one of this filter bank");
             if (t < last) return fail(h, VNECT_E_TIMEORDER, "timestamp is earlier than the previous one of this filter bank");
@@ -488,8 +477,8 @@ int vnect_joint_filter(vnect_handle* h, int dim, const double* joints_in, int va
         memcpy(h->h_filt, joints_in, sizeof(double) * n);
         HIPCK(h, launch_filter(h->d_fb, dim, values_are_f32 != 0, h->cfg.numpy_promotion, t, h->h_filt_dev, h->h_filt_dev + 64, h->st));
         HIPCK(h, hipStreamSynchronize(h->st));
-        if (dim == 2) h->have2[0] = true, h->last2[0] = t;
-        else h->have3[0] = true, h->last3[0] = t;
+        if (dim == 2) ts.have2 = true, ts.last2 = t;
+        else ts.have3 = true, ts.last3 = t;
         memcpy(joints_out, h->h_filt + 64, sizeof(double) * n);
         return VNECT_OK;
     });
@@ -603,8 +592,8 @@ int vnect_get_batch_layer_info(vnect_handle* h, int idx, vnect_layer_info* out)
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        if (h->blanes.empty()) return fail(h, VNECT_E_STATE, "vnect_get_batch_layer_info: no batched plan (vnect_set_stream_batch(h, 2), then vnect_finalize)");
-        return layer_info(h->blanes[0]->layers, idx, out);
+        if (h->bplans.empty()) return fail(h, VNECT_E_STATE, "vnect_get_batch_layer_info: no batched plan (vnect_set_stream_batch(h, 2), then vnect_finalize)");
+        return layer_info(h->bplans[0]->layers, idx, out);
     });
 }
 
@@ -643,7 +632,7 @@ int vnect_track_begin(vnect_handle* h, int stream, int H, int W, const int32_t* 
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a pyramid-sharded handle is not supported");
-        if (h->stream_batch == 2 || !h->blanes.empty())
+        if (h->stream_batch == 2 || !h->bplans.empty())
             return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
         if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_track_begin before vnect_finalize");
         HIPCK(h, hipSetDevice(h->cfg.device));
@@ -655,8 +644,8 @@ static int tracked_ok(vnect_handle* h, int stream)
 {
     if (!h->finalized) return fail(h, VNECT_E_STATE, "inference before vnect_finalize");
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
-    if (!h->track_on[stream]) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
-    if (h->track_stopped[stream]) return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
+    if (!h->streams[stream].track_on) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
+    if (h->streams[stream].track_stopped) return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
     return VNECT_OK;
 }
 
@@ -680,7 +669,7 @@ int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, i
         int rc = tracked_ok(h, stream);
         if (rc) return rc;
         if (buffer_index < 0 || buffer_index > 1 || !h->stage[buffer_index]) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: no such pinned buffer (vnect_frame_buffer)");
-        const int H = h->track_H[stream], W = h->track_W[stream];
+        const int H = h->streams[stream].track_H, W = h->streams[stream].track_W;
         if (row_stride < (int64_t)W * 3 || (size_t)(H - 1) * (size_t)row_stride + (size_t)W * 3 > h->stage_cap[buffer_index])
             return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: the frame does not fit the pinned buffer at this row stride");
         HIPCK(h, hipSetDevice(h->cfg.device));
@@ -705,9 +694,10 @@ int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4)
     return guarded(&h, [&]() -> int {
         if (!h || !rect4) return VNECT_E_ARG;
         if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
-        if (!h->track_on[stream]) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
+        const Stream& sm = h->streams[stream];
+        if (!sm.track_on) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
         HIPCK(h, hipSetDevice(h->cfg.device));
-        if (h->stream_seq[stream] >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->done[h->stream_seq[stream] % RING]));
+        if (sm.seq >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->ring[sm.seq % RING].done));
         std::vector<TrackState> ts(1);
         HIPCK(h, hipMemcpy(&ts[0], h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
         rect4[0] = ts[0].x, rect4[1] = ts[0].y, rect4[2] = ts[0].uw, rect4[3] = ts[0].uh;
@@ -748,11 +738,12 @@ int vnect_test_track_state(vnect_handle* h, int stream, uint8_t* out, int32_t ca
 {
     return guarded(&h, [&]() -> int {
         if (!h || !out || !size) return VNECT_E_ARG;
-        if (stream < 0 || stream >= VNECT_MAX_STREAMS || !h->track_on[stream]) return fail(h, VNECT_E_STATE, "vnect_test_track_state: stream is not tracking");
+        if (stream < 0 || stream >= VNECT_MAX_STREAMS || !h->streams[stream].track_on) return fail(h, VNECT_E_STATE, "vnect_test_track_state: stream is not tracking");
         *size = (int32_t)sizeof(TrackState);
         if (cap < *size) return fail(h, VNECT_E_ARG, "vnect_test_track_state: buffer too small");
         HIPCK(h, hipSetDevice(h->cfg.device));
-        if (h->stream_seq[stream] >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->done[h->stream_seq[stream] % RING]));
+        const Stream& sm = h->streams[stream];
+        if (sm.seq >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->ring[sm.seq % RING].done));
         HIPCK(h, hipMemcpy(out, h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
         return VNECT_OK;
     });

@@ -1,4 +1,4 @@
-// rt_exec.cpp -- running frames on the plan: launch sequences, the hipGraph and its profiling twin, lanes, video streams, submit /
+// rt_exec.cpp -- running frames on a plan: launch sequences, the hipGraph and its profiling twin, lane choice, video streams, submit /
 // collect, host -> device staging, the warm start.  One call of VNectEstimator.__call__ (/root/reference/src/estimator.py:97-142)
 // is enqueue_frame + collect_impl.
 #include "runtime.h"
@@ -7,27 +7,35 @@ namespace vnect {
 namespace rt {
 
 // ---- launch sequences -------------------------------------------------------------------------------
+// the stem's or a conv layer's arguments for layer li of plan p: stamping into the layer's profiling slots (timed), or not at all
+template <typename Args>
+static Args stamped(const Plan* p, const Args& args, int li, bool timed)
+{
+    Args a = args;
+    a.prof = timed ? p->d_prof + PROF_SLOTS * li : nullptr;
+    a.prof_end = timed ? p->d_prof_end + (size_t)PROF_WGS * li : nullptr;
+    return a;
+}
+
+// the maps the merge reads: the plan's own, or on a pyramid-sharded handle all ranks'
+static const float* maps_of(const Plan* p) { return p->owner->sharded ? p->owner->gather : p->tensors[p->t_out].d; }
+
 // `stem_done`: the caller has launched the stem from the frame already (enqueue_frame: it takes the frame's arguments by value)
-int run_network(vnect_handle* h, bool timed, bool stem_done)
+int run_network(Plan* h, bool timed, bool stem_done)
 {
     for (Layer& L : h->layers) {
         const int li = (int)(&L - h->layers.data());
         if (h->stem_mode && (li == h->l_conv1 || li == h->l_pool1)) {
             if (li == h->l_conv1 && !stem_done) {  // from the batch tensor (stem_mode 1, or vnect_forward on a stem_mode 2 handle)
-                StemArgs a = h->stem;
+                StemArgs a = stamped(h, h->stem, li, timed);
                 a.from_frame = 0;
-                a.prof = timed ? h->d_prof + PROF_SLOTS * li : nullptr;
-                a.prof_end = timed ? h->d_prof_end + (size_t)PROF_WGS * li : nullptr;
                 HIPCK(h, launch_stem(a, h->st));
             }
             continue;
         }
         if (h->stem_mode && h->stem_pair && li == h->l_pool1 + 1) continue;  // ran inside the stem launch
         if (L.op == OP_CONV) {
-            ConvArgs a = L.a;
-            a.prof = timed ? h->d_prof + PROF_SLOTS * (&L - h->layers.data()) : nullptr;
-            a.prof_end = timed ? h->d_prof_end + (size_t)PROF_WGS * (&L - h->layers.data()) : nullptr;
-            HIPCK(h, launch_conv(a, L.BM, L.BN, L.KG, h->st));
+            HIPCK(h, launch_conv(stamped(h, L.a, li, timed), L.BM, L.BN, L.KG, h->st));
             if (L.a.ksplit > 1) HIPCK(h, launch_reduce(L.r, h->st));
         } else if (L.op == OP_POOL) {
             const Tensor &i = h->tensors[L.in], &o = h->tensors[L.out];
@@ -42,7 +50,7 @@ int run_network(vnect_handle* h, bool timed, bool stem_done)
 
 // Crop geometry -> d_fp, only if it differs from what the device holds (a stream of equally sized crops never uploads).
 // In-stream, so frames still in flight keep the geometry they were launched with.
-int sync_geometry(vnect_handle* h, const FrameParams& fp, int which)
+int sync_geometry(Plan* h, const FrameParams& fp, int which)
 {
     FrameParams& held = which ? h->fp_dev2 : h->fp_dev;
     bool& valid = which ? h->fp_dev2_valid : h->fp_dev_valid;
@@ -54,12 +62,12 @@ int sync_geometry(vnect_handle* h, const FrameParams& fp, int which)
     return VNECT_OK;
 }
 
-int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed, bool want_batch)
+int run_pre(Plan* h, const FrameDyn& dyn, bool timed, bool want_batch)
 {
+    const vnect_handle* o = h->owner;
+    const int scale0 = o->sharded ? o->cfg.pyramid_rank : 0;
     if (h->stem_mode == 2 && !want_batch) {
-        StemArgs a = h->stem;
-        a.prof = timed ? h->d_prof + PROF_SLOTS * h->l_conv1 : nullptr;
-        a.prof_end = timed ? h->d_prof_end + (size_t)PROF_WGS * h->l_conv1 : nullptr;
+        StemArgs a = stamped(h, h->stem, h->l_conv1, timed);
         // gen_input_batch + conv1 + pool1 in ONE launch, the batch tensor never written: for frames whose squarify step is a copy (long
         // side == 368) at scales whose rectangles fit the kernel's scratch.  Any other frame: pyramid_kernel, then the stem from the
         // batch tensor -- both in front of the graph, which starts at res2a either way.  Same results bit for bit.
@@ -68,54 +76,50 @@ int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed, bool want_batch)
             HIPCK(h, launch_stem(a, h->st));
             return VNECT_OK;
         }
-        HIPCK(h, launch_pyramid(h->d_fp, dyn, h->d_stabs, h->tensors[h->t_input4].d, h->Snet,
-                                h->sharded ? h->cfg.pyramid_rank : 0, h->el(), h->st));
+        HIPCK(h, launch_pyramid(h->d_fp, dyn, o->d_stabs, h->tensors[h->t_input4].d, h->Snet, scale0, h->el(), h->st));
         a.from_frame = 0;
         HIPCK(h, launch_stem(a, h->st));
         return VNECT_OK;
     }
-    HIPCK(h, launch_pyramid(h->d_fp, dyn, h->d_stabs, h->tensors[h->t_input4].d, h->Snet,
-                            h->sharded ? h->cfg.pyramid_rank : 0, h->el(), h->st));
+    HIPCK(h, launch_pyramid(h->d_fp, dyn, o->d_stabs, h->tensors[h->t_input4].d, h->Snet, scale0, h->el(), h->st));
     return VNECT_OK;
 }
 
 // multi-scale merge + arg-max (graph-capturable: no per-frame arguments)
-int run_argmax(vnect_handle* h)
+int run_argmax(Plan* h)
 {
-    const float* maps = h->sharded ? h->gather : h->tensors[h->t_out].d;
-    HIPCK(h, launch_argmax(maps, h->mgeo, h->d_part, h->st));
+    HIPCK(h, launch_argmax(maps_of(h), h->owner->mgeo, h->d_part, h->st));
     return VNECT_OK;
 }
 
 // filters + read-off; results go straight to `out` (a device-mapped pinned host slot)
-int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
+int run_joints(Plan* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
 {
-    const float* maps = h->sharded ? h->gather : h->tensors[h->t_out].d;
-    HIPCK(h, launch_joints(h->d_part, maps, h->mgeo, h->d_fb + stream, fp ? fp : h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
+    const vnect_handle* o = h->owner;
+    HIPCK(h, launch_joints(h->d_part, maps_of(h), o->mgeo, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st));
     return VNECT_OK;
 }
 
 // both in one launch (post.hip: post_kernel): takes the frame's arguments by value, so it runs behind the graph, not inside it
-int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
+int run_post(Plan* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
 {
-    const float* maps = h->sharded ? h->gather : h->tensors[h->t_out].d;
-    HIPCK(h, launch_post(maps, h->mgeo, h->d_part, h->d_ticket, h->d_fb + stream, fp ? fp : h->d_fp, dyn, h->cfg.numpy_promotion, out, h->st));
+    const vnect_handle* o = h->owner;
+    HIPCK(h, launch_post(maps_of(h), o->mgeo, h->d_part, h->d_ticket, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st));
     return VNECT_OK;
 }
 
 // gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the pinned frame when
 // the frame lies in one), the pyramid from it, and on a stem_mode 2 lane the stem from the batch tensor (the host does not know whether
 // the crop's squarify step is a copy, which the stem's frame form needs; the results are the same bit for bit)
-static int run_pre_tracked(vnect_handle* h, vnect_handle* L, int stream, const FrameDyn& dyn, const TrackedSrc& tk, bool timed)
+static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn& dyn, const TrackedSrc& tk, bool timed)
 {
     TrackState* ts = h->d_track + stream;
+    const Stream& sm = h->streams[stream];
     if (tk.pinned_dev)
-        HIPCK(h, launch_frame_copy_track(ts, tk.pinned_dev, h->track_buf[stream], h->track_H[stream], h->track_W[stream], tk.stride, tk.pinned_end, L->st));
-    HIPCK(h, launch_pyramid_track(ts, dyn, tk.pinned_dev != nullptr, L->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
+        HIPCK(h, launch_frame_copy_track(ts, tk.pinned_dev, sm.track_buf, sm.track_H, sm.track_W, tk.stride, tk.pinned_end, L->st));
+    HIPCK(h, launch_pyramid_track(ts, dyn, tk.pinned_dev != nullptr, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
     if (L->stem_mode == 2) {
-        StemArgs a = L->stem;
-        a.prof = timed ? L->d_prof + PROF_SLOTS * L->l_conv1 : nullptr;
-        a.prof_end = timed ? L->d_prof_end + (size_t)PROF_WGS * L->l_conv1 : nullptr;
+        StemArgs a = stamped(L, L->stem, L->l_conv1, timed);
         a.from_frame = 0;
         HIPCK(h, launch_stem(a, L->st));
     }
@@ -128,23 +132,20 @@ static int run_pre_tracked(vnect_handle* h, vnect_handle* L, int stream, const F
 //                 (OneEuroFilter.py:19-23) -> VNECT_E_TIMEORDER.
 // Nothing is committed here: the reference would leave half-updated filters behind its exception, this path rejects the call
 // before any state changes, and the host-side copy of the last timestamps moves only after the frame has been enqueued.
-int check_time(vnect_handle* h, double t2d, double t3d, int s)
+int check_time(vnect_handle* h, const Stream& s, double t2d, double t3d)
 {
-    if (h->have2[s] && h->last2[s] != 0.0 && t2d != 0.0) {
-        if (t2d == h->last2[s]) return fail(h, VNECT_E_TIMESTAMP, "t2d equals the previous 2-D filter timestamp");
-        if (t2d < h->last2[s]) return fail(h, VNECT_E_TIMEORDER, "t2d is earlier than the previous 2-D filter timestamp");
+    if (s.t.have2 && s.t.last2 != 0.0 && t2d != 0.0) {
+        if (t2d == s.t.last2) return fail(h, VNECT_E_TIMESTAMP, "t2d equals the previous 2-D filter timestamp");
+        if (t2d < s.t.last2) return fail(h, VNECT_E_TIMEORDER, "t2d is earlier than the previous 2-D filter timestamp");
     }
-    if (h->have3[s] && h->last3[s] != 0.0 && t3d != 0.0) {
-        if (t3d == h->last3[s]) return fail(h, VNECT_E_TIMESTAMP, "t3d equals the previous 3-D filter timestamp");
-        if (t3d < h->last3[s]) return fail(h, VNECT_E_TIMEORDER, "t3d is earlier than the previous 3-D filter timestamp");
+    if (s.t.have3 && s.t.last3 != 0.0 && t3d != 0.0) {
+        if (t3d == s.t.last3) return fail(h, VNECT_E_TIMESTAMP, "t3d equals the previous 3-D filter timestamp");
+        if (t3d < s.t.last3) return fail(h, VNECT_E_TIMEORDER, "t3d is earlier than the previous 3-D filter timestamp");
     }
     return VNECT_OK;
 }
 // `self.__lasttime = timestamp` runs on every call, also with timestamp 0.0 / None
-void commit_time(vnect_handle* h, double t2d, double t3d, int s)
-{
-    h->have2[s] = h->have3[s] = true, h->last2[s] = t2d, h->last3[s] = t3d;
-}
+void commit_time(Stream& s, double t2d, double t3d) { s.t = {true, true, t2d, t3d}; }
 
 int reset_filters_impl(vnect_handle* h, int stream)  // -1: every stream
 {
@@ -163,7 +164,7 @@ int reset_filters_impl(vnect_handle* h, int stream)  // -1: every stream
     for (int s = 0; s < VNECT_MAX_STREAMS; s++) {
         if (stream >= 0 && s != stream) continue;
         HIPCK(h, hipMemcpyAsync(h->d_fb + s, fb.data(), sizeof(FilterBank), hipMemcpyHostToDevice, h->st));
-        h->have2[s] = h->have3[s] = false;
+        h->streams[s].t.have2 = h->streams[s].t.have3 = false;
     }
     HIPCK(h, hipStreamSynchronize(h->st));
     return VNECT_OK;
@@ -202,12 +203,12 @@ struct RoctxRange {
 // pyramid-sharded handle's graph ends with the conv stack: the exchange (whose flag value / parity change every frame) and the
 // merge + arg-max launch behind it are eager (two captured parts around the exchange -- the
 // second part is the single arg-max launch, which gains nothing from a graph of its own).
-static int run_frame_kernels(vnect_handle* h, bool timed)
+static int run_frame_kernels(Plan* h, bool timed)
 {
     const size_t pbytes = h->layers.size() * PROF_SLOTS * sizeof(unsigned long long);
     int rc = run_network(h, timed, h->stem_mode == 2);  // stem_mode 2: run_pre has launched the stem in front of this
     if (rc) return rc;
-    if (!h->sharded && !h->post_merged && (rc = run_argmax(h))) return rc;
+    if (!h->owner->sharded && !h->post_merged && (rc = run_argmax(h))) return rc;
     if (timed) {
         HIPCK(h, hipMemcpyAsync(h->h_prof, h->d_prof, pbytes, hipMemcpyDeviceToHost, h->st));
         HIPCK(h, hipMemcpyAsync(h->h_prof_end, h->d_prof_end, h->layers.size() * PROF_WGS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
@@ -215,20 +216,20 @@ static int run_frame_kernels(vnect_handle* h, bool timed)
     return VNECT_OK;
 }
 
-int build_graph(vnect_handle* h)
+int build_graph(Plan* h)
 {
     if (h->gexec) hipGraphExecDestroy(h->gexec), h->gexec = nullptr;
     if (h->graph) hipGraphDestroy(h->graph), h->graph = nullptr;
     if (h->pgexec) hipGraphExecDestroy(h->pgexec), h->pgexec = nullptr;
     if (h->pgraph) hipGraphDestroy(h->pgraph), h->pgraph = nullptr;
-    if (!h->cfg.use_graph) return VNECT_OK;
+    if (!h->owner->cfg.use_graph) return VNECT_OK;
     HIPCK(h, hipStreamBeginCapture(h->st, hipStreamCaptureModeThreadLocal));
     int rc = run_frame_kernels(h, false);
     hipError_t e = hipStreamEndCapture(h->st, &h->graph);
     if (rc) return rc;
     HIPCK(h, e);
     HIPCK(h, hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0));
-    if (h->is_twin) return VNECT_OK;  // profiled frames always run on the first lane
+    if (!h->prof_graph) return VNECT_OK;
     // profiling twin: identical launches, but every conv kernel stamps {min start, max end} (s_memrealtime)
     HIPCK(h, hipStreamBeginCapture(h->st, hipStreamCaptureModeThreadLocal));
     rc = run_frame_kernels(h, true);
@@ -239,88 +240,28 @@ int build_graph(vnect_handle* h)
     return VNECT_OK;
 }
 
-void destroy_twins(vnect_handle* h)
-{
-    for (vnect_handle* t : h->twins) {
-        if (t->st) hipStreamSynchronize(t->st);
-        if (t->gexec) hipGraphExecDestroy(t->gexec);
-        if (t->graph) hipGraphDestroy(t->graph);
-        for (int i = 0; i < RING; i++)
-            if (t->h_fp[i]) hipHostFree(t->h_fp[i]);
-        for (void* p : t->dev_allocs) hipFree(p);
-        if (t->st) hipStreamDestroy(t->st);
-        delete t;
-    }
-    h->twins.clear();
-    h->last_lane = nullptr;
-}
-
-// One more lane of the frame pipeline (vnect_config::lanes): same layers and weights, its own stream, activation arena,
-// workspace, arg-max scratch, geometry block and graph.
-static int build_twin(vnect_handle* h)
-{
-    vnect_handle* t = new vnect_handle();
-    h->twins.push_back(t);
-    t->is_twin = true;
-    t->cfg = h->cfg, t->S = h->S, t->Snet = h->Snet, t->bf16 = h->bf16, t->f16 = h->f16, t->keep_activations = false;
-    HIPCK(h, hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
-    // shared: read-only tables and frames; the filter bank (its users are chained by events)
-    t->frames = h->frames, t->d_stabs = h->d_stabs, t->mgeo = h->mgeo, t->d_fb = h->d_fb;
-    t->slots = h->slots;
-    int rc;
-    if ((rc = dev_alloc(t, &t->d_fp, 1))) return fail(h, rc, t->err);
-    if ((rc = dev_alloc(t, &t->d_part, (size_t)NJ * ARG_SLABS_MAX))) return fail(h, rc, t->err);
-    if ((rc = dev_alloc(t, &t->d_ticket, 4))) return fail(h, rc, t->err);
-    HIPCK(h, hipMemset(t->d_ticket, 0, 4 * sizeof(unsigned)));
-    t->post_merged = h->post_merged;
-    for (int i = 0; i < RING; i++) HIPCK(h, hipHostMalloc((void**)&t->h_fp[i], sizeof(FrameParams), hipHostMallocDefault));
-    t->tensors = h->tensors, t->layers = h->layers, t->tensor_by_name = h->tensor_by_name;
-    t->t_input4 = h->t_input4, t->t_out = h->t_out;
-    char* base = nullptr;
-    if ((rc = dev_alloc(t, &base, h->arena_bytes))) return fail(h, rc, t->err);
-    HIPCK(h, hipMemset(base, 0, h->arena_bytes));
-    for (size_t i = 0; i < t->tensors.size(); i++) t->tensors[i].d = (float*)(base + h->arena_off[i]);
-    t->ws_floats = h->ws_floats;
-    if (t->ws_floats && (rc = dev_alloc(t, &t->ws, t->ws_floats))) return fail(h, rc, t->err);
-    for (Layer& L : t->layers)
-        if (L.op == OP_CONV) bind_activations(t, L);
-    t->l_conv1 = h->l_conv1, t->l_pool1 = h->l_pool1;
-    t->stabs_host = h->stabs_host;
-    setup_stem(t);  // same plan as lane 0, this lane's arena and geometry block
-    t->finalized = true;
-    if ((rc = build_graph(t))) return fail(h, rc, t->err);
-    HIPCK(h, hipStreamSynchronize(t->st));
-    return VNECT_OK;
-}
-
-int build_twins(vnect_handle* h)
-{
-    destroy_twins(h);
-    if (h->cfg.lanes < 2 || h->sharded || h->keep_activations) return VNECT_OK;
-    for (int i = 1; i < h->cfg.lanes; i++) {
-        int rc = build_twin(h);
-        if (rc) return rc;
-    }
-    return VNECT_OK;
-}
-
 // Frames (or batches of two streams' frames) in flight, and how many may be: one lane queues two on its stream, more lanes one each
 static unsigned long long units_in_flight(const vnect_handle* h)
 {
-    return h->seq_submit == h->seq_collect ? 0 : h->unit_submit - h->ring_unit[h->seq_collect % RING];
+    return h->seq_submit == h->seq_collect ? 0 : h->unit_submit - h->ring[h->seq_collect % RING].unit;
 }
-static unsigned long long max_in_flight(const vnect_handle* h) { return h->twins.empty() ? 2 : h->twins.size() + 1; }
+static unsigned long long max_in_flight(const vnect_handle* h) { return std::max<size_t>(h->lanes.size(), 2); }
 
 // the lane a frame (or batch) submitted now runs on: the first whose last frame has been collected (lane 0 when nothing is in flight)
-static vnect_handle* pick_lane(vnect_handle* h, bool timed)
+static Plan* pick_lane(vnect_handle* h, bool timed)
 {
-    if (!h->twins.empty() && !timed && h->lane_seq >= (long long)h->seq_collect)
-        for (vnect_handle* t : h->twins)
-            if (t->lane_seq < (long long)h->seq_collect) return t;
+    if (!timed)
+        for (Plan* l : h->lanes)
+            if (l->lane_seq < (long long)h->seq_collect) return l;
     return h;
 }
 
-// enqueue one frame from a resident slot; results land in h_out[ring].  `tk`: a tracked frame (vnect_submit_tracked*) -- its crop and
+// use_graph 2 (auto): a frame submitted while nothing is in flight -- the synchronous pattern -- is launched eagerly (median
+// 6.6 us shorter than pyramid + graph replay + joints, A/B in one call, both precisions; the host has nothing else to do
+// meanwhile), a frame submitted behind others replays the graph (the host must stay ahead of two or three lanes)
+static bool replays(const vnect_handle* h, const Plan* p) { return p->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect); }
+
+// enqueue one frame from a resident slot; results land in its ring entry's slot.  `tk`: a tracked frame (vnect_submit_tracked*) -- its crop and
 // geometry are the stream's state on the device, the frame is the whole one (in `slot`, or in a pinned buffer: then slot is -1)
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream, const TrackedSrc* tk)
 {
@@ -328,7 +269,8 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     if (stream != 0 && h->sharded) return fail(h, VNECT_E_ARG, "a pyramid-sharded handle serves one stream");
     if (!(tk && tk->pinned_dev) && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0))
         return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
-    if (tk && !tk->pinned_dev && (h->slots[slot].H != h->track_H[stream] || h->slots[slot].W != h->track_W[stream]))
+    Stream& sm = h->streams[stream];
+    if (tk && !tk->pinned_dev && (h->slots[slot].H != sm.track_H || h->slots[slot].W != sm.track_W))
         return fail(h, VNECT_E_ARG, "the slot's frame is not of the size vnect_track_begin gave for this stream");
     if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
     if (h->sharded && !comm_ready(h))  // refuse before any filter / timestamp state changes
@@ -336,90 +278,82 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     FrameParams fp;
     int rc = tk ? VNECT_OK : squarify_params(h, h->slots[slot].H, h->slots[slot].W, &fp);
     if (rc) return rc;
-    rc = check_time(h, t2d, t3d, stream);
+    rc = check_time(h, sm, t2d, t3d);
     if (rc) return rc;
     const int ring = (int)(h->seq_submit % RING);
+    InFlight& e = h->ring[ring];
     FrameDyn dyn{};
     dyn.t2d = t2d, dyn.t3d = t3d;
     if (tk && tk->pinned_dev) {
-        dyn.frame = h->track_buf[stream];  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
+        dyn.frame = sm.track_buf;  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
     } else {
         dyn.row_stride = h->slots[slot].stride;
         dyn.frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
     }
-    if (tk) dyn.xfail = &h->d_track[stream].fail, dyn.xseq = h->track_seq[stream];  // a refused crop skips the joints stage
+    if (tk) dyn.xfail = &h->d_track[stream].fail, dyn.xseq = sm.track_seq;  // a refused crop skips the joints stage
     const bool timed = h->profiling;
     // Lane: the first whose last frame has been collected (lane 0 when nothing is in flight).  Frames on different lanes
     // overlap -- the idle CUs between one frame's launches are the other frames' -- and only the post-processing launch of a frame
     // (post_kernel: merge + arg-max + joints; with VNECT_NO_POST_MERGE=1 only the joints kernel) waits for the SAME video's previous
     // frame.  Measured (round 3, A/B in one call): 1 388-1 390 frames/s three deep with the merged launch, 1 388-1 389 with the two
     // launches -- ordering the 17-us merged launch instead of the 11-us joints kernel costs nothing measurable.
-    vnect_handle* L = pick_lane(h, timed);
+    Plan* L = pick_lane(h, timed);
     // the stream's previous frame ran on another lane and may still be in flight: the filters are a chain (its post-processing waits
     // for it), and a tracked frame's crop is that frame's box kernel's output (everything of it waits)
-    const bool after_prev = h->stream_seq[stream] >= (long long)h->seq_collect && h->stream_lane[stream] && h->stream_lane[stream] != L;
-    if (!tk && (rc = sync_geometry(L, fp))) return fail(h, rc, L->err);
-    if (tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->done[h->stream_seq[stream] % RING], 0));
+    const bool after_prev = sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L;
+    if (!tk && (rc = sync_geometry(L, fp))) return rc;
+    if (tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
     if (timed) HIPCK(h, hipEventRecord(h->ev[0], L->st));
     {
         RoctxRange r("vnect:gen_input_batch");
-        if ((rc = tk ? run_pre_tracked(h, L, stream, dyn, *tk, timed) : run_pre(L, dyn, timed))) return fail(h, rc, tk ? h->err : L->err);
+        if ((rc = tk ? run_pre_tracked(h, L, stream, dyn, *tk, timed) : run_pre(L, dyn, timed))) return rc;
     }
     RoctxRange r_net("vnect:conv_stack+merge+argmax");
-    // use_graph 2 (auto): a frame submitted while nothing is in flight -- the synchronous pattern -- is launched eagerly (median
-    // 6.6 us shorter than pyramid + graph replay + joints, A/B in one call, both precisions; the host has nothing else to do
-    // meanwhile), a frame submitted behind others replays the graph (the host must stay ahead of two or three lanes)
-    const bool replay = L->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect);
-    if (replay && !timed) {
+    if (replays(h, L) && !timed) {
         HIPCK(h, hipGraphLaunch(L->gexec, L->st));
     } else if (L->pgexec && timed) {
         HIPCK(h, hipGraphLaunch(L->pgexec, L->st));
-    } else {
-        rc = run_frame_kernels(L, timed);
-        if (rc) return fail(h, rc, L->err);
+    } else if ((rc = run_frame_kernels(L, timed))) {
+        return rc;
     }
 #if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
     // test build only (vnect_test_maps_override): the conv stack's output replaced by the caller's maps, on the frame's own lane stream --
     // everything behind it (post-processing, box stage, ring slot, collect) is the product's path on chosen maps
-    if (h->test_maps_cur >= 0 && !L->sharded)
+    if (h->test_maps_cur >= 0 && !h->sharded)
         HIPCK(h, hipMemcpyAsync(L->tensors[L->t_out].d, h->test_maps[h->test_maps_cur], (size_t)h->S * HM * HM * MAPC * sizeof(float),
                                 hipMemcpyDeviceToDevice, L->st));
 #endif
-    if (L->sharded) {  // the one exchange of the pyramid path, then the merge + arg-max over everybody's maps
+    if (h->sharded) {  // (one lane.)  The one exchange of the pyramid path, then the merge + arg-max over everybody's maps
         if (g_roctx.pop) g_roctx.pop(), g_roctx.push("vnect:exchange+merge+argmax");
-        if ((rc = exchange_maps(L, h->seq_submit, ring))) return fail(h, rc, L->err);
-        dyn.xfail = L->d_xfail, dyn.xseq = (unsigned)(h->seq_submit + 1);  // post_kernel skips the joints stage of a frame whose exchange failed
-        if (!L->post_merged && (rc = run_argmax(L))) return fail(h, rc, L->err);
+        if ((rc = exchange_maps(h, h->seq_submit, ring))) return rc;
+        dyn.xfail = h->d_xfail, dyn.xseq = (unsigned)(h->seq_submit + 1);  // post_kernel skips the joints stage of a frame whose exchange failed
+        if (!L->post_merged && (rc = run_argmax(L))) return rc;
     }
     if (g_roctx.pop) g_roctx.pop(), g_roctx.push(L->post_merged ? "vnect:merge+argmax+filters+readoff" : "vnect:filters+readoff");  // r_net's pop now closes this range
     // the filters are a chain WITHIN a video stream: this frame's post-processing waits for the stream's previous frame if that one
     // ran on another lane and may still be in flight (frames of other streams are no concern of it)
-    if (!tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->done[h->stream_seq[stream] % RING], 0));
+    if (!tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
     // writes the ring slot in pinned host memory
     // A tracked frame also turns its joints into frame coordinates and grows the next crop and its geometry (trackbox.h): as the tail of
     // post_kernel (the default: measured faster, TRACKING.md), or -- the two-launch post-processing, VNECT_TRACK_BOX_LAUNCH=1 (A/B, read per
     // frame) -- as a launch of its own behind it, which reads the joints back from the result ring slot
     const bool box_tail = tk && L->post_merged && !getenv("VNECT_TRACK_BOX_LAUNCH");
     if (box_tail) {
-        const float* maps = L->sharded ? L->gather : L->tensors[L->t_out].d;
-        HIPCK(h, launch_post_track(maps, L->mgeo, L->d_part, L->d_ticket, L->d_fb + stream, h->d_track + stream, dyn, h->cfg.numpy_promotion,
-                                   h->h_out_dev[ring], h->h_tout_dev + ring, L->st));
+        HIPCK(h, launch_post_track(maps_of(L), h->mgeo, L->d_part, L->d_ticket, h->d_fb + stream, h->d_track + stream, dyn, h->cfg.numpy_promotion,
+                                   e.out_dev, h->h_tout_dev + ring, L->st));
     } else {
         const FrameParams* tfp = tk ? &h->d_track[stream].fp : nullptr;
-        if ((rc = L->post_merged ? run_post(L, dyn, h->h_out_dev[ring], stream, tfp) : run_joints(L, dyn, h->h_out_dev[ring], stream, tfp)))
-            return fail(h, rc, L->err);
-        if (tk) HIPCK(h, launch_track_box(h->d_track + stream, h->h_out_dev[ring], h->h_tout_dev + ring, dyn.xseq, L->st));
+        if ((rc = L->post_merged ? run_post(L, dyn, e.out_dev, stream, tfp) : run_joints(L, dyn, e.out_dev, stream, tfp))) return rc;
+        if (tk) HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st));
     }
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
-    HIPCK(h, hipEventRecord(h->done[ring], L->st));
-    if (tk) h->ring_time[ring] = {h->have2[stream], h->have3[stream], h->last2[stream], h->last3[stream]};  // (a refused crop rolls back)
-    commit_time(h, t2d, t3d, stream);  // only now: every launch of the frame has been accepted
-    h->stream_seq[stream] = (long long)h->seq_submit, h->stream_lane[stream] = L, h->ring_stream[ring] = stream;
-    h->ring_unit[ring] = h->unit_submit++, h->ring_batch[ring] = false, h->ring_prof[ring] = nullptr;
-    h->ring_track[ring] = tk != nullptr;
-    if (tk) h->track_seq[stream]++;
-    h->last_lane = L;
-    L->lane_seq = (long long)h->seq_submit;
+    HIPCK(h, hipEventRecord(e.done, L->st));
+    // only now: every launch of the frame has been accepted
+    e.stream = stream, e.unit = h->unit_submit++, e.batch = false, e.prof = nullptr, e.tracked = tk != nullptr;
+    e.before = sm.t;  // (a tracked frame's refused crop rolls back)
+    commit_time(sm, t2d, t3d);
+    sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
+    if (tk) sm.track_seq++;
     if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
     h->seq_submit++;
     *ring_out = ring;
@@ -427,7 +361,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
 }
 
 // a profiled batch's per-layer times (vnect_get_batch_layer_info): first workgroup start to last workgroup end of every conv launch
-static void read_layer_ms(vnect_handle* b)
+static void read_layer_ms(Plan* b)
 {
     for (size_t i = 0; i < b->layers.size(); i++) {
         Layer& L = b->layers[i];
@@ -447,8 +381,9 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     // the caller is about to consume the joints: poll (a frame is ~1 ms) before falling back to a blocking wait, whose
     // wake-up alone costs tens of microseconds of idle GPU per frame
     hipError_t q = hipErrorNotReady;
-    for (int spin = 0; spin < 200000 && (q = hipEventQuery(h->done[ring])) == hipErrorNotReady; spin++) {}
-    if (q == hipErrorNotReady) q = hipEventSynchronize(h->done[ring]);
+    InFlight& e = h->ring[ring];
+    for (int spin = 0; spin < 200000 && (q = hipEventQuery(e.done)) == hipErrorNotReady; spin++) {}
+    if (q == hipErrorNotReady) q = hipEventSynchronize(e.done);
     HIPCK(h, q);
     h->seq_collect++;
     if (h->h_xstatus && h->h_xstatus[ring]) {  // one word per ring slot: the error lands on the frame it belongs to
@@ -458,24 +393,23 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         return fail(h, VNECT_E_COMM, "pyramid exchange: a peer's maps did not arrive within the bound (ranks out of step?); "
                                      "destroy the handles of every rank and reconnect");
     }
-    if (stream_out) *stream_out = h->ring_stream[ring];
+    if (stream_out) *stream_out = e.stream;
     if (rect_out)
-        for (int k = 0; k < 4; k++) rect_out[k] = h->ring_track[ring] ? h->h_tout[ring].rect[k] : -1;
-    if (h->ring_track[ring] && h->h_tout[ring].status != SQ_OK) {  // the frame's crop was refused: its joints stage was skipped
-        const int s = h->ring_stream[ring];
-        if (h->track_stopped[s])
+        for (int k = 0; k < 4; k++) rect_out[k] = e.tracked ? h->h_tout[ring].rect[k] : -1;
+    if (e.tracked && h->h_tout[ring].status != SQ_OK) {  // the frame's crop was refused: its joints stage was skipped
+        Stream& sm = h->streams[e.stream];
+        if (sm.track_stopped)
             return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
-        h->track_stopped[s] = true;
+        sm.track_stopped = true;
         // vnect_infer's refusal commits no timestamp, and the device's filters did not see this frame (nor the stream's later ones, which
         // are refused too): the host's last timestamps go back to what they were before it
-        const auto& tb = h->ring_time[ring];
-        h->have2[s] = tb.have2, h->have3[s] = tb.have3, h->last2[s] = tb.last2, h->last3[s] = tb.last3;
+        sm.t = e.before;
         return fail(h, VNECT_E_ARG, crop_refusal(h->h_tout[ring].status));
     }
-    if (j2) memcpy(j2, h->h_out[ring]->j2d, sizeof(double) * NJ * 2);
-    if (j3) memcpy(j3, h->h_out[ring]->j3d, sizeof(float) * NJ * 3);
-    if (h->ring_prof[ring]) read_layer_ms(h->ring_prof[ring]), h->ring_prof[ring] = nullptr;
-    if (h->profiling && !h->ring_batch[ring]) {
+    if (j2) memcpy(j2, e.out->j2d, sizeof(double) * NJ * 2);
+    if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
+    if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
+    if (h->profiling && !e.batch) {
         float frame_ms = 0;
         hipEventElapsedTime(&frame_ms, h->ev[0], h->ev[3]);
         unsigned long long first = ~0ull, last = 0;
@@ -601,7 +535,7 @@ int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int 
     // a frame still being read by an in-flight inference must not be overwritten: wait for that inference only (frames in
     // other slots keep running, so a pipelined caller uploads frame k+1 while frames k and k-1 compute)
     const long long q = h->slots[slot].last_use;
-    if (q >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->done[q % RING]));
+    if (q >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->ring[q % RING].done));
     HIPCK(h, hipMemcpy2D(dst, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, H, hipMemcpyHostToDevice));
     h->slots[slot].H = H, h->slots[slot].W = W, h->slots[slot].stride = (long long)W * 3;
     return VNECT_OK;
@@ -651,22 +585,21 @@ int prime(vnect_handle* h)
         rc = enqueue_frame(h, ps, t, t, &ring);
         if (!rc) rc = collect_impl(h, nullptr, nullptr);
     }
-    for (int rep = 0; rep < 2 && !rc && !h->twins.empty(); rep++) {  // the other lanes: as many frames in flight as there are lanes
-        const int depth = (int)h->twins.size() + 1;
+    for (int rep = 0; rep < 2 && !rc && h->lanes.size() > 1; rep++) {  // the other lanes: as many frames in flight as there are lanes
+        const int depth = (int)h->lanes.size();
         for (int i = 0; i < depth && !rc; i++, t += 1.0) rc = enqueue_frame(h, ps, t, t, &ring);
         for (int i = 0; i < depth && !rc; i++) rc = collect_impl(h, nullptr, nullptr);
     }
     // the batched plan of two streams (vnect_set_stream_batch): synchronous batches, then as many in flight as there are lanes
-    for (int i = 0; i < 8 && !rc && !h->blanes.empty(); i++) {
+    for (int i = 0; i < 8 && !rc && !h->bplans.empty(); i++) {
         const int32_t st2[2] = {0, 1}, sl[2] = {ps, ps};
-        const int depth = i < 6 ? 1 : (int)h->blanes.size();
+        const int depth = i < 6 ? 1 : (int)h->bplans.size();
         for (int d = 0; d < depth && !rc; d++, t += 1.0) {
             const double tt[2] = {t, t};
             rc = enqueue_batch(h, st2, sl, tt, tt);
         }
         for (int d = 0; d < 2 * depth && !rc; d++) rc = collect_impl(h, nullptr, nullptr);
     }
-    for (vnect_handle* b : h->blanes) b->fp_dev_valid = b->fp_dev2_valid = false;
     // A fresh handle's state comes back UNCONDITIONALLY: whatever is still in flight is drained and dropped, the slot is emptied, the
     // filter banks are rebuilt.  What the failure means for vnect_finalize depends on its kind (advisor, round 4):
     //  * VNECT_E_HIP / VNECT_E_INTERNAL / VNECT_E_COMM -- a launch was refused or the device faulted on the launch plan this handle
@@ -675,16 +608,15 @@ int prime(vnect_handle* h)
     //    vnect_last_error, vnect_finalize succeeds.
     const std::string why = rc ? h->err : std::string();
     if (rc) {
-        (void)hipStreamSynchronize(h->st);
-        for (vnect_handle* tw : h->twins) (void)hipStreamSynchronize(tw->st);
+        for (Plan* l : h->lanes) (void)hipStreamSynchronize(l->st);
         (void)hipGetLastError();
         h->seq_collect = h->seq_submit;
     }
     h->slots[ps] = vnect_handle::SlotInfo();
     const int rf = reset_filters_impl(h);  // (sets h->err itself when it fails)
-    for (int s = 0; s < VNECT_MAX_STREAMS; s++) h->stream_seq[s] = -1, h->stream_lane[s] = nullptr;
-    h->fp_dev_valid = false;  // (the next frame uploads its own geometry)
-    for (vnect_handle* tw : h->twins) tw->fp_dev_valid = false;
+    for (Stream& sm : h->streams) sm = Stream{};  // (no crop buffer to lose yet: tracking begins on a finalized handle, and this runs inside vnect_finalize)
+    for (Plan* l : h->lanes) l->fp_dev_valid = false;  // (the next frame uploads its own geometry)
+    for (Plan* b : h->bplans) b->fp_dev_valid = b->fp_dev2_valid = false;
     const bool serious = rc == VNECT_E_HIP || rc == VNECT_E_INTERNAL || rc == VNECT_E_COMM;
     if (rf) {  // the filter banks could not be rebuilt: the handle must not be used; keep both reasons
         if (rc) h->err += "; behind a failed warm start: " + why;
@@ -706,7 +638,7 @@ int prime(vnect_handle* h)
 // timestamp and every slot as it was.
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d)
 {
-    if (h->blanes.empty()) return fail(h, VNECT_E_STATE, "vnect_submit_streams of two frames needs vnect_set_stream_batch(h, 2) before vnect_finalize");
+    if (h->bplans.empty()) return fail(h, VNECT_E_STATE, "vnect_submit_streams of two frames needs vnect_set_stream_batch(h, 2) before vnect_finalize");
     FrameParams fp[2];
     FrameDyn dyn[2] = {};
     for (int k = 0; k < 2; k++) {
@@ -720,84 +652,64 @@ int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots,
     for (int k = 0; k < 2; k++) {
         const auto& si = h->slots[slots[k]];
         if ((rc = squarify_params(h, si.H, si.W, &fp[k]))) return rc;
-        if ((rc = check_time(h, t2d[k], t3d[k], streams[k]))) return rc;
+        if ((rc = check_time(h, h->streams[streams[k]], t2d[k], t3d[k]))) return rc;
         dyn[k].t2d = t2d[k], dyn[k].t3d = t3d[k];
         dyn[k].row_stride = si.stride;
         dyn[k].frame = h->frames + (size_t)slots[k] * h->cfg.max_frame_bytes;
     }
     const bool timed = h->profiling;
-    vnect_handle* L = pick_lane(h, timed);
-    vnect_handle* b = h->blanes[L == h ? 0 : 1 + (std::find(h->twins.begin(), h->twins.end(), L) - h->twins.begin())];
-    if ((rc = sync_geometry(b, fp[0], 0)) || (rc = sync_geometry(b, fp[1], 1))) return fail(h, rc, b->err);
+    Plan* L = pick_lane(h, timed);
+    Plan* b = h->bplans[std::find(h->lanes.begin(), h->lanes.end(), L) - h->lanes.begin()];
+    if ((rc = sync_geometry(b, fp[0], 0)) || (rc = sync_geometry(b, fp[1], 1))) return rc;
     // gen_input_batch of both frames inside the stem launch (as run_pre does for one frame), or the batch tensor first
     const bool frame_stem = b->stem_mode == 2 && b->stem_frame_ok && fp[0].sq.copy && fp[1].sq.copy;
     if (!frame_stem)
-        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], b->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
+        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], h->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
     if (b->stem_mode == 2) {
-        StemArgs a = b->stem;
-        a.prof = timed ? b->d_prof + PROF_SLOTS * b->l_conv1 : nullptr;
-        a.prof_end = timed ? b->d_prof_end + (size_t)PROF_WGS * b->l_conv1 : nullptr;
+        StemArgs a = stamped(b, b->stem, b->l_conv1, timed);
         a.from_frame = frame_stem;
         a.dyn = dyn[0], a.frame2 = dyn[1].frame, a.stride2 = dyn[1].row_stride;
         HIPCK(h, launch_stem(a, b->st));
     }
-    const bool replay = b->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect);
-    if (replay && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
-    else if ((rc = run_frame_kernels(b, timed))) return fail(h, rc, b->err);
+    if (replays(h, b) && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
+    else if ((rc = run_frame_kernels(b, timed))) return rc;
     const size_t half = (size_t)b->S * HM * HM * MAPC;
     const float* maps = b->tensors[b->t_out].d;
     for (int k = 0; k < 2; k++) {
-        const int s = streams[k], ring = (int)((h->seq_submit + k) % RING);
+        const Stream& sm = h->streams[streams[k]];
+        const InFlight& e = h->ring[(h->seq_submit + k) % RING];
         // the filters are a chain within a stream: wait for its previous frame if that one ran on another lane and may be in flight
-        if (h->stream_seq[s] >= (long long)h->seq_collect && h->stream_lane[s] && h->stream_lane[s] != L)
-            HIPCK(h, hipStreamWaitEvent(b->st, h->done[h->stream_seq[s] % RING], 0));
-        HIPCK(h, launch_post(maps + k * half, b->mgeo, b->d_part, b->d_ticket, h->d_fb + s, k ? b->d_fp2 : b->d_fp, dyn[k], h->cfg.numpy_promotion,
-                             h->h_out_dev[ring], b->st));
-        HIPCK(h, hipEventRecord(h->done[ring], b->st));
+        if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L) HIPCK(h, hipStreamWaitEvent(b->st, h->ring[sm.seq % RING].done, 0));
+        HIPCK(h, launch_post(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + streams[k], k ? b->d_fp2 : b->d_fp, dyn[k], h->cfg.numpy_promotion,
+                             e.out_dev, b->st));
+        HIPCK(h, hipEventRecord(e.done, b->st));
     }
     for (int k = 0; k < 2; k++) {  // every launch of the batch has been accepted: commit
-        const int s = streams[k], ring = (int)(h->seq_submit % RING);
-        commit_time(h, t2d[k], t3d[k], s);
-        h->stream_seq[s] = (long long)h->seq_submit, h->stream_lane[s] = L, h->ring_stream[ring] = s;
-        h->ring_unit[ring] = h->unit_submit, h->ring_batch[ring] = true, h->ring_prof[ring] = (timed && k == 1) ? b : nullptr;
+        Stream& sm = h->streams[streams[k]];
+        InFlight& e = h->ring[h->seq_submit % RING];
+        e.stream = streams[k], e.unit = h->unit_submit, e.batch = true, e.prof = (timed && k == 1) ? b : nullptr, e.tracked = false;
+        commit_time(sm, t2d[k], t3d[k]);
+        sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
         h->slots[slots[k]].last_use = (long long)h->seq_submit;
-        L->lane_seq = (long long)h->seq_submit;
         h->seq_submit++;
     }
     h->unit_submit++;
-    h->last_lane = L;
     return VNECT_OK;
 }
 
 // vnect_forward of 2 S images on the batched plan (parity / debug aid): the first lane's batched plan on the handle's stream
 int forward_batch(vnect_handle* h, const float* batch, float* out)
 {
-    vnect_handle* b = h->blanes[0];
+    Plan* b = h->bplans[0];
     const long long npix = (long long)b->Snet * BOX * BOX;
     HIPCK(h, hipMemcpyAsync(h->in3, batch, npix * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
     HIPCK(h, launch_pad3to4(h->in3, b->tensors[b->t_input4].d, npix, b->el(), h->st));
     int rc = run_network(b, false);
-    if (rc) return fail(h, rc, b->err);
+    if (rc) return rc;
     const Tensor& t = b->tensors[b->t_out];
     HIPCK(h, hipMemcpyAsync(out, t.d, t.bytes(), hipMemcpyDeviceToHost, h->st));
     HIPCK(h, hipStreamSynchronize(h->st));
     return VNECT_OK;
-}
-
-void destroy_batch_lanes(vnect_handle* h)
-{
-    for (vnect_handle* b : h->blanes) {
-        if (b->st) hipStreamSynchronize(b->st);  // (the lane's stream: its owner destroys it)
-        if (b->gexec) hipGraphExecDestroy(b->gexec);
-        if (b->graph) hipGraphDestroy(b->graph);
-        for (int i = 0; i < RING; i++)
-            if (b->h_fp[i]) hipHostFree(b->h_fp[i]);
-        if (b->h_prof) hipHostFree(b->h_prof);
-        if (b->h_prof_end) hipHostFree(b->h_prof_end);
-        for (void* p : b->dev_allocs) hipFree(p);
-        delete b;
-    }
-    h->blanes.clear();
 }
 
 // ---- tracking on the device (vnect_track_begin) --------------------------------------------------------------------------------------
@@ -806,10 +718,11 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
 {
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
     if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a pyramid-sharded handle is not supported");
-    if (!h->blanes.empty()) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
+    if (!h->bplans.empty()) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
     if (H < 1 || W < 1 || H > 65532 || (size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes)
         return fail(h, VNECT_E_ARG, "vnect_track_begin: frame size out of range (1 .. 65532 rows, at most max_frame_bytes)");
-    if (h->stream_seq[stream] >= (long long)h->seq_collect) return fail(h, VNECT_E_STATE, "vnect_track_begin: frames of this stream in flight");
+    Stream& sm = h->streams[stream];
+    if (sm.seq >= (long long)h->seq_collect) return fail(h, VNECT_E_STATE, "vnect_track_begin: frames of this stream in flight");
     int r[4] = {0, 0, W, H};
     if (rect4) {
         for (int k = 0; k < 4; k++) r[k] = rect4[k];
@@ -825,23 +738,20 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
     t.status = crop_squarify(t.h, t.w, &t.fp);
     t.fail = t.status != SQ_OK ? 1u : 0u;  // (the first tracked frame is number 1)
     const size_t need = (size_t)H * W * 3 + 16;
-    if (h->track_cap[stream] < need) {  // the crop buffer of pinned frames (the largest crop is the frame)
-        for (vnect_handle* tw : h->twins) HIPCK(h, hipStreamSynchronize(tw->st));
-        HIPCK(h, hipStreamSynchronize(h->st));
-        if (h->track_buf[stream]) {
-            HIPCK(h, hipFree(h->track_buf[stream]));
-            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->track_buf[stream]));
-            h->track_buf[stream] = nullptr, h->track_cap[stream] = 0;
+    if (sm.track_cap < need) {  // the crop buffer of pinned frames (the largest crop is the frame)
+        for (Plan* l : h->lanes) HIPCK(h, hipStreamSynchronize(l->st));
+        if (sm.track_buf) {
+            HIPCK(h, hipFree(sm.track_buf));
+            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)sm.track_buf));
+            sm.track_buf = nullptr, sm.track_cap = 0;
         }
-        int rc = dev_alloc(h, &h->track_buf[stream], need);
+        int rc = dev_alloc(h, &sm.track_buf, need);
         if (rc) return rc;
-        h->track_cap[stream] = need;
+        sm.track_cap = need;
     }
     HIPCK(h, hipMemcpyAsync(h->d_track + stream, &t, sizeof(TrackState), hipMemcpyHostToDevice, h->st));
     HIPCK(h, hipStreamSynchronize(h->st));
-    h->track_on[stream] = true, h->track_stopped[stream] = false;
-    h->track_H[stream] = H, h->track_W[stream] = W;
-    h->track_seq[stream] = 1;
+    sm.track_on = true, sm.track_stopped = false, sm.track_H = H, sm.track_W = W, sm.track_seq = 1;
     return VNECT_OK;
 }
 

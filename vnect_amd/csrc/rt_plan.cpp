@@ -50,12 +50,13 @@ int build_scale_tables(vnect_handle* h)
     HIPCK(h, hipMemcpy(h->d_stabs, &st, sizeof st, hipMemcpyHostToDevice));
     h->mgeo = mg;
     h->stabs_host = st;
-    // the stem's from-the-frame form: do all tiles' frame rectangles still fit its LDS scratch at these scales?  (lanes share the tables)
-    if (h->stem_mode == 2) h->stem_frame_ok = plan::stem_frame_fits(st, h->stem.S, h->stem.scale_base, h->stem.groups, h->stem.row0, h->bf16);
-    for (vnect_handle* tw : h->twins) tw->stabs_host = st, tw->mgeo = mg, tw->stem_frame_ok = h->stem_frame_ok;
-    for (vnect_handle* b : h->blanes) {
-        b->stabs_host = st, b->mgeo = mg;
-        b->stem_frame_ok = b->stem_mode == 2 && plan::stem_frame_fits(st, b->stem.S, 0, b->stem.groups, b->stem.row0, b->bf16, b->stem.per_stream);
+    // the stem's from-the-frame form: do all tiles' frame rectangles still fit its LDS scratch at these scales?  (every plan reads these
+    // tables; a batched plan's tiles differ from its lane's)
+    std::vector<Plan*> all = h->lanes;
+    all.insert(all.end(), h->bplans.begin(), h->bplans.end());
+    for (Plan* p : all) {
+        const StemArgs& a = p->stem;
+        p->stem_frame_ok = p->stem_mode == 2 && plan::stem_frame_fits(st, a.S, a.scale_base, a.groups, a.row0, p->bf16, a.per_stream);
     }
     return VNECT_OK;
 }
@@ -369,7 +370,7 @@ static int add_conv_tail(vnect_handle* h, const std::string& sb, const std::stri
 }
 
 // point a conv layer's arguments at h's activation buffers and workspace (weights are whatever L already holds)
-void bind_activations(vnect_handle* h, Layer& L)
+static void bind_activations(Plan* h, Layer& L)
 {
     ConvArgs& a = L.a;
     a.in = h->tensors[L.in].d;
@@ -385,7 +386,7 @@ void bind_activations(vnect_handle* h, Layer& L)
 // on handles whose layers share the arena; handles with per-layer read-back keep the stand-alone layers (their "conv1" activation
 // must exist) unless VNECT_FORCE_STEM says otherwise (the parity test reads pool1 from both forms).  VNECT_NO_STEM=1 restores the
 // three launches, VNECT_STEM=batch keeps pyramid_kernel and fuses conv1 + pool1 only (A/B runs).
-void setup_stem(vnect_handle* h)
+static void setup_stem(Plan* h)
 {
     h->stem_mode = 0, h->stem_pair = false;
     if (h->l_conv1 < 0 || h->l_pool1 != h->l_conv1 + 1) return;
@@ -402,14 +403,13 @@ void setup_stem(vnect_handle* h)
     StemArgs& a = h->stem;
     memset(&a, 0, sizeof a);
     a.batch = tin.d, a.w = C.w, a.bias = C.bias, a.out = tp.d;
-    a.fp = h->d_fp, a.tabs = h->d_stabs;
-    a.S = h->Snet, a.scale_base = h->sharded ? h->cfg.pyramid_rank : 0, a.bf16 = h->bf16, a.f16 = h->f16;
+    a.fp = h->d_fp, a.tabs = h->owner->d_stabs;
+    a.S = h->Snet, a.scale_base = h->owner->sharded ? h->owner->cfg.pyramid_rank : 0, a.bf16 = h->bf16, a.f16 = h->f16;
     // a batched plan's stem reads two frames: images 0 .. S-1 from the first stream's, S .. 2 S-1 from the second's (d_fp2)
-    a.per_stream = h->batched ? h->S : 0, a.fp2 = h->batched ? h->d_fp2 : nullptr;
+    a.per_stream = h->two_frames ? h->S : 0, a.fp2 = h->two_frames ? h->d_fp2 : nullptr;
     // row groups of 4 and 5 pooled rows (hostplan.h)
     a.groups = plan::stem_groups(a.S, a.row0);
-    // (a lane's tables are lane 0's: build_twin / build_batch_lane copy stabs_host before calling this)
-    h->stem_frame_ok = h->stem_mode == 2 && plan::stem_frame_fits(h->stabs_host, a.S, a.scale_base, a.groups, a.row0, h->bf16, a.per_stream);
+    h->stem_frame_ok = h->stem_mode == 2 && plan::stem_frame_fits(h->owner->stabs_host, a.S, a.scale_base, a.groups, a.row0, h->bf16, a.per_stream);
     // PAIR form: the launch behind pool1 is res2a_branch2a + res2a_branch1 (1x1 on pool1's 64 channels) and nothing else reads pool1:
     // the stem runs it on the pooled tile and pool1 is never written.  Not with per-layer read-back (pool1 must exist there).
     // VNECT_NO_STEM_PAIR=1: A/B runs.
@@ -433,7 +433,7 @@ static size_t padded(const Tensor& t) { return (t.bytes() + (size_t)64 * t.Cs * 
 // disjoint lifetimes share addresses (first fit over the live intervals).  The per-frame working set is then the
 // peak live set (~0.1 GB at S = 3) instead of one buffer per layer output (~0.35 GB), so weights + activations stay
 // inside the 256 MiB Infinity Cache from frame to frame.
-static int alloc_arena(vnect_handle* h)
+static int alloc_arena(Plan* h)
 {
     const int nt = (int)h->tensors.size(), nl = (int)h->layers.size();
     std::vector<int> first(nt, nl + 1), last(nt, -2);
@@ -461,23 +461,17 @@ static int alloc_arena(vnect_handle* h)
     if (rc) return rc;
     HIPCK(h, hipMemset(base, 0, total));
     for (int t = 0; t < nt; t++) h->tensors[t].d = (float*)(base + off[t]);
-    h->arena_bytes = total, h->arena_off = off;
     return VNECT_OK;
 }
 
 // the split-K slabs of the largest K-split launch
-static int alloc_workspace(vnect_handle* h)
+static int alloc_workspace(Plan* h)
 {
     size_t ws = 0;
     for (Layer& L : h->layers)
         if (L.op == OP_CONV && L.a.ksplit > 1)
             ws = std::max(ws, (size_t)L.a.ksplit * ((size_t)L.a.S * L.a.OH * L.a.OW + 64) * L.a.Npad);
-    h->ws_floats = ws;
-    if (ws) {
-        int rc = dev_alloc(h, &h->ws, ws);
-        if (rc) return rc;
-    }
-    return VNECT_OK;
+    return ws ? dev_alloc(h, &h->ws, ws) : VNECT_OK;
 }
 
 int finalize_impl(vnect_handle* h)
@@ -765,55 +759,89 @@ int finalize_impl(vnect_handle* h)
 // round of resident workgroups (conv.hip, launch_stream: one item per workgroup at any grid).  Only the arena, the split-K workspace and the
 // geometry blocks are new, once per lane.  The stem builds both frames' pyramids itself (stem.hip, per_stream) where every tile's frame
 // rectangle fits its LDS scratch and both frames' squarify step is a copy; otherwise pyramid_streams_kernel writes the batch tensor first.
-static int build_batch_lane(vnect_handle* h, vnect_handle* lane)
+//
+// build_plan makes either kind of further plan from lane 0's: a lane (lane 0's plan as it is, on a stream of its own) or, `batch`, the
+// batched plan that runs on `lane`'s stream.  Same layers and weights; its own activation arena, split-K workspace, arg-max scratch,
+// geometry block(s) and graph.
+static int build_plan(vnect_handle* h, bool batch, Plan* lane = nullptr)
 {
-    vnect_handle* b = new vnect_handle();
-    h->blanes.push_back(b);
-    b->is_twin = true, b->batched = true, b->st = lane->st;
-    b->cfg = h->cfg, b->S = h->S, b->Snet = 2 * h->Snet, b->bf16 = h->bf16, b->f16 = h->f16, b->x3 = h->x3, b->keep_activations = false;
-    b->frames = h->frames, b->d_stabs = h->d_stabs, b->mgeo = h->mgeo, b->d_fb = h->d_fb, b->stabs_host = h->stabs_host;
-    b->post_merged = true;  // each stream's merge + arg-max + joints as one post_kernel launch (its maps, bank and geometry)
+    Plan* p = new Plan();
+    (batch ? h->bplans : h->lanes).push_back(p);
+    p->owner = h, p->S = h->S, p->Snet = batch ? 2 * h->Snet : h->Snet, p->bf16 = h->bf16, p->f16 = h->f16, p->two_frames = batch;
+    p->owns_stream = !batch;
+    if (batch) p->st = lane->st;
+    else HIPCK(h, hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+    // a batch: each stream's merge + arg-max + joints as one post_kernel launch (its maps, bank and geometry)
+    p->post_merged = batch || h->post_merged;
     int rc;
-    if ((rc = dev_alloc(b, &b->d_fp, 1)) || (rc = dev_alloc(b, &b->d_fp2, 1))) return fail(h, rc, b->err);
-    if ((rc = dev_alloc(b, &b->d_part, (size_t)NJ * ARG_SLABS_MAX))) return fail(h, rc, b->err);
-    if ((rc = dev_alloc(b, &b->d_ticket, 4))) return fail(h, rc, b->err);
-    HIPCK(h, hipMemset(b->d_ticket, 0, 4 * sizeof(unsigned)));
-    for (int i = 0; i < RING; i++) HIPCK(h, hipHostMalloc((void**)&b->h_fp[i], sizeof(FrameParams), hipHostMallocDefault));
-    b->tensors = h->tensors, b->layers = h->layers, b->tensor_by_name = h->tensor_by_name;
-    b->t_input4 = h->t_input4, b->t_out = h->t_out, b->l_conv1 = h->l_conv1, b->l_pool1 = h->l_pool1;
-    for (Tensor& t : b->tensors) t.S *= 2;
-    for (Layer& L : b->layers) {
-        L.flops *= 2, L.last_ms = 0;
-        if (L.op != OP_CONV) continue;
-        ConvArgs& a = L.a;
-        a.S *= 2, a.M *= 2;
-        if (a.ksplit > 1) a.slab_pix = (long long)a.S * a.OH * a.OW + 64, L.r.slab_pix = a.slab_pix, L.r.npix = (long long)a.S * a.OH * a.OW;
+    if ((rc = dev_alloc(p, &p->d_fp, 1)) || (batch && (rc = dev_alloc(p, &p->d_fp2, 1)))) return rc;
+    if ((rc = dev_alloc(p, &p->d_part, (size_t)NJ * ARG_SLABS_MAX)) || (rc = dev_alloc(p, &p->d_ticket, 4))) return rc;
+    HIPCK(h, hipMemset(p->d_ticket, 0, 4 * sizeof(unsigned)));
+    for (int i = 0; i < RING; i++) HIPCK(h, hipHostMalloc((void**)&p->h_fp[i], sizeof(FrameParams), hipHostMallocDefault));
+    p->tensors = h->tensors, p->layers = h->layers, p->tensor_by_name = h->tensor_by_name;
+    p->t_input4 = h->t_input4, p->t_out = h->t_out, p->l_conv1 = h->l_conv1, p->l_pool1 = h->l_pool1;
+    if (batch) {
+        for (Tensor& t : p->tensors) t.S *= 2;
+        for (Layer& L : p->layers) {
+            L.flops *= 2, L.last_ms = 0;
+            if (L.op != OP_CONV) continue;
+            ConvArgs& a = L.a;
+            a.S *= 2, a.M *= 2;
+            if (a.ksplit > 1) a.slab_pix = (long long)a.S * a.OH * a.OW + 64, L.r.slab_pix = a.slab_pix, L.r.npix = (long long)a.S * a.OH * a.OW;
+        }
     }
-    if ((rc = alloc_arena(b)) || (rc = alloc_workspace(b))) return fail(h, rc, b->err);
-    b->conv_flops = 0, b->conv_launches = 0;
-    for (Layer& L : b->layers)
-        if (L.op == OP_CONV) bind_activations(b, L), b->conv_flops += L.flops, b->conv_launches += 1;
-    setup_stem(b);  // the two-frame form of the stem (StemArgs::per_stream) where it fits, else pyramid_streams_kernel + the batch-tensor form
-    if (b->stem_pair) b->conv_launches -= 1;
-    // profiled batches (vnect_set_profiling) stamp into buffers of their own
-    if ((rc = dev_alloc(b, &b->d_prof, PROF_SLOTS * 128)) || (rc = dev_alloc(b, &b->d_prof_end, (size_t)PROF_WGS * 128))) return fail(h, rc, b->err);
-    HIPCK(h, hipMemset(b->d_prof_end, 0, (size_t)PROF_WGS * 128 * sizeof(unsigned long long)));
-    HIPCK(h, hipHostMalloc((void**)&b->h_prof_end, (size_t)PROF_WGS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
-    HIPCK(h, hipHostMalloc((void**)&b->h_prof, PROF_SLOTS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
-    b->finalized = true;
-    if ((rc = build_graph(b))) return fail(h, rc, b->err);
-    HIPCK(h, hipStreamSynchronize(b->st));
+    if ((rc = alloc_arena(p)) || (rc = alloc_workspace(p))) return rc;  // (a lane's arena: lane 0's offsets, first fit over the same intervals)
+    for (Layer& L : p->layers)
+        if (L.op == OP_CONV) bind_activations(p, L), p->conv_flops += L.flops, p->conv_launches += 1;
+    setup_stem(p);  // a lane: lane 0's form on this arena and geometry block; a batch: the two-frame form of the stem (StemArgs::per_stream)
+                    // where it fits, else pyramid_streams_kernel + the batch-tensor form
+    if (p->stem_pair) p->conv_launches -= 1;
+    if (batch) {  // profiled batches (vnect_set_profiling) stamp into buffers of their own
+        if ((rc = dev_alloc(p, &p->d_prof, PROF_SLOTS * 128)) || (rc = dev_alloc(p, &p->d_prof_end, (size_t)PROF_WGS * 128))) return rc;
+        HIPCK(h, hipMemset(p->d_prof_end, 0, (size_t)PROF_WGS * 128 * sizeof(unsigned long long)));
+        HIPCK(h, hipHostMalloc((void**)&p->h_prof_end, (size_t)PROF_WGS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIPCK(h, hipHostMalloc((void**)&p->h_prof, PROF_SLOTS * 128 * sizeof(unsigned long long), hipHostMallocDefault));
+    }
+    if ((rc = build_graph(p))) return rc;
+    HIPCK(h, hipStreamSynchronize(p->st));
     return VNECT_OK;
 }
 
-int build_batch_lanes(vnect_handle* h)
+int build_plans(vnect_handle* h)
 {
-    destroy_batch_lanes(h);
-    if (h->stream_batch < 2) return VNECT_OK;
+    destroy_plans(h);
+    int rc = VNECT_OK;
+    if (h->cfg.lanes >= 2 && !h->sharded && !h->keep_activations)
+        for (int i = 1; i < h->cfg.lanes && !rc; i++) rc = build_plan(h, false);
+    if (rc || h->stream_batch < 2) return rc;
     if (h->layers.size() > 128) return fail(h, VNECT_E_STATE, "internal: more layers than the profiling buffers hold");
-    int rc = build_batch_lane(h, h);
-    for (size_t i = 0; i < h->twins.size() && !rc; i++) rc = build_batch_lane(h, h->twins[i]);
+    for (size_t i = 0; i < h->lanes.size() && !rc; i++) rc = build_plan(h, true, h->lanes[i]);
     return rc;
+}
+
+// Every stream is synchronised before its buffers go; a plan on a borrowed stream goes before the plan that owns the stream.
+void destroy_plan(Plan* p)
+{
+    if (p->st) hipStreamSynchronize(p->st);
+    if (p->gexec) hipGraphExecDestroy(p->gexec);
+    if (p->graph) hipGraphDestroy(p->graph);
+    if (p->pgexec) hipGraphExecDestroy(p->pgexec);
+    if (p->pgraph) hipGraphDestroy(p->pgraph);
+    for (int i = 0; i < RING; i++)
+        if (p->h_fp[i]) hipHostFree(p->h_fp[i]);
+    if (p->h_prof) hipHostFree(p->h_prof);
+    if (p->h_prof_end) hipHostFree(p->h_prof_end);
+    for (void* q : p->dev_allocs) hipFree(q);
+    if (p->owns_stream && p->st) hipStreamDestroy(p->st);
+    if (p != p->owner) delete p;  // (lane 0 is the handle: vnect_destroy deletes it)
+}
+
+void destroy_plans(vnect_handle* h)
+{
+    for (Plan* b : h->bplans) destroy_plan(b);
+    h->bplans.clear();
+    for (size_t i = 1; i < h->lanes.size(); i++) destroy_plan(h->lanes[i]);
+    h->lanes.resize(1);
 }
 
 }  // namespace rt

@@ -1,7 +1,8 @@
 // runtime.h -- internal header of the host runtime of libvnect_hip.so (not part of the ABI: include/vnect_abi.h is).
 // The runtime is four translation units along its seams (round 6; one 2 300-line file before):
-//   rt_plan.cpp  weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables
-//   rt_exec.cpp  running frames: launch sequences, hipGraph, lanes (twins), streams, submit / collect, staging, warm start, roctx ranges
+//   rt_plan.cpp  weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables,
+//                the further plans built from lane 0's (lanes, batched plans)
+//   rt_exec.cpp  running frames: launch sequences, hipGraph, lanes, streams, submit / collect, staging, warm start, roctx ranges
 //   rt_comm.cpp  the pyramid exchange: RCCL (dlopen'ed) and peer writes, vnect_comm_*
 //   rt_abi.cpp   the extern "C" entry points of include/vnect_abi.h (argument checks, device selection, the no-exception guard)
 #pragma once
@@ -62,30 +63,25 @@ struct Layer {
     float last_ms = 0;
 };
 
-// result ring: one entry per frame in flight -- up to three lanes of two-frame batches (vnect_submit_streams)
-constexpr int RING = 8;
+constexpr int RING = 8;  // result ring entries: up to three lanes of two-frame batches (vnect_submit_streams) in flight
 constexpr int MAX_LANES = 3;
 
-}  // namespace rt
-}  // namespace vnect
-
-using namespace vnect;
-using namespace vnect::rt;
-
-struct vnect_handle {
-    vnect_config cfg{};
+// What one lane runs: the launch plan (layers over this plan's activation buffers), its stream and graph, and the per-launch scratch.
+// Lane 0's plan is the handle itself (vnect_handle derives from Plan).  More lanes (cfg.lanes == 2, 3): a frame submitted while others are
+// in flight runs on another plan over the same layers and weights -- its own stream, activation arena, split-K workspace, arg-max scratch,
+// geometry block and graph.  A batched plan (vnect_set_stream_batch) is the same with M doubled, on its lane's stream.  Everything shared --
+// config, tables, merge geometry, resident frames, the result ring, the filter banks (their users are chained by events) -- is read
+// through `owner`, where errors go too.
+struct Plan {
+    vnect_handle* owner = nullptr;
+    hipStream_t st = nullptr;
+    bool owns_stream = false;  // (a batched plan runs on its lane's)
     int S = 0;      // scales of the pyramid (merge, tables)
-    int Snet = 0;   // images this handle pushes through the conv stack: S, or 1 when pyramid-sharded
-    std::string err;
-    bool finalized = false;
-    bool pre_only = false;  // vnect_config::preprocess_only: the input batch buffer and the resize tables, nothing else
-    bool x3 = false;    // VNECT_FP32_SPLIT: fp32 tensors; the 64x64-tile layers multiply on the bf16 pipe by three-way splits (conv.hip, X3)
+    int Snet = 0;   // images this plan pushes through the conv stack: S, 1 when pyramid-sharded, 2 S for a batched plan
     bool bf16 = false;  // VNECT_BF16: bf16 activations + weights, fp32 accumulate; final maps and post-processing stay fp32/f64
                         // (VNECT_FP16 too: this flag means "16-bit elements" -- the plan, layouts and fused forms key on it alone)
     bool f16 = false;   // VNECT_FP16: the 16-bit elements are fp16 (IEEE binary16) instead of bf16; everything else is the bf16 handle's
     int el() const { return bf16 ? (f16 ? EL_F16 : EL_BF16) : EL_F32; }  // the element format the kernel launchers take
-    hipStream_t st = nullptr;
-    std::map<std::string, HostArray> weights;
     std::vector<Tensor> tensors;
     std::vector<Layer> layers;
     std::map<std::string, int> tensor_by_name;
@@ -95,25 +91,91 @@ struct vnect_handle {
     int stem_mode = 0;
     bool stem_pair = false;  // the stem launch also runs res2a_branch2a + res2a_branch1 (stem.hip, PAIR): layer l_pool1 + 1 is skipped
     bool stem_frame_ok = false;  // every tile's rectangle of frame bytes fits the kernel's LDS scratch at the current scales
-    ScaleTabs stabs_host{};      // the host's copy of d_stabs (plan::stem_frame_fits reads it)
+    bool two_frames = false;     // a batched plan: images 0 .. S-1 come from one stream's frame, S .. 2 S-1 from another's (d_fp2; StemArgs::per_stream)
     int l_conv1 = -1, l_pool1 = -1;  // the two layers a stem launch stands for
     StemArgs stem{};
-    float* in3 = nullptr;  // (S,368,368,3) staging for vnect_forward / preprocess read-back
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    bool keep_activations = false;  // one private buffer per layer output (vnect_read_activation needs it); false = arena.  Lane 0's is the
+                                    // config's; every other plan's is false (a batched plan has an arena on a keep_activations handle too)
+    float* ws = nullptr;            // the split-K slabs of the largest K-split launch
     std::vector<void*> dev_allocs;
+    FrameParams* d_fp = nullptr;   // crop geometry on the device; re-uploaded only when it differs from fp_dev
+    FrameParams* h_fp[RING] = {};  // pinned staging for those uploads
+    FrameParams fp_dev{};          // what d_fp holds
+    bool fp_dev_valid = false;
+    int fp_ring = 0;
+    FrameParams* d_fp2 = nullptr;  // two_frames: the second stream's geometry
+    FrameParams fp_dev2{};
+    bool fp_dev2_valid = false;
+    ArgPartial* d_part = nullptr;
+    unsigned* d_ticket = nullptr;  // post_kernel's arrival counter (zero between launches)
+    bool post_merged = true;       // merge + arg-max + joints as ONE launch (post_kernel); false: two launches (VNECT_NO_POST_MERGE=1)
+    long long lane_seq = -1;       // sequence number of the last frame submitted on this lane
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t gexec = nullptr;
+    bool prof_graph = false;      // build_graph also captures the profiling graph (lane 0: profiled frames always run there)
+    hipGraph_t pgraph = nullptr;  // profiling twin: same launches, every conv kernel stamps its start/end
+    hipGraphExec_t pgexec = nullptr;
+    unsigned long long* d_prof = nullptr;       // [layer][2] device stamps (100 MHz)
+    unsigned long long* h_prof = nullptr;       // pinned read-back
+    unsigned long long* d_prof_end = nullptr;   // [128 layers][PROF_WGS] per-workgroup end stamps of the profiling twin
+    unsigned long long* h_prof_end = nullptr;   // pinned read-back
+    double conv_flops = 0;
+    int conv_launches = 0;
+};
+
+// a stream's filter timestamps as the host holds them (check_time / commit_time; the device has them in d_fb[stream])
+struct TimeState { bool have2 = false, have3 = false; double last2 = 0, last3 = 0; };
+
+// A frame in flight: one entry of the result ring.
+struct InFlight {
+    JointsOut* out = nullptr;      // pinned, device-mapped: joints_kernel writes a frame's results straight into its ring slot
+    JointsOut* out_dev = nullptr;  // the same slot as the device addresses it
+    hipEvent_t done = nullptr;
+    int stream = 0;
+    unsigned long long unit = 0;  // the in-flight limit counts UNITS (a frame, or a batch of two streams' frames): this entry's
+    bool batch = false;           // the entry is a frame of a batch (the handle's own profiling figures skip it)
+    Plan* prof = nullptr;         // a profiled batch's plan, on the ring entry of its last frame (collect reads its layer times)
+    bool tracked = false;
+    TimeState before{};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
+};
+
+// A video stream (vnect_submit_stream; stream 0 is what every other entry point uses): d_fb[stream] and d_track[stream] on the device, and here
+// the host's copy of the last timestamps, the sequence number of the stream's last frame and the lane it ran on.  Tracking (vnect_track_begin;
+// track.hip): the frame size, the number the next tracked frame gets (FrameDyn::xseq against TrackState::fail), and whether a refused
+// crop has stopped the stream.
+struct Stream {
+    TimeState t;
+    long long seq = -1;
+    Plan* lane = nullptr;
+    bool track_on = false, track_stopped = false;
+    int track_H = 0, track_W = 0;
+    unsigned track_seq = 0;
+    uint8_t* track_buf = nullptr;  // the stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
+    size_t track_cap = 0;          // waits for this frame's box kernel, which runs after everything that reads the crop)
+};
+
+}  // namespace rt
+}  // namespace vnect
+
+using namespace vnect;
+using namespace vnect::rt;
+
+// The object behind the C ABI, and lane 0's plan.
+struct vnect_handle : Plan {
+    vnect_config cfg{};
+    std::string err;
+    bool finalized = false;
+    bool pre_only = false;  // vnect_config::preprocess_only: the input batch buffer and the resize tables, nothing else
+    bool x3 = false;    // VNECT_FP32_SPLIT: fp32 tensors; the 64x64-tile layers multiply on the bf16 pipe by three-way splits (conv.hip, X3)
+    std::map<std::string, HostArray> weights;
+    ScaleTabs stabs_host{};      // the host's copy of d_stabs (plan::stem_frame_fits reads it)
+    float* in3 = nullptr;  // (S,368,368,3) staging for vnect_forward / preprocess read-back
     char* param_cur = nullptr;     // bump allocator over large blocks for packed weights / biases (param_alloc)
     size_t param_left = 0;
-    bool keep_activations = true;  // one private buffer per layer output (vnect_read_activation needs it); false = arena
-    size_t arena_bytes = 0;
-    std::vector<size_t> arena_off;  // byte offset of every tensor in the arena
-    // More lanes (cfg.lanes == 2, 3): a frame submitted while others are in flight runs on a twin -- its own stream, activation
-    // arena, split-K workspace, arg-max scratch and graph; weights, tables, resident frames, the result ring and the filter
-    // bank are this handle's.  The two frames overlap everywhere except in the joints kernel (the filters are a chain).
-    std::vector<vnect_handle*> twins;  // lanes 1 .. cfg.lanes-1 (lane 0 is this handle)
-    bool is_twin = false;
-    long long lane_seq = -1;           // sequence number of the last frame submitted on this lane
-    vnect_handle* last_lane = nullptr;  // lane of the most recently submitted frame
+    std::vector<Plan*> lanes;   // [0] is this handle, then cfg.lanes - 1 more.  Frames on different lanes overlap everywhere except in the
+                                // joints kernel (the filters are a chain)
+    int stream_batch = 1;
+    std::vector<Plan*> bplans;  // two video streams per launch: the batched plan once per lane, bplans[i] on lanes[i]'s stream
     // pre/post
     uint8_t* frames = nullptr;  // num_frame_slots * max_frame_bytes
     // vnect_infer's way from host memory to slot 0: pinned (page-locked) buffers.  [0], [1] are the caller's capture buffers
@@ -126,55 +188,18 @@ struct vnect_handle {
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
     std::vector<SlotInfo> slots;
-    FrameParams* d_fp = nullptr;   // crop geometry on the device; re-uploaded only when it differs from fp_dev
-    FrameParams* h_fp[RING] = {};  // pinned staging for those uploads
-    FrameParams fp_dev{};          // what d_fp holds
-    bool fp_dev_valid = false;
-    int fp_ring = 0;
     ScaleTabs* d_stabs = nullptr;
     MergeGeo mgeo{};  // the merge's resize geometry: passed to the post kernels by value, they compute table entries themselves
-    ArgPartial* d_part = nullptr;
-    unsigned* d_ticket = nullptr;  // post_kernel's arrival counter (zero between launches)
-    bool post_merged = true;       // merge + arg-max + joints as ONE launch (post_kernel); false: two launches (VNECT_NO_POST_MERGE=1)
     FilterBank* d_fb = nullptr;    // [VNECT_MAX_STREAMS]
     double* h_filt = nullptr;      // pinned, device-mapped: vnect_joint_filter's values in ([0, 64)) and out ([64, 128))
     double* h_filt_dev = nullptr;
-    JointsOut* h_out[RING] = {};   // pinned, device-mapped: joints_kernel writes a frame's results straight into its ring slot
-    JointsOut* h_out_dev[RING] = {};  // the same slots as the device addresses them
-    hipEvent_t done[RING] = {};
+    InFlight ring[RING];
     unsigned long long seq_submit = 0, seq_collect = 0;
-    // per video stream (vnect_submit_stream; stream 0 is what every other entry point uses): d_fb[stream] on the device, and here
-    // the host's copy of the last timestamps, the sequence number of the stream's last frame and the lane it ran on
-    bool have2[VNECT_MAX_STREAMS] = {}, have3[VNECT_MAX_STREAMS] = {};
-    double last2[VNECT_MAX_STREAMS] = {}, last3[VNECT_MAX_STREAMS] = {};
-    long long stream_seq[VNECT_MAX_STREAMS] = {-1, -1, -1, -1};
-    vnect_handle* stream_lane[VNECT_MAX_STREAMS] = {};
-    int ring_stream[RING] = {};
-    // in-flight limit in UNITS (a frame, or a batch of two streams' frames): unit_submit counts them, ring_unit[r] is the unit of ring entry r
-    unsigned long long unit_submit = 0;
-    unsigned long long ring_unit[RING] = {};
-    bool ring_batch[RING] = {};          // the entry is a frame of a batch (the handle's own profiling figures skip it)
-    vnect_handle* ring_prof[RING] = {};  // a profiled batch's plan, on the ring entry of its last frame (collect reads its layer times)
-    // Two video streams per launch (vnect_set_stream_batch): the batched plan for 2 S images -- the S-image plan's layers, tiles, K splits and
-    // fused forms with M doubled, the same packed weights -- once per lane: blanes[i] runs on lane i's stream (0: this handle) with an arena
-    // of its own.  A batch's second stream keeps its geometry in d_fp2.
-    int stream_batch = 1;
-    std::vector<vnect_handle*> blanes;
-    bool batched = false;  // this is a batched plan (its `st` is its lane's; its stem takes two frames: StemArgs::per_stream)
-    FrameParams* d_fp2 = nullptr;
-    FrameParams fp_dev2{};
-    bool fp_dev2_valid = false;
-    // tracking on the device (vnect_track_begin; track.hip): per stream the next crop and its geometry on the device, the frame size,
-    // the number the next tracked frame gets (FrameDyn::xseq against TrackState::fail), and whether a refused crop has stopped the stream
-    TrackState* d_track = nullptr;  // [VNECT_MAX_STREAMS]
+    unsigned long long unit_submit = 0;  // units submitted so far (InFlight::unit)
+    Stream streams[VNECT_MAX_STREAMS];
+    TrackState* d_track = nullptr;  // [VNECT_MAX_STREAMS]: per stream the next crop and its geometry on the device
     TrackOut* h_tout = nullptr;     // pinned, device-mapped, [RING]: rect_used + status of every tracked frame in flight
     TrackOut* h_tout_dev = nullptr;
-    bool track_on[VNECT_MAX_STREAMS] = {}, track_stopped[VNECT_MAX_STREAMS] = {};
-    int track_H[VNECT_MAX_STREAMS] = {}, track_W[VNECT_MAX_STREAMS] = {};
-    unsigned track_seq[VNECT_MAX_STREAMS] = {};
-    uint8_t* track_buf[VNECT_MAX_STREAMS] = {};  // a stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
-    size_t track_cap[VNECT_MAX_STREAMS] = {};    // waits for this frame's box kernel, which runs after everything that reads the crop)
-    bool ring_track[RING] = {};
 #if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
     // test build only (make testhooks; tests/test_gpu_track_maps.py): vnect_test_maps_override's maps on the device, RING + 1 buffers taken in
     // turn (a frame in flight keeps reading the one it was enqueued with), and the stream the uploads run on
@@ -182,26 +207,13 @@ struct vnect_handle {
     int test_maps_cur = -1;  // -1: no override
     hipStream_t test_st = nullptr;
 #endif
-    struct TimeState { bool have2, have3; double last2, last3; };
-    TimeState ring_time[RING] = {};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
     // cached squarify table
     int sq_H = -1, sq_W = -1;
     FrameParams sq_cache{};
-    // graph
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    hipGraph_t pgraph = nullptr;  // profiling twin: same launches, every conv kernel stamps its start/end
-    hipGraphExec_t pgexec = nullptr;
-    unsigned long long* d_prof = nullptr;       // [layer][2] device stamps (100 MHz)
-    unsigned long long* h_prof = nullptr;       // pinned read-back
-    unsigned long long* d_prof_end = nullptr;   // [128 layers][PROF_WGS] per-workgroup end stamps of the profiling twin
-    unsigned long long* h_prof_end = nullptr;   // pinned read-back
     // profiling
     bool profiling = false;
     hipEvent_t ev[4] = {};
     vnect_timings tim{};
-    double conv_flops = 0;
-    int conv_launches = 0;
     // comm
     void* comm = nullptr;
     bool sharded = false;
@@ -223,10 +235,11 @@ namespace rt {
 // message of the last vnect_create failure on THIS thread (handles are created from several threads / processes); rt_abi.cpp
 extern thread_local std::string g_create_error;
 
-inline int fail(vnect_handle* h, int code, const std::string& msg) noexcept
+// the message goes to the plan's handle (vnect_last_error), whichever lane reports it
+inline int fail(Plan* p, int code, const std::string& msg) noexcept
 {
     try {
-        if (h) h->err = msg;
+        if (p) p->owner->err = msg;
         else g_create_error = msg;
     } catch (...) {  // out of memory while recording the message: the code still goes back
     }
@@ -257,12 +270,12 @@ int guarded(vnect_handle* const* hp, F&& body) noexcept
     } while (0)
 
 template <typename T>
-int dev_alloc(vnect_handle* h, T** p, size_t count)
+int dev_alloc(Plan* p, T** out, size_t count)
 {
     void* q = nullptr;
-    HIPCK(h, hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16)));
-    h->dev_allocs.push_back(q);
-    *p = (T*)q;
+    HIPCK(p, hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16)));
+    p->dev_allocs.push_back(q);
+    *out = (T*)q;
     return VNECT_OK;
 }
 
@@ -299,25 +312,23 @@ int build_scale_tables(vnect_handle* h);
 int build_up_table(vnect_handle* h);
 int squarify_params(vnect_handle* h, int H, int W, FrameParams* fp);
 int add_tensor(vnect_handle* h, const std::string& name, int S, int H, int W, int C, int Cs, bool force_f32 = false);
-void bind_activations(vnect_handle* h, Layer& L);
-void setup_stem(vnect_handle* h);
 int finalize_impl(vnect_handle* h);
-int build_batch_lanes(vnect_handle* h);
+int build_plans(vnect_handle* h);   // lanes 1 .. cfg.lanes - 1 and the batched plans
+void destroy_plan(Plan* p);         // every plan's teardown, lane 0's (the handle's) included
+void destroy_plans(vnect_handle* h);  // all but lane 0
 
 // ---- rt_exec.cpp ---------------------------------------------------------------------------------------------------------------
-int run_network(vnect_handle* h, bool timed, bool stem_done = false);
-int sync_geometry(vnect_handle* h, const FrameParams& fp, int which = 0);  // which 1: a batch's second stream (d_fp2)
-int run_pre(vnect_handle* h, const FrameDyn& dyn, bool timed = false, bool want_batch = false);
-int run_argmax(vnect_handle* h);
-int run_joints(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);  // fp: d_fp
-int run_post(vnect_handle* h, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);
-int check_time(vnect_handle* h, double t2d, double t3d, int s = 0);
-void commit_time(vnect_handle* h, double t2d, double t3d, int s = 0);
+int run_network(Plan* p, bool timed, bool stem_done = false);
+int sync_geometry(Plan* p, const FrameParams& fp, int which = 0);  // which 1: a batch's second stream (d_fp2)
+int run_pre(Plan* p, const FrameDyn& dyn, bool timed = false, bool want_batch = false);
+int run_argmax(Plan* p);
+int run_joints(Plan* p, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);  // fp: d_fp
+int run_post(Plan* p, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);
+int check_time(vnect_handle* h, const Stream& s, double t2d, double t3d);
+void commit_time(Stream& s, double t2d, double t3d);
 int reset_filters_impl(vnect_handle* h, int stream = -1);  // -1: every stream
 void roctx_load();
-int build_graph(vnect_handle* h);
-void destroy_twins(vnect_handle* h);
-int build_twins(vnect_handle* h);
+int build_graph(Plan* p);
 // a tracked frame (vnect_submit_tracked*): the whole frame in a resident slot (pinned_dev == nullptr) or in a pinned buffer
 struct TrackedSrc {
     const uint8_t* pinned_dev = nullptr;  // the frame as the device addresses it
@@ -333,7 +344,6 @@ int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int 
 int prime(vnect_handle* h);
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 int forward_batch(vnect_handle* h, const float* batch, float* out);
-void destroy_batch_lanes(vnect_handle* h);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);
