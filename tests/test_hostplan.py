@@ -136,7 +136,8 @@ def test_per_entry_axis_functions_equal_the_tables(hp):
     assert hp.hp_axis_mismatches(46, 368, 1.0 / 8.0) == 0
     for ssize, dsize in ((5, 17), (368, 294), (7, 7), (2, 9), (1, 4), (100, 3)):
         assert hp.hp_axis_mismatches(ssize, dsize, ssize / dsize) == 0, (ssize, dsize)
-    for scales in ([1.0, 0.8, 0.6], [1, 0.85, 0.7], [1.0], [0.9, 0.75, 0.5, 0.45, 1.0]):
+    # ([1.0, 0.99], [0.7, 1.0, 0.9999]: sizes that round back to 46 -- a plain copy, which the geometry must describe as the identity)
+    for scales in ([1.0, 0.8, 0.6], [1, 0.85, 0.7], [1.0], [0.9, 0.75, 0.5, 0.45, 1.0], [1.0, 0.99], [0.7, 1.0, 0.9999]):
         maps = helpers.synth_maps(78, len(scales))
         want = oracle.merge_scales(maps, scales)
         got = np.empty((46, 46, 84), np.float64)

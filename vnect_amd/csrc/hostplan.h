@@ -139,7 +139,9 @@ inline const char* build_merge_tab(double s, MergeTab* m)
     if (ds < HM) return "scale > 1 not supported";
     memset(m, 0, sizeof *m);
     m->copy = ds == HM;
-    const double scale = 1.0 / f;
+    // A size that rounds back to 46 (46 / 46.5 < s <= 1) makes cv2's resize a plain copy, whatever s is: the tables must then be the
+    // identity -- step 1.0 -- because the consumers read tap (s0(r), s0(c)) alone for a copy, and with step s that tap is (r - 1, c - 1).
+    const double scale = m->copy ? 1.0 : 1.0 / f;
     AxisTab x = axis_x(HM, ds, scale), y = axis_y(HM, ds, scale);
     const int off = ds / 2 - HM / 2;
     for (int r = 0; r < HM; r++) {
@@ -159,7 +161,7 @@ inline const char* build_merge_geo(double s, MergeGeo* g, int i)
     if (const char* why = build_merge_tab(s, &m)) return why;
     const double f = 1.0 / s;
     const int ds = cv_round(HM * f);
-    g->scale[i] = 1.0 / f, g->off[i] = ds / 2 - HM / 2, g->copy[i] = ds == HM;
+    g->scale[i] = ds == HM ? 1.0 : 1.0 / f, g->off[i] = ds / 2 - HM / 2, g->copy[i] = ds == HM;  // (a copy: the identity, as in build_merge_tab)
     return nullptr;
 }
 

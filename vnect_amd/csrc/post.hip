@@ -186,8 +186,9 @@ template <int SMAX>
 __device__ __forceinline__ double merged_cell(const float* __restrict__ maps, const MergeGeo& geo, int ch, int r, int c)
 {
     // All taps of all scales are requested before any is used (no load sits behind a data-dependent branch), so a
-    // thread pays one memory round trip, not one per scale.  For a scale that is a plain copy (size unchanged) the
-    // entries are the identity: tap (s0(r), s0(c)) IS element (r, c).
+    // thread pays one memory round trip, not one per scale.  For a scale that is a plain copy (size unchanged: 46 / 46.5 < s <= 1) the
+    // host passes step 1.0 and offset 0 instead of s (hostplan.h: build_merge_geo), and only therefore are the entries the identity:
+    // (d + 0.5) * 1.0 - 0.5 == d exactly, so tap (s0(r), s0(c)) IS element (r, c).  With the step left at s < 1 it would be (r - 1, c - 1).
     const int S = geo.S;
     float p00[SMAX], p01[SMAX], p10[SMAX], p11[SMAX];
     AxE X[SMAX], Y[SMAX];

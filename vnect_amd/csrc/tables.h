@@ -47,6 +47,8 @@ struct MergeTab {  // cv2.resize(map, fx=fy=1/s) restricted to the 46x46 centre 
 // What the post-processing kernels need to rebuild a MergeTab entry on the fly (round 3: they compute the taps and weights from these few
 // numbers with axis.h's two functions, which tests/test_hostplan.py holds to the host's tables, instead of loading 4 KB of tables first): per scale the source
 // step of cv2.resize(map, fx = fy = 1 / s) as the host computed it, the centre crop's offset, and whether the resize is a plain copy.
+// A plain copy (cv_round(46 / s) == 46, i.e. 46 / 46.5 < s <= 1) has scale 1.0 and off 0, NOT s: the kernels read the single tap
+// (s0(r), s0(c)) for it, which is element (r, c) only under the identity step.
 struct MergeGeo {
     int S, pad_;
     double scale[8];
