@@ -212,6 +212,43 @@ int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, i
 int vnect_collect_tracked(vnect_handle* h, int32_t* stream_out, double* joints_2d, float* joints_3d, int32_t* rect4);
 int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4);
 
+/* ABI v7, additive.  NV12 frames.  The reference's loop takes its frame from camera_capture.read() (run_estimator_ps.py:79,109), and
+ * cv2.VideoCapture hands out BGR: whatever the camera or decoder delivered -- on this hardware NV12, a full-resolution Y plane and one
+ * half-resolution plane of interleaved U, V -- OpenCV has converted by then.  That colour conversion is OpenCV's, not the reference's own
+ * code; these entry points do it on the device, inside the copy that brings the frame into its resident slot (1.5 bytes per pixel cross
+ * PCIe instead of 3), with the integer arithmetic of cv2.cvtColor(nv12, cv2.COLOR_YUV2BGR_NV12): BT.601 limited range, 20-bit fixed point,
+ * chroma replicated (vnect_amd/csrc/nv12.h; NV12.md).  Everything behind the slot sees the BGR frame it always saw, so every result is
+ * bit-identical to the BGR entry point given the converted frame.
+ * y / uv: the two planes, rows y_stride / uv_stride bytes apart (each >= W), at any byte address; H and W are even.  rect4 = (x, y, w, h)
+ * or NULL: only that crop of the frame is converted (chroma by absolute frame coordinates; odd origins and sizes are fine) and the call is
+ * the BGR call on the converted frame's crop, as the tracking loop slices it (run_estimator_ps.py:88) -- joints in crop coordinates.  A
+ * rect past the frame's far edges crops what that slicing crops.  Planes INSIDE one of the vnect_frame_buffer buffers are read where they
+ * lie; anything else is first copied into an internal pinned stage by the CPU.
+ * VNECT_E_ARG, before anything changes (no timestamp, no slot geometry): odd W or H; a stride below W; a UV plane that overlaps the Y plane
+ * or planes that run past the pinned buffer they start in; a rect whose origin lies outside the frame or that is empty; more BGR bytes
+ * (3 per pixel of the frame, or of the crop) than max_frame_bytes.
+ * vnect_upload_frame_nv12: afterwards the slot holds the H x W BGR frame exactly as if vnect_upload_frame had been given the converted
+ * frame (src/estimator.py:97-99 takes it from there): every resident-slot submit and vnect_submit_tracked work on it unchanged.
+ * vnect_upload_frame_nv12_rect: the same with a crop, which lands at the slot's origin: the slot holds the converted frame's
+ * [y:y + h, x:x + w] (run_estimator_ps.py:88).  Both return when the slot is filled and, like vnect_upload_frame, wait only for the slot's
+ * last reader, not for frames computing from other slots.
+ * vnect_infer_nv12: vnect_infer (src/estimator.py:97-142) of the converted frame's crop.
+ * vnect_preprocess_nv12: vnect_preprocess (src/estimator.py:70-81) of it; also on a preprocess_only handle.
+ * vnect_submit_tracked_pinned_nv12: vnect_submit_tracked_pinned with the NV12 frame in pinned buffer buffer_index -- Y plane at its start,
+ * UV plane uv_offset bytes in; only the crop's rows of both planes cross PCIe.  Same refusals, status and rollback as the BGR form.
+ * vnect_read_frame: the BGR bytes of a resident slot, packed (H, W, 3), and its size in hw2 = (H, W); out may be NULL (size only).  A
+ * debugging read like vnect_read_activation (what the reference would see as the img_input of src/estimator.py:97). */
+int vnect_upload_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W);
+int vnect_upload_frame_nv12_rect(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                                 const int32_t* rect4);
+int vnect_infer_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                     const int32_t* rect4, double t2d, double t3d, double* joints_2d, float* joints_3d);
+int vnect_preprocess_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                          const int32_t* rect4, float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y);
+int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_index, int64_t y_stride, int64_t uv_offset, int64_t uv_stride,
+                                     double t2d, double t3d);
+int vnect_read_frame(vnect_handle* h, int slot, uint8_t* out, int64_t capacity, int32_t* hw2);
+
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
  * per call, :84).  Values travel as float64; values_are_f32 = 1 says they are numpy float32 scalars -- what the reference

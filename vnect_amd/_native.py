@@ -93,6 +93,12 @@ SYMBOLS = {
     "vnect_submit_tracked_pinned": (C.c_int, [_H, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double]),
     "vnect_collect_tracked": (C.c_int, [_H, _i32p, _f64p, _f32p, _i32p]),
     "vnect_track_box": (C.c_int, [_H, C.c_int, _i32p]),
+    "vnect_upload_frame_nv12": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int]),
+    "vnect_upload_frame_nv12_rect": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p]),
+    "vnect_infer_nv12": (C.c_int, [_H, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p, C.c_double, C.c_double, _f64p, _f32p]),
+    "vnect_preprocess_nv12": (C.c_int, [_H, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p, _f32p, _f64p, _i32p, _i32p]),
+    "vnect_submit_tracked_pinned_nv12": (C.c_int, [_H, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double]),
+    "vnect_read_frame": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _i32p]),
 }
 
 
@@ -100,6 +106,10 @@ TESTHOOKS_LIB = os.path.join(_HERE, "lib", "libvnect_hip_testhooks.so")   # the 
 
 
 TRACKPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_trackprobe.so")     # track.o + post.o behind csrc/track_probe.cpp (tests only)
+
+
+NV12PROBE_LIB = os.path.join(_HERE, "lib", "libvnect_nv12probe.so")       # post.o + track.o behind csrc/nv12_probe.cpp (tests only)
+NV12_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_nv12.so")             # g++'s build of csrc/nv12.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -112,6 +122,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "testhooks"], stdout=subprocess.DEVNULL)
     # the tracking kernels' probe (tests/test_gpu_track_kernels.py): the same track.o / post.o behind a test shim
     subprocess.check_call(["make", "-C", src, "trackprobe"], stdout=subprocess.DEVNULL)
+    # the NV12 copies' probe (tests/test_gpu_nv12_kernels.py) and g++'s build of the conversion itself (tests/test_nv12_cpu.py)
+    subprocess.check_call(["make", "-C", src, "nv12probe", "nv12"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -350,6 +362,54 @@ class Handle:
         self._ck(lib().vnect_track_box(self._h, stream, r))
         return list(r)
 
+    # -- NV12 frames: converted to BGR on the device, inside the frame's copy (include/vnect_abi.h; NV12.md) --------------------------
+    def frame_buffer_nv12(self, index, H, W):
+        """(H * 3 // 2, W) uint8 array over pinned staging buffer `index`: the contiguous NV12 layout -- H rows of Y, then H / 2 rows of
+        interleaved U, V directly behind, all W bytes apart.  Pass it (or a row-strided view) to the *_nv12 methods: read in place."""
+        if H % 2 or W % 2:
+            raise ValueError("an NV12 frame needs even H and W")
+        p = _u8p()
+        self._ck(lib().vnect_frame_buffer(self._h, index, H * W * 3 // 2, C.byref(p)))
+        return np.ctypeslib.as_array(p, shape=(H * 3 // 2, W))
+
+    def upload_frame_nv12(self, slot, nv12, rect=None):
+        """The converted frame -- or, with rect (x, y, w, h), its crop, cut on the device -- into resident slot `slot`."""
+        y, ys, uv, uvs, H, W = _as_nv12(nv12)
+        if rect is None:
+            self._ck(lib().vnect_upload_frame_nv12(self._h, slot, y, ys, uv, uvs, H, W))
+        else:
+            r = np.asarray([int(v) for v in rect], np.int32)
+            self._ck(lib().vnect_upload_frame_nv12_rect(self._h, slot, y, ys, uv, uvs, H, W, _ptr(r, _i32p)))
+
+    def infer_nv12(self, nv12, t2d, t3d, rect=None):
+        y, ys, uv, uvs, H, W = _as_nv12(nv12)
+        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
+        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        self._ck(lib().vnect_infer_nv12(self._h, y, ys, uv, uvs, H, W, None if r is None else _ptr(r, _i32p), t2d, t3d,
+                                        _ptr(j2, _f64p), _ptr(j3, _f32p)))
+        return j2, j3
+
+    def preprocess_nv12(self, nv12, rect=None, want_batch=True):
+        y, ys, uv, uvs, H, W = _as_nv12(nv12)
+        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
+        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
+        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
+        self._ck(lib().vnect_preprocess_nv12(self._h, y, ys, uv, uvs, H, W, None if r is None else _ptr(r, _i32p),
+                                             _ptr(batch, _f32p) if want_batch else None, C.byref(scaler), C.byref(ox), C.byref(oy)))
+        return batch, scaler.value, [ox.value, oy.value]
+
+    def submit_tracked_pinned_nv12(self, stream, index, y_stride, uv_offset, uv_stride, t2d, t3d):
+        """The stream's next frame, the whole NV12 frame in pinned buffer `index` (Y plane at its start, UV plane `uv_offset` bytes in)."""
+        self._ck(lib().vnect_submit_tracked_pinned_nv12(self._h, stream, index, int(y_stride), int(uv_offset), int(uv_stride), t2d, t3d))
+
+    def read_frame(self, slot):
+        """The (H, W, 3) BGR frame resident slot `slot` holds (a debugging read)."""
+        hw = (C.c_int32 * 2)()
+        self._ck(lib().vnect_read_frame(self._h, slot, None, 0, hw))
+        out = np.empty((hw[0], hw[1], 3), np.uint8)
+        self._ck(lib().vnect_read_frame(self._h, slot, _ptr(out, _u8p), out.size, hw))
+        return out
+
     def batch_layers(self):
         """The batched plan's layers (vnect_get_batch_layer_info), in the layout of layers()."""
         return self._layer_list(lib().vnect_get_batch_layer_info)
@@ -456,3 +516,20 @@ def _as_frame(img):
     if img.strides[2] != 1 or img.strides[1] != 3 or img.strides[0] < img.shape[1] * 3:
         img = np.ascontiguousarray(img)
     return img
+
+
+def _as_nv12(nv12):
+    """(y pointer, y stride, uv pointer, uv stride, H, W) of a 2-D uint8 array of H * 3 // 2 rows: H rows of Y, then H / 2 rows of
+    interleaved U, V.  A view with a positive row stride is passed by stride (no copy); anything else is copied."""
+    a = np.asarray(nv12)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 3 or a.shape[0] % 3 or a.shape[1] < 2:
+        raise ValueError("an NV12 frame must be a uint8 (H * 3 // 2, W) array")
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    H, W = a.shape[0] * 2 // 3, a.shape[1]
+    base = a.ctypes.data
+    a_keep = a  # (the pointers below are into it)
+    y = C.cast(C.c_void_p(base), _u8p)
+    uv = C.cast(C.c_void_p(base + H * a.strides[0]), _u8p)
+    y._keep = uv._keep = a_keep
+    return y, a.strides[0], uv, a.strides[0], H, W

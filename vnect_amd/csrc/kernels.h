@@ -162,6 +162,18 @@ hipError_t launch_pyramid_streams(const FrameParams* fp0, const FrameParams* fp1
 // vnect_infer: H rows of `row` bytes from device-mapped pinned host memory (`stride` bytes apart) into a resident frame slot, as a kernel
 hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int row, long long stride, const uint8_t* src_end, hipStream_t st);
 
+// The same from an NV12 frame in device-mapped pinned memory, converted to BGR inside the read (post.hip: nv12_copy_kernel; nv12.h).
+struct Nv12Src {
+    const uint8_t* y;       // the Y plane's first byte (any alignment), rows y_stride bytes apart
+    long long y_stride;
+    const uint8_t* uv;      // the interleaved U, V plane's first byte, rows uv_stride bytes apart
+    long long uv_stride;
+    const uint8_t* lo;      // the pinned buffer both planes lie in, [lo, end): multiples of 4; no dword is loaded outside it
+    const uint8_t* end;
+};
+// the crop (x, y, w, h) of the frame -> `dst`, rows packed 3 w bytes apart (whole frame: 0, 0, W, H); chroma by absolute coordinates
+hipError_t launch_nv12_copy(const Nv12Src& s, int x, int y, int w, int h, uint8_t* dst, hipStream_t st);
+
 // ---- the stem as one launch (stem.hip): [gen_input_batch ->] conv1 + ReLU -> 3x3 / stride-2 max-pool on spatial tiles -------------
 struct StemArgs {
     const void* batch;     // (S,368,368,4) NHWC4 batch (fp32 / bf16), or nullptr with from_frame
@@ -275,6 +287,8 @@ hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, 
 // the crop's rows (rect from the stream's state) out of a pinned frame of H rows into `dst`, packed; grid sized for the whole frame
 hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev, uint8_t* dst, int H, int W, long long stride, const uint8_t* src_end,
                                    hipStream_t st);
+// the same out of a pinned NV12 frame of (H, W) pixels, converted to BGR on the way
+hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_t* dst, int H, int W, hipStream_t st);
 // behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
 // its geometry to `ts`
 hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st);

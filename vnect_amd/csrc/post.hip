@@ -6,6 +6,7 @@
 #include "pyramid.h"
 #include "axis.h"  // axis_x_at / axis_y_at: one entry of cv2.resize's per-axis tables, computed where it is used
 #include "trackbox.h"  // the box stage of a tracked frame (post_kernel<.., true>)
+#include "nv12.h"  // NV12 -> BGR of one pixel / one group of four (nv12_copy_kernel)
 
 #include <stddef.h>
 
@@ -171,6 +172,148 @@ hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int ro
                                dst + (long long)y0 * row, hh, row, stride, src_end);
         }
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same copies from an NV12 frame (vnect_infer_nv12 / vnect_submit_tracked_pinned_nv12): the conversion to BGR (nv12.h: OpenCV's
+// integers) happens inside the read of the pinned buffer, so 1.5 bytes per pixel cross PCIe instead of 3 and everything behind the
+// slot sees the BGR frame it always saw.  The rules of the copies above hold:
+//   * a lane owns one GROUP -- absolute frame columns 4 G .. 4 G + 3 -- in BOTH rows of a chroma row (a 2-row strip): one dword of each Y
+//     row and the one UV dword under them (U0 V0 U1 V1 = exactly those four columns), so a UV row crosses PCIe once for its two Y rows;
+//   * groups are counted in frame columns, not from the crop's first column, so with plane bases and strides that are multiples of 4
+//     (a decoder's surface) every lane's dword IS an aligned dword and a wave reads 64 consecutive ones per row: whole PCIe requests.
+//     A row at another alignment is assembled from the lane's aligned dword and its neighbour's (lane + 1 through a shuffle; the
+//     last lane of a wave or of the row loads that one dword itself -- one dword per wave and row read twice, in that case only);
+//   * the 12 converted bytes of a group land at byte 12 G - 3 x of a packed crop row, at any alignment e of the destination's dword
+//     grid: dword k of the lane's window is bytes of its own dwords k - 1 and k (k = 0: the previous lane's last dword, a shuffle).
+//     Dwords that lie wholly inside the row and whose bytes the wave holds are whole stores (all three at once where they are); the
+//     first and last dword of a row -- shared with the neighbouring rows -- and the dword two WAVES share (lane 63's tail, lane 0's
+//     head) are written byte by byte, each wave the bytes it holds.
+// grid = (ceil(groups / 256), strips), 256 threads; workgroups past the crop leave at once.  Dwords are loaded only inside [lo, end),
+// the pinned buffer (base and capacity multiples of 4); bytes outside the crop are never stored.
+__device__ __forceinline__ unsigned nv12_load(uintptr_t a, const Nv12Src& s)
+{
+    return (a >= (uintptr_t)s.lo && a + 4 <= (uintptr_t)s.end) ? *(const unsigned*)a : 0u;
+}
+// the four bytes at byte `sh` of the dword pair (hi, lo)
+__device__ __forceinline__ unsigned nv12_funnel(unsigned hi, unsigned lo, int sh) { return (unsigned)((((unsigned long long)hi << 32) | lo) >> (8 * sh)); }
+// one packed destination row of the strip: P = the lane's 12 converted bytes, `drow` the row's first byte
+__device__ __forceinline__ void nv12_store_row(uint8_t* drow, int x, int w, int G, int G1, const unsigned* P)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned prev = (unsigned)__shfl_up((int)P[2], 1);  // (every lane of the wave is here: the callers branch wave-uniformly)
+    if (G > G1) return;
+    const long long t0 = 12LL * G - 3LL * x;        // row byte index of the group's byte 0 (negative for pixels in front of the crop)
+    const long long row = 3LL * w;
+    const uintptr_t E = (uintptr_t)((long long)(uintptr_t)drow + t0);
+    const int e = (int)(E & 3);                     // (the same for every group of the row: 12 G is a multiple of 4)
+    unsigned* const E0 = (unsigned*)(E - (unsigned)e);
+    const unsigned Q[4] = {nv12_funnel(P[0], prev, 4 - e), nv12_funnel(P[1], P[0], 4 - e), nv12_funnel(P[2], P[1], 4 - e), nv12_funnel(0u, P[2], 4 - e)};
+    const bool head = e == 0 || lane > 0;           // bytes in front of the group's byte 0 are the previous lane's, held through the shuffle
+    const bool tail = e != 0 && (lane == 63 || G == G1);  // nobody behind this lane in the wave writes dword 3
+    bool whole[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) whole[k] = t0 + 4 * k - e >= 0 && t0 + 4 * k - e + 4 <= row && (k > 0 || head);
+    if (whole[0] && whole[1] && whole[2]) {
+        typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+        *(u32x3*)E0 = u32x3{Q[0], Q[1], Q[2]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if (whole[k]) {
+                E0[k] = Q[k];
+                continue;
+            }
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int sbyte = 4 * k + b - e;    // byte of the group (negative: the previous group's)
+                const long long t = t0 + sbyte;
+                if (t >= 0 && t < row && (sbyte >= 0 || head)) ((uint8_t*)E0)[4 * k + b] = (uint8_t)(Q[k] >> (8 * b));
+            }
+        }
+    }
+    if (tail) {
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            const long long t = t0 + 12 + b - e;
+            if (b < e && t >= 0 && t < row) ((uint8_t*)E0)[12 + b] = (uint8_t)(Q[3] >> (8 * b));
+        }
+    }
+}
+// strip `strip` (counted from the crop's first chroma row) of the crop (x, y, w, h): rows 2 cr, 2 cr + 1 of the frame where they lie in it
+__device__ __forceinline__ void nv12_strip(const Nv12Src& s, int x, int y, int w, int h, uint8_t* __restrict__ dst, int strip)
+{
+    const int lane = threadIdx.x & 63;
+    const int G0 = x >> 2, G1 = (x + w - 1) >> 2;
+    const int Gw = G0 + (int)blockIdx.x * (NV12_WG_PX / NV12_LANE_PX) + (int)(threadIdx.x & ~63u);  // the wave's first group
+    const int cr = (y >> 1) + strip;
+    if (Gw > G1 || 2 * cr >= y + h) return;         // (wave-uniform)
+    const int G = Gw + lane;
+    const bool act = G <= G1, self_hi = act && (lane == 63 || G == G1);
+    const int r0 = 2 * cr, r1 = r0 + 1;
+    const bool row_on[2] = {r0 >= y, r1 < y + h};   // (r0 < y + h and r1 > y hold)
+    // the three streams' byte addresses of this group: every load is requested before any is used
+    const uintptr_t a[3] = {(uintptr_t)s.uv + (unsigned long long)cr * (unsigned long long)s.uv_stride + 4ull * (unsigned)G,
+                            (uintptr_t)s.y + (unsigned long long)r0 * (unsigned long long)s.y_stride + 4ull * (unsigned)G,
+                            (uintptr_t)s.y + (unsigned long long)r1 * (unsigned long long)s.y_stride + 4ull * (unsigned)G};
+    const bool on[3] = {true, row_on[0], row_on[1]};
+    unsigned lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if (!on[i]) continue;
+        const uintptr_t al = a[i] & ~(uintptr_t)3;
+        if (act) lo[i] = nv12_load(al, s);
+        if (self_hi && (a[i] & 3)) hi[i] = nv12_load(al + 4, s);
+    }
+    unsigned v[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int sh = (int)(a[i] & 3);             // (wave-uniform: the lanes' addresses differ by multiples of 4)
+        v[i] = lo[i];
+        if (on[i] && sh) {
+            const unsigned next = (unsigned)__shfl_down((int)lo[i], 1);
+            v[i] = nv12_funnel(self_hi ? hi[i] : next, lo[i], sh);
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < 2; rr++) {
+        if (!row_on[rr]) continue;
+        unsigned P[3];
+        nv12_quad(v[1 + rr], v[0], P);
+        nv12_store_row(dst + (unsigned long long)(r0 + rr - y) * (3ull * (unsigned)w), x, w, G, G1, P);
+    }
+}
+__global__ __launch_bounds__(256) void nv12_copy_kernel(const Nv12Src s, int x, int y, int w, int h, uint8_t* __restrict__ dst, int strip_base)
+{
+    nv12_strip(s, x, y, w, h, dst, strip_base + (int)blockIdx.y);
+}
+// the tracked form (frame_copy_track_kernel's contract with NV12 on the source side): the rect is the stream's state on the device, the
+// grid covers the whole frame, `dst` gets the crop's rows packed, 3 w bytes apart (pyramid_track_kernel with packed = 1)
+__global__ __launch_bounds__(256) void nv12_copy_track_kernel(const TrackState* __restrict__ ts, const Nv12Src s, uint8_t* __restrict__ dst)
+{
+    nv12_strip(s, ts->x, ts->y, ts->w, ts->h, dst, (int)blockIdx.y);
+}
+static bool nv12_src_ok(const Nv12Src& s)
+{
+    return s.y && s.uv && s.lo && s.end && s.y_stride > 0 && s.uv_stride > 0 && (((uintptr_t)s.lo | (uintptr_t)s.end) & 3) == 0;
+}
+hipError_t launch_nv12_copy(const Nv12Src& s, int x, int y, int w, int h, uint8_t* dst, hipStream_t st)
+{
+    if (!nv12_src_ok(s) || x < 0 || y < 0 || w < 1 || h < 1 || (long long)x + w > (1 << 30) || (long long)y + h > (1 << 30)) return hipErrorInvalidValue;
+    const int groups = ((x + w - 1) >> 2) - (x >> 2) + 1, strips = ((y + h - 1) >> 1) - (y >> 1) + 1;
+    const int per = NV12_WG_PX / NV12_LANE_PX;
+    for (int sb = 0; sb < strips; sb += 65535) {  // grid.y is 16 bits
+        const int n = strips - sb < 65535 ? strips - sb : 65535;
+        hipLaunchKernelGGL(nv12_copy_kernel, dim3((unsigned)((groups + per - 1) / per), (unsigned)n), dim3(256), 0, st, s, x, y, w, h, dst, sb);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_t* dst, int H, int W, hipStream_t st)
+{
+    if (!nv12_src_ok(s) || H < 2 || W < 2 || ((H | W) & 1) || H > 2 * 65535) return hipErrorInvalidValue;
+    const int per = NV12_WG_PX / NV12_LANE_PX;
+    hipLaunchKernelGGL(nv12_copy_track_kernel, dim3((unsigned)((((W + 3) >> 2) + per - 1) / per), (unsigned)(H >> 1)), dim3(256), 0, st, ts, s, dst);
     return hipGetLastError();
 }
 

@@ -182,6 +182,7 @@ void vnect_destroy(vnect_handle* h)
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
+    if (h->upload_st) hipStreamDestroy(h->upload_st);
 #if VNECT_TEST_HOOKS
     if (h->test_st) hipStreamDestroy(h->test_st);
 #endif
@@ -292,6 +293,28 @@ int vnect_forward(vnect_handle* h, const float* batch, int num_images, float* ou
     });
 }
 
+// gen_input_batch of the frame in slot 0 (vnect_preprocess, vnect_preprocess_nv12)
+static int preprocess_slot0(vnect_handle* h, float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y)
+{
+    FrameParams fp;
+    int rc;
+    if ((rc = squarify_params(h, h->slots[0].H, h->slots[0].W, &fp))) return rc;
+    FrameDyn dyn{};
+    dyn.row_stride = h->slots[0].stride, dyn.frame = h->frames;
+    if ((rc = sync_geometry(h, fp))) return rc;
+    if ((rc = run_pre(h, dyn, false, true))) return rc;
+    if (batch_out) {
+        const long long npix = (long long)h->Snet * BOX * BOX;
+        HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
+        HIPCK(h, hipMemcpyAsync(batch_out, h->in3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCK(h, hipStreamSynchronize(h->st));
+    if (scaler) *scaler = fp.scaler;
+    if (offset_x) *offset_x = fp.offx;
+    if (offset_y) *offset_y = fp.offy;
+    return VNECT_OK;
+}
+
 int vnect_preprocess(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, float* batch_out,
                      double* scaler, int32_t* offset_x, int32_t* offset_y)
 {
@@ -302,22 +325,7 @@ int vnect_preprocess(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t 
         HIPCK(h, hipSetDevice(h->cfg.device));
         int rc = upload_frame_impl(h, 0, bgr, H, W, row_stride);
         if (rc) return rc;
-        FrameParams fp;
-        if ((rc = squarify_params(h, H, W, &fp))) return rc;
-        FrameDyn dyn{};
-        dyn.row_stride = h->slots[0].stride, dyn.frame = h->frames;
-        if ((rc = sync_geometry(h, fp))) return rc;
-        if ((rc = run_pre(h, dyn, false, true))) return rc;
-        if (batch_out) {
-            const long long npix = (long long)h->Snet * BOX * BOX;
-            HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
-            HIPCK(h, hipMemcpyAsync(batch_out, h->in3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, h->st));
-        }
-        HIPCK(h, hipStreamSynchronize(h->st));
-        if (scaler) *scaler = fp.scaler;
-        if (offset_x) *offset_x = fp.offx;
-        if (offset_y) *offset_y = fp.offy;
-        return VNECT_OK;
+        return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
     });
 }
 
@@ -701,6 +709,96 @@ int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4)
         std::vector<TrackState> ts(1);
         HIPCK(h, hipMemcpy(&ts[0], h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
         rect4[0] = ts[0].x, rect4[1] = ts[0].y, rect4[2] = ts[0].uw, rect4[3] = ts[0].uh;
+        return VNECT_OK;
+    });
+}
+
+// ---- NV12 frames (additive): the conversion to BGR happens on the device, inside the frame's copy (post.hip: nv12_copy_kernel) ----------
+int vnect_upload_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return upload_nv12_impl(h, slot, y, y_stride, uv, uv_stride, H, W, nullptr, "vnect_upload_frame_nv12");
+    });
+}
+
+int vnect_upload_frame_nv12_rect(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                                 const int32_t* rect4)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return upload_nv12_impl(h, slot, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_upload_frame_nv12_rect");
+    });
+}
+
+int vnect_infer_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W, const int32_t* rect4,
+                     double t2d, double t3d, double* j2, float* j3)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !y || !uv || !j2 || !j3) return VNECT_E_ARG;
+        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_infer_nv12 before vnect_finalize");
+        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        // nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the stream the conversion runs on
+        int rc = stage_frame_nv12(h, 0, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_infer_nv12");
+        if (rc) return rc;
+        return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+    });
+}
+
+int vnect_preprocess_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W, const int32_t* rect4,
+                          float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !y || !uv) return VNECT_E_ARG;
+        if (!h->finalized && !h->pre_only) return fail(h, VNECT_E_STATE, "vnect_preprocess_nv12 before vnect_finalize");
+        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        int rc = upload_nv12_impl(h, 0, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_preprocess_nv12");
+        if (rc) return rc;
+        return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
+    });
+}
+
+int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_index, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, double t2d,
+                                     double t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = tracked_ok(h, stream);
+        if (rc) return rc;
+        if (buffer_index < 0 || buffer_index > 1 || !h->stage[buffer_index])
+            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: no such pinned buffer (vnect_frame_buffer)");
+        const int H = h->streams[stream].track_H, W = h->streams[stream].track_W;
+        if ((H | W) & 1) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: an NV12 frame needs even W and H (vnect_track_begin gave odd ones)");
+        if (y_stride < (int64_t)W || uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: y_stride and uv_stride must be at least W");
+        const size_t y_span = (size_t)(H - 1) * (size_t)y_stride + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)uv_stride + (size_t)W;
+        if (uv_offset < 0 || (size_t)uv_offset < y_span) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: the UV plane overlaps the Y plane");
+        if ((size_t)uv_offset + uv_span > h->stage_cap[buffer_index])
+            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: the planes run past the pinned buffer at these strides");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        TrackedSrc tk;
+        tk.pinned_dev = tk.pinned_lo = h->stage_dev[buffer_index], tk.pinned_end = h->stage_dev[buffer_index] + h->stage_cap[buffer_index], tk.stride = y_stride;
+        tk.nv12 = true, tk.uv_dev = h->stage_dev[buffer_index] + uv_offset, tk.uv_stride = uv_stride;
+        int ring;
+        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+    });
+}
+
+int vnect_read_frame(vnect_handle* h, int slot, uint8_t* out, int64_t capacity, int32_t* hw2)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !hw2) return VNECT_E_ARG;
+        if (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0) return fail(h, VNECT_E_ARG, "vnect_read_frame: frame slot empty or out of range");
+        const vnect_handle::SlotInfo& si = h->slots[slot];
+        hw2[0] = si.H, hw2[1] = si.W;
+        if (!out) return VNECT_OK;
+        if ((int64_t)si.H * si.W * 3 > capacity) return fail(h, VNECT_E_ARG, "vnect_read_frame: capacity too small");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        HIPCK(h, hipStreamSynchronize(h->st));  // (a staged frame's copy runs on the handle's stream)
+        HIPCK(h, hipMemcpy2D(out, (size_t)si.W * 3, h->frames + (size_t)slot * h->cfg.max_frame_bytes, (size_t)si.stride, (size_t)si.W * 3, si.H, hipMemcpyDeviceToHost));
         return VNECT_OK;
     });
 }

@@ -115,7 +115,10 @@ static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn&
 {
     TrackState* ts = h->d_track + stream;
     const Stream& sm = h->streams[stream];
-    if (tk.pinned_dev)
+    if (tk.pinned_dev && tk.nv12) {
+        const Nv12Src src = {tk.pinned_dev, tk.stride, tk.uv_dev, tk.uv_stride, tk.pinned_lo, tk.pinned_end};
+        HIPCK(h, launch_nv12_copy_track(ts, src, sm.track_buf, sm.track_H, sm.track_W, L->st));
+    } else if (tk.pinned_dev)
         HIPCK(h, launch_frame_copy_track(ts, tk.pinned_dev, sm.track_buf, sm.track_H, sm.track_W, tk.stride, tk.pinned_end, L->st));
     HIPCK(h, launch_pyramid_track(ts, dyn, tk.pinned_dev != nullptr, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
     if (L->stem_mode == 2) {
@@ -515,27 +518,102 @@ int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int
     return VNECT_OK;
 }
 
-int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride)
+// `slot` is about to be overwritten with a frame of `bytes` BGR bytes
+static int claim_slot(vnect_handle* h, int slot, size_t bytes)
 {
-    if (!bgr || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
-    if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return fail(h, VNECT_E_ARG, "bad frame geometry");
-    if ((size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes) return fail(h, VNECT_E_ARG, "frame larger than max_frame_bytes");
-    if (h->pre_only && (size_t)H * W * 3 > h->pre_frame_cap) {  // the one slot of a pre-processing-only handle grows with its frames
+    if (h->pre_only && bytes > h->pre_frame_cap) {  // the one slot of a pre-processing-only handle grows with its frames
         HIPCK(h, hipStreamSynchronize(h->st));
         if (h->frames) {
             HIPCK(h, hipFree(h->frames));
             h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->frames));
             h->frames = nullptr, h->pre_frame_cap = 0;
         }
-        int rc = dev_alloc(h, &h->frames, (size_t)H * W * 3);
+        int rc = dev_alloc(h, &h->frames, bytes);
         if (rc) return rc;
-        h->pre_frame_cap = (size_t)H * W * 3;
+        h->pre_frame_cap = bytes;
     }
-    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
     // a frame still being read by an in-flight inference must not be overwritten: wait for that inference only (frames in
     // other slots keep running, so a pipelined caller uploads frame k+1 while frames k and k-1 compute)
     const long long q = h->slots[slot].last_use;
     if (q >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->ring[q % RING].done));
+    return VNECT_OK;
+}
+
+// ---- NV12 frames (vnect_infer_nv12 and its kin) ------------------------------------------------------------------------------------------
+// stage_frame's rules with NV12 on the source side: planes inside one of the caller's pinned buffers are read where they lie, anything
+// else is first copied by the CPU into the internal stage (1.5 bytes per pixel: Y rows W apart, the UV plane directly behind); the
+// conversion is the copy kernel's (post.hip: nv12_copy_kernel), on the handle's stream, in front of the frame.  With a rect only the crop
+// is converted and lands at the slot's origin -- what stage_frame does for a BGR crop cut out of a pinned buffer; a rect that runs past the
+// frame's far edges crops what numpy slicing crops.  Every refusal comes before anything changes.
+int stage_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                     const int32_t* rect4, const char* who, hipStream_t st)
+{
+    const std::string w_ = std::string(who) + ": ";
+    if (!y || !uv || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, w_ + "bad frame slot or plane pointer");
+    if (H < 2 || W < 2 || ((H | W) & 1)) return fail(h, VNECT_E_ARG, w_ + "an NV12 frame needs even W and H (>= 2)");
+    if (y_stride < (int64_t)W || uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, w_ + "y_stride and uv_stride must be at least W");
+    const size_t y_span = (size_t)(H - 1) * (size_t)y_stride + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)uv_stride + (size_t)W;
+    if (y < uv + uv_span && uv < y + y_span) return fail(h, VNECT_E_ARG, w_ + "the UV plane overlaps the Y plane");
+    int r[4] = {0, 0, W, H};
+    if (rect4) {
+        for (int k = 0; k < 4; k++) r[k] = rect4[k];
+        if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H) return fail(h, VNECT_E_ARG, w_ + "the rect's origin must lie inside the frame");
+        if (r[2] < 1 || r[3] < 1) return fail(h, VNECT_E_ARG, w_ + "the rect must be at least one pixel wide and high");
+        r[2] = std::min(r[2], W - r[0]), r[3] = std::min(r[3], H - r[1]);
+    }
+    if ((size_t)r[2] * r[3] * 3 > (size_t)h->cfg.max_frame_bytes)
+        return fail(h, VNECT_E_ARG, w_ + "frame larger than max_frame_bytes (the slot holds BGR: 3 bytes per pixel)");
+    Nv12Src src{};
+    for (int i = 0; i < 2 && !src.y; i++) {  // already in pinned memory (a decoder's surface captured into vnect_frame_buffer)?
+        const uint8_t *lo = h->stage[i], *end = lo ? lo + h->stage_cap[i] : nullptr;
+        const bool y_in = lo && y >= lo && y < end, uv_in = lo && uv >= lo && uv < end;
+        if (!y_in && !uv_in) continue;
+        if (!y_in || !uv_in || y + y_span > end || uv + uv_span > end)
+            return fail(h, VNECT_E_ARG, w_ + "the planes run past the pinned buffer they start in");
+        src = {h->stage_dev[i] + (y - lo), (long long)y_stride, h->stage_dev[i] + (uv - lo), (long long)uv_stride, h->stage_dev[i], h->stage_dev[i] + h->stage_cap[i]};
+    }
+    if (!src.y) {
+        // only what the crop needs: its Y rows from the even row at or above its first, and the chroma rows under them, as a frame of
+        // its own (rows W apart, the UV plane directly behind); the rect moves up by the rows left out
+        const int i = 2, y0 = r[1] & ~1, rows = (r[1] + r[3] - y0 + 1) & ~1;   // (y0 + rows <= H: H is even)
+        const size_t plane = (size_t)rows * W;
+        int rc = ensure_stage(h, i, plane + plane / 2);
+        if (rc) return rc;
+        for (int q = 0; q < rows; q++) memcpy(h->stage[i] + (size_t)q * W, y + (size_t)(y0 + q) * (size_t)y_stride, (size_t)W);
+        for (int q = 0; q < rows / 2; q++) memcpy(h->stage[i] + plane + (size_t)q * W, uv + (size_t)(y0 / 2 + q) * (size_t)uv_stride, (size_t)W);
+        src = {h->stage_dev[i], (long long)W, h->stage_dev[i] + plane, (long long)W, h->stage_dev[i], h->stage_dev[i] + h->stage_cap[i]};
+        r[1] -= y0;
+    }
+    int rc = claim_slot(h, slot, (size_t)r[2] * r[3] * 3);
+    if (rc) return rc;
+    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+    HIPCK(h, launch_nv12_copy(src, r[0], r[1], r[2], r[3], dst, st ? st : h->st));
+    h->slots[slot].H = r[3], h->slots[slot].W = r[2], h->slots[slot].stride = 3LL * r[2];
+    return VNECT_OK;
+}
+
+// vnect_upload_frame_nv12 / vnect_preprocess_nv12: the same, and done when it returns (vnect_upload_frame's copy is synchronous as well).
+// The conversion runs on a stream of its own, not on lane 0's: like vnect_upload_frame's blocking copy it waits only for the slot's last
+// reader (claim_slot), so a pipelined caller uploads frame k + 1 while frame k computes.  (The internal stage is free again on return,
+// and vnect_infer_nv12, its other user, runs only with nothing in flight.)
+int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                     const int32_t* rect4, const char* who)
+{
+    if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
+    int rc = stage_frame_nv12(h, slot, y, y_stride, uv, uv_stride, H, W, rect4, who, h->upload_st);
+    if (rc) return rc;
+    HIPCK(h, hipStreamSynchronize(h->upload_st));
+    return VNECT_OK;
+}
+
+int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride)
+{
+    if (!bgr || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
+    if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return fail(h, VNECT_E_ARG, "bad frame geometry");
+    if ((size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes) return fail(h, VNECT_E_ARG, "frame larger than max_frame_bytes");
+    int rc = claim_slot(h, slot, (size_t)H * W * 3);
+    if (rc) return rc;
+    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
     HIPCK(h, hipMemcpy2D(dst, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, H, hipMemcpyHostToDevice));
     h->slots[slot].H = H, h->slots[slot].W = W, h->slots[slot].stride = (long long)W * 3;
     return VNECT_OK;

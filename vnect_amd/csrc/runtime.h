@@ -186,6 +186,7 @@ struct vnect_handle : Plan {
     uint8_t* stage_dev[3] = {};  // the same buffers as the device addresses them (hipHostMallocMapped)
     size_t stage_cap[3] = {};
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
+    hipStream_t upload_st = nullptr;  // vnect_upload_frame_nv12's conversion kernel (made on first use): not a lane's compute stream
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
     std::vector<SlotInfo> slots;
     ScaleTabs* d_stabs = nullptr;
@@ -334,6 +335,11 @@ struct TrackedSrc {
     const uint8_t* pinned_dev = nullptr;  // the frame as the device addresses it
     const uint8_t* pinned_end = nullptr;  // end of its pinned buffer
     long long stride = 0;                 // its row stride
+    // an NV12 frame (vnect_submit_tracked_pinned_nv12): pinned_dev is the Y plane (rows `stride` apart), converted to BGR by the copy
+    bool nv12 = false;
+    const uint8_t* uv_dev = nullptr;      // the interleaved U, V plane
+    long long uv_stride = 0;
+    const uint8_t* pinned_lo = nullptr;   // start of the pinned buffer
 };
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const TrackedSrc* tk = nullptr);
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
@@ -341,6 +347,12 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
 int ensure_stage(vnect_handle* h, int i, size_t bytes);
 int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
 int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
+// an NV12 frame (Y rows y_stride apart, U/V rows uv_stride apart), or its crop rect4 = (x, y, w, h), converted to BGR on its way into
+// `slot` by a kernel on the handle's stream (asynchronous, like stage_frame); upload_nv12_impl also waits for it (like upload_frame_impl)
+int stage_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                     const int32_t* rect4, const char* who, hipStream_t st = nullptr);  // st: nullptr = the handle's stream
+int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                     const int32_t* rect4, const char* who);
 int prime(vnect_handle* h);
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 int forward_batch(vnect_handle* h, const float* batch, float* out);

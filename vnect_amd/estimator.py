@@ -142,11 +142,23 @@ class VNectEstimator:
             return float(timestamp[0]), float(timestamp[1])
         return float(timestamp), float(timestamp)
 
-    def __call__(self, img_input, timestamp=None):
+    @staticmethod
+    def _format(pixel_format, rect):
+        if pixel_format not in ("bgr", "nv12"):
+            raise ValueError("pixel_format must be 'bgr' or 'nv12'")
+        if rect is not None and pixel_format != "nv12":
+            raise ValueError("rect= is for pixel_format='nv12' (a BGR caller slices the frame)")
+        return pixel_format == "nv12"
+
+    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None):
+        """``pixel_format="nv12"`` (additive): ``img_input`` is a 2-D uint8 array of ``H * 3 // 2`` rows -- H rows of Y, the interleaved
+        U, V plane from row H on; row-strided views are fine -- converted to BGR on the device (NV12.md).  ``rect=(x, y, w, h)``: only
+        that crop, as ``frame[y:y + h, x:x + w]`` of the converted frame; the joints are in crop coordinates."""
         t0 = time.time()
         t2d, t3d = self._stamps(timestamp)
+        nv12 = self._format(pixel_format, rect)
         try:
-            joints_2d, joints_3d = self._h.infer(img_input, t2d, t3d)
+            joints_2d, joints_3d = self._h.infer_nv12(img_input, t2d, t3d, rect) if nv12 else self._h.infer(img_input, t2d, t3d)
         except _native.VnectError as e:
             self._raise_like_reference(e)
         if self.verbose:
@@ -154,15 +166,19 @@ class VNectEstimator:
         return joints_2d, joints_3d
 
     # -- pipelined use (additive; the reference's loop is strictly one frame at a time) --------------------------------
-    def submit(self, img_input, timestamp=None):
+    def submit(self, img_input, timestamp=None, pixel_format="bgr", rect=None):
         """Queue a frame and return at once; at most ``max(lanes, 2)`` may be in flight.  With ``lanes=2`` / ``3`` the frames
         overlap on the GPU (+29 % frames/s for one video stream at three lanes -- `pipelined_frames_per_s_per_gpu` against `value` in
         profiles/r06_bench_line.json -- at the price of their latency); ``collect()`` returns
         results in order and they are bit-identical to calling the estimator frame by frame."""
         t2d, t3d = self._stamps(timestamp)
         slot = self._submitted % 4
+        nv12 = self._format(pixel_format, rect)
         try:
-            self._h.upload_frame(slot, img_input)
+            if nv12:
+                self._h.upload_frame_nv12(slot, img_input, rect)
+            else:
+                self._h.upload_frame(slot, img_input)
             self._h.submit_resident(slot, t2d, t3d)
         except _native.VnectError as e:
             self._raise_like_reference(e)
@@ -172,10 +188,13 @@ class VNectEstimator:
         """(joints_2d, joints_3d) of the oldest frame in flight."""
         return self._h.collect()
 
-    def frame_buffer(self, height, width, index=0):
+    def frame_buffer(self, height, width, index=0, pixel_format="bgr"):
         """Additive: a (height, width, 3) uint8 array in PINNED host memory (two exist, ``index`` 0 / 1).  Capture into it
         (``cap.read(buf)``, ``buf[...] = frame``) and pass it -- or a crop of it, as the tracking loop does -- to the estimator: the
-        frame then crosses PCIe without the CPU copy a pageable array needs first."""
+        frame then crosses PCIe without the CPU copy a pageable array needs first.  ``pixel_format="nv12"``: the same buffer as a
+        (height * 3 // 2, width) NV12 array (Y rows, then the U, V rows)."""
+        if self._format(pixel_format, None):
+            return self._h.frame_buffer_nv12(index, height, width)
         return self._h.frame_buffer(index, height, width)
 
     def reset(self):
@@ -185,3 +204,4 @@ class VNectEstimator:
         if self._h is not None:
             self._h.close()
             self._h = None
+

@@ -67,25 +67,40 @@ def init_box(estimator, frame, timestamp=None):
     return [x, y, w, h]
 
 
-def track(estimator, frames, rect=None, transpose=False, timestamps=None):
+def _nv12_checks(pixel_format, transpose):
+    if pixel_format not in ("bgr", "nv12"):
+        raise ValueError("pixel_format must be 'bgr' or 'nv12'")
+    if pixel_format == "nv12" and transpose:
+        raise ValueError("transpose=True is not supported with pixel_format='nv12': rotate the two planes before passing the frame")
+    return pixel_format == "nv12"
+
+
+def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_format="bgr"):
     """run_estimator_ps.py:80-109 without capture / drawing.  Yields (joints_2d, joints_3d, rect_used).
 
     frames: iterable of uint8 BGR arrays of one size; rect: initial (x, y, w, h), default the full frame;
     transpose: the reference's `T` option (np.rot90(frame, 3)); timestamps: optional iterable for reproducible
-    filtering (default wall clock, like the reference).
+    filtering (default wall clock, like the reference); pixel_format="nv12": the frames are (H * 3 // 2, W) NV12 arrays, converted
+    and cropped on the device (no transpose).
     """
     ts = iter(timestamps) if timestamps is not None else None
+    nv12 = _nv12_checks(pixel_format, transpose)
     for frame in frames:
         if transpose:
             frame = np.rot90(frame, 3)
         H_img, W_img = frame.shape[:2]
+        if nv12:                                   # (H * 3 // 2, W): Y rows, then the U, V rows
+            H_img = H_img * 2 // 3
         if rect is None:
             rect = [0, 0, W_img, H_img]
         x, y, w, h = rect
         if w < 1 or h < 1:  # a degenerate box (all joints on one pixel): fall back to the whole frame
             x, y, w, h = rect = [0, 0, W_img, H_img]
-        frame_cropped = frame[y:y + h, x:x + w, :]
-        joints_2d, joints_3d = estimator(frame_cropped, timestamp=next(ts) if ts is not None else None)
+        t = next(ts) if ts is not None else None
+        if nv12:                                   # the device converts and crops: the rect goes along instead of a slice
+            joints_2d, joints_3d = estimator(frame, timestamp=t, pixel_format="nv12", rect=[x, y, w, h])
+        else:
+            joints_2d, joints_3d = estimator(frame[y:y + h, x:x + w, :], timestamp=t)
         joints_2d[:, 0] += y
         joints_2d[:, 1] += x
         used = [x, y, w, h]
@@ -93,7 +108,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None):
         yield joints_2d, joints_3d, used
 
 
-def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0):
+def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr"):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -103,17 +118,21 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     ``rect`` must start inside the frame (``track`` would slice from outside it); one that runs past the far edges is cropped as
     ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight."""
     for _, j2, j3, used in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
-                                                None if timestamps is None else [timestamps], ahead, source, [stream]):
+                                                None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format):
         yield j2, j3, used
 
 
-def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None):
+def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
+                         pixel_format="bgr"):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
-    ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None)."""
+    ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
+    ``pixel_format="nv12"``: every frame is an (H * 3 // 2, W) NV12 array; the device converts the crop's rows as it reads them out of
+    the pinned buffer (or, ``source="resident"``, the whole frame on upload)."""
     from collections import deque
 
     from . import _native
+    nv12 = _nv12_checks(pixel_format, transpose)
     h = estimator.handle
     n = len(videos)
     streams = list(range(n)) if streams is None else [int(s) for s in streams]
@@ -125,6 +144,9 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     if source not in ("pinned", "resident"):
         raise ValueError("source must be 'pinned' or 'resident'")
 
+    def size_of(f):                            # (H, W) of the picture a frame array holds
+        return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
+
     def prep(f):
         f = np.rot90(f, 3) if transpose else f
         return np.ascontiguousarray(f, dtype=np.uint8)
@@ -134,7 +156,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
         f = next(its[i], None)
         if f is not None:
             pending[i] = prep(f)
-            H, W = pending[i].shape[:2]
+            H, W = size_of(pending[i])
             h.track_begin(streams[i], H, W, rects[i])
     flat = []
     if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
@@ -163,19 +185,25 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                     continue
                 frame = pending[i]
                 t2d, t3d = estimator._stamps(next(tss[i]) if tss[i] is not None else None)
-                H, W = frame.shape[:2]
+                H, W = size_of(frame)
                 try:
                     if source == "pinned":
                         b = count % 2                  # a frame captured into this buffer already (the view itself) is not copied
-                        view = flat[b][:H * W * 3].reshape(H, W, 3)
+                        view = flat[b][:frame.size].reshape(frame.shape)
                         if frame.ctypes.data != view.ctypes.data:
                             while any(k == count - 2 for _, k in inflight):   # the buffer's last frame must have been copied: collected
                                 yield collect()
                             view[...] = frame
-                        h.submit_tracked_pinned(streams[i], b, W * 3, t2d, t3d)
+                        if nv12:
+                            h.submit_tracked_pinned_nv12(streams[i], b, W, H * W, W, t2d, t3d)
+                        else:
+                            h.submit_tracked_pinned(streams[i], b, W * 3, t2d, t3d)
                     else:
                         slot = count % nslots
-                        h.upload_frame(slot, frame)
+                        if nv12:
+                            h.upload_frame_nv12(slot, frame)
+                        else:
+                            h.upload_frame(slot, frame)
                         h.submit_tracked(streams[i], slot, t2d, t3d)
                 except _native.VnectError as e:           # as in track: every earlier frame's results first
                     while inflight:
@@ -190,7 +218,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                     live[i] = False
                 else:
                     pending[i] = prep(f)
-                    if pending[i].shape[:2] != (H, W):
+                    if size_of(pending[i]) != (H, W):
                         raise ValueError("frames of one video must have one size")
         while inflight:
             yield collect()
