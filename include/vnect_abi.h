@@ -262,6 +262,9 @@ int vnect_reset_filters(vnect_handle* h);
 /* Layer output of the last vnect_forward / vnect_infer, by reference scope name ("conv1", "pool1",
  * "res2a_branch2a", block outputs "res2a".."res5a", "res5c_branch2a_feat", "res5c_branch2c", ...).
  * Writes N,H,W,C to shape4 and up to capacity floats (dense NHWC, padding channels stripped).
+ * A tensor of the plan that none of its launches writes -- "conv1" where the fused stem runs, "pool1" too where the stem also runs
+ * res2a_branch2a + res2a_branch1 -- is refused with VNECT_E_STATE and a message naming it (its buffer holds nothing); a name the plan
+ * never created (the inner layer of a fused tail launch among them) is VNECT_E_ARG as before.
  * Parity/debug aid; not on the hot path. */
 int vnect_read_activation(vnect_handle* h, const char* name, float* out, int64_t capacity, int32_t* shape4);
 

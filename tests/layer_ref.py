@@ -1,5 +1,9 @@
 """Per-launch float64 reference and per-element error gate for the conv stack (test helper, no GPU).
 
+The launches of an arena plan that keep a layer's output on chip (tail and chain GEMMs, the stem's PAIR form) have no reference here: they
+are gated by equality, tensor by tensor, to a plan of stand-alone launches that passes THIS gate in the same test
+(tests/test_gpu_fused_plan.py; VNECT_KEEP_FUSED=1 builds them on private buffers), which carries the bounds below over to them.
+
 Every tensor a keep_activations handle can return is checked ON ITS OWN: its reference is computed in float64 from the
 device's own input tensors (exact fp32 widenings of what the device holds), so no error of an earlier layer reaches it, and
 every output element is held to a bound on what the launch's arithmetic may owe -- no allowance for a fraction of elements.
@@ -38,7 +42,7 @@ import torch.nn.functional as F
 U = 2.0 ** -24
 UB = 2.0 ** -8
 # Calibrated fp32 accumulation constant, one for every precision, launch form and tile shape: the worst d / (u A) measured on an
-# MI355X over the 36 configurations of tests/test_gpu_layer_bounds.py is 7.21 (fp32, six scales, res2a_branch2b; split-product
+# MI355X over the 42 configurations of tests/test_gpu_layer_bounds.py is 7.21 (fp32, six scales, res2a_branch2b; split-product
 # 6.05 at conv1; bf16 1.91 on its fp32 final maps), the CPU stand-in's torch fp32 7.4.  C_CAL leaves 3.9x headroom over the GPU.
 MEASURED_CAL = 7.21
 C_CAL = 28.0
@@ -106,14 +110,23 @@ def table():
 TABLE = table()
 
 
-def launch_tensors(name, stem=False):
+def launch_tensors(name, stem=False, pair=False):
     """Tensors a launch of h.layers() writes (the names test_conv_stack_every_layer derives).  Raises KeyError on a launch form
-    this module does not know, so that a new one cannot escape the gate."""
+    this module does not know, so that a new one cannot escape the gate.  stem: the fused stem stands for conv1 + pool1; pair: in
+    its PAIR form, which runs res2a_branch2a + res2a_branch1 on the pooled tile and stores neither conv1 nor pool1.
+    Fused launches "<3x3 scope>><1x1 scope>[><next branch2a>]" (rt_plan.cpp add_conv_tail) store the block output (the head: the final
+    maps) and, chained, the next block's branch2a; the 3x3 layer's output stays in LDS."""
     if stem and name in ("conv1", "pool1"):  # the fused stem writes pool1 only; it is checked from `input`
-        return ["pool1"]
-    if ">" in name:                           # fused tail / chain GEMMs: their inner layer is not readable
-        raise KeyError("launch %r: a fused launch has no per-element gate (keep_activations plans do not build it)" % name)
-    if name in ("res5c_deconv", "res5c_deconv+bone_length", "res5c_bone_length"):
+        return ["res2a_branch2a", "res2a_branch1"] if pair else ["pool1"]
+    if ">" in name:
+        parts = name.split(">")
+        b, c = parts[0], parts[1]
+        if len(parts) > 3 or not b.endswith("_branch2b") or c != b[:-1] + "c" or (len(parts) == 3 and not parts[2].endswith("_branch2a")):
+            raise KeyError("launch %r: not a tail or chain form this module knows" % name)
+        out = [c if c == "res5c_branch2c" else c.split("_")[0]] + parts[2:]
+        if len(parts) == 3 and (TABLE.get(parts[2], (None, [None]))[1][0] != out[0]):
+            raise KeyError("launch %r: the chained layer does not read the block output" % name)
+    elif name in ("res5c_deconv", "res5c_deconv+bone_length", "res5c_bone_length"):
         out = ["res5c_branch2a_feat"]
     elif "[" in name:                           # "<scope>[:N]": head split of a paired launch
         out = [name.split("[")[0]]

@@ -11,9 +11,12 @@ from tests.gpu_common import BASELINE_SCALES, G, OUT, T0, _EndToEnd, _handle, _l
 pytestmark = pytest.mark.gpu
 
 
+EIGHT = [1.0, 0.93, 0.86, 0.79, 0.72, 0.65, 0.58, 0.45]   # VNECT_MAX_SCALES; 0.45: the stem's from-the-frame form does not fit
+
+
 @pytest.mark.parametrize("shape,smooth", [((368, 368), False), ((538, 368), True), ((300, 500), True),
                                           ((720, 1280), True), ((97, 61), False), ((368, 367), False)])
-@pytest.mark.parametrize("scales", [BASELINE_SCALES, [1, 0.85, 0.7]])
+@pytest.mark.parametrize("scales", [BASELINE_SCALES, [1, 0.85, 0.7], EIGHT])
 def test_preprocess_bit_exact(weights, shape, smooth, scales):
     """a10: gen_input_batch on the device == oracle, bit for bit (8-bit fixed-point bilinear + pad + /255-0.4)."""
     import oracle
@@ -102,6 +105,37 @@ def test_four_scales_whole_path(weights, oracle_net):
         a2, a3 = h.postprocess(rmaps, t, t + 0.0005, sc, off[0], off[1])
         r2, r3 = ref.postprocess(rmaps, t, t + 0.0005, sc, off[0], off[1])
         assert np.array_equal(a2, r2) and np.array_equal(a3, r3), k
+    h.close()
+
+
+def test_eight_scales_whole_path(weights, oracle_net):
+    """VNECT_MAX_SCALES images: the edge of every per-image table, of the merge geometry and of the arena.  Pre-processing and
+    post-processing bit-exact, final maps within the fp32 tolerance -- through vnect_forward, and through vnect_infer of one frame whose
+    squarify step is a copy (the stem would read the frame, but 0.45 does not fit its scratch: pyramid kernel + the stem from the batch
+    tensor), whose joints must be the oracle's post-processing of the handle's own maps, bit for bit."""
+    import oracle
+    from tests import helpers
+    h = _handle(EIGHT, weights)
+    ref = oracle.OracleEstimator(scales=EIGHT, net=oracle_net)
+    frame = helpers.synth_frame(321, 400, 310, smooth=True)
+    b, sc, off = h.preprocess(frame)
+    rb, rs, roff = oracle.gen_input_batch(frame, EIGHT)
+    assert np.array_equal(b, rb) and sc == rs and off == roff
+    maps, rmaps = h.forward(b), oracle_net.forward(rb)
+    assert np.abs(maps - rmaps).max() <= 1e-4 * np.abs(rmaps).max()
+    for k in range(3):
+        t = T0 + k / 30
+        a2, a3 = h.postprocess(rmaps, t, t + 0.0005, sc, off[0], off[1])
+        r2, r3 = ref.postprocess(rmaps, t, t + 0.0005, sc, off[0], off[1])
+        assert np.array_equal(a2, r2) and np.array_equal(a3, r3), k
+    h.reset_filters()
+    frame = helpers.synth_frame(322, 368, 300, smooth=True)
+    rb, rs, roff = oracle.gen_input_batch(frame, EIGHT)
+    j2, j3 = h.infer(frame, T0 + 1, T0 + 1.0005)
+    maps, rmaps = h.activation("res5c_branch2c"), oracle_net.forward(rb)
+    assert np.abs(maps - rmaps).max() <= 1e-4 * np.abs(rmaps).max()
+    r2, r3 = oracle.OracleEstimator(scales=EIGHT).postprocess(maps, T0 + 1, T0 + 1.0005, rs, roff[0], roff[1])
+    assert np.array_equal(j2, r2) and np.array_equal(j3, r3)
     h.close()
 
 

@@ -49,9 +49,10 @@ def _same(got, want):
 
 
 @pytest.mark.parametrize("prec", sorted(PRECISIONS))
-@pytest.mark.parametrize("scales", [[1.0, 0.8, 0.6], [1.0, 0.7], [1.0]], ids=["s3", "s2", "s1"])
+@pytest.mark.parametrize("scales", [[1.0, 0.8, 0.6], [1.0, 0.7], [1.0], [1.0, 0.9, 0.75, 0.6]], ids=["s3", "s2", "s1", "s4"])
 def test_batched_streams_equal_handles_of_their_own(weights, prec, scales):
-    """Streams 0 and 1 as batches of two (8 batches, irregular timestamps), stream 2 submitted singly in between on the same handle."""
+    """Streams 0 and 1 as batches of two (8 batches, irregular timestamps), stream 2 submitted singly in between on the same handle.
+    Four scales: 8 images per launch, the largest batch the ABI admits (2 S <= VNECT_MAX_SCALES)."""
     n = 8
     vids, times = _videos(n), _times(n)
     want = _own(weights, scales, PRECISIONS[prec], vids, times)
@@ -77,17 +78,37 @@ def test_batched_streams_equal_handles_of_their_own(weights, prec, scales):
             assert _same(got[s][k], want[s][k]), (prec, scales, s, k)
 
 
+def _forward_of_two_batches(weights, prec, scales):
+    from tests import helpers
+    S = len(scales)
+    h = _make(weights, scales, precision=PRECISIONS[prec], stream_batch=2)
+    x = np.stack([helpers.synth_frame(9400 + i, smooth=True).astype(np.float32) / 255.0 - 0.4 for i in range(2 * S)])
+    one = np.concatenate([h.forward(x[:S]), h.forward(x[S:])])
+    both = h.forward(x)
+    assert both.shape == (2 * S, 46, 46, 84) and np.array_equal(both, one)
+    swapped = h.forward(np.concatenate([x[S:], x[:S]]))
+    assert np.array_equal(swapped, np.concatenate([one[S:], one[:S]]))
+
+
 @pytest.mark.parametrize("prec", sorted(PRECISIONS))
 def test_forward_of_two_batches_equals_two_forwards(weights, prec):
-    from tests import helpers
-    scales = [1.0, 0.8, 0.6]
-    h = _make(weights, scales, precision=PRECISIONS[prec], stream_batch=2)
-    x = np.stack([helpers.synth_frame(9400 + i, smooth=True).astype(np.float32) / 255.0 - 0.4 for i in range(6)])
-    one = np.concatenate([h.forward(x[:3]), h.forward(x[3:])])
-    both = h.forward(x)
-    assert both.shape == (6, 46, 46, 84) and np.array_equal(both, one)
-    swapped = h.forward(np.concatenate([x[3:], x[:3]]))
-    assert np.array_equal(swapped, np.concatenate([one[3:], one[:3]]))
+    _forward_of_two_batches(weights, prec, [1.0, 0.8, 0.6])
+
+
+@pytest.mark.parametrize("prec", sorted(PRECISIONS))
+def test_forward_of_two_four_scale_batches_equals_two_forwards(weights, prec):
+    """8 images per launch: the largest batch the ABI admits"""
+    _forward_of_two_batches(weights, prec, [1.0, 0.9, 0.75, 0.6])
+
+
+def test_two_streams_of_five_scales_are_refused(weights):
+    """2 S <= VNECT_MAX_SCALES: ten images do not fit the per-image tables; the handle without the batch setting still finalizes."""
+    from vnect_amd import _native
+    five = [1.0, 0.9, 0.8, 0.7, 0.6]
+    with pytest.raises(_native.VnectError) as e:
+        _native.Handle(five, stream_batch=2)
+    assert e.value.code == _native.E_ARG and "VNECT_MAX_SCALES" in str(e.value)
+    _make(weights, five).close()
 
 
 @pytest.mark.parametrize("prec", sorted(PRECISIONS))

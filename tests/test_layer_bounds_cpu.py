@@ -6,6 +6,13 @@ but the fp32 final maps), the BN scale / shift of plan::fold_bn, the bone length
 pass the gate on every tensor in fp32 and in bf16; each planted fault must fail it on exactly the tensor it was planted in (the
 stand-in recomputes everything behind a fault from the faulty tensor, as a device would, so only that tensor's own launch is
 wrong).  One scale at 368 x 368, synthetic weights.
+
+The fused launches of the product plan (rt_plan.cpp: tails, chains, the stem's PAIR form) are gated on the device by equality to the
+stand-alone plan, tensor by tensor (tests/test_gpu_fused_plan.py).  Here the stand-in has a fused mode: the same arithmetic at the
+kernels' rounding points (conv.hip tail_gemm / tail_wide: the 3x3 layer's relu(acc + bias) goes to LDS in the activations' type and is
+never stored; chain_gemm / chain_narrow read the block output from LDS as it is stored, rounded; stem.hip: the pooled tile in the
+activations' type, conv1 and pool1 never stored).  Clean, it must equal the plain stand-in on every tensor it stores; each planted
+fused-launch fault must break that equality first -- in launch order -- on the tensor its launch writes.
 """
 import numpy as np
 import pytest
@@ -29,6 +36,27 @@ FAULTS = {
 }
 
 
+# The fused launches of the one-scale bf16 product plan (h.layers() names; VNECT_FORCE_CHAIN gives fp32 the wide chains too), and the
+# stem in its PAIR form
+FUSED_LAUNCHES = ["res2a_branch2b>res2a_branch2c>res2b_branch2a", "res2b_branch2b>res2b_branch2c", "res2c_branch2b>res2c_branch2c",
+                  "res3a_branch2b>res3a_branch2c>res3b_branch2a", "res3b_branch2b>res3b_branch2c>res3c_branch2a",
+                  "res3c_branch2b>res3c_branch2c>res3d_branch2a", "res3d_branch2b>res3d_branch2c", "res5c_branch2b>res5c_branch2c"]
+HIDDEN = {"conv1", "pool1"} | {n.split(">")[0] for n in FUSED_LAUNCHES}
+# fused-launch fault -> (the first tensor, in launch order, that differs from the plain stand-in; precision).  (a) the tail GEMM's bias
+# lost on 4 channels, (b) the 3x3 layer's tile put into LDS without its ReLU, (c) the shortcut rows of the last, partial tile (M = 2116 =
+# 66 x 32 + 4) read one row further down, (d) the second half of the tail's K = 64 lost for the column block 32..63, (e) the PAIR form's
+# pool windows at the right border reading on into the next row's first pixel instead of the -inf padding column (a zero there would
+# hide behind conv1's ReLU), (f) a chain GEMM reading the block output before its 16-bit rounding
+FUSED_FAULTS = {
+    "tail_bias": ("res3b", "bf16"),
+    "inner_relu": ("res3c", "fp32"),
+    "resid_row": ("res3d", "bf16"),
+    "half_k": ("res2c", "fp32"),
+    "pair_pad": ("res2a_branch2a", "fp32"),
+    "chain_unrounded": ("res3b_branch2a", "bf16"),
+}
+
+
 def _trunc_bf16(t):
     return (t.view(torch.int32) & -65536).view(torch.float32)
 
@@ -44,18 +72,23 @@ def _low_channel(y):
     return int(torch.argmin(m))
 
 
-def device_forward(weights, batch, prec, fault=None):
-    """Every tensor of TABLE (name -> NHWC float32 numpy) as a device with fp32 accumulation computes it; fault: a key of FAULTS."""
+def device_forward(weights, batch, prec, fault=None, fused=False):
+    """Every tensor of TABLE (name -> NHWC float32 numpy) as a device with fp32 accumulation computes it; fault: a key of FAULTS.
+    fused: as the launches of FUSED_LAUNCHES and the PAIR stem compute them -- the tensors of HIDDEN stay on chip and are not returned;
+    fault: a key of FUSED_FAULTS."""
     bf = prec == "bf16"
     lw = layer_ref.layer_weights(weights, prec)
-    target = FAULTS[fault][0] if fault else None
+    assert fault is None or (fault in FUSED_FAULTS) == fused
+    target = (FUSED_FAULTS if fused else FAULTS)[fault][0] if fault else None
     T = {}
+    RAW = {}   # a block output as the tail GEMM's epilogue holds it, before the store rounds it
     info = {}
 
     def f32(a):
         return torch.from_numpy(np.ascontiguousarray(a, np.float32))
 
     def store(name, v, f32_out=False):
+        RAW[name] = v
         if bf and not f32_out:
             v = _trunc_bf16(v) if (fault == "truncate" and name == target) else _rne_bf16(v)
         T[name] = v
@@ -74,7 +107,12 @@ def device_forward(weights, batch, prec, fault=None):
             x = f32(batch).permute(0, 3, 1, 2)
             T[name] = _rne_bf16(x) if bf else x
         elif op == "pool":
-            T[name] = layer_ref.maxpool_same(T[ins[0]])
+            x = T[ins[0]]
+            if fault == "pair_pad":   # the right padding column holds the next row's first pixel (the last row's: the slack's zero)
+                nxt = torch.cat([x[:, :, 1:, :1], torch.zeros_like(x[:, :, :1, :1])], 2)
+                T[name] = F.max_pool2d(F.pad(torch.cat([x, nxt], 3), (0, 0, 0, 1), value=float("-inf")), 3, 2)
+            else:
+                T[name] = layer_ref.maxpool_same(x)
         elif op in ("conv", "head"):
             x = T[ins[0]]
             if op == "head":
@@ -82,10 +120,17 @@ def device_forward(weights, batch, prec, fault=None):
             else:
                 w, b = lw[p["scope"] + "/weights"], np.array(lw[p["scope"] + "/biases"], np.float32)
                 k, stride, relu = p["k"], p["stride"], p["relu"]
-            if fault == "bias" and name == target:
+            if fault == "chain_unrounded" and name == target:
+                x = RAW[ins[0]]
+            if fault == "inner_relu" and name == TABLE[target][1][0]:
+                relu = False
+            if fault in ("bias", "tail_bias") and name == target:
                 b = b.copy()
                 b[:4] = 0
             wt = f32(w).permute(3, 2, 0, 1)
+            if fault == "half_k" and name == target:
+                wt = wt.clone()
+                wt[32:64, wt.shape[1] // 2:] = 0
             acc = F.conv2d(same(x, k, stride) if k > 1 else x, wt, stride=stride)
             if fault == "kchunk" and name == target:   # the last tile's rows without K chunk 0 (tap (0,0), channels 0..63)
                 wc = wt.clone()
@@ -102,7 +147,15 @@ def device_forward(weights, batch, prec, fault=None):
             if len(ins) > 1:
                 if fault == "double_round" and name == target:
                     v = _rne_bf16(v)
-                v = v + T[ins[1]]
+                s = T[ins[1]]
+                if fault == "resid_row" and name == target:   # rows of the last 32-row tile: the shortcut of the row below
+                    S, C, H, W = s.shape
+                    s2 = s.permute(0, 2, 3, 1).reshape(-1, C).clone()
+                    m0 = s2.shape[0] // 32 * 32
+                    s2[m0:-1] = s2[m0 + 1:].clone()
+                    s2[-1] = 0
+                    s = s2.reshape(S, H, W, C).permute(0, 3, 1, 2)
+                v = v + s
             if relu:
                 v = F.relu(v)
             if fault == "channel" and name == target:
@@ -121,7 +174,7 @@ def device_forward(weights, batch, prec, fault=None):
             dx, dy, dz = deltas[:, 0:21], deltas[:, 21:42], deltas[:, 42:63]
             bone = torch.sqrt((dx * dx + dy * dy) + dz * dz)
             store(name, torch.cat([bn, d1, bone], 1))
-    return {k: v.permute(0, 2, 3, 1).contiguous().numpy() for k, v in T.items()}, info
+    return {k: v.permute(0, 2, 3, 1).contiguous().numpy() for k, v in T.items() if not (fused and k in HIDDEN)}, info
 
 
 @pytest.fixture(scope="module")
@@ -166,6 +219,33 @@ def test_planted_fault_fails_the_gate_on_its_tensor(weights, batch, fault):
         assert row["cal"] > 1.0 and row["rig"] <= 1.0, row
 
 
+@pytest.fixture(scope="module")
+def plain_acts(weights, batch):
+    return {prec: device_forward(weights, batch, prec)[0] for prec in ("fp32", "bf16")}
+
+
+def _first_difference(fused, plain):
+    """the first tensor, in launch order (TABLE's), that the fused stand-in stores and that differs from the plain one's"""
+    return next((n for n in TABLE if n in fused and not np.array_equal(fused[n], plain[n])), None)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_clean_fused_stand_in_equals_the_plain_one(weights, batch, plain_acts, prec):
+    acts, _ = device_forward(weights, batch, prec, fused=True)
+    written = {"input"}
+    for n in ["conv1", "pool1"] + FUSED_LAUNCHES:
+        written.update(layer_ref.launch_tensors(n, stem=True, pair=True))
+    assert set(TABLE) - set(acts) == HIDDEN and written <= set(acts)
+    assert _first_difference(acts, plain_acts[prec]) is None
+
+
+@pytest.mark.parametrize("fault", sorted(FUSED_FAULTS))
+def test_planted_fused_fault_breaks_equality_first_on_its_tensor(weights, batch, plain_acts, fault):
+    target, prec = FUSED_FAULTS[fault]
+    acts, _ = device_forward(weights, batch, prec, fault, fused=True)
+    assert _first_difference(acts, plain_acts[prec]) == target
+
+
 def test_table_wiring_matches_the_float64_graph(weights, batch):
     """The input table is the graph of tests/torch_net.py: each tensor's reference, fed torch_net's own float64 activations (as
     float32), reproduces torch_net's activation of that name (a wrong input, scope, stride, padding, ReLU or BN fold would not)."""
@@ -185,8 +265,9 @@ def test_table_wiring_matches_the_float64_graph(weights, batch):
 
 
 def test_every_launch_form_maps_to_a_checked_tensor():
-    """launch_tensors: the launch names of keep_activations plans (rt_plan.cpp) map to table tensors; fused launches and unknown
-    names raise, so that the GPU test's coverage assertion fails on a launch form it does not know."""
+    """launch_tensors: the launch names of rt_plan.cpp's plans map to the table tensors they write -- a fused tail to its block output (the
+    head's to the final maps), a chain also to the next block's branch2a, the stem's PAIR form to res2a_branch2a and res2a_branch1; unknown
+    names raise, so that the GPU tests' coverage assertions fail on a launch form they do not know."""
     lt = layer_ref.launch_tensors
     assert lt("res2a_branch2a+branch1") == ["res2a_branch2a", "res2a_branch1"]
     assert lt("res2b_branch2b+res2c_branch2b") == ["res2b_branch2b", "res2c_branch2b"]
@@ -195,7 +276,14 @@ def test_every_launch_form_maps_to_a_checked_tensor():
     assert lt("res3b_branch2c") == ["res3b"] and lt("res5a_branch2c_new") == ["res5a"]
     assert lt("res5c_deconv") == lt("res5c_bone_length") == ["res5c_branch2a_feat"]
     assert lt("res5c_branch2c") == ["res5c_branch2c"] and lt("res5b_branch2c_new") == ["res5b_branch2c_new"]
-    assert lt("conv1", stem=True) == ["pool1"]
-    for bad in ("res2a_branch2b>res2a_branch2c", "res3a_branch2b>res3a_branch2c>res3b_branch2a", "res2c_branch2a", "res6a"):
+    assert lt("conv1", stem=True) == lt("pool1", stem=True) == ["pool1"]
+    assert lt("conv1", stem=True, pair=True) == lt("pool1", stem=True, pair=True) == ["res2a_branch2a", "res2a_branch1"]
+    assert lt("res2a_branch2b>res2a_branch2c") == ["res2a"] and lt("res3d_branch2b>res3d_branch2c") == ["res3d"]
+    assert lt("res2a_branch2b>res2a_branch2c>res2b_branch2a") == ["res2a", "res2b_branch2a"]
+    assert lt("res3a_branch2b>res3a_branch2c>res3b_branch2a") == ["res3a", "res3b_branch2a"]
+    assert lt("res5c_branch2b>res5c_branch2c") == ["res5c_branch2c"]
+    for bad in ("res2a_branch2b>res2b_branch2c", "res3a_branch2b>res3a_branch2c>res3c_branch2a", "res3a_branch2b>res3a_branch2c>res3b_branch2b",
+                "res2b_branch2b>res2b_branch2c>res2c_branch2a", "res3a_branch2a>res3a_branch2c", "res3a_branch2b>res3a_branch2c>res3b_branch2a>res3b",
+                "res2c_branch2a", "res6a"):
         with pytest.raises(KeyError):
             lt(bad)

@@ -515,6 +515,8 @@ int vnect_read_activation(vnect_handle* h, const char* name, float* out, int64_t
         if (!out) return VNECT_OK;
         if (!h->keep_activations && it->second != h->t_out)
             return fail(h, VNECT_E_STATE, "vnect_read_activation: inner layers share an arena; create the handle with keep_activations = 1");
+        if (!plan_writes(h, it->second))
+            return fail(h, VNECT_E_STATE, std::string("vnect_read_activation: no launch of this plan writes ") + name + " (a fused launch keeps it on chip)");
         const size_t npix = (size_t)t.S * t.H * t.W;
         if ((int64_t)(npix * t.C) > capacity) return fail(h, VNECT_E_ARG, "vnect_read_activation: capacity too small");
         HIPCK(h, hipSetDevice(h->cfg.device));

@@ -305,7 +305,7 @@ static int add_conv_tail(vnect_handle* h, const std::string& sb, const std::stri
     const long long wide_wgs = (pixels + 31) / 32;
     const bool wide = mid == 128 && cout <= 512 && wide_wgs <= cus && (h->bf16 || wide_wgs >= cus / 2 || getenv("VNECT_FORCE_WIDE_TAIL")) && !h->x3 &&
                       !getenv("VNECT_NO_WIDE_TAIL") && !getenv("VNECT_FORCE_TILE");
-    *fits = (narrow || wide) && tin.Cs % EPR == 0 && !h->keep_activations && !getenv("VNECT_NO_TAIL");
+    *fits = (narrow || wide) && tin.Cs % EPR == 0 && !h->private_only() && !getenv("VNECT_NO_TAIL");
     if (!*fits) return -1;
     const int cin = tin.C;
     const HostArray* Wb = get_w(h, sb + "/weights", {3, 3, cin, mid});
@@ -369,6 +369,19 @@ static int add_conv_tail(vnect_handle* h, const std::string& sb, const std::stri
     return L.out;
 }
 
+// Does a launch of the plan write tensor t?  The stem keeps conv1 in LDS, and pool1 too in its PAIR form (which writes the pair's outputs);
+// the inner layer of a tail launch is no tensor at all.  (The batch tensor counts: the pre-processing or vnect_forward writes it.)
+bool plan_writes(const Plan* p, int t)
+{
+    if (t == p->t_input4) return true;
+    for (int li = 0; li < (int)p->layers.size(); li++) {
+        if (p->stem_mode && (li == p->l_conv1 || (p->stem_pair && li == p->l_pool1))) continue;
+        const Layer& L = p->layers[li];
+        if (L.out == t || L.out2 == t || L.out3 == t) return true;
+    }
+    return false;
+}
+
 // point a conv layer's arguments at h's activation buffers and workspace (weights are whatever L already holds)
 static void bind_activations(Plan* h, Layer& L)
 {
@@ -397,7 +410,7 @@ static void setup_stem(Plan* h)
     const char* force = getenv("VNECT_FORCE_STEM");
     const char* mode = getenv("VNECT_STEM");
     if (getenv("VNECT_NO_STEM")) return;
-    if (h->keep_activations && !force) return;
+    if (h->private_only() && !force) return;
     if (force) mode = force;
     h->stem_mode = (mode && !strcmp(mode, "batch")) ? 1 : 2;
     StemArgs& a = h->stem;
@@ -415,7 +428,7 @@ static void setup_stem(Plan* h)
     // VNECT_NO_STEM_PAIR=1: A/B runs.
     h->stem_pair = false;
     const size_t lp = (size_t)h->l_pool1 + 1;
-    if (!h->keep_activations && !getenv("VNECT_NO_STEM_PAIR") && lp < h->layers.size()) {
+    if (!h->private_only() && !getenv("VNECT_NO_STEM_PAIR") && lp < h->layers.size()) {
         const Layer& P = h->layers[lp];
         if (P.op == OP_CONV && P.frag_w && P.in == h->layers[h->l_pool1].out && P.out >= 0 && P.out2 >= 0 && P.a.Npad == 320 &&
             P.a.split_n == 64 && P.a.relu_cols == 64 && P.a.ldc == 64 && P.a.ldc2 == 256 && P.a.M == a.S * 92 * 92) {
@@ -478,6 +491,9 @@ int finalize_impl(vnect_handle* h)
 {
     const int S = h->Snet;
     h->tensors.clear(), h->layers.clear(), h->tensor_by_name.clear();
+    // VNECT_KEEP_FUSED=1 (the parity tests): a keep_activations handle builds the launches an arena handle builds -- tails, chains, the stem
+    // from the frame with its PAIR form, the bone features inside the transposed conv -- each tensor still in a buffer of its own
+    h->keep_fused = h->keep_activations && getenv("VNECT_KEEP_FUSED");
     h->t_input4 = add_tensor(h, "input", S, BOX, BOX, 3, 4);
     auto conv = [&](const std::string& scope, int in, int k, int stride, int cout, bool relu, int resid = -1,
                     const std::string& out_name = "") {
@@ -662,7 +678,7 @@ int finalize_impl(vnect_handle* h)
         const bool shape96 = L.BM == 64 && L.BN == 96 && L.KG == 2;
         const long long deconv_items = (long long)((a.M + L.BM - 1) / L.BM) * (a.Npad / L.BN) * 4;
         const bool fuse_bone = ((L.BM == 64 && L.BN == 64 && L.KG == 1 && deconv_items <= 2 * conv_cu_count()) || (shape96 && deconv_items <= conv_cu_count())) && a.ksplit == 1 &&
-                               !h->keep_activations && !getenv("VNECT_NO_BONE_FUSE");
+                               !h->private_only() && !getenv("VNECT_NO_BONE_FUSE");
         a.bone = fuse_bone;
         if (fuse_bone) L.name = "res5c_deconv+bone_length";
         h->layers.push_back(L);

@@ -96,6 +96,8 @@ struct Plan {
     StemArgs stem{};
     bool keep_activations = false;  // one private buffer per layer output (vnect_read_activation needs it); false = arena.  Lane 0's is the
                                     // config's; every other plan's is false (a batched plan has an arena on a keep_activations handle too)
+    bool keep_fused = false;        // keep_activations with VNECT_KEEP_FUSED=1: private buffers, but the fused launches of an arena plan
+    bool private_only() const { return keep_activations && !keep_fused; }  // the plan must store every layer's output: no fused forms
     float* ws = nullptr;            // the split-K slabs of the largest K-split launch
     std::vector<void*> dev_allocs;
     FrameParams* d_fp = nullptr;   // crop geometry on the device; re-uploaded only when it differs from fp_dev
@@ -317,6 +319,7 @@ int finalize_impl(vnect_handle* h);
 int build_plans(vnect_handle* h);   // lanes 1 .. cfg.lanes - 1 and the batched plans
 void destroy_plan(Plan* p);         // every plan's teardown, lane 0's (the handle's) included
 void destroy_plans(vnect_handle* h);  // all but lane 0
+bool plan_writes(const Plan* p, int tensor);  // does a launch of the plan (or the pre-processing) write this tensor?
 
 // ---- rt_exec.cpp ---------------------------------------------------------------------------------------------------------------
 int run_network(Plan* p, bool timed, bool stem_done = false);
