@@ -28,15 +28,15 @@ def _handle(scales, weights, **kw):
     return h
 
 
-def _read_table(h, unwritten=()):
-    """Every tensor of tests/layer_ref.py's TABLE from a keep_activations handle (a missing one raises).  `unwritten`: tensors of the plan
+def _read_table(h, unwritten=(), table=None):
+    """Every tensor of tests/layer_ref.py's TABLE (or of `table`: TABLE_PAPER) from a keep_activations handle (a missing one raises).  `unwritten`: tensors of the plan
     that none of its launches writes (conv1 under the fused stem): vnect_read_activation must refuse each with VNECT_E_STATE, by name,
     and the tensor is left out."""
     import pytest
     from tests import layer_ref
     n = _native()
     acts = {}
-    for name in layer_ref.TABLE:
+    for name in (layer_ref.TABLE if table is None else table):
         if name in unwritten:
             with pytest.raises(n.VnectError) as e:
                 h.activation(name)

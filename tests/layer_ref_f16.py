@@ -57,14 +57,14 @@ def check_tensor(name, gpu, r, f16_out):
     return dict(tensor=name, rig=rig, cal=cal, match=match, ok=ok)
 
 
-def check_all(acts, weights, batch, stem=False):
-    """Gate every tensor of TABLE present in `acts` (name -> NHWC float32 read from an fp16 handle); the input must be the batch's fp16
+def check_all(acts, weights, batch, stem=False, table=TABLE):
+    """Gate every tensor of `table` (layer_ref.TABLE or TABLE_PAPER) present in `acts` (name -> NHWC float32 read from an fp16 handle); the input must be the batch's fp16
     rounding, the final maps (res5c_branch2c) are fp32.  Returns the rows, input first."""
     lw = layer_weights(weights)
     rows = []
     eq = bool(np.array_equal(acts["input"], round_f16(batch)))
     rows.append(dict(tensor="input", rig=0.0 if eq else float("inf"), cal=0.0 if eq else float("inf"), match=None, ok=eq))
-    for name in TABLE:
+    for name in table:
         if name == "input" or name not in acts or (stem and name == "conv1"):
             continue
         f16_out = name != "res5c_branch2c"
@@ -79,5 +79,5 @@ def check_all(acts, weights, batch, stem=False):
             rows.append(dict(tensor="pool1", rig=rig, cal=cal, match=match,
                              ok=rig <= 1.0 and cal <= 1.0 and match >= MATCH_FLOOR_F16))
             continue
-        rows.append(check_tensor(name, acts[name], layer_ref.reference(name, acts, lw), f16_out))
+        rows.append(check_tensor(name, acts[name], layer_ref.reference(name, acts, lw, table), f16_out))
     return rows

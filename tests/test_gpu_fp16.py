@@ -29,11 +29,16 @@ def _configs():
     c.append(("stem", BASELINE_SCALES, "square", {"VNECT_FORCE_STEM": "batch"}, "synthetic"))
     c.append(("seed7", BASELINE_SCALES, "square", {}, "seed7"))
     c.append(("planted", BASELINE_SCALES, "planted", {}, "planted"))
+    c = [x + (False,) for x in c]
+    # the paper wiring of res2c (paper_res2c=True; layer_ref.TABLE_PAPER)
+    c.append(("paper_base", BASELINE_SCALES, "square", {}, "synthetic", True))
+    c.append(("paper_S1", [1.0], "square", {}, "synthetic", True))
     return c
 
 
 CONFIGS = _configs()
 RESULTS = {}
+PAPER = []   # the configurations with paper_res2c=True
 
 
 def _weights(kind, default):
@@ -55,48 +60,58 @@ def _plan(layers):
     return [(L["name"], L["M"], L["N"], L["K"], L["tile_m"], L["tile_n"], L["split_k"], L["workgroups"]) for L in layers]
 
 
-@pytest.mark.parametrize("scales", [[1.0], [1.0, 0.7], BASELINE_SCALES, SIX], ids=["S1", "S2", "S3", "S6"])
-def test_fp16_plan_is_the_bf16_plan(weights, scales):
+@pytest.mark.parametrize("scales,paper", [([1.0], False), ([1.0, 0.7], False), (BASELINE_SCALES, False), (SIX, False),
+                                          ([1.0], True), (BASELINE_SCALES, True)], ids=["S1", "S2", "S3", "S6", "paper_S1", "paper_S3"])
+def test_fp16_plan_is_the_bf16_plan(weights, scales, paper):
     n = _native()
-    hb = _handle(scales, weights, precision=n.BF16, stream_batch=2 if len(scales) <= 4 else 1)
-    hh = _handle(scales, weights, precision=n.FP16, stream_batch=2 if len(scales) <= 4 else 1)
+    hb = _handle(scales, weights, precision=n.BF16, stream_batch=2 if len(scales) <= 4 else 1, paper_res2c=paper)
+    hh = _handle(scales, weights, precision=n.FP16, stream_batch=2 if len(scales) <= 4 else 1, paper_res2c=paper)
     assert _plan(hh.layers()) == _plan(hb.layers())
+    # (the paper wiring's own chain launch, in the scale plan and the batched one)
+    assert any(L["name"] == "res2b_branch2b>res2b_branch2c>res2c_branch2a" for L in hh.layers()) == paper
     if len(scales) <= 4:
         assert _plan(hh.batch_layers()) == _plan(hb.batch_layers())
     hb.close(), hh.close()
 
 
-@pytest.mark.parametrize("cid,scales,frame,env,wkind", CONFIGS, ids=[c[0] for c in CONFIGS])
-def test_fp16_every_tensor_within_its_element_bounds(weights, monkeypatch, cid, scales, frame, env, wkind):
+@pytest.mark.parametrize("cid,scales,frame,env,wkind,paper", CONFIGS, ids=[c[0] for c in CONFIGS])
+def test_fp16_every_tensor_within_its_element_bounds(weights, monkeypatch, cid, scales, frame, env, wkind, paper):
     import oracle
     n = _native()
     w = _weights(wkind, weights)
+    table = layer_ref.TABLE_PAPER if paper else layer_ref.TABLE
     batch, _, _ = oracle.gen_input_batch(_frame(frame), scales)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    h = _handle(scales, w, precision=n.FP16, keep_activations=True)
+    h = _handle(scales, w, precision=n.FP16, keep_activations=True, paper_res2c=paper)
     for k in env:
         monkeypatch.delenv(k)
     try:
         launches = h.layers()
         out = h.forward(batch)
-        acts = _read_table(h, unwritten=("conv1",) if "VNECT_FORCE_STEM" in env else ())
+        acts = _read_table(h, unwritten=("conv1",) if "VNECT_FORCE_STEM" in env else (), table=table)
     finally:
         h.close()
     assert np.array_equal(out, acts["res5c_branch2c"])
     stem = "VNECT_FORCE_STEM" in env
-    rows = layer_ref_f16.check_all(acts, w, batch, stem=stem)
+    rows = layer_ref_f16.check_all(acts, w, batch, stem=stem, table=table)
     checked = {r["tensor"] for r in rows}
-    uncovered = [L["name"] for L in launches if not set(layer_ref.launch_tensors(L["name"], stem)) & checked]
+    uncovered = [L["name"] for L in launches if not set(layer_ref.launch_tensors(L["name"], stem, table=table)) & checked]
+    names = [L["name"] for L in launches]
     RESULTS[cid] = rows
+    if paper:
+        PAPER.append(cid)
     worst = {k: max((r[k], c, r["tensor"]) for c, rs in RESULTS.items() for r in rs) for k in ("rig", "cal")}
     low = min((r["match"], c, r["tensor"]) for c, rs in RESULTS.items() for r in rs if r["match"] is not None)
-    _log("fp16_bounds.json", dict(match_floor=layer_ref_f16.MATCH_FLOOR_F16, worst=worst, lowest_match=low, configs=RESULTS))
+    _log("fp16_bounds.json", dict(match_floor=layer_ref_f16.MATCH_FLOOR_F16, worst=worst, lowest_match=low, paper_res2c=PAPER,
+                                  configs=RESULTS))
     for r in rows:
         print("%-16s %-22s rigorous %.3g calibrated %.3g match %s" % (cid, r["tensor"], r["rig"], r["cal"],
                                                                        "-" if r["match"] is None else "%.5f" % r["match"]))
     assert not uncovered, uncovered
-    assert len(rows) == len(layer_ref.TABLE) - (1 if stem else 0)
+    if paper:
+        assert "res2c_branch2a" in names and not any("res2b_branch2b+res2c_branch2b" in x for x in names), names
+    assert len(rows) == len(table) - (1 if stem else 0)
     bad = [r for r in rows if not r["ok"]]
     assert not bad, bad[:4]
 

@@ -7,6 +7,9 @@ claims a fused launch sums what its stand-alone layers sum, in their order; so e
 that name on a handle without fused forms whose absorbed layers run whole-K 64 x 64 tiles -- and that handle passes the per-element
 float64 gate of tests/layer_ref.py in the same test, which carries its bounds over to the fused plan.  S = 1, 2, 3 (67 / 133 / 199
 workgroups of the wide tail; M = 2116 = 33 x 64 + 4 at one scale: a partial last tile) in every precision.
+The paper wiring of res2c (paper_res2c=True, configurations paper_*; gated by layer_ref.TABLE_PAPER) builds launches the default one never
+does -- in bf16 / fp16 the narrow chain res2b_branch2b>res2b_branch2c>res2c_branch2a, whose shortcut is the block input itself; in fp32 two
+stand-alone 1x1 launches between three narrow tails -- and goes through the same body.
 Tables: fused_plan.json in the tests' log directory (gpu_common.OUT)."""
 import json
 import os
@@ -30,9 +33,15 @@ SCALES = {1: [1.0], 2: [1.0, 0.7], 3: BASELINE_SCALES}
 #   res2a_branch1), so only `input` is in front of it.
 NOT_EQUAL = {"fp32_split": (lambda name: name == "conv1" or ">" in name, "fp32-instruction tail GEMM against split products", 1e-5)}
 
-CONFIGS = [("%s_S%d" % (prec, S), prec, S, {}) for prec in ("fp32", "bf16", "fp16", "fp32_split") for S in (1, 2, 3)]
-CONFIGS += [("fp32_S%d_wide" % S, "fp32", S, {"VNECT_FORCE_WIDE_TAIL": "1"}) for S in (1, 2)]
-CONFIGS += [("fp32_S3_chain", "fp32", 3, {"VNECT_FORCE_CHAIN": "1"})]
+CONFIGS = [("%s_S%d" % (prec, S), prec, S, {}, False) for prec in ("fp32", "bf16", "fp16", "fp32_split") for S in (1, 2, 3)]
+CONFIGS += [("fp32_S%d_wide" % S, "fp32", S, {"VNECT_FORCE_WIDE_TAIL": "1"}, False) for S in (1, 2)]
+CONFIGS += [("fp32_S3_chain", "fp32", 3, {"VNECT_FORCE_CHAIN": "1"}, False)]
+CONFIGS += [("paper_%s_S%d" % (prec, S), prec, S, {}, True) for prec in ("bf16", "fp16") for S in (1, 2, 3)]
+CONFIGS += [("paper_%s_S%d" % (prec, S), prec, S, {}, True) for prec in ("fp32", "fp32_split") for S in (1, 3)]
+# the res2 stage of the paper wiring's arena plan, by launch name (rt_plan.cpp, the paper_res2c block): 16-bit handles chain every next
+# branch2a; fp32 handles run res2b_branch2a and res2c_branch2a as launches of their own between three two-part tails
+PAPER_CHAINS = ["res2a_branch2b>res2a_branch2c>res2b_branch2a", "res2b_branch2b>res2b_branch2c>res2c_branch2a", "res2c_branch2b>res2c_branch2c"]
+PAPER_TAILS = ["res2a_branch2b>res2a_branch2c", "res2b_branch2a", "res2b_branch2b>res2b_branch2c", "res2c_branch2a", "res2c_branch2b>res2c_branch2c"]
 RESULTS = {}
 
 
@@ -60,15 +69,15 @@ def _stem_pair(names):
     return names[:3] == ["conv1", "pool1", "res2a_branch2a+branch1"]
 
 
-def _written(names):
+def _written(names, table=layer_ref.TABLE):
     """launch name -> tensors it stores, for the seam plan (launch order); the pair behind pool1 runs inside the PAIR stem"""
     pair = _stem_pair(names)
     out = []
     for n in names:
         if n in ("conv1", "pool1"):
-            out.append((n, layer_ref.launch_tensors(n, stem=True, pair=pair)))
+            out.append((n, layer_ref.launch_tensors(n, stem=True, pair=pair, table=table)))
         else:
-            out.append((n, layer_ref.launch_tensors(n)))
+            out.append((n, layer_ref.launch_tensors(n, table=table)))
     return out
 
 
@@ -87,19 +96,41 @@ def _is_absorbed(name, absorbed):
     return name in absorbed or all(part in absorbed for part in name.split("+"))   # (res2b_branch2b+res2c_branch2b: both 3x3 layers)
 
 
+def _paper_res2_stage(names, prec):
+    """the paper plan's shape, by name: the launches between the stem's pair and res3a's"""
+    i0, i1 = names.index("res2a_branch2a+branch1") + 1, names.index("res3a_branch2a+branch1")
+    assert names[i0:i1] == (PAPER_CHAINS if prec in ("bf16", "fp16") else PAPER_TAILS), names[i0:i1]
+    if prec in ("bf16", "fp16"):
+        assert "res2b_branch2a" not in names and "res2c_branch2a" not in names
+
+
 @pytest.mark.parametrize("S", [1, 2, 3])
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 def test_seam_plan_is_the_arena_plan(weights, monkeypatch, prec, S):
     """VNECT_KEEP_FUSED=1 on a keep_activations handle: the launches of a default arena handle, name for name and tile for tile; on an
     arena handle, and unset, it changes nothing."""
-    arena = _handle(SCALES[S], weights, precision=_prec(prec))
-    keep = _handle(SCALES[S], weights, precision=_prec(prec), keep_activations=True)
-    seam = _with_env(monkeypatch, {"VNECT_KEEP_FUSED": "1"}, SCALES[S], weights, precision=_prec(prec), keep_activations=True)
-    arena2 = _with_env(monkeypatch, {"VNECT_KEEP_FUSED": "1"}, SCALES[S], weights, precision=_prec(prec))
+    _seam_is_arena(weights, monkeypatch, prec, S, False)
+
+
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_seam_plan_is_the_arena_plan_with_paper_wiring(weights, monkeypatch, prec, S):
+    """... and with paper_res2c=True: the seam handle of the paper_* configurations below runs what a paper arena handle runs."""
+    _seam_is_arena(weights, monkeypatch, prec, S, True)
+
+
+def _seam_is_arena(weights, monkeypatch, prec, S, paper):
+    kw = dict(precision=_prec(prec), paper_res2c=paper)
+    arena = _handle(SCALES[S], weights, **kw)
+    keep = _handle(SCALES[S], weights, keep_activations=True, **kw)
+    seam = _with_env(monkeypatch, {"VNECT_KEEP_FUSED": "1"}, SCALES[S], weights, keep_activations=True, **kw)
+    arena2 = _with_env(monkeypatch, {"VNECT_KEEP_FUSED": "1"}, SCALES[S], weights, **kw)
     try:
         want = _plan(arena.layers())
         assert _plan(seam.layers()) == want
         assert _plan(arena2.layers()) == want
+        if paper:
+            _paper_res2_stage([x[0] for x in want], prec)
         # (one scale: the transposed conv runs 64 x 32 tiles with two K groups, which do not take the bone features)
         assert any(">" in n for n, *_ in want) and any(n == "res5c_deconv+bone_length" for n, *_ in want) == (S >= 2)
         assert not any(">" in L["name"] or "bone_length" in L["name"].split("+") for L in keep.layers())
@@ -123,21 +154,26 @@ def test_default_plans_are_unchanged(weights):
         assert got == [tuple(x) for x in want], key
 
 
-@pytest.mark.parametrize("cid,prec,S,env", CONFIGS, ids=[c[0] for c in CONFIGS])
-def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, monkeypatch, cid, prec, S, env):
+@pytest.mark.parametrize("cid,prec,S,env,paper", CONFIGS, ids=[c[0] for c in CONFIGS])
+def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, monkeypatch, cid, prec, S, env, paper):
     import oracle
     from tests import helpers, layer_ref_f16
     n = _native()
     scales = SCALES[S]
-    fused = _with_env(monkeypatch, dict(env, VNECT_KEEP_FUSED="1"), scales, weights, precision=_prec(prec), keep_activations=True)
+    table = layer_ref.TABLE_PAPER if paper else layer_ref.TABLE
+    fused = _with_env(monkeypatch, dict(env, VNECT_KEEP_FUSED="1"), scales, weights, precision=_prec(prec), keep_activations=True,
+                      paper_res2c=paper)
     plain = None
     try:
         names = [L["name"] for L in fused.layers()]
         assert any(">" in x for x in names) and _stem_pair(names) and ("res5c_deconv+bone_length" in names) == (S >= 2), names
         absorbed = _absorbed(names)
+        if paper:
+            _paper_res2_stage(names, prec)
+            assert ("res2c_branch2a" in absorbed) == (prec in ("bf16", "fp16"))
         pins = ";".join("%s=64,64,1,1" % x for x in sorted(absorbed))
         plain = _with_env(monkeypatch, {"VNECT_NO_TAIL": "1", "VNECT_NO_STEM": "1", "VNECT_PLAN": pins}, scales, weights,
-                          precision=_prec(prec), keep_activations=True)
+                          precision=_prec(prec), keep_activations=True, paper_res2c=paper)
         pl = plain.layers()
         assert not any(">" in L["name"] for L in pl) and [L["name"] for L in pl][:2] == ["conv1", "pool1"]
         pinned = [L for L in pl if _is_absorbed(L["name"], absorbed)]
@@ -147,9 +183,9 @@ def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, m
         assert all((L["tile_m"], L["tile_n"], L["split_k"]) == (64, 64, 1) for L in pinned), [x for x in _plan(pinned)]
 
         # what the fused plan stores, from its launch names; exactly that can be read back
-        written = _written(names)
+        written = _written(names, table)
         stored = {"input"} | {t for _, ts in written for t in ts}
-        for name in layer_ref.TABLE:
+        for name in table:
             if name in stored:
                 continue
             with pytest.raises(n.VnectError) as e:
@@ -157,7 +193,7 @@ def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, m
             created = name in ("conv1", "pool1")   # tensors of the plan that the stem keeps on chip; a tail's 3x3 layer is no tensor at all
             assert e.value.code == (n.E_STATE if created else n.E_ARG), (name, e.value)
             assert name in str(e.value)
-        order = [t for t in layer_ref.TABLE if t in stored]   # TABLE is in launch order
+        order = [t for t in table if t in stored]   # the table is in launch order
         launch_of = {t: ln for ln, ts in reversed(written) for t in ts}
 
         def first_approx():
@@ -193,7 +229,7 @@ def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, m
         out_f, out_p = fused.forward(batch), plain.forward(batch)
         worst_fwd = compare("forward")
         assert np.array_equal(out_f, fused.activation("res5c_branch2c")) and np.array_equal(out_p, plain.activation("res5c_branch2c"))
-        acts = {name: plain.activation(name) for name in layer_ref.TABLE}
+        acts = {name: plain.activation(name) for name in table}
         # one frame whose squarify step is a copy (long side 368): the stem builds the pyramid from the frame, the batch tensor is not written
         frame = helpers.synth_frame(91 + S, 368, 300, smooth=True)
         jf, jp = fused.infer(frame, T0 + 5, T0 + 5.001), plain.infer(frame, T0 + 5, T0 + 5.001)
@@ -207,18 +243,18 @@ def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, m
 
     # the plain plan inside its float64 bounds, per element
     if prec == "fp16":
-        rows = layer_ref_f16.check_all(acts, weights, batch)
+        rows = layer_ref_f16.check_all(acts, weights, batch, table=table)
     else:
         split = set()
         if prec == "fp32_split":
             for L in pl:
                 if L["M"] and L["tile_m"] == 64 and L["tile_n"] in (32, 64) and L["name"] != "conv1":
-                    split.update(layer_ref.launch_tensors(L["name"]))
-        rows = layer_ref.check_all(acts, weights, prec, batch, split_tensors=split)
-    RESULTS[cid] = dict(prec=prec, scales=scales, env=env, fused_launches=names, stored=order, pinned=sorted(absorbed),
+                    split.update(layer_ref.launch_tensors(L["name"], table=table))
+        rows = layer_ref.check_all(acts, weights, prec, batch, split_tensors=split, table=table)
+    RESULTS[cid] = dict(prec=prec, scales=scales, env=env, paper_res2c=paper, fused_launches=names, stored=order, pinned=sorted(absorbed),
                         equal=order if approx_at is None else order[:approx_at], worst_of_max=dict(forward=worst_fwd, infer=worst_inf),
                         plain_rows=rows)
     _log("fused_plan.json", RESULTS)
-    assert len(rows) == len(layer_ref.TABLE)
+    assert len(rows) == len(table)
     bad = [r for r in rows if not r["ok"]]
     assert not bad, bad[:4]
