@@ -306,6 +306,12 @@ int vnect_get_layer_info(vnect_handle* h, int idx, vnect_layer_info* out);
 /* ABI v7.  The same for the batched plan of vnect_set_stream_batch(h, 2) (VNECT_E_STATE without one); last_ms is from the last batch
  * submitted while profiling.  Its counterpart in the reference is the batch dimension of the one graph (src/estimator.py:100-104). */
 int vnect_get_batch_layer_info(vnect_handle* h, int idx, vnect_layer_info* out);
+/* Additive (the version and vnect_layer_info stay): the rows layer idx of the plan (batch != 0: of the batched plan) COMPUTES.  That is
+ * vnect_layer_info::M for every launch but a live-rows one -- a tail launch whose output only stride-s 1x1 convs read computes the pixels
+ * (s y, s x) alone and keeps M, tile and workgroups of the full grid; vnect_layer_info::flops and vnect_timings::conv_flops count the
+ * computed rows.  live_rule_stride (may be NULL): the stride s by the plan rule for this launch, 0 where it does not apply -- the rule's
+ * answer, whether or not the launch's kernel form takes the mode. */
+int vnect_get_layer_rows(vnect_handle* h, int idx, int batch, int32_t* rows_computed, int32_t* live_rule_stride);
 /* Raw 100 MHz device-clock stamps of layer idx in the last profiled frame (tuning aid): [0] earliest workgroup start,
  * [1..8] latest workgroup ends, [9..13] workgroup 0: start, operands requested, first chunk in LDS, K loop done,
  * stores done; [15] start of the last-dispatched workgroups; [16..18] shader-clock cycles producer wave 0 of workgroup

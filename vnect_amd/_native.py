@@ -82,6 +82,7 @@ SYMBOLS = {
     "vnect_get_timings": (C.c_int, [_H, C.POINTER(Timings)]),
     "vnect_reset_timings": (C.c_int, [_H]),
     "vnect_get_layer_info": (C.c_int, [_H, C.c_int, C.POINTER(LayerInfo)]),
+    "vnect_get_layer_rows": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vnect_get_layer_stamps": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint64)]),
     "vnect_comm_unique_id": (C.c_int, [C.c_void_p]),
     "vnect_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
@@ -493,6 +494,19 @@ class Handle:
 
     def layers(self):
         return self._layer_list(lib().vnect_get_layer_info)
+
+    def layer_rows(self, batch=False):
+        """Per launch of the plan (batch: of the batched plan): (rows_computed, live_rule_stride) -- vnect_get_layer_rows."""
+        out, i = [], 0
+        while True:
+            rows, rule = C.c_int32(), C.c_int32()
+            rc = lib().vnect_get_layer_rows(self._h, i, int(batch), C.byref(rows), C.byref(rule))
+            if rc == E_STATE:
+                self._ck(rc)
+            if rc:
+                return out
+            out.append((rows.value, rule.value))
+            i += 1
 
     def _layer_list(self, fn):
         out, i = [], 0

@@ -22,6 +22,7 @@
 #endif
 
 #include <array>
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -139,6 +140,45 @@ __device__ __forceinline__ void bload_lds(srd_t, float*, unsigned, unsigned) {}
 #endif
 
 // ---------------------------------------------------------------------------------------------------------
+// LIVE ROWS (fp32 64-wide tail, ConvArgs::live_s): the block output is read by stride-s 1x1 convs only, so the launch
+// computes the pixels (image, s oy', s ox') and nothing else -- the launcher hands the kernel the live grid (Ho / s x Wo / s, input
+// stride s: an ordinary 3x3 pad-1 conv at output stride s) and os = s, OH x OW = the full grid.  Row j of a tile then lies at pixel
+// (image * OH + s oy') * OW + s ox' of the shortcut and the output tensor: the distance between a lane's rows is no longer uniform.
+// Every wave keeps a table of its tile's 64 row offsets (bytes; one lane decodes one row) in LDS, in a slot of its own, and reads a
+// row's entry where it needs it (one ds_read_b32: no registers held across the blocks of the tail GEMM, which has none to spare).  A row at or past the live count gets offset 2^31: the
+// buffer-addressed shortcut loads and output stores below are then out of range -- the hardware fetches nothing and writes nothing.
+typedef __attribute__((address_space(3))) unsigned lds_u32;  // (said outright: a table read must be a ds_read, never a FLAT access)
+__device__ __forceinline__ void live_fill(const ConvArgs& a, int M, int Wo, int Ho, unsigned mg_wo, unsigned mg_ho, int m0, int lane, lds_u32* tab)
+{
+    const int m = m0 + lane;
+    const bool ok = m < M;
+    const int mm = ok ? m : 0;
+    const int t = fdiv(mm, mg_wo, Wo), ox = mm - t * Wo;
+    const int sI = fdiv(t, mg_ho, Ho), oy = t - sI * Ho;
+    const int pix = (sI * a.OH + oy * a.os) * a.OW + ox * a.os;
+    tab[lane] = ok ? (unsigned)(pix * a.ldc) * 4u : 0x80000000u;  // (ldr == ldc: the launcher checks)
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ unsigned bload_u32(srd_t r, unsigned voff, unsigned soff) { return __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0); }
+__device__ __forceinline__ void bstore_f32(srd_t r, float v, unsigned voff, unsigned soff)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 16);  // aux 16 = sc1: write-through, like put_f32
+}
+#else
+__device__ __forceinline__ unsigned bload_u32(srd_t, unsigned, unsigned) { return 0; }
+__device__ __forceinline__ void bstore_f32(srd_t, float, unsigned, unsigned) {}
+#endif
+// shortcut values of column block cb for the lane's 16 rows; rb = the lane's first row within the tile (32 wm + 4 (lane >> 5))
+__device__ __forceinline__ void live_load_resid(srd_t rs, const lds_u32* tab, int rb, int cb, int lane, unsigned (&rw)[16])
+{
+    const unsigned colb = (unsigned)((lane & 31) * 4);
+    const lds_u32* lt = tab + rb;
+    asm volatile("" ::: "memory");  // read the table here, every time: sixteen offsets held from block to block are registers the tail GEMM does not have
+#pragma unroll
+    for (int r = 0; r < 16; r++) rw[r] = bload_u32(rs, lt[(r & 3) + 8 * (r >> 2)] + colb, (unsigned)(cb * 128));
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Bone-length features (vnect_model.py:198-209) inside the transposed conv's launch (FUSE = 2): the tile with output columns
 // 128 .. 191 holds delta_x (128 + j), delta_y (149 + j), delta_z (170 + j), j < 21; its accumulators are in LDS ([64 rows][BONE_LS]),
 // and the four producer waves (256 threads) write bone_j = sqrt((dx^2 + dy^2) + dz^2) to column 191 + j of every row's output
@@ -246,7 +286,8 @@ __device__ __forceinline__ void tail_write_out(const ConvArgs& a, const float* s
 }
 // NBLK blocks cb0, cb0 + cbs, ...; PRE: T.rw[0], T.rw[1] (blocks 0, 1) and T.Bf (block 0) were requested by the caller
 template <int BF, int NBLK, bool PRE, bool CH = false>
-__device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, int m0, int wm, int cb0, int cbs, int lane, TailRegs<BF>& T)
+__device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, int m0, int wm, int cb0, int cbs, int lane, TailRegs<BF>& T,
+                                          const lds_u32* ltab = nullptr)  // ltab: live rows -- this wave's table of row offsets (live_fill)
 {
     static_assert(!CH || BF, "the 64-wide chain exists in bf16 only");
     constexpr int MS = TAIL_MS<BF>, NQ = TailRegs<BF>::NQ;
@@ -263,10 +304,18 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
             else Af[q] = *(const f32x4*)(smem + arow * MS + UQ * q + UH * hh);
         }
     }
+    const bool live = !BF && ltab != nullptr;  // (uniform)
+    const int rb = wm * 32 + 4 * hh;
+    const srd_t srdR = make_srd(a.resid), srdO = make_srd(a.out);
     if constexpr (!PRE) {
         tail_load_b<BF>(a, cb0, lane, T.Bf);
-        if (a.resid) tail_load_resid<BF>(a, mb, cb0, lane, T.rw[0]);
-        if (a.resid && NBLK > 1) tail_load_resid<BF>(a, mb, cb0 + cbs, lane, T.rw[1]);
+        if (live) {
+            live_load_resid(srdR, ltab, rb, cb0, lane, T.rw[0]);
+            if (NBLK > 1) live_load_resid(srdR, ltab, rb, cb0 + cbs, lane, T.rw[1]);
+        } else {
+            if (a.resid) tail_load_resid<BF>(a, mb, cb0, lane, T.rw[0]);
+            if (a.resid && NBLK > 1) tail_load_resid<BF>(a, mb, cb0 + cbs, lane, T.rw[1]);
+        }
     }
     const bool t_of32 = !BF || a.out_f32;
 #pragma unroll
@@ -299,6 +348,17 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
                 const float o = __builtin_fmaxf(acc[r] + bias2 + widen<BF>(rw[r]), 0.f);
                 ((h16<BF>*)smem)[NCHAIN_OFF + (wm * 32 + 4 * hh + (r & 3) + 8 * (r >> 2)) * NCHAIN_OS + n2] = (h16<BF>)o;
             }
+        } else if (live) {
+            // live rows (shortcut + all tail_n columns valid: the launcher checks): the same arithmetic, the row's offset from the table
+            const lds_u32* lt = ltab + rb;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                if ((r & 3) == 0) asm volatile("" ::: "memory");  // (as in live_load_resid; and at most four offsets in registers at a time)
+                float o = acc[r] + bias2;
+                o = o + widen<BF>(rw[r]);
+                if (relu2) o = __builtin_fmaxf(o, 0.f);
+                bstore_f32(srdO, o, lt[(r & 3) + 8 * (r >> 2)] + (unsigned)(col * 4), (unsigned)(cb * 128));
+            }
         } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
@@ -312,7 +372,10 @@ __device__ __forceinline__ void tail_gemm(const ConvArgs& a, const float* smem, 
                 }
             }
         }
-        if (b + 2 < NBLK && a.resid) tail_load_resid<BF>(a, mb, cb + 2 * cbs, lane, T.rw[b & 1]);  // the slot just consumed
+        if (b + 2 < NBLK && a.resid) {  // the slot just consumed
+            if (live) live_load_resid(srdR, ltab, rb, cb + 2 * cbs, lane, T.rw[b & 1]);
+            else tail_load_resid<BF>(a, mb, cb + 2 * cbs, lane, T.rw[b & 1]);
+        }
     }
 }
 
@@ -651,6 +714,8 @@ template <int BM, int BN, int KG, int NS, int BF, int PROF, int FUSE = 0, bool S
 __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_stream_kernel(const ConvArgs a)
 {
     constexpr bool TAIL = FUSE == 1 || FUSE == 3, BONE = FUSE == 2, CHAIN = FUSE == 3;  // 3: the wide tail with a chain GEMM behind it
+    constexpr bool WIDE_TILE = BN == 128;
+    constexpr bool LIVE = FUSE == 1 && !WIDE_TILE && !BF;  // the forms that can run a live-rows launch (a.os != 1 then: uniform, per launch)
     constexpr bool SINGLE = ONE || FUSE != 0;  // one item per workgroup, ksplit == 1
     static_assert(!SPAN || (BM == 64 && BN == 64 && KG == 1 && !BF && FUSE == 0), "span mode is conv1's fp32 form");
     // NACC (round 4): 32-column blocks per consumer wave.  64 x 96 x 2 -- two K groups x two row blocks, every wave THREE accumulators that share
@@ -723,6 +788,11 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
         // one item per workgroup (grid == items, most layers): skip the integer division (~35 cold instructions)
         if (SINGLE || h.items == nwg) my_n = 1;
         else my_n = __builtin_amdgcn_readfirstlane(l < cnt ? (cnt - l + nwx - 1) / nwx : 0);
+        // live rows: the grid keeps the recorded count, the items are the live tiles only -- XCD x's are its lowest workgroup ids (dispatched
+        // first, one per CU); a workgroup behind them has no tile and leaves here, before any barrier and any access to memory
+        if constexpr (LIVE) {
+            if (l >= cnt) return;
+        }
     }
     if (!SINGLE && my_n == 0) return;  // whole workgroup: no barrier has been issued yet
     const int nch = h.ntaps * h.cpt;  // K steps per tile (the launcher passes cpt in steps of KG chunks)
@@ -962,10 +1032,23 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
         WideRegs<BF> TW;
         const int wm2 = wave & 1, g2 = wave >> 1;
         if constexpr (TAIL && WIDE) wide_load_weights<BF>(a, wave, lane, TW), wide_load_resid<BF>(a, decode(0).m0, wave, lane, TW);  // tail waves 0..3
+        // live rows: this wave's table of row offsets, in the last stage of the ring -- nothing lands there before the first chunk barrier,
+        // and the table has been read by then (the shortcut loads below are issued in front of it); written again behind the K loop
+        lds_u32* const ltab = (lds_u32*)smem + (NS - 1) * STAGE + (4 + wave) * 64;
+        const bool live = LIVE && a.os != 1;
         if constexpr (TAIL && !WIDE) {
             const int mb2 = decode(0).m0 + wm2 * 32 + 4 * (lane >> 5);
-            tail_load_resid<BF>(a, mb2, 2 + g2, lane, T.rw[0]);
-            tail_load_resid<BF>(a, mb2, 4 + g2, lane, T.rw[1]);
+            if (live) {
+                if constexpr (LIVE) {
+                    live_fill(a, h.M, h.Wo, h.Ho, h.mg_wo, h.mg_ho, decode(0).m0, lane, ltab);
+                    const srd_t srdR = make_srd(a.resid);
+                    live_load_resid(srdR, ltab, wm2 * 32 + 4 * (lane >> 5), 2 + g2, lane, T.rw[0]);
+                    live_load_resid(srdR, ltab, wm2 * 32 + 4 * (lane >> 5), 4 + g2, lane, T.rw[1]);
+                }
+            } else {
+                tail_load_resid<BF>(a, mb2, 2 + g2, lane, T.rw[0]);
+                tail_load_resid<BF>(a, mb2, 4 + g2, lane, T.rw[1]);
+            }
             tail_load_b<BF>(a, 2 + g2, lane, T.Bf);
         }
         const bool pst = P2 && threadIdx.x == 256 && blockIdx.x == 0;
@@ -1048,7 +1131,16 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                     }
                 }
             } else {
-                tail_gemm<BF, 3, true, CHAIN>(a, smem, decode(0).m0, wm2, 2 + g2, 2, lane, T);
+                // (live rows or not: asked of the argument block again -- held across the K loop the flag cost the scalar registers whose spill
+                // slot took a vector register from the shortcut values in flight)
+                bool live2 = false;
+                if constexpr (LIVE) {
+                    int os2;
+                    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(os2) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(offsetof(ConvArgs, os)) : "memory");
+                    live2 = os2 != 1;
+                }
+                if (live2) live_fill(a, h.M, h.Wo, h.Ho, h.mg_wo, h.mg_ho, decode(0).m0, lane, ltab);  // (the K loop's chunks went over it)
+                tail_gemm<BF, 3, true, CHAIN>(a, smem, decode(0).m0, wm2, 2 + g2, 2, lane, T, live2 ? ltab : nullptr);
                 if constexpr (CHAIN) chain_narrow<BF>(a, smem, decode(0).m0, wave, lane);
                 else if constexpr (BF) {
                     if (tail_staged<BF>(a)) {  // (uniform) the block output leaves from the LDS tile: all eight waves, behind one barrier
@@ -1508,7 +1600,10 @@ __global__ __launch_bounds__(512, (KG == 1 && BN <= 64) ? 4 : 2) void conv_strea
                 }
             } else {
                 TailRegs<BF> T;
-                tail_gemm<BF, 1, false, CHAIN>(a, smem, it.m0, wm2, g2, 0, lane, T);
+                lds_u32* const ltab = (lds_u32*)smem + (NS - 1) * STAGE + wave * 64;  // (the ring is free: see above)
+                const bool live = LIVE && c.os != 1;
+                if (live) live_fill(a, h.M, h.Wo, h.Ho, h.mg_wo, h.mg_ho, it.m0, lane, ltab);
+                tail_gemm<BF, 1, false, CHAIN>(a, smem, it.m0, wm2, g2, 0, lane, T, live ? ltab : nullptr);
                 if constexpr (CHAIN) {  // the chain GEMM belongs to the producer waves; this wave delivers its block and its share of the write-out
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
@@ -1815,6 +1910,20 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
 {
     if (a.cpt % KG != 0 || a.Npad % BN != 0) return hipErrorInvalidValue;
     a.cpt /= KG;  // the kernel counts K in steps of KG chunks
+    // Live rows (ConvArgs::live_s; the kernel's side is at live_fill): the launch keeps the grid of its full row count, the kernel gets the live
+    // grid -- rows (image, oy', ox'), input and output pixel (s oy', s ox') -- as an ordinary geometry: stride = os = s, OH x OW the full grid.
+    // Only the form that has the code takes it (the fp32 64-wide tail with shortcut, instruction path); anything else is refused, not dropped.
+    int live_grid = 0;
+    if (a.live_s != 0) {
+        const bool form = BM == 64 && BN == 64 && KG == 1 && a.tail_n == 256 && !a.bf16 && !a.x3 && a.chain_n == 0 && !a.bone;
+        if (!form || a.live_s < 2 || !a.resid || a.ldr != a.ldc || a.Nvalid != a.tail_n || a.stride != 1 || a.os != 1 || a.nphase != 1 || a.ksplit != 1 ||
+            a.tapgrid != 3 || a.OH != a.Ho || a.OW != a.Wo || a.H != a.Ho || a.W != a.Wo)
+            return hipErrorInvalidValue;
+        live_grid = ((a.M + BM - 1) / BM) * (a.Npad / BN);
+        a.stride = a.os = a.live_s;
+        a.Ho = (a.Ho + a.live_s - 1) / a.live_s, a.Wo = (a.Wo + a.live_s - 1) / a.live_s;
+        a.M = a.S * a.Ho * a.Wo;
+    }
     a.tiles_m = (a.M + BM - 1) / BM, a.tiles_n = a.Npad / BN;
     auto magic = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
     a.mg_wo = magic(a.Wo), a.mg_ho = magic(a.Ho), a.mg_tn = magic(a.tiles_n), a.mg_tm = magic(a.tiles_m);
@@ -1839,7 +1948,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     // batched plan of two video streams (vnect_set_stream_batch) keeps them at twice the items, and the later workgroups start as the
     // earlier ones retire (profiles/stream_batch_rate.txt has the per-layer times).
     const bool fused = a.tail_n > 0 || a.bone;
-    dim3 grid((one || fused) ? a.items : (a.items < maxwg ? a.items : maxwg));
+    dim3 grid(live_grid ? live_grid : (one || fused) ? a.items : (a.items < maxwg ? a.items : maxwg));
     // profiling twin: start / end stamps only, or (VNECT_PROF_DETAIL=1, tools/phase_table.py) the per-phase stamps too
     static const bool detail = getenv("VNECT_PROF_DETAIL") && atoi(getenv("VNECT_PROF_DETAIL")) != 0;
     const int prof = a.prof ? (detail ? 2 : 1) : 0;
@@ -1856,7 +1965,7 @@ static hipError_t launch_stream(ConvArgs a, hipStream_t st)
     }
     if (a.tail_n > 0) {
         // tail GEMM: ONE tile per workgroup that holds all of the layer's channels, one phase, no K slabs, never with the bone features
-        if (a.bone || a.ksplit != 1 || a.nphase != 1 || a.os != 1 || !a.tail_w || !a.tail_bias) return hipErrorInvalidValue;
+        if (a.bone || a.ksplit != 1 || a.nphase != 1 || (a.os != 1 && !live_grid) || !a.tail_w || !a.tail_bias) return hipErrorInvalidValue;
         if constexpr (BN == 128) {  // the wide tail (tail_wide): one 32x128 tile per workgroup, K = 128, at most 16 column blocks
             if (a.Npad != 128 || a.tail_n > 512 ||
                 (a.chain_n != 0 && (a.chain_n != 128 || a.tail_n != 512 || !a.chain_w || !a.chain_bias || !a.chain_out || a.chain_ld < 128)))

@@ -531,5 +531,59 @@ inline bool stem_frame_fits(const ScaleTabs& st, int S, int scale_base, int grou
     return true;
 }
 
+// ---- live rows of a tail launch (conv.hip: live_fill) ---------------------------------------------
+// A tail launch whose output tensor is read ONLY by 1x1 convs of one stride s > 1 without padding (res2c -> res3a_branch1 / _branch2a,
+// res3d -> res4a's: vnect_model.py:60-67,102-109) needs that tensor at the pixels (s oy', s ox') only -- and, its second GEMM being 1x1,
+// its 3x3 layer and its shortcut at those pixels only.  The rule over the launch table: the stride, or 0.
+struct LiveNode {
+    int in, resid, out, out2, out3;  // tensor indices, -1: none
+    int ntaps, stride;               // filter taps (0: not a conv) and stride of the launch
+    int tap00;                       // its single tap is (0, 0): a 1x1 conv without padding
+    int tail;                        // a tail launch (ConvArgs::tail_n > 0)
+};
+inline int live_rows_stride(const LiveNode* L, int n, int li, int t_final)
+{
+    if (li < 0 || li >= n || !L[li].tail || L[li].out < 0 || L[li].out3 >= 0) return 0;  // (a chain GEMM reads every row of the output tile)
+    const int t = L[li].out;
+    if (t == t_final) return 0;  // the post-processing reads the final maps whole
+    int s = 0;
+    for (int j = 0; j < n; j++) {
+        if (j == li) continue;
+        if (L[j].resid == t) return 0;  // a shortcut of another launch: read at every pixel
+        if (L[j].out == t || L[j].out2 == t || L[j].out3 == t) return 0;  // (another launch writes columns of it)
+        if (L[j].in != t) continue;
+        if (L[j].ntaps != 1 || !L[j].tap00 || L[j].stride < 2 || (s && L[j].stride != s)) return 0;
+        s = L[j].stride;
+    }
+    return s;
+}
+inline int live_dim(int n, int s) { return (n + s - 1) / s; }  // pixels s i < n: what a 1x1 stride-s conv without padding reads of n
+inline int live_rows(int S, int Ho, int Wo, int s) { return S * live_dim(Ho, s) * live_dim(Wo, s); }
+// The launch's rows, live rows first: row j < live_rows is pixel (image, s oy', s ox'), j = (image * Ho' + oy') * Wo' + ox'; the other
+// pixels follow in raster order (they are never computed: the enumeration says which rows the recorded M - live_rows are).
+// pix[j] = pixel index (image * Ho + oy) * Wo + ox.
+inline void live_enumeration(int S, int Ho, int Wo, int s, std::vector<int>& pix)
+{
+    const int Hl = live_dim(Ho, s), Wl = live_dim(Wo, s);
+    pix.clear();
+    pix.reserve((size_t)S * Ho * Wo);
+    for (int j = 0; j < S * Hl * Wl; j++) {
+        const int ox = j % Wl, t = j / Wl, oy = t % Hl, im = t / Hl;
+        pix.push_back((im * Ho + oy * s) * Wo + ox * s);
+    }
+    for (int p = 0; p < S * Ho * Wo; p++)
+        if ((p % Wo) % s != 0 || ((p / Wo) % Ho) % s != 0) pix.push_back(p);
+}
+// The tile of 64 rows workgroup `id` of `grid` takes, or -1: conv.hip deals a launch's items to the XCDs in contiguous eighths (workgroup
+// id runs on XCD id & 7 and takes item lo(xcd) + (id >> 3)), and a live-rows launch's items are its `tiles` live tiles -- so they are
+// the lowest workgroup ids of every XCD, dispatched first and one per CU; every other workgroup of the recorded grid leaves at once.
+inline int live_wg_tile(int tiles, int grid, int id)
+{
+    if (id < 0 || id >= grid) return -1;
+    const int xcd = id & 7, l = id >> 3, qd = tiles >> 3, rm = tiles & 7;
+    const int lo = xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd, cnt = qd + (xcd < rm ? 1 : 0);
+    return l < cnt ? lo + l : -1;
+}
+
 }  // namespace plan
 }  // namespace vnect

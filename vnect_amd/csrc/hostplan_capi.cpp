@@ -310,4 +310,25 @@ void hp_box_update(const double* j2, int n, int W, int H, int fallback, int32_t*
     }
 }
 
+// ---- live rows (hostplan.h: live_rows_stride and the enumeration conv.hip's live-rows launches follow) ----
+// nodes: n x 9 ints (in, resid, out, out2, out3, ntaps, stride, tap00, tail), as rt_plan.cpp fills LiveNode from its launches
+int hp_live_rows_stride(const int32_t* nodes, int n, int li, int t_final)
+{
+    std::vector<plan::LiveNode> L(n > 0 ? n : 0);
+    for (int i = 0; i < n; i++) {
+        const int32_t* q = nodes + (size_t)i * 9;
+        L[i] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
+    }
+    return plan::live_rows_stride(L.data(), n, li, t_final);
+}
+int hp_live_rows(int S, int Ho, int Wo, int s) { return plan::live_rows(S, Ho, Wo, s); }
+// pix: S * Ho * Wo ints
+void hp_live_enumeration(int S, int Ho, int Wo, int s, int32_t* pix)
+{
+    std::vector<int> v;
+    plan::live_enumeration(S, Ho, Wo, s, v);
+    for (size_t i = 0; i < v.size(); i++) pix[i] = v[i];
+}
+int hp_live_wg_tile(int tiles, int grid, int id) { return plan::live_wg_tile(tiles, grid, id); }
+
 }  // extern "C"

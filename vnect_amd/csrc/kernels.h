@@ -92,6 +92,10 @@ struct ConvArgs {
     float* chain_out;
     int chain_n;  // 0: none; else 128
     int chain_ld;
+    // Live rows (rt_plan.cpp: the plan rule is plan::live_rows_stride): every reader of this tail launch's output is a 1x1 conv of stride
+    // live_s > 1, so only the pixels (s oy', s ox') are computed, read as shortcut and stored; M, Ho, Wo above stay the full grid's (the
+    // recorded plan and the launch's grid), the launcher derives the live grid.  0: off.
+    int live_s;
 };
 
 struct ReduceArgs {  // split-K second pass: out = epilogue(sum_ks ws[ks])

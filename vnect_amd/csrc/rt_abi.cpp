@@ -607,6 +607,27 @@ int vnect_get_batch_layer_info(vnect_handle* h, int idx, vnect_layer_info* out)
     });
 }
 
+// rows a launch computes: M (x phases) for every launch but a live-rows one
+static int rows_computed(const std::vector<Layer>& layers, int idx, int32_t* rows)
+{
+    if (!rows || idx < 0 || idx >= (int)layers.size()) return VNECT_E_ARG;
+    const Layer& L = layers[idx];
+    *rows = L.op != OP_CONV ? 0 : L.a.live_s ? plan::live_rows(L.a.S, L.a.Ho, L.a.Wo, L.a.live_s) : L.a.M * L.a.nphase;
+    return VNECT_OK;
+}
+
+int vnect_get_layer_rows(vnect_handle* h, int idx, int batch, int32_t* rows_computed_out, int32_t* live_rule_stride)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (batch && h->bplans.empty()) return fail(h, VNECT_E_STATE, "vnect_get_layer_rows: no batched plan (vnect_set_stream_batch(h, 2), then vnect_finalize)");
+        const std::vector<Layer>& layers = batch ? h->bplans[0]->layers : h->layers;
+        const int rc = rows_computed(layers, idx, rows_computed_out);
+        if (rc == VNECT_OK && live_rule_stride) *live_rule_stride = live_rows_of(layers, idx, h->t_out);
+        return rc;
+    });
+}
+
 int vnect_set_stream_batch(vnect_handle* h, int n)
 {
     return guarded(&h, [&]() -> int {

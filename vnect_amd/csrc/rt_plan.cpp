@@ -369,6 +369,40 @@ static int add_conv_tail(vnect_handle* h, const std::string& sb, const std::stri
     return L.out;
 }
 
+// Live rows (hostplan.h: live_rows_stride; conv.hip: live_fill): a tail launch whose output only stride-s 1x1 convs read computes the
+// pixels they read -- res2c_branch2b>res2c_branch2c in both res2c wirings (res3a's pair reads res2c at even pixels: three quarters of
+// the 92x92 block output, of the 3x3 layer under it and of the shortcut read were never used) and res3d_branch2b>res3d_branch2c by the
+// rule.  The launch takes the mode where its kernel has it: the fp32 64-wide tail on the instruction path, i.e. res2c's; the wide tail
+// (res3d) and the 16-bit formats' chained and staged forms keep all rows.  Arena plans only: a tensor that can be read back is
+// whole, so a keep_activations handle -- the VNECT_KEEP_FUSED seam too -- never takes it on its own; VNECT_FORCE_LIVE_ROWS=1 turns it on for
+// the seam (the tests that read res2c from both forms), VNECT_NO_LIVE_ROWS=1 off everywhere (A/B runs).  M, the tile and the workgroup
+// count of the launch stay the full grid's; flops count the computed rows.
+int live_rows_of(const std::vector<Layer>& layers, int li, int t_out)
+{
+    std::vector<plan::LiveNode> n(layers.size());
+    for (size_t i = 0; i < layers.size(); i++) {
+        const Layer& L = layers[i];
+        const bool cv = L.op == OP_CONV;
+        n[i] = {L.in, L.resid, L.out, L.out2, L.out3, cv ? L.a.ntaps * L.a.nphase : 0, cv ? L.a.stride : 1,
+                cv && L.dy[0] == 0 && L.dx[0] == 0 && !L.a.pixmode, cv && L.a.tail_n > 0};
+    }
+    return plan::live_rows_stride(n.data(), (int)n.size(), li, t_out);
+}
+static void mark_live_rows(vnect_handle* h)
+{
+    if (getenv("VNECT_NO_LIVE_ROWS")) return;
+    if (h->keep_activations && !(h->keep_fused && getenv("VNECT_FORCE_LIVE_ROWS"))) return;
+    for (size_t li = 0; li < h->layers.size(); li++) {
+        Layer& L = h->layers[li];
+        ConvArgs& a = L.a;
+        if (L.op != OP_CONV || a.tail_n != 256 || L.BM != 64 || L.BN != 64 || a.bf16 || a.x3 || a.chain_n || L.resid < 0) continue;
+        const int s = live_rows_of(h->layers, (int)li, h->t_out);
+        if (s < 2) continue;
+        a.live_s = s;
+        L.flops *= (double)plan::live_rows(a.S, a.Ho, a.Wo, s) / a.M;
+    }
+}
+
 // Does a launch of the plan write tensor t?  The stem keeps conv1 in LDS, and pool1 too in its PAIR form (which writes the pair's outputs);
 // the inner layer of a tail launch is no tensor at all.  (The batch tensor counts: the pre-processing or vnect_forward writes it.)
 bool plan_writes(const Plan* p, int t)
@@ -707,6 +741,7 @@ int finalize_impl(vnect_handle* h)
         NEED(h->t_out);
     }
 #undef NEED
+    mark_live_rows(h);
     // buffers
     if (!h->keep_activations) {
         int rc = alloc_arena(h);

@@ -320,6 +320,7 @@ int build_plans(vnect_handle* h);   // lanes 1 .. cfg.lanes - 1 and the batched 
 void destroy_plan(Plan* p);         // every plan's teardown, lane 0's (the handle's) included
 void destroy_plans(vnect_handle* h);  // all but lane 0
 bool plan_writes(const Plan* p, int tensor);  // does a launch of the plan (or the pre-processing) write this tensor?
+int live_rows_of(const std::vector<Layer>& layers, int li, int t_out);  // the live-rows rule for launch li: the readers' stride, or 0
 
 // ---- rt_exec.cpp ---------------------------------------------------------------------------------------------------------------
 int run_network(Plan* p, bool timed, bool stem_done = false);
