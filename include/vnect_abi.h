@@ -249,6 +249,59 @@ int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_ind
                                      double t2d, double t3d);
 int vnect_read_frame(vnect_handle* h, int slot, uint8_t* out, int64_t capacity, int32_t* hw2);
 
+/* ABI v7, additive.  Frames that already lie in DEVICE memory: a decoder's surface in VRAM, a torch tensor, another model's output.  The
+ * reference reads its frame on the host (src/estimator.py:97-99 takes img_input from there) and its loop crops it with a numpy slice
+ * (run_estimator_ps.py:88); these entry points take the same pixels from the caller's device allocation, and a kernel writes them -- or
+ * the crop `rect` -- into a resident slot as the packed BGR rows every other entry point leaves there (vnect_amd/csrc/ingest.h;
+ * DEVICE_FRAMES.md).  Everything behind the slot sees the frame it always saw, so every result is bit-identical to the host entry point
+ * given the same BGR pixels.
+ * format VNECT_PIX_BGR / VNECT_PIX_RGB: `data` is pixel (0, 0) channel 0 and channel c of pixel (y, x) lies at
+ * data + y stride_y + x stride_x + c stride_c, all three strides positive: packed 3-byte pixels (., 3, 1), 4-byte pixels (., 4, 1: BGRA,
+ * RGBA, BGRX -- the fourth byte is never read), planar CHW (., 1, plane stride) are read with coalesced dword loads, any other strides one
+ * pixel per lane.  VNECT_PIX_NV12: `data` is the Y plane (rows stride_y apart), `uv` the interleaved U, V plane (rows uv_stride apart), in
+ * one allocation or two; converted as vnect_infer_nv12 converts.  rect = (x, y, w, h) with has_rect: the crop, as numpy slicing crops it
+ * (a rect past the far edges is cut there); joints in crop coordinates.
+ * producer_stream: the hipStream_t on which the frame's last writes were enqueued; NULL is HIP's default stream; VNECT_STREAM_SYNCED: the
+ * caller has synchronised, wait for nothing.  Otherwise the library records an event on that stream and the stream it ingests on waits
+ * for it: the host never blocks on the producer.
+ * VNECT_E_ARG, before any launch and before anything changes (no timestamp, no slot geometry, no filter): struct_size wrong; `data` (or
+ * `uv`) not device memory of the handle's device as THIS process's HIP runtime knows it -- host memory, managed memory, another device's
+ * memory: use vnect_infer / vnect_upload_frame for host memory; a frame whose last byte lies outside the allocation `data` points into
+ * (hipMemGetAddressRange); a stride below 1; NV12 with odd W or H, a pitch below W or overlapping planes; a rect whose origin lies
+ * outside the frame or that is empty; more BGR bytes (3 per pixel of the frame, or of the crop) than max_frame_bytes.
+ * ONE HIP RUNTIME PER PROCESS: a pointer means something only to the runtime that allocated it.  A process that loads this library first
+ * and imports torch afterwards can end up with two copies of libamdhip64 (torch ships its own), and torch's pointers are then refused here
+ * with VNECT_E_ARG; import torch first, and there is one.
+ * vnect_upload_frame_device: afterwards the slot is indistinguishable from one vnect_upload_frame filled with the same BGR pixels.  It
+ * returns when the slot is filled (the caller's buffer is free again) and waits only for the slot's last reader.
+ * vnect_infer_device: vnect_infer (src/estimator.py:97-142) of those pixels.  vnect_preprocess_device: vnect_preprocess
+ * (src/estimator.py:70-81); also on a preprocess_only handle.  Both are done with the caller's buffer when they return.
+ * vnect_submit_tracked_device: vnect_submit_tracked_pinned with the whole frame in device memory (a rect is refused: the crop is the
+ * stream's box on the device, run_estimator_ps.py:88 and :99-107).  The buffer is read when the frame RUNS: keep it untouched until that
+ * frame has been collected.  Same refusals (a frame of another size than vnect_track_begin's, a sharded or batched handle), status and
+ * rollback as the pinned form. */
+#define VNECT_PIX_BGR 0
+#define VNECT_PIX_RGB 1
+#define VNECT_PIX_NV12 2
+#define VNECT_STREAM_SYNCED ((void*)-1)
+typedef struct vnect_device_frame {
+    int32_t struct_size;
+    int32_t format;      /* VNECT_PIX_BGR | VNECT_PIX_RGB | VNECT_PIX_NV12 */
+    int32_t H, W;        /* of the whole frame */
+    const void* data;    /* pixel (0,0) channel 0; NV12: the Y plane */
+    int64_t stride_y, stride_x, stride_c; /* bytes; NV12: stride_y = Y pitch, the other two ignored */
+    const void* uv;      /* NV12 only */
+    int64_t uv_stride;
+    int32_t has_rect;
+    int32_t rect[4];     /* (x, y, w, h) */
+} vnect_device_frame;
+int vnect_upload_frame_device(vnect_handle* h, int slot, const vnect_device_frame* frame, void* producer_stream);
+int vnect_infer_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d, double* joints_2d,
+                       float* joints_3d);
+int vnect_preprocess_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, float* batch_out, double* scaler,
+                            int32_t* offset_x, int32_t* offset_y);
+int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d);
+
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
  * per call, :84).  Values travel as float64; values_are_f32 = 1 says they are numpy float32 scalars -- what the reference

@@ -48,6 +48,21 @@ class LayerInfo(C.Structure):
                 ("flops", C.c_double), ("last_ms", C.c_double)]
 
 
+PIX_BGR, PIX_RGB, PIX_NV12 = 0, 1, 2          # vnect_device_frame::format
+STREAM_SYNCED = C.c_void_p(-1).value          # VNECT_STREAM_SYNCED: the caller has synchronised, wait for nothing
+
+
+class DeviceFrame(C.Structure):
+    """vnect_device_frame: a uint8 frame in device memory (include/vnect_abi.h; DEVICE_FRAMES.md)."""
+    _fields_ = [("struct_size", C.c_int32), ("format", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("data", C.c_void_p),
+                ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64), ("uv", C.c_void_p),
+                ("uv_stride", C.c_int64), ("has_rect", C.c_int32), ("rect", C.c_int32 * 4)]
+
+
+class DeviceFrameError(VnectError, ValueError):
+    """VNECT_E_ARG of a device-frame entry point: the frame as given cannot be read (a ValueError, like every refused argument)."""
+
+
 # every symbol include/vnect_abi.h declares: name -> (restype, argtypes)
 _f32p, _f64p, _u8p, _i32p = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_uint8, C.c_int32))
 _H = C.c_void_p
@@ -100,6 +115,10 @@ SYMBOLS = {
     "vnect_preprocess_nv12": (C.c_int, [_H, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p, _f32p, _f64p, _i32p, _i32p]),
     "vnect_submit_tracked_pinned_nv12": (C.c_int, [_H, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double]),
     "vnect_read_frame": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _i32p]),
+    "vnect_upload_frame_device": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p]),
+    "vnect_infer_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double, _f64p, _f32p]),
+    "vnect_preprocess_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, _f32p, _f64p, _i32p, _i32p]),
+    "vnect_submit_tracked_device": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double]),
 }
 
 
@@ -111,6 +130,8 @@ TRACKPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_trackprobe.so")     # trac
 
 NV12PROBE_LIB = os.path.join(_HERE, "lib", "libvnect_nv12probe.so")       # post.o + track.o behind csrc/nv12_probe.cpp (tests only)
 NV12_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_nv12.so")             # g++'s build of csrc/nv12.h (tests only; no GPU code)
+INGESTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_ingestprobe.so")   # post.o + track.o behind csrc/ingest_probe.hip (tests only)
+INGEST_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_ingest.so")         # g++'s build of csrc/ingest.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -125,6 +146,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "trackprobe"], stdout=subprocess.DEVNULL)
     # the NV12 copies' probe (tests/test_gpu_nv12_kernels.py) and g++'s build of the conversion itself (tests/test_nv12_cpu.py)
     subprocess.check_call(["make", "-C", src, "nv12probe", "nv12"], stdout=subprocess.DEVNULL)
+    # the device-frame copies' probe (tests/test_gpu_device_ingest_kernels.py) and g++'s build of their lane windows (tests/test_device_frames_cpu.py)
+    subprocess.check_call(["make", "-C", src, "ingestprobe", "ingest"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -272,7 +295,11 @@ class Handle:
         self._ck(lib().vnect_frame_buffer(self._h, index, H * W * 3, C.byref(p)))
         return np.ctypeslib.as_array(p, shape=(H, W, 3))
 
-    def upload_frame(self, slot, img):
+    def upload_frame(self, slot, img, pixel_format="bgr", rect=None, stream=None):
+        if is_device_array(img):  # a frame in device memory (DEVICE_FRAMES.md): the other three arguments are for it alone
+            return self.upload_frame_device(slot, device_frame(img, pixel_format, rect), stream)
+        if pixel_format != "bgr" or rect is not None or stream is not None:
+            raise ValueError("pixel_format=, rect= and stream= are for frames in device memory")
         img = _as_frame(img)
         H, W = img.shape[:2]
         self._ck(lib().vnect_upload_frame(self._h, slot, _ptr(img, _u8p), H, W, img.strides[0]))
@@ -402,6 +429,33 @@ class Handle:
     def submit_tracked_pinned_nv12(self, stream, index, y_stride, uv_offset, uv_stride, t2d, t3d):
         """The stream's next frame, the whole NV12 frame in pinned buffer `index` (Y plane at its start, UV plane `uv_offset` bytes in)."""
         self._ck(lib().vnect_submit_tracked_pinned_nv12(self._h, stream, index, int(y_stride), int(uv_offset), int(uv_stride), t2d, t3d))
+
+    # -- frames in device memory: written into the slot by a kernel (include/vnect_abi.h; DEVICE_FRAMES.md) --------------------------
+    def _ck_device(self, rc):
+        if rc == E_ARG:
+            raise DeviceFrameError(rc, lib().vnect_last_error(self._h).decode() + _runtime_hint())
+        self._ck(rc)
+
+    def upload_frame_device(self, slot, frame, stream=None):
+        """`frame`: a DeviceFrame (device_frame()).  Done with the caller's buffer on return."""
+        self._ck_device(lib().vnect_upload_frame_device(self._h, slot, C.byref(frame), _stream_arg(stream)))
+
+    def infer_device(self, frame, t2d, t3d, stream=None):
+        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        self._ck_device(lib().vnect_infer_device(self._h, C.byref(frame), _stream_arg(stream), t2d, t3d, _ptr(j2, _f64p), _ptr(j3, _f32p)))
+        return j2, j3
+
+    def preprocess_device(self, frame, stream=None, want_batch=True):
+        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
+        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
+        self._ck_device(lib().vnect_preprocess_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(batch, _f32p) if want_batch else None,
+                                                      C.byref(scaler), C.byref(ox), C.byref(oy)))
+        return batch, scaler.value, [ox.value, oy.value]
+
+    def submit_tracked_device(self, stream, frame, t2d, t3d, producer=None):
+        """The stream's next frame, the whole frame in device memory (`frame`: a DeviceFrame without a rect).  The buffer is read when the
+        frame runs: keep it alive and untouched until the frame has been collected."""
+        self._ck_device(lib().vnect_submit_tracked_device(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d))
 
     def read_frame(self, slot):
         """The (H, W, 3) BGR frame resident slot `slot` holds (a debugging read)."""
@@ -547,3 +601,135 @@ def _as_nv12(nv12):
     uv = C.cast(C.c_void_p(base + H * a.strides[0]), _u8p)
     y._keep = uv._keep = a_keep
     return y, a.strides[0], uv, a.strides[0], H, W
+
+
+# ---- frames in device memory ----------------------------------------------------------------------------------------------------------
+def is_device_array(x):
+    """True for an object that exposes device memory through __cuda_array_interface__ (a torch / cupy array on the GPU) -- or a
+    (y, uv) pair of such objects (NV12 in separate planes)."""
+    if isinstance(x, (tuple, list)):
+        return len(x) == 2 and all(hasattr(p, "__cuda_array_interface__") for p in x)
+    return hasattr(x, "__cuda_array_interface__")
+
+
+def _cai(x, ndim, what):
+    """(pointer, shape, strides in bytes) of a uint8 device array of `ndim` dimensions."""
+    try:
+        d = x.__cuda_array_interface__
+    except AttributeError:
+        raise ValueError("%s must expose device memory through __cuda_array_interface__" % what) from None
+    if d.get("typestr") != "|u1":
+        raise ValueError("%s must be uint8 (typestr '|u1'), not %r" % (what, d.get("typestr")))
+    shape = tuple(int(v) for v in d["shape"])
+    if len(shape) != ndim or any(v < 1 for v in shape):
+        raise ValueError("%s must have %d non-empty dimensions, not shape %r" % (what, ndim, shape))
+    strides = d.get("strides")
+    if strides is None:  # C-contiguous
+        strides, n = [], 1
+        for v in reversed(shape):
+            strides.insert(0, n)
+            n *= v
+    strides = tuple(int(v) for v in strides)
+    if any(v < 1 for v in strides):
+        raise ValueError("%s has a zero or negative stride %r: flip or broadcast it on the device first (.contiguous())" % (what, strides))
+    ptr = d["data"][0]
+    if not ptr:
+        raise ValueError("%s has a null data pointer" % what)
+    return int(ptr), shape, strides
+
+
+FORM_NAMES = ("packed-3", "packed-4", "planar", "generic")
+
+
+def device_form(stride_x, stride_c):
+    """The kernel form the strides select (ingest.h: ingest_form) -- 0 packed-3, 1 packed-4, 2 planar, 3 generic."""
+    if stride_x == 3 and stride_c == 1:
+        return 0
+    if stride_x == 4 and stride_c == 1:
+        return 1
+    if stride_x == 1 and stride_c >= 1:
+        return 2
+    return 3
+
+
+def device_frame(x, pixel_format="bgr", rect=None):
+    """The vnect_device_frame of `x`: for "bgr" / "rgb" an (H, W, 3) uint8 device array with any positive strides (a packed tensor,
+    chw.permute(1, 2, 0), bgra[..., :3], any slice); for "nv12" an (H * 3 // 2, W) device array (Y rows, then the U, V rows) or a
+    (y, uv) pair of (H, W) and (H // 2, W) arrays.  The structure keeps `x` alive."""
+    if pixel_format not in ("bgr", "rgb", "nv12"):
+        raise ValueError("pixel_format must be 'bgr', 'rgb' or 'nv12'")
+    f = DeviceFrame()
+    f.struct_size = C.sizeof(DeviceFrame)
+    if pixel_format == "nv12":
+        f.format = PIX_NV12
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2:
+                raise ValueError("separate NV12 planes are a (y, uv) pair")
+            yp, ysh, yst = _cai(x[0], 2, "the Y plane")
+            up, ush, ust = _cai(x[1], 2, "the UV plane")
+            if ysh[0] % 2 or ysh[1] % 2 or ush != (ysh[0] // 2, ysh[1]):
+                raise ValueError("NV12 planes must be (H, W) and (H // 2, W) with even H and W, not %r and %r" % (ysh, ush))
+            if yst[1] != 1 or ust[1] != 1:
+                raise ValueError("NV12 planes must have unit column stride")
+            f.H, f.W, f.data, f.stride_y, f.uv, f.uv_stride = ysh[0], ysh[1], yp, yst[0], up, ust[0]
+        else:
+            p, sh, st = _cai(x, 2, "an NV12 frame")
+            if sh[0] < 3 or sh[0] % 3 or sh[1] < 2 or sh[1] % 2 or st[1] != 1:
+                raise ValueError("an NV12 frame must be a uint8 (H * 3 // 2, W) array with even H and W and unit column stride")
+            H = sh[0] * 2 // 3
+            f.H, f.W, f.data, f.stride_y, f.uv, f.uv_stride = H, sh[1], p, st[0], p + H * st[0], st[0]
+    else:
+        f.format = PIX_RGB if pixel_format == "rgb" else PIX_BGR
+        p, sh, st = _cai(x, 3, "a device frame")
+        if sh[2] != 3:
+            raise ValueError("a device frame must be a uint8 (H, W, 3) array, not shape %r" % (sh,))
+        f.H, f.W, f.data, f.stride_y, f.stride_x, f.stride_c = sh[0], sh[1], p, st[0], st[1], st[2]
+    if rect is not None:
+        f.has_rect = 1
+        for k, v in enumerate(rect):
+            f.rect[k] = int(v)
+    f._keep = x
+    return f
+
+
+def default_stream():
+    """The producer stream when the caller names none: torch's current stream if torch is already imported (never imported here), else
+    HIP's default stream (0)."""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is not None:
+        try:
+            return int(torch.cuda.current_stream().cuda_stream)
+        except Exception:
+            return 0
+    return 0
+
+
+def _stream_arg(stream):
+    if stream is None:
+        stream = default_stream()
+    return C.c_void_p(int(stream))
+
+
+def hip_runtimes_mapped():
+    """The distinct libamdhip64 files this process has mapped (more than one: two HIP runtimes, whose pointers mean nothing to each other)."""
+    out = set()
+    try:
+        with open("/proc/self/maps") as fh:
+            for ln in fh:
+                path = ln.split(None, 5)[-1].strip() if ln.count(" ") >= 5 else ""
+                if "libamdhip64" in os.path.basename(path):
+                    out.add(os.path.realpath(path))
+    except OSError:
+        pass
+    return sorted(out)
+
+
+IMPORT_ORDER_HINT = "import torch before vnect_amd, so that the process holds one HIP runtime"
+
+
+def _runtime_hint():
+    libs = hip_runtimes_mapped()
+    if len(libs) > 1:
+        return " -- this process has %d HIP runtimes mapped (%s): %s" % (len(libs), ", ".join(libs), IMPORT_ORDER_HINT)
+    return ""

@@ -174,9 +174,27 @@ struct Nv12Src {
     long long uv_stride;
     const uint8_t* lo;      // the pinned buffer both planes lie in, [lo, end): multiples of 4; no dword is loaded outside it
     const uint8_t* end;
+    // planes in DEVICE memory (vnect_infer_device), possibly in two allocations: [lo, end) bounds the Y plane's loads, [uv_lo, uv_end) the UV
+    // plane's (nullptr: [lo, end) holds both, as above).  `any_bounds`: the bounds are a caller's allocation and need not be multiples of 4 --
+    // a dword an end cuts is then assembled from byte loads of the bytes inside
+    const uint8_t* uv_lo = nullptr;
+    const uint8_t* uv_end = nullptr;
+    int any_bounds = 0;
 };
 // the crop (x, y, w, h) of the frame -> `dst`, rows packed 3 w bytes apart (whole frame: 0, 0, W, H); chroma by absolute coordinates
 hipError_t launch_nv12_copy(const Nv12Src& s, int x, int y, int w, int h, uint8_t* dst, hipStream_t st);
+
+// The same from a uint8 frame that already lies in DEVICE memory, in a caller's allocation (post.hip: ingest_copy_kernel; ingest.h).
+struct IngestSrc {
+    const uint8_t* data;    // pixel (0, 0), channel 0 (any alignment)
+    long long stride_y, stride_x, stride_c;  // bytes, all positive: packed-3 (., 3, 1), packed-4 (., 4, 1), planar (., 1, plane), or anything else
+    const uint8_t* lo;      // the allocation the frame lies in, [lo, end) at any alignment: no byte outside it is loaded
+    const uint8_t* end;
+    int order;              // INGEST_BGR / INGEST_RGB: the source's channel order
+};
+// the crop (x, y, w, h) of the (H, W) frame -> `dst`, rows packed 3 w bytes apart, BGR.  force_generic: the one-pixel-per-lane kernel
+// whatever the strides (tests: what the coalesced forms must equal)
+hipError_t launch_ingest_copy(const IngestSrc& s, int H, int W, int x, int y, int w, int h, uint8_t* dst, hipStream_t st, int force_generic = 0);
 
 // ---- the stem as one launch (stem.hip): [gen_input_batch ->] conv1 + ReLU -> 3x3 / stride-2 max-pool on spatial tiles -------------
 struct StemArgs {
@@ -293,6 +311,8 @@ hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev,
                                    hipStream_t st);
 // the same out of a pinned NV12 frame of (H, W) pixels, converted to BGR on the way
 hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_t* dst, int H, int W, hipStream_t st);
+// the same out of an (H, W) frame in device memory (H <= 65535)
+hipError_t launch_ingest_copy_track(const TrackState* ts, const IngestSrc& s, uint8_t* dst, int H, int W, hipStream_t st, int force_generic = 0);
 // behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
 // its geometry to `ts`
 hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st);

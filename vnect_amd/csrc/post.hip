@@ -7,8 +7,11 @@
 #include "axis.h"  // axis_x_at / axis_y_at: one entry of cv2.resize's per-axis tables, computed where it is used
 #include "trackbox.h"  // the box stage of a tracked frame (post_kernel<.., true>)
 #include "nv12.h"  // NV12 -> BGR of one pixel / one group of four (nv12_copy_kernel)
+#include "ingest.h"  // a frame in device memory -> a slot: the lane windows of ingest_copy_kernel
 
 #include <stddef.h>
+
+#include <type_traits>
 
 namespace vnect {
 
@@ -192,9 +195,17 @@ hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int ro
 //     head) are written byte by byte, each wave the bytes it holds.
 // grid = (ceil(groups / 256), strips), 256 threads; workgroups past the crop leave at once.  Dwords are loaded only inside [lo, end),
 // the pinned buffer (base and capacity multiples of 4); bytes outside the crop are never stored.
-__device__ __forceinline__ unsigned nv12_load(uintptr_t a, const Nv12Src& s)
+__device__ __forceinline__ unsigned nv12_load(uintptr_t a, const Nv12Src& s, bool uv_plane = false)
 {
-    return (a >= (uintptr_t)s.lo && a + 4 <= (uintptr_t)s.end) ? *(const unsigned*)a : 0u;
+    const uintptr_t lo = (uintptr_t)(uv_plane && s.uv_lo ? s.uv_lo : s.lo), end = (uintptr_t)(uv_plane && s.uv_lo ? s.uv_end : s.end);
+    if (a >= lo && a + 4 <= end) return *(const unsigned*)a;
+    unsigned v = 0;
+    if (s.any_bounds) {  // (device planes only: a pinned buffer's bounds are multiples of 4, and a dword outside them has no byte inside)
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (a + j >= lo && a + j < end) v |= (unsigned)(*(const uint8_t*)(a + j)) << (8 * j);
+    }
+    return v;
 }
 // the four bytes at byte `sh` of the dword pair (hi, lo)
 __device__ __forceinline__ unsigned nv12_funnel(unsigned hi, unsigned lo, int sh) { return (unsigned)((((unsigned long long)hi << 32) | lo) >> (8 * sh)); }
@@ -263,8 +274,8 @@ __device__ __forceinline__ void nv12_strip(const Nv12Src& s, int x, int y, int w
     for (int i = 0; i < 3; i++) {
         if (!on[i]) continue;
         const uintptr_t al = a[i] & ~(uintptr_t)3;
-        if (act) lo[i] = nv12_load(al, s);
-        if (self_hi && (a[i] & 3)) hi[i] = nv12_load(al + 4, s);
+        if (act) lo[i] = nv12_load(al, s, i == 0);
+        if (self_hi && (a[i] & 3)) hi[i] = nv12_load(al + 4, s, i == 0);
     }
     unsigned v[3];
 #pragma unroll
@@ -296,7 +307,8 @@ __global__ __launch_bounds__(256) void nv12_copy_track_kernel(const TrackState* 
 }
 static bool nv12_src_ok(const Nv12Src& s)
 {
-    return s.y && s.uv && s.lo && s.end && s.y_stride > 0 && s.uv_stride > 0 && (((uintptr_t)s.lo | (uintptr_t)s.end) & 3) == 0;
+    if (!s.uv_lo != !s.uv_end) return false;
+    return s.y && s.uv && s.lo && s.end && s.y_stride > 0 && s.uv_stride > 0 && (s.any_bounds || (((uintptr_t)s.lo | (uintptr_t)s.end) & 3) == 0);
 }
 hipError_t launch_nv12_copy(const Nv12Src& s, int x, int y, int w, int h, uint8_t* dst, hipStream_t st)
 {
@@ -314,6 +326,172 @@ hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_
     if (!nv12_src_ok(s) || H < 2 || W < 2 || ((H | W) & 1) || H > 2 * 65535) return hipErrorInvalidValue;
     const int per = NV12_WG_PX / NV12_LANE_PX;
     hipLaunchKernelGGL(nv12_copy_track_kernel, dim3((unsigned)((((W + 3) >> 2) + per - 1) / per), (unsigned)(H >> 1)), dim3(256), 0, st, ts, s, dst);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same copies from a frame that already lies in DEVICE memory (vnect_infer_device and its kin): a caller's allocation, in the layouts a
+// device producer has -- packed BGR / RGB, 4-byte pixels, planar CHW, or any other positive strides.  ingest.h holds the arithmetic (and
+// says what a lane loads); here are the loads' shuffles and the stores.  A lane owns the four pixels of group G of a crop row, a wave 64
+// groups, a workgroup four waves; grid = (ceil(groups / 256), rows), workgroups past the crop leave at once.  The crop's origin is folded
+// into `origin` (pixel (x, y), channel 0).  Loads stay inside [s.lo, s.end), the caller's allocation; bytes outside the crop's 3 w h are
+// never stored.
+__device__ __forceinline__ void ingest_store_row(uint8_t* drow, long long row, int G, int G1, const unsigned* P)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned prev = (unsigned)__shfl_up((int)P[2], 1);  // (every lane of the wave is here: the callers branch wave-uniformly)
+    if (G > G1) return;
+    const long long t0 = 12LL * G;
+    const uintptr_t E = (uintptr_t)drow + (unsigned long long)t0;
+    const int e = (int)(E & 3);
+    unsigned* const E0 = (unsigned*)(E - (unsigned)e);
+    const unsigned m = ingest_dst_mask(t0, e, row, e == 0 || lane > 0, e != 0 && (lane == 63 || G == G1));
+    if ((m & 0xfffu) == 0xfffu) {
+        typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+        *(u32x3*)E0 = u32x3{ingest_window_dword(P, prev, e, 0), ingest_window_dword(P, prev, e, 1), ingest_window_dword(P, prev, e, 2)};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const unsigned q = ingest_window_dword(P, prev, e, k), mk = (m >> (4 * k)) & 15u;
+            if (mk == 15u) {
+                E0[k] = q;
+                continue;
+            }
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if (mk & (1u << b)) ((uint8_t*)E0)[4 * k + b] = (uint8_t)(q >> (8 * b));
+        }
+    }
+    if (m >> 12) {
+        const unsigned q = ingest_window_dword(P, prev, e, 3);
+#pragma unroll
+        for (int b = 0; b < 3; b++)
+            if (m & (1u << (12 + b))) ((uint8_t*)E0)[12 + b] = (uint8_t)(q >> (8 * b));
+    }
+}
+// row `y` of the crop whose pixel (0, 0) is `origin`, w pixels wide -> dst + y * 3 w
+template <int FORM, int ORDER>
+__device__ __forceinline__ void ingest_row(const IngestSrc& s, const uint8_t* origin, int w, int y, uint8_t* __restrict__ dst)
+{
+    constexpr int NS = FORM == INGEST_PLANAR ? 3 : 1, ND = FORM == INGEST_PACKED3 ? 3 : (FORM == INGEST_PACKED4 ? 4 : 1);
+    const int lane = threadIdx.x & 63;
+    const int G1 = (w - 1) >> 2;
+    const int Gw = (int)blockIdx.x * (INGEST_WG_PX / INGEST_LANE_PX) + (int)(threadIdx.x & ~63u);  // the wave's first group
+    if (Gw > G1) return;                            // (wave-uniform)
+    const int G = Gw + lane;
+    const bool act = G <= G1, self_hi = act && (lane == 63 || G == G1);
+    const uintptr_t row0 = (uintptr_t)origin + (unsigned long long)y * (unsigned long long)s.stride_y;
+    const uintptr_t lo = (uintptr_t)s.lo, end = (uintptr_t)s.end;
+    unsigned d[NS][ND + 1];
+    int sh[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) {                  // every load is requested before any is used
+        const uintptr_t a0 = row0 + (unsigned long long)c * (unsigned long long)s.stride_c, need_end = a0 + (unsigned long long)ingest_row_need(FORM, w);
+        const uintptr_t a = a0 + 4ull * ND * (unsigned)G, al = a & ~(uintptr_t)3;
+        sh[c] = (int)(a & 3);                       // (wave-uniform: the lanes' addresses differ by multiples of 4)
+#pragma unroll
+        for (int i = 0; i <= ND; i++) d[c][i] = 0u;
+        if (act) {
+#pragma unroll
+            for (int i = 0; i < ND; i++) d[c][i] = ingest_load(al + 4u * i, a0, need_end, lo, end);
+            if (self_hi && sh[c]) d[c][ND] = ingest_load(al + 4u * ND, a0, need_end, lo, end);
+        }
+    }
+    unsigned v[NS * ND];
+#pragma unroll
+    for (int c = 0; c < NS; c++) {
+        if (sh[c]) {
+            const unsigned next = (unsigned)__shfl_down((int)d[c][0], 1);
+            if (!self_hi) d[c][ND] = next;
+        }
+#pragma unroll
+        for (int i = 0; i < ND; i++) v[c * ND + i] = sh[c] ? ingest_funnel(d[c][i + 1], d[c][i], sh[c]) : d[c][i];
+    }
+    unsigned P[3];
+    ingest_pack(FORM, ORDER, v, P);
+    ingest_store_row(dst + (unsigned long long)y * (3ull * (unsigned)w), 3LL * w, G, G1, P);
+}
+template <int FORM, int ORDER>
+__global__ __launch_bounds__(256) void ingest_copy_kernel(const IngestSrc s, const uint8_t* origin, int w, int row_base, uint8_t* __restrict__ dst)
+{
+    ingest_row<FORM, ORDER>(s, origin, w, row_base + (int)blockIdx.y, dst);
+}
+// the tracked form (frame_copy_track_kernel's contract with a device frame on the source side): the rect is the stream's state on the
+// device, the grid covers the whole frame, `dst` gets the crop's rows packed, 3 w bytes apart (pyramid_track_kernel with packed = 1)
+template <int FORM, int ORDER>
+__global__ __launch_bounds__(256) void ingest_copy_track_kernel(const TrackState* __restrict__ ts, const IngestSrc s, uint8_t* __restrict__ dst)
+{
+    const int x0 = ts->x, y0 = ts->y, w = ts->w, h = ts->h;
+    if ((int)blockIdx.y >= h) return;
+    ingest_row<FORM, ORDER>(s, s.data + (long long)y0 * s.stride_y + (long long)x0 * s.stride_x, w, (int)blockIdx.y, dst);
+}
+// any other positive strides: one pixel per lane, three byte loads, three byte stores.  (Every byte it loads is a pixel's, and the host has
+// checked that the frame's span lies inside the allocation.)
+__device__ __forceinline__ void ingest_pixel_generic(const IngestSrc& s, const uint8_t* origin, int w, int y, uint8_t* __restrict__ dst)
+{
+    const int px = (int)blockIdx.x * INGEST_GENERIC_WG_PX + (int)threadIdx.x;
+    if (px >= w) return;
+    const uint8_t* p = origin + (long long)y * s.stride_y + (long long)px * s.stride_x;
+    uint8_t* q = dst + ((unsigned long long)y * (unsigned)w + (unsigned)px) * 3ull;
+    const uint8_t c0 = p[0], c1 = p[s.stride_c], c2 = p[2 * s.stride_c];
+    q[0] = s.order == INGEST_RGB ? c2 : c0, q[1] = c1, q[2] = s.order == INGEST_RGB ? c0 : c2;
+}
+__global__ __launch_bounds__(256) void ingest_generic_kernel(const IngestSrc s, const uint8_t* origin, int w, int row_base, uint8_t* __restrict__ dst)
+{
+    ingest_pixel_generic(s, origin, w, row_base + (int)blockIdx.y, dst);
+}
+__global__ __launch_bounds__(256) void ingest_generic_track_kernel(const TrackState* __restrict__ ts, const IngestSrc s, uint8_t* __restrict__ dst)
+{
+    const int x0 = ts->x, y0 = ts->y, w = ts->w, h = ts->h;
+    if ((int)blockIdx.y >= h) return;
+    ingest_pixel_generic(s, s.data + (long long)y0 * s.stride_y + (long long)x0 * s.stride_x, w, (int)blockIdx.y, dst);
+}
+static bool ingest_src_ok(const IngestSrc& s, int H, int W)
+{
+    if (!s.data || !s.lo || !s.end || s.stride_y < 1 || s.stride_x < 1 || s.stride_c < 1 || (s.order != INGEST_BGR && s.order != INGEST_RGB)) return false;
+    if (H < 1 || W < 1 || H > (1 << 30) || W > (1 << 28)) return false;
+    return s.data >= s.lo && (long long)(s.end - s.data) >= ingest_span(H, W, s.stride_y, s.stride_x, s.stride_c);
+}
+// f(form tag, order tag) with the source's form and order as compile-time constants
+template <class F>
+static void ingest_dispatch(int form, int order, F&& f)
+{
+    auto by_order = [&](auto fm) {
+        if (order == INGEST_RGB) f(fm, std::integral_constant<int, INGEST_RGB>{});
+        else f(fm, std::integral_constant<int, INGEST_BGR>{});
+    };
+    if (form == INGEST_PACKED3) by_order(std::integral_constant<int, INGEST_PACKED3>{});
+    else if (form == INGEST_PACKED4) by_order(std::integral_constant<int, INGEST_PACKED4>{});
+    else by_order(std::integral_constant<int, INGEST_PLANAR>{});
+}
+hipError_t launch_ingest_copy(const IngestSrc& s, int H, int W, int x, int y, int w, int h, uint8_t* dst, hipStream_t st, int force_generic)
+{
+    if (!ingest_src_ok(s, H, W) || !dst || x < 0 || y < 0 || w < 1 || h < 1 || (long long)x + w > W || (long long)y + h > H) return hipErrorInvalidValue;
+    const uint8_t* origin = s.data + (long long)y * s.stride_y + (long long)x * s.stride_x;
+    const int form = force_generic ? INGEST_GENERIC : ingest_form(s.stride_x, s.stride_c);
+    const int per = form == INGEST_GENERIC ? INGEST_GENERIC_WG_PX : INGEST_WG_PX;
+    const dim3 g((unsigned)((w + per - 1) / per), 1);
+    for (int rb = 0; rb < h; rb += 65535) {  // grid.y is 16 bits (a row's destination is computed from its number: no phase to keep)
+        const dim3 gg(g.x, (unsigned)(h - rb < 65535 ? h - rb : 65535));
+        if (form == INGEST_GENERIC) hipLaunchKernelGGL(ingest_generic_kernel, gg, dim3(256), 0, st, s, origin, w, rb, dst);
+        else
+            ingest_dispatch(form, s.order, [&](auto fm, auto od) {
+                hipLaunchKernelGGL((ingest_copy_kernel<decltype(fm)::value, decltype(od)::value>), gg, dim3(256), 0, st, s, origin, w, rb, dst);
+            });
+    }
+    return hipGetLastError();
+}
+hipError_t launch_ingest_copy_track(const TrackState* ts, const IngestSrc& s, uint8_t* dst, int H, int W, hipStream_t st, int force_generic)
+{
+    if (!ingest_src_ok(s, H, W) || !ts || !dst || H > 65535) return hipErrorInvalidValue;
+    const int form = force_generic ? INGEST_GENERIC : ingest_form(s.stride_x, s.stride_c);
+    const int per = form == INGEST_GENERIC ? INGEST_GENERIC_WG_PX : INGEST_WG_PX;
+    const dim3 g((unsigned)((W + per - 1) / per), (unsigned)H);
+    if (form == INGEST_GENERIC) hipLaunchKernelGGL(ingest_generic_track_kernel, g, dim3(256), 0, st, ts, s, dst);
+    else
+        ingest_dispatch(form, s.order, [&](auto fm, auto od) {
+            hipLaunchKernelGGL((ingest_copy_track_kernel<decltype(fm)::value, decltype(od)::value>), g, dim3(256), 0, st, ts, s, dst);
+        });
     return hipGetLastError();
 }
 

@@ -183,6 +183,7 @@ void vnect_destroy(vnect_handle* h)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
     if (h->upload_st) hipStreamDestroy(h->upload_st);
+    if (h->producer_ev) hipEventDestroy(h->producer_ev);
 #if VNECT_TEST_HOOKS
     if (h->test_st) hipStreamDestroy(h->test_st);
 #endif
@@ -805,6 +806,71 @@ int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_ind
         TrackedSrc tk;
         tk.pinned_dev = tk.pinned_lo = h->stage_dev[buffer_index], tk.pinned_end = h->stage_dev[buffer_index] + h->stage_cap[buffer_index], tk.stride = y_stride;
         tk.nv12 = true, tk.uv_dev = h->stage_dev[buffer_index] + uv_offset, tk.uv_stride = uv_stride;
+        int ring;
+        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+    });
+}
+
+// ---- frames in the caller's device memory (additive): a kernel writes them into the slot (post.hip: ingest_copy_kernel; ingest.h) ---------
+int vnect_upload_frame_device(vnect_handle* h, int slot, const vnect_device_frame* frame, void* producer_stream)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "vnect_upload_frame_device: bad frame slot");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        DeviceFrame f;
+        int rc = check_device_frame(h, frame, producer_stream, "vnect_upload_frame_device", true, &f);
+        if (rc) return rc;
+        return upload_device_impl(h, slot, f);
+    });
+}
+
+int vnect_infer_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d, double* j2, float* j3)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !j2 || !j3) return VNECT_E_ARG;
+        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_infer_device before vnect_finalize");
+        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        DeviceFrame f;
+        int rc = check_device_frame(h, frame, producer_stream, "vnect_infer_device", true, &f);
+        if (rc) return rc;
+        // nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the stream the copy runs on.  The result
+        // is back when this returns, so the copy has long read the caller's buffer
+        if ((rc = stage_frame_device(h, 0, f))) return rc;
+        return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+    });
+}
+
+int vnect_preprocess_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, float* batch_out, double* scaler,
+                            int32_t* offset_x, int32_t* offset_y)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (!h->finalized && !h->pre_only) return fail(h, VNECT_E_STATE, "vnect_preprocess_device before vnect_finalize");
+        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        DeviceFrame f;
+        int rc = check_device_frame(h, frame, producer_stream, "vnect_preprocess_device", true, &f);
+        if (rc) return rc;
+        if ((rc = upload_device_impl(h, 0, f))) return rc;
+        return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
+    });
+}
+
+int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = tracked_ok(h, stream);
+        if (rc) return rc;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        DeviceFrame f;
+        if ((rc = check_device_frame(h, frame, producer_stream, "vnect_submit_tracked_device", false, &f))) return rc;
+        if (f.H != h->streams[stream].track_H || f.W != h->streams[stream].track_W)
+            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_device: the frame is not of the size vnect_track_begin gave for this stream");
+        TrackedSrc tk;
+        tk.pinned_dev = f.nv12 ? f.nv.y : f.ing.data, tk.dev = &f;
         int ring;
         return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
     });

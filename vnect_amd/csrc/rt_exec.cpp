@@ -115,7 +115,12 @@ static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn&
 {
     TrackState* ts = h->d_track + stream;
     const Stream& sm = h->streams[stream];
-    if (tk.pinned_dev && tk.nv12) {
+    if (tk.dev) {  // the frame lies in the caller's device memory: this lane's stream waits for its producer, then copies the crop's rows
+        int rc = wait_for_producer(h, tk.dev->producer, L->st);
+        if (rc) return rc;
+        if (tk.dev->nv12) HIPCK(h, launch_nv12_copy_track(ts, tk.dev->nv, sm.track_buf, sm.track_H, sm.track_W, L->st));
+        else HIPCK(h, launch_ingest_copy_track(ts, tk.dev->ing, sm.track_buf, sm.track_H, sm.track_W, L->st));
+    } else if (tk.pinned_dev && tk.nv12) {
         const Nv12Src src = {tk.pinned_dev, tk.stride, tk.uv_dev, tk.uv_stride, tk.pinned_lo, tk.pinned_end};
         HIPCK(h, launch_nv12_copy_track(ts, src, sm.track_buf, sm.track_H, sm.track_W, L->st));
     } else if (tk.pinned_dev)
@@ -601,6 +606,127 @@ int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stri
 {
     if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
     int rc = stage_frame_nv12(h, slot, y, y_stride, uv, uv_stride, H, W, rect4, who, h->upload_st);
+    if (rc) return rc;
+    HIPCK(h, hipStreamSynchronize(h->upload_st));
+    return VNECT_OK;
+}
+
+// ---- frames in the caller's DEVICE memory (vnect_infer_device and its kin) ---------------------------------------------------------------
+// `p` must be device memory of the handle's device as this process's HIP runtime knows it; [*lo, *end) = the allocation it lies in
+static int device_range(vnect_handle* h, const void* p, const std::string& w_, const char* what, const uint8_t** lo, const uint8_t** end)
+{
+    static const char* advice =
+        ": device-frame entry points take hipMalloc'ed memory of the handle's device only -- pass host memory to vnect_infer / vnect_upload_frame "
+        "(vnect_infer_nv12 / vnect_upload_frame_nv12 for NV12); a pointer of another HIP runtime in this process means nothing to this one "
+        "(torch ships its own libamdhip64: import torch BEFORE vnect_amd, so that the process holds one runtime)";
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (an unknown pointer is the caller's mistake, not a sticky error of the handle)
+        return fail(h, VNECT_E_ARG, w_ + what + " is not memory this process's HIP runtime allocated" + advice);
+    }
+    if (at.type != hipMemoryTypeDevice || at.isManaged) return fail(h, VNECT_E_ARG, w_ + what + " is host or managed memory, not device memory" + advice);
+    if (at.device != h->cfg.device) return fail(h, VNECT_E_ARG, w_ + what + " lies on another device than the handle's" + advice);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base || !size) {
+        (void)hipGetLastError();
+        return fail(h, VNECT_E_ARG, w_ + "hipMemGetAddressRange does not know the allocation " + what + " points into" + advice);
+    }
+    *lo = (const uint8_t*)base, *end = (const uint8_t*)base + size;
+    if ((const uint8_t*)p < *lo || (const uint8_t*)p >= *end) return fail(h, VNECT_E_ARG, w_ + what + " lies outside the allocation the runtime reports for it");
+    return VNECT_OK;
+}
+
+int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, DeviceFrame* out)
+{
+    const std::string w_ = std::string(who) + ": ";
+    if (!f) return fail(h, VNECT_E_ARG, w_ + "no frame descriptor");
+    if (f->struct_size != (int32_t)sizeof(vnect_device_frame)) return fail(h, VNECT_E_ARG, w_ + "vnect_device_frame::struct_size is not sizeof(vnect_device_frame)");
+    if (f->format != VNECT_PIX_BGR && f->format != VNECT_PIX_RGB && f->format != VNECT_PIX_NV12)
+        return fail(h, VNECT_E_ARG, w_ + "format must be VNECT_PIX_BGR, VNECT_PIX_RGB or VNECT_PIX_NV12");
+    const bool nv12 = f->format == VNECT_PIX_NV12;
+    const int H = f->H, W = f->W;
+    if (!f->data || (nv12 && !f->uv)) return fail(h, VNECT_E_ARG, w_ + "null frame pointer");
+    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail(h, VNECT_E_ARG, w_ + "bad frame geometry");
+    size_t span = 0, uv_span = 0;
+    if (nv12) {  // the rules of stage_frame_nv12
+        if (H < 2 || W < 2 || ((H | W) & 1)) return fail(h, VNECT_E_ARG, w_ + "an NV12 frame needs even W and H (>= 2)");
+        if (f->stride_y < (int64_t)W || f->uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, w_ + "stride_y and uv_stride must be at least W");
+        if (f->stride_y > ((int64_t)1 << 32) || f->uv_stride > ((int64_t)1 << 32)) return fail(h, VNECT_E_ARG, w_ + "stride out of range");
+        span = (size_t)(H - 1) * (size_t)f->stride_y + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)f->uv_stride + (size_t)W;
+        const uint8_t *y = (const uint8_t*)f->data, *uv = (const uint8_t*)f->uv;
+        if (y < uv + uv_span && uv < y + span) return fail(h, VNECT_E_ARG, w_ + "the UV plane overlaps the Y plane");
+    } else {
+        if (f->stride_y < 1 || f->stride_x < 1 || f->stride_c < 1) return fail(h, VNECT_E_ARG, w_ + "strides must be positive (flip or broadcast on the device first)");
+        if (f->stride_y > ((int64_t)1 << 32) || f->stride_x > ((int64_t)1 << 32) || f->stride_c > ((int64_t)1 << 36)) return fail(h, VNECT_E_ARG, w_ + "stride out of range");
+        span = (size_t)ingest_span(H, W, f->stride_y, f->stride_x, f->stride_c);
+    }
+    int r[4] = {0, 0, W, H};
+    if (f->has_rect) {
+        if (!allow_rect) return fail(h, VNECT_E_ARG, w_ + "a tracked frame takes no rect: the crop is the stream's box on the device");
+        for (int k = 0; k < 4; k++) r[k] = f->rect[k];
+        if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H) return fail(h, VNECT_E_ARG, w_ + "the rect's origin must lie inside the frame");
+        if (r[2] < 1 || r[3] < 1) return fail(h, VNECT_E_ARG, w_ + "the rect must be at least one pixel wide and high");
+        r[2] = std::min(r[2], W - r[0]), r[3] = std::min(r[3], H - r[1]);
+    }
+    if (allow_rect && (size_t)r[2] * r[3] * 3 > (size_t)h->cfg.max_frame_bytes)
+        return fail(h, VNECT_E_ARG, w_ + "frame larger than max_frame_bytes (the slot holds BGR: 3 bytes per pixel)");
+    const uint8_t *lo = nullptr, *end = nullptr, *uv_lo = nullptr, *uv_end = nullptr;
+    int rc = device_range(h, f->data, w_, "data", &lo, &end);
+    if (rc) return rc;
+    if ((size_t)(end - (const uint8_t*)f->data) < span)
+        return fail(h, VNECT_E_ARG, w_ + "the frame's last byte lies past the end of the allocation `data` points into (at these strides)");
+    if (nv12) {
+        if ((rc = device_range(h, f->uv, w_, "uv", &uv_lo, &uv_end))) return rc;
+        if ((size_t)(uv_end - (const uint8_t*)f->uv) < uv_span) return fail(h, VNECT_E_ARG, w_ + "the UV plane's last byte lies past the end of the allocation `uv` points into");
+    }
+    DeviceFrame d;
+    d.nv12 = nv12, d.H = H, d.W = W, d.producer = producer_stream;
+    for (int k = 0; k < 4; k++) d.r[k] = r[k];
+    if (nv12) {
+        d.nv = {(const uint8_t*)f->data, (long long)f->stride_y, (const uint8_t*)f->uv, (long long)f->uv_stride, lo, end};
+        d.nv.uv_lo = uv_lo, d.nv.uv_end = uv_end, d.nv.any_bounds = 1;
+    } else {
+        d.ing = {(const uint8_t*)f->data, (long long)f->stride_y, (long long)f->stride_x, (long long)f->stride_c, lo, end,
+                 f->format == VNECT_PIX_RGB ? INGEST_RGB : INGEST_BGR};
+    }
+    *out = d;
+    return VNECT_OK;
+}
+
+// `consumer` waits for what has been enqueued on the producer's stream so far; the host does not
+int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer)
+{
+    if (producer_stream == VNECT_STREAM_SYNCED) return VNECT_OK;
+    if (!h->producer_ev) HIPCK(h, hipEventCreateWithFlags(&h->producer_ev, hipEventDisableTiming));
+    HIPCK(h, hipEventRecord(h->producer_ev, (hipStream_t)producer_stream));  // (NULL: HIP's default stream)
+    HIPCK(h, hipStreamWaitEvent(consumer, h->producer_ev, 0));
+    return VNECT_OK;
+}
+
+int stage_frame_device(vnect_handle* h, int slot, const DeviceFrame& f, hipStream_t st)
+{
+    if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
+    int rc = claim_slot(h, slot, (size_t)f.r[2] * f.r[3] * 3);
+    if (rc) return rc;
+    if (!st) st = h->st;
+    if ((rc = wait_for_producer(h, f.producer, st))) return rc;
+    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+    if (f.nv12) HIPCK(h, launch_nv12_copy(f.nv, f.r[0], f.r[1], f.r[2], f.r[3], dst, st));
+    else HIPCK(h, launch_ingest_copy(f.ing, f.H, f.W, f.r[0], f.r[1], f.r[2], f.r[3], dst, st));
+    h->slots[slot].H = f.r[3], h->slots[slot].W = f.r[2], h->slots[slot].stride = 3LL * f.r[2];
+    return VNECT_OK;
+}
+
+// vnect_upload_frame_device / vnect_preprocess_device: done with the caller's buffer on return.  On upload_st, like upload_nv12_impl: it
+// waits only for the slot's last reader (claim_slot) and for the producer
+int upload_device_impl(vnect_handle* h, int slot, const DeviceFrame& f)
+{
+    if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
+    if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
+    int rc = stage_frame_device(h, slot, f, h->upload_st);
     if (rc) return rc;
     HIPCK(h, hipStreamSynchronize(h->upload_st));
     return VNECT_OK;

@@ -25,6 +25,7 @@
 #include "../../include/vnect_abi.h"
 #include "crop.h"
 #include "hostplan.h"
+#include "ingest.h"
 #include "kernels.h"
 
 namespace vnect {
@@ -189,6 +190,7 @@ struct vnect_handle : Plan {
     size_t stage_cap[3] = {};
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
     hipStream_t upload_st = nullptr;  // vnect_upload_frame_nv12's conversion kernel (made on first use): not a lane's compute stream
+    hipEvent_t producer_ev = nullptr; // a device frame's producer stream -> the stream that ingests it (wait_for_producer; made on first use)
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
     std::vector<SlotInfo> slots;
     ScaleTabs* d_stabs = nullptr;
@@ -334,6 +336,15 @@ void commit_time(Stream& s, double t2d, double t3d);
 int reset_filters_impl(vnect_handle* h, int stream = -1);  // -1: every stream
 void roctx_load();
 int build_graph(Plan* p);
+// a validated vnect_device_frame (check_device_frame): what the ingest kernels take, the crop clipped to the frame
+struct DeviceFrame {
+    bool nv12 = false;
+    IngestSrc ing{};          // BGR / RGB
+    Nv12Src nv{};             // NV12: both planes with their allocations' bounds
+    int H = 0, W = 0;
+    int r[4] = {0, 0, 0, 0};  // (x, y, w, h)
+    void* producer = nullptr; // the producer's stream as the caller gave it
+};
 // a tracked frame (vnect_submit_tracked*): the whole frame in a resident slot (pinned_dev == nullptr) or in a pinned buffer
 struct TrackedSrc {
     const uint8_t* pinned_dev = nullptr;  // the frame as the device addresses it
@@ -344,6 +355,8 @@ struct TrackedSrc {
     const uint8_t* uv_dev = nullptr;      // the interleaved U, V plane
     long long uv_stride = 0;
     const uint8_t* pinned_lo = nullptr;   // start of the pinned buffer
+    // a frame in the caller's DEVICE memory (vnect_submit_tracked_device): pinned_dev is its first byte, everything else is here
+    const DeviceFrame* dev = nullptr;
 };
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const TrackedSrc* tk = nullptr);
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
@@ -357,6 +370,14 @@ int stage_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stri
                      const int32_t* rect4, const char* who, hipStream_t st = nullptr);  // st: nullptr = the handle's stream
 int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
                      const int32_t* rect4, const char* who);
+// Frames in the caller's device memory (vnect_infer_device and its kin).  check_device_frame validates everything -- the descriptor, the
+// pointers (device memory of the handle's device, the frame's span inside its allocation), the rect, the slot's room -- and changes
+// nothing; stage_frame_device makes `st` (nullptr: the handle's stream) wait for the producer and launches the copy (asynchronous, like
+// stage_frame); upload_device_impl runs it on upload_st and waits for it (like upload_nv12_impl)
+int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, DeviceFrame* out);
+int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer);
+int stage_frame_device(vnect_handle* h, int slot, const DeviceFrame& f, hipStream_t st = nullptr);
+int upload_device_impl(vnect_handle* h, int slot, const DeviceFrame& f);
 int prime(vnect_handle* h);
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 int forward_batch(vnect_handle* h, const float* batch, float* out);

@@ -143,22 +143,37 @@ class VNectEstimator:
         return float(timestamp), float(timestamp)
 
     @staticmethod
-    def _format(pixel_format, rect):
+    def _format(pixel_format, rect, device=False):
+        if device:  # a frame in device memory: 'rgb' exists here only (a host caller flips with a slice), and any format takes a rect
+            if pixel_format not in ("bgr", "rgb", "nv12"):
+                raise ValueError("pixel_format must be 'bgr', 'rgb' or 'nv12'")
+            return pixel_format == "nv12"
+        if pixel_format == "rgb":
+            raise ValueError("pixel_format='rgb' is for frames in device memory (a host caller passes frame[..., ::-1])")
         if pixel_format not in ("bgr", "nv12"):
             raise ValueError("pixel_format must be 'bgr' or 'nv12'")
         if rect is not None and pixel_format != "nv12":
             raise ValueError("rect= is for pixel_format='nv12' (a BGR caller slices the frame)")
         return pixel_format == "nv12"
 
-    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None):
+    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None):
         """``pixel_format="nv12"`` (additive): ``img_input`` is a 2-D uint8 array of ``H * 3 // 2`` rows -- H rows of Y, the interleaved
         U, V plane from row H on; row-strided views are fine -- converted to BGR on the device (NV12.md).  ``rect=(x, y, w, h)``: only
-        that crop, as ``frame[y:y + h, x:x + w]`` of the converted frame; the joints are in crop coordinates."""
+        that crop, as ``frame[y:y + h, x:x + w]`` of the converted frame; the joints are in crop coordinates.
+
+        A frame already in DEVICE memory (additive; DEVICE_FRAMES.md): any object with ``__cuda_array_interface__`` -- a uint8 (H, W, 3)
+        torch tensor on the GPU with any positive strides (packed, ``chw.permute(1, 2, 0)``, ``bgra[..., :3]``, any slice), read where it
+        lies; ``pixel_format="rgb"`` for RGB order, ``"nv12"`` for an (H * 3 // 2, W) array or a ``(y, uv)`` pair.  ``stream=``: the
+        integer handle of the stream that wrote it (default: torch's current stream if torch is imported, else the default stream)."""
         t0 = time.time()
         t2d, t3d = self._stamps(timestamp)
-        nv12 = self._format(pixel_format, rect)
+        device = _native.is_device_array(img_input)
+        nv12 = self._format(pixel_format, rect, device)
         try:
-            joints_2d, joints_3d = self._h.infer_nv12(img_input, t2d, t3d, rect) if nv12 else self._h.infer(img_input, t2d, t3d)
+            if device:
+                joints_2d, joints_3d = self._h.infer_device(_native.device_frame(img_input, pixel_format, rect), t2d, t3d, stream)
+            else:
+                joints_2d, joints_3d = self._h.infer_nv12(img_input, t2d, t3d, rect) if nv12 else self._h.infer(img_input, t2d, t3d)
         except _native.VnectError as e:
             self._raise_like_reference(e)
         if self.verbose:
@@ -166,16 +181,19 @@ class VNectEstimator:
         return joints_2d, joints_3d
 
     # -- pipelined use (additive; the reference's loop is strictly one frame at a time) --------------------------------
-    def submit(self, img_input, timestamp=None, pixel_format="bgr", rect=None):
+    def submit(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None):
         """Queue a frame and return at once; at most ``max(lanes, 2)`` may be in flight.  With ``lanes=2`` / ``3`` the frames
         overlap on the GPU (+29 % frames/s for one video stream at three lanes -- `pipelined_frames_per_s_per_gpu` against `value` in
         profiles/r06_bench_line.json -- at the price of their latency); ``collect()`` returns
         results in order and they are bit-identical to calling the estimator frame by frame."""
         t2d, t3d = self._stamps(timestamp)
         slot = self._submitted % 4
-        nv12 = self._format(pixel_format, rect)
+        device = _native.is_device_array(img_input)
+        nv12 = self._format(pixel_format, rect, device)
         try:
-            if nv12:
+            if device:  # (the upload is done with the caller's buffer when it returns)
+                self._h.upload_frame_device(slot, _native.device_frame(img_input, pixel_format, rect), stream)
+            elif nv12:
                 self._h.upload_frame_nv12(slot, img_input, rect)
             else:
                 self._h.upload_frame(slot, img_input)

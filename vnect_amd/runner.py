@@ -67,7 +67,13 @@ def init_box(estimator, frame, timestamp=None):
     return [x, y, w, h]
 
 
-def _nv12_checks(pixel_format, transpose):
+def _nv12_checks(pixel_format, transpose, source=None):
+    if source == "device":  # frames in device memory (DEVICE_FRAMES.md): 'rgb' exists there, rotating does not
+        if pixel_format not in ("bgr", "rgb", "nv12"):
+            raise ValueError("pixel_format must be 'bgr', 'rgb' or 'nv12'")
+        if transpose:
+            raise ValueError("transpose=True is not supported with source='device': rotate the frame on the device before passing it")
+        return pixel_format == "nv12"
     if pixel_format not in ("bgr", "nv12"):
         raise ValueError("pixel_format must be 'bgr' or 'nv12'")
     if pixel_format == "nv12" and transpose:
@@ -114,7 +120,9 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
     frame t+1 without waiting for frame t.  ``ahead``: frames submitted before the oldest is collected (0: one at a time; at most
     ``max(lanes, 2) - 1``).  ``source``: "pinned" -- the frame is written into the handle's pinned buffers and only the crop's rows cross
-    PCIe -- or "resident" (vnect_upload_frame of the whole frame).  ``stream``: which of the handle's video streams (its filter bank).
+    PCIe -- "resident" (vnect_upload_frame of the whole frame) -- or "device": the frames are arrays in device memory (anything with
+    ``__cuda_array_interface__``; ``pixel_format`` may then be "rgb" as well), read where they lie when the frame runs and held until it
+    is collected (no ``transpose``).  ``stream``: which of the handle's video streams (its filter bank).
     ``rect`` must start inside the frame (``track`` would slice from outside it); one that runs past the far edges is cropped as
     ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight."""
     for _, j2, j3, used in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
@@ -132,7 +140,10 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     from collections import deque
 
     from . import _native
-    nv12 = _nv12_checks(pixel_format, transpose)
+    nv12 = _nv12_checks(pixel_format, transpose, source)
+    if source not in ("pinned", "resident", "device"):
+        raise ValueError("source must be 'pinned', 'resident' or 'device'")
+    device = source == "device"
     h = estimator.handle
     n = len(videos)
     streams = list(range(n)) if streams is None else [int(s) for s in streams]
@@ -141,13 +152,17 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     rects = rects if rects is not None else [None] * n
     limit = max(int(estimator._cfg.get("lanes", 1)), 2)
     window = max(0, min(int(ahead), limit - 1)) + 1
-    if source not in ("pinned", "resident"):
-        raise ValueError("source must be 'pinned' or 'resident'")
 
     def size_of(f):                            # (H, W) of the picture a frame array holds
+        if device:
+            return (f.H, f.W)
         return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
 
     def prep(f):
+        if device:                             # its descriptor (which keeps the array alive); the producer is the stream current now
+            d = _native.device_frame(f, pixel_format)
+            d._producer = _native.default_stream()
+            return d
         f = np.rot90(f, 3) if transpose else f
         return np.ascontiguousarray(f, dtype=np.uint8)
 
@@ -164,15 +179,18 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
         flat = [h.frame_buffer(b, 1, (nbytes + 2) // 3).reshape(-1) for b in range(2)]
     nslots = int(getattr(h, "num_frame_slots", 0) or 4)
     inflight = deque()                         # (video, submission number)
+    held = {}                                  # submission number -> the device frame it reads, until it has been collected
     video_of = {s: i for i, s in enumerate(streams)}
     count = 0
 
     def collect():
-        inflight.popleft()
+        _, k = inflight.popleft()
         try:
             s, j2, j3, used = h.collect_tracked()
         except _native.VnectError as e:
             estimator._raise_like_reference(e)
+        finally:
+            held.pop(k, None)
         return video_of[s], j2, j3, used
 
     # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
@@ -187,7 +205,10 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 t2d, t3d = estimator._stamps(next(tss[i]) if tss[i] is not None else None)
                 H, W = size_of(frame)
                 try:
-                    if source == "pinned":
+                    if device:
+                        h.submit_tracked_device(streams[i], frame, t2d, t3d, frame._producer)
+                        held[count] = frame
+                    elif source == "pinned":
                         b = count % 2                  # a frame captured into this buffer already (the view itself) is not copied
                         view = flat[b][:frame.size].reshape(frame.shape)
                         if frame.ctypes.data != view.ctypes.data:
@@ -229,6 +250,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 h.collect_tracked()
             except _native.VnectError:
                 pass
+        held.clear()
 
 
 def synthetic_stream(stream, n_frames, height=368, width=368, smooth=True):
