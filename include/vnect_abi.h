@@ -212,6 +212,30 @@ int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, i
 int vnect_collect_tracked(vnect_handle* h, int32_t* stream_out, double* joints_2d, float* joints_3d, int32_t* rect4);
 int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4);
 
+/* ABI v7, additive.  Per-joint confidence, and what a tracked stream does when it has lost its person (CONFIDENCE.md).  The reference has
+ * no counterpart: it returns 21 joints for every frame, whether or not anybody is in it, and its loop grows the next crop from them
+ * unconditionally (run_estimator_ps.py:96-107).
+ *
+ * vnect_result_confidence: confidence21[j] (float64, j = 0 .. 20) of the frame most recently DELIVERED by a successful call on this handle
+ * -- vnect_infer*, vnect_postprocess, vnect_collect, vnect_collect_stream, vnect_collect_tracked; one result of a two-stream batch is one
+ * delivery.  The value is the maximum of the 368 x 368 bilinear x8 upsample of joint j's merged heat-map, i.e. the element that np.argmax
+ * picks in src/utils.py:169-172; for finite maps bit for bit that float64.  It comes from the frame's raw maps: the OneEuro filters do not
+ * touch it.  Non-finite maps follow the arg-max's documented deviation: NaN cells never win, and an all-NaN heat-map gives -inf, which is
+ * below every threshold.  The values are taken from the delivered frame's own result slot, so with frames in flight they belong to the
+ * collected frame, not the newest one.  VNECT_E_STATE before any delivery; a failed call leaves the previous values standing.
+ * lost_out (may be NULL): 1 if the loss rule below called the frame lost; 0 for untracked frames and for action 0.
+ *
+ * vnect_track_policy: the loss rule of tracked stream `stream`, applied on the device by the box stage of every tracked frame:
+ *   confident = #{ j : confidence[j] >= min_confidence },  lost = confident < min_joints.
+ * action 0 (off, the default): the loop as it is, lost reported 0.  action 1 (hold): a lost frame leaves the stream's box as it is -- the
+ * next frame is cropped with this frame's crop.  action 2 (reset): the next crop is the whole frame (if squarify refuses the whole frame,
+ * the stream stops as at any refused crop).  A lost frame's joints are still delivered and the filters advance as on any frame.
+ * The rule belongs to the stream and survives vnect_track_begin, until it is set again.  VNECT_E_ARG for min_joints outside 1 .. 21, an
+ * action outside 0 .. 2, a NaN threshold, and on the handles vnect_track_begin refuses; VNECT_E_STATE while the stream has a tracked frame
+ * in flight. */
+int vnect_result_confidence(vnect_handle* h, double* confidence21, int32_t* lost_out);
+int vnect_track_policy(vnect_handle* h, int stream, double min_confidence, int min_joints, int action);
+
 /* ABI v7, additive.  NV12 frames.  The reference's loop takes its frame from camera_capture.read() (run_estimator_ps.py:79,109), and
  * cv2.VideoCapture hands out BGR: whatever the camera or decoder delivered -- on this hardware NV12, a full-resolution Y plane and one
  * half-resolution plane of interleaved U, V -- OpenCV has converted by then.  That colour conversion is OpenCV's, not the reference's own

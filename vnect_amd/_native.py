@@ -48,6 +48,7 @@ class LayerInfo(C.Structure):
                 ("flops", C.c_double), ("last_ms", C.c_double)]
 
 
+LOST_ACTIONS = {"off": 0, "hold": 1, "reset": 2}   # vnect_track_policy's action
 PIX_BGR, PIX_RGB, PIX_NV12 = 0, 1, 2          # vnect_device_frame::format
 STREAM_SYNCED = C.c_void_p(-1).value          # VNECT_STREAM_SYNCED: the caller has synchronised, wait for nothing
 
@@ -109,6 +110,8 @@ SYMBOLS = {
     "vnect_submit_tracked_pinned": (C.c_int, [_H, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_double]),
     "vnect_collect_tracked": (C.c_int, [_H, _i32p, _f64p, _f32p, _i32p]),
     "vnect_track_box": (C.c_int, [_H, C.c_int, _i32p]),
+    "vnect_result_confidence": (C.c_int, [_H, _f64p, _i32p]),
+    "vnect_track_policy": (C.c_int, [_H, C.c_int, C.c_double, C.c_int, C.c_int]),
     "vnect_upload_frame_nv12": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int]),
     "vnect_upload_frame_nv12_rect": (C.c_int, [_H, C.c_int, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p]),
     "vnect_infer_nv12": (C.c_int, [_H, _u8p, C.c_int64, _u8p, C.c_int64, C.c_int, C.c_int, _i32p, C.c_double, C.c_double, _f64p, _f32p]),
@@ -389,6 +392,17 @@ class Handle:
         r = (C.c_int32 * 4)()
         self._ck(lib().vnect_track_box(self._h, stream, r))
         return list(r)
+
+    # -- per-joint confidence and the loss rule (include/vnect_abi.h; CONFIDENCE.md) ---------------------------------------------------
+    def result_confidence(self):
+        """((21,) float64 confidences, lost flag) of the frame most recently delivered on this handle (a fresh array)."""
+        conf, lost = np.empty(21, np.float64), C.c_int32(0)
+        self._ck(lib().vnect_result_confidence(self._h, _ptr(conf, _f64p), C.byref(lost)))
+        return conf, int(lost.value)
+
+    def track_policy(self, stream, min_confidence, min_joints, action):
+        """The stream's loss rule: action 0 / "off", 1 / "hold", 2 / "reset" (LOST_ACTIONS)."""
+        self._ck(lib().vnect_track_policy(self._h, int(stream), float(min_confidence), int(min_joints), int(LOST_ACTIONS.get(action, action))))
 
     # -- NV12 frames: converted to BGR on the device, inside the frame's copy (include/vnect_abi.h; NV12.md) --------------------------
     def frame_buffer_nv12(self, index, H, W):

@@ -250,16 +250,36 @@ struct JointsOut {
     float j3d[NJ * 3];
     int status;
 };
+// Per-joint confidence (CONFIDENCE.md), per result-ring slot beside JointsOut (device-mapped pinned host memory): conf[j] is the value of
+// the element np.argmax picks in utils.py:169-172 -- the maximum of the x8 upsample of joint j's merged heat-map, the `bv` that wins
+// the arg-max (NaN cells never win; an all-NaN map gives -inf).  It comes from the frame's raw maps: the filters do not touch it.
+// lost / confident: the box stage's verdict on a tracked frame under the stream's TrackPolicy (0 / 0 on an untracked frame).
+struct ConfOut {
+    double conf[NJ];
+    int lost;
+    int confident;
+};
+// The loss rule of a tracked stream, device memory (vnect_track_policy): confident = #{j : conf[j] >= min_confidence},
+// lost = action != 0 && confident < min_joints.
+enum { TRACK_LOST_OFF = 0, TRACK_LOST_HOLD = 1, TRACK_LOST_RESET = 2 };
+struct TrackPolicy {
+    double min_confidence;
+    int min_joints;
+    int action;  // TRACK_LOST_OFF: today's loop; HOLD: the next frame is cropped with this frame's crop; RESET: with the whole frame
+};
 
 // merge + arg-max + joints in ONE launch: the last of the 168 arg-max workgroups (agent-scope ticket, zero between launches) runs the
-// joints stage
+// joints stage.  conf: the frame's ConfOut (like `out`, pinned host memory) or nullptr; conf_dev: nullptr, or NJ doubles of device memory
+// that get the confidences too (what a box stage launched behind this reads)
 hipError_t launch_post(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket,
-                       FilterBank* fb, const FrameParams* fp, FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st);
+                       FilterBank* fb, const FrameParams* fp, FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st,
+                       ConfOut* conf = nullptr, double* conf_dev = nullptr);
 // multi-scale merge of the heat-maps (in LDS, the rows each workgroup needs) + arg-max of the virtual x8 upsample
 hipError_t launch_argmax(const float* maps, MergeGeo geo, ArgPartial* part, hipStream_t st);
 // out may be (device-mapped) pinned HOST memory: the kernel's 21x2 + 21x3 results then need no device-to-host copy
 hipError_t launch_joints(const ArgPartial* part, const float* maps, MergeGeo geo, FilterBank* fb,
-                         const FrameParams* fp, FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st);
+                         const FrameParams* fp, FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st,
+                         ConfOut* conf = nullptr, double* conf_dev = nullptr);  // (conf, conf_dev: as launch_post)
 
 // ---- pyramid sharding: the exchange by peer writes (SURVEY 8e "plain peer writes ... into the gather buffer") -----------
 // Every rank owns one exchange block [2 parities][nranks slots][XCHG_MAPS floats] + flags[2][8] (u32, one 128-B line per
@@ -314,11 +334,14 @@ hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_
 // the same out of an (H, W) frame in device memory (H <= 65535)
 hipError_t launch_ingest_copy_track(const TrackState* ts, const IngestSrc& s, uint8_t* dst, int H, int W, hipStream_t st, int force_generic = 0);
 // behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
-// its geometry to `ts`
-hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st);
-// post_kernel with the same box stage as its tail (the last arriver's joints stage hands its frame-coordinate joints over in LDS)
+// its geometry to `ts`.  conf_dev: the frame's NJ confidences in device memory (launch_post / launch_joints left them there), pol: the
+// stream's loss rule (device memory), conf: the frame's ConfOut, which gets lost / confident -- all three or none (no rule: today's loop)
+hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st, const double* conf_dev = nullptr,
+                            const TrackPolicy* pol = nullptr, ConfOut* conf = nullptr);
+// post_kernel with the same box stage as its tail (the last arriver's joints stage hands its frame-coordinate joints -- and the
+// confidences -- over in LDS).  conf: the frame's ConfOut or nullptr; pol: the stream's loss rule or nullptr (off)
 hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
-                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st);
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf = nullptr, const TrackPolicy* pol = nullptr);
 
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);

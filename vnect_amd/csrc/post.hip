@@ -766,7 +766,7 @@ __device__ double pt_interp(const float* __restrict__ maps, const MergeGeo& geo,
 template <int SMAX>
 __device__ __forceinline__ void joints_body(const ArgPartial* part, const float* __restrict__ maps, const MergeGeo& geo,
                                             FilterBank* fb, Filt& f2, Filt& f3, double scaler, double off, const FrameDyn& dyn,
-                                            int nep50, JointsOut* __restrict__ out)
+                                            int nep50, JointsOut* __restrict__ out, ConfOut* __restrict__ cf, double* __restrict__ conf_dev)
 {
     __shared__ double c2[NJ * 2];
     __shared__ float p3[NJ * 3];
@@ -788,6 +788,10 @@ __device__ __forceinline__ void joints_body(const ArgPartial* part, const float*
         for (int s = 1; s < ARG_SLABS; s++)  // slabs ascend in row order
             if (better(pv[s], pi[s], bv, bi)) bv = pv[s], bi = pi[s];
         if (bi == 0x7fffffff) bi = 0;  // all-NaN map: np.argmax would return the first NaN; documented deviation
+        if (k2 == 0) {  // the joint's confidence (kernels.h: ConfOut): the value that won the arg-max (-inf for an all-NaN map)
+            if (cf) cf->conf[j2] = bv;
+            if (conf_dev) conf_dev[j2] = bv;
+        }
         const double raw = k2 == 0 ? (double)(bi / BOX) : (double)(bi % BOX);  // [row, col]
         c2[t] = oef_f64(f2, raw, t2d);
         fb->f2[j2][k2] = f2;
@@ -801,7 +805,10 @@ __device__ __forceinline__ void joints_body(const ArgPartial* part, const float*
         fb->f3[j3][k3] = f3;
     }
     if (t < NJ * 2) out->j2d[t] = (c2[t] - off) / scaler;
-    if (t == 0) out->status = 0;
+    if (t == 0) {
+        out->status = 0;
+        if (cf) cf->lost = 0, cf->confident = 0;  // (a tracked frame's box kernel, behind this launch, writes its verdict over them)
+    }
 }
 // this thread's filter states and un-mapping constants (threads past 63 hold copies of joint 0's: never written back)
 __device__ __forceinline__ void load_filters(const FilterBank* fb, const FrameParams* __restrict__ fp, Filt& f2, Filt& f3, double& scaler,
@@ -819,7 +826,7 @@ template <int SMAX>
 __global__ __launch_bounds__(128) void joints_kernel(const ArgPartial* __restrict__ part, const float* __restrict__ maps,
                                                      const MergeGeo geo, FilterBank* fb,
                                                      const FrameParams* __restrict__ fp, const FrameDyn dyn, int nep50,
-                                                     JointsOut* __restrict__ out)
+                                                     JointsOut* __restrict__ out, ConfOut* __restrict__ cf, double* __restrict__ conf_dev)
 {
     // Every global read that does not depend on a computed value is requested up front (both filter states, frame
     // parameters; the partials at the top of joints_body): the kernel is one workgroup and is priced in memory round trips.
@@ -830,7 +837,7 @@ __global__ __launch_bounds__(128) void joints_kernel(const ArgPartial* __restric
         if (threadIdx.x == 0) out->status = 1;  // as in post_kernel: THIS frame's exchange timed out -- stale maps, the filters stay
         return;
     }
-    joints_body<SMAX>(part, maps, geo, fb, f2, f3, scaler, off, dyn, nep50, out);
+    joints_body<SMAX>(part, maps, geo, fb, f2, f3, scaler, off, dyn, nep50, out, cf, conf_dev);
 }
 
 // The joints stage of post_kernel, spread over the last arriver's six waves (round 5; joints_body above is the 128-thread form of the
@@ -851,12 +858,15 @@ __device__ __forceinline__ WideRole wide_role()
     return r;
 }
 // TRACK: a tracked frame -- the 2-D joints are written in FRAME coordinates (+ the crop origin `shift`, [row, col]; run_estimator_ps.py:92-93)
-// and also left in LDS (`jf`) for the box stage behind this one
+// and also left in LDS (`jf`) for the box stage behind this one.
+// Confidences (kernels.h: ConfOut): wave 0's threads with k2 == 0 hold the `bv` that won joint j2's arg-max; it goes to cf->conf (the ring
+// slot, beside the joints: a store to host memory that nobody waits for) and to conf2 -- TRACK: LDS, for the box stage's loss rule;
+// otherwise nullptr or device memory, for a box kernel launched behind this one.
 template <int SMAX, bool TRACK = false>
 __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const float* __restrict__ maps, const MergeGeo& geo, FilterBank* fb,
                                                   Filt& f2, Filt& f3, const OefPrep& pr2, const OefPrep& pr3, double scaler, double off,
-                                                  const FrameDyn& dyn, int nep50, JointsOut* __restrict__ out, const int* shift = nullptr,
-                                                  double* jf = nullptr)
+                                                  const FrameDyn& dyn, int nep50, JointsOut* __restrict__ out, ConfOut* __restrict__ cf,
+                                                  double* conf2, const int* shift = nullptr, double* jf = nullptr)
 {
     __shared__ double c2[NJ * 2];
     __shared__ double mc[NJ * 3 * 4];
@@ -877,6 +887,10 @@ __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const 
         for (int sl = 1; sl < ARG_SLABS; sl++)  // slabs ascend in row order
             if (better(pv[sl], pi[sl], bv, bi)) bv = pv[sl], bi = pi[sl];
         if (bi == 0x7fffffff) bi = 0;  // all-NaN map: np.argmax would return the first NaN; documented deviation
+        if (ro.k2 == 0) {  // (-inf for an all-NaN map: below every threshold)
+            if (cf) cf->conf[ro.j2] = bv;
+            if (conf2) conf2[ro.j2] = bv;
+        }
         const double raw = ro.k2 == 0 ? (double)(bi / BOX) : (double)(bi % BOX);  // [row, col]
         c2[t] = oef_f64_fin(f2, pr2, raw, dyn.t2d);
         fb->f2[ro.j2][ro.k2] = f2;
@@ -925,7 +939,11 @@ __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const 
             out->j2d[t] = (c2[t] - off) / scaler;
         }
     }
-    if (t == 0) out->status = 0;
+    if (t == 0) {
+        out->status = 0;
+        if constexpr (!TRACK)  // (TRACK: the box stage behind this one writes the verdict)
+            if (cf) cf->lost = 0, cf->confident = 0;
+    }
 }
 
 // Both in ONE launch (round 2): the 168 arg-max workgroups publish their partials write-through and take an agent-scope ticket; the
@@ -944,12 +962,14 @@ __device__ __forceinline__ void joints_stage_wide(const ArgPartial* part, const 
 // Round 5: the joints stage runs on all six waves of the last arriver (joints_stage_wide), and the value-independent half of the filter
 // steps is computed here, in every workgroup, between the partial's store and the wait for it.
 // TRACK (a tracked frame, launch_post_track): fp is the stream's TrackState's, and the last arriver runs the box stage (trackbox.h) behind the
-// joints stage -- the joints it needs are in its LDS, not in the result ring slot in host memory.
+// joints stage -- the joints it needs, and the confidences its loss rule counts, are in its LDS, not in the result ring slot in host
+// memory; the stream's policy is read up front with the state.
+// cf: the frame's ConfOut (ring slot) or nullptr.  conf_dev (not TRACK): nullptr, or device memory that gets the confidences too.
 template <int SMAX, bool TRACK = false>
 __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restrict__ maps, const MergeGeo geo, ArgPartial* part, unsigned* ticket,
                                                            FilterBank* fb, const FrameParams* __restrict__ fp, const FrameDyn dyn,
-                                                           int nep50, JointsOut* __restrict__ out, TrackState* ts = nullptr,
-                                                           TrackOut* tout = nullptr)
+                                                           int nep50, JointsOut* __restrict__ out, ConfOut* __restrict__ cf, double* conf_dev,
+                                                           TrackState* ts = nullptr, TrackOut* tout = nullptr, const TrackPolicy* polp = nullptr)
 {
     __shared__ int last;
     if (POST_DBG == 4) return;
@@ -958,7 +978,8 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
     Filt f2 = fb->f2[ro.j2][ro.k2], f3 = fb->f3[ro.j3][ro.k3];
     const double scaler = fp->scaler, off = ro.k2 == 0 ? (double)fp->offy : (double)fp->offx;
     TrackNow c{};
-    if constexpr (TRACK) c = track_now(ts);  // (with the filters: the last arriver starts no round trip for it; the box stage writes the
+    TrackPolicy pol{0.0, 1, TRACK_LOST_OFF};
+    if constexpr (TRACK) c = track_now(ts), pol = track_policy_now(polp);  // (with the filters: the last arriver starts no round trip for it; the box stage writes the
                                              // state only behind the barriers of its own workgroup, and no other workgroup uses it)
     argmax_body<SMAX>(maps, geo, part);
     const OefPrep pr2 = oef_prep(f2, dyn.t2d), pr3 = oef_prep(f3, dyn.t3d);  // (thread 0: behind its partial's stores, in front of the wait for them)
@@ -977,38 +998,40 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
             return;
         }
         __shared__ double jf[NJ * 2];
+        __shared__ double cl[NJ];
         const int shift[2] = {c.y, c.x};
-        joints_stage_wide<SMAX, true>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out, shift, jf);
+        joints_stage_wide<SMAX, true>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out, cf, cl, shift, jf);
         __syncthreads();
-        track_box_stage(ts, c, jf, tout, dyn.xseq);
+        track_box_stage(ts, c, jf, tout, dyn.xseq, cl, pol, cf);
     } else {
         if (dyn.xfail && __hip_atomic_load(dyn.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == dyn.xseq) {
             if (threadIdx.x == 0) out->status = 1;  // the exchange of THIS frame timed out: stale maps, leave the filters alone
             return;
         }
-        joints_stage_wide<SMAX>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out);
+        joints_stage_wide<SMAX>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out, cf, conf_dev);
     }
 }
 hipError_t launch_post(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, const FrameParams* fp,
-                       FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st)
+                       FrameDyn dyn, int nep50, JointsOut* out, hipStream_t st, ConfOut* conf, double* conf_dev)
 {
-    if (geo.S <= 3) hipLaunchKernelGGL(post_kernel<3>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out);
-    else hipLaunchKernelGGL(post_kernel<VNECT_MAX_S>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out);
+    if (geo.S <= 3) hipLaunchKernelGGL(post_kernel<3>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, conf_dev);
+    else hipLaunchKernelGGL(post_kernel<VNECT_MAX_S>, dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, conf_dev);
     return hipGetLastError();
 }
 hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
-                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st)
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf, const TrackPolicy* pol)
 {
     const FrameParams* fp = &ts->fp;
-    if (geo.S <= 3) hipLaunchKernelGGL((post_kernel<3, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, ts, tout);
-    else hipLaunchKernelGGL((post_kernel<VNECT_MAX_S, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, ts, tout);
+    double* const none = nullptr;
+    if (geo.S <= 3) hipLaunchKernelGGL((post_kernel<3, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol);
+    else hipLaunchKernelGGL((post_kernel<VNECT_MAX_S, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol);
     return hipGetLastError();
 }
 hipError_t launch_joints(const ArgPartial* part, const float* maps, MergeGeo geo, FilterBank* fb, const FrameParams* fp, FrameDyn dyn,
-                         int nep50, JointsOut* out, hipStream_t st)
+                         int nep50, JointsOut* out, hipStream_t st, ConfOut* conf, double* conf_dev)
 {
-    if (geo.S <= 3) hipLaunchKernelGGL(joints_kernel<3>, dim3(1), dim3(128), 0, st, part, maps, geo, fb, fp, dyn, nep50, out);
-    else hipLaunchKernelGGL(joints_kernel<VNECT_MAX_S>, dim3(1), dim3(128), 0, st, part, maps, geo, fb, fp, dyn, nep50, out);
+    if (geo.S <= 3) hipLaunchKernelGGL(joints_kernel<3>, dim3(1), dim3(128), 0, st, part, maps, geo, fb, fp, dyn, nep50, out, conf, conf_dev);
+    else hipLaunchKernelGGL(joints_kernel<VNECT_MAX_S>, dim3(1), dim3(128), 0, st, part, maps, geo, fb, fp, dyn, nep50, out, conf, conf_dev);
     return hipGetLastError();
 }
 

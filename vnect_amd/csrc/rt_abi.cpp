@@ -100,6 +100,13 @@ int vnect_create(const vnect_config* cfg, vnect_handle** out)
             HIPCK(h, hipHostMalloc((void**)&h->h_tout, RING * sizeof(TrackOut), hipHostMallocMapped | hipHostMallocCoherent));
             memset(h->h_tout, 0, RING * sizeof(TrackOut));
             HIPCK(h, hipHostGetDevicePointer((void**)&h->h_tout_dev, h->h_tout, 0));
+            HIPCK(h, hipHostMalloc((void**)&h->h_conf, RING * sizeof(ConfOut), hipHostMallocMapped | hipHostMallocCoherent));
+            memset(h->h_conf, 0, RING * sizeof(ConfOut));
+            HIPCK(h, hipHostGetDevicePointer((void**)&h->h_conf_dev, h->h_conf, 0));
+            if ((rc = dev_alloc(h, &h->d_conf, (size_t)VNECT_MAX_STREAMS * NJ))) return rc;
+            if ((rc = dev_alloc(h, &h->d_policy, VNECT_MAX_STREAMS))) return rc;
+            std::vector<TrackPolicy> off(VNECT_MAX_STREAMS, TrackPolicy{0.0, 1, TRACK_LOST_OFF});
+            HIPCK(h, hipMemcpy(h->d_policy, off.data(), off.size() * sizeof(TrackPolicy), hipMemcpyHostToDevice));
         }
         if ((rc = dev_alloc(h, &h->in3, (size_t)(pre ? h->Snet : VNECT_MAX_SCALES) * BOX * BOX * 3))) return rc;
         if (!pre && (rc = dev_alloc(h, &h->gather, (size_t)VNECT_MAX_SCALES * HM * HM * MAPC))) return rc;
@@ -179,6 +186,7 @@ void vnect_destroy(vnect_handle* h)
         if (h->xopened[r] && h->xpeer[r]) hipIpcCloseMemHandle(h->xpeer[r]);
     if (h->h_xstatus) hipHostFree(h->h_xstatus);
     if (h->h_tout) hipHostFree(h->h_tout);
+    if (h->h_conf) hipHostFree(h->h_conf);
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
@@ -350,15 +358,16 @@ int vnect_postprocess(vnect_handle* h, const float* maps, double t2d, double t3d
         dyn.t2d = t2d, dyn.t3d = t3d;
         if ((rc = sync_geometry(h, fp))) return rc;
         if (h->post_merged) {
-            if ((rc = run_post(h, dyn, h->ring[0].out_dev))) return rc;
+            if ((rc = run_post(h, dyn, h->ring[0].out_dev, h->h_conf_dev))) return rc;
         } else {
             if ((rc = run_argmax(h))) return rc;
-            if ((rc = run_joints(h, dyn, h->ring[0].out_dev))) return rc;
+            if ((rc = run_joints(h, dyn, h->ring[0].out_dev, h->h_conf_dev))) return rc;
         }
         commit_time(h->streams[0], t2d, t3d);
         HIPCK(h, hipStreamSynchronize(h->st));
         memcpy(j2, h->ring[0].out->j2d, sizeof(double) * NJ * 2);
         memcpy(j3, h->ring[0].out->j3d, sizeof(float) * NJ * 3);
+        deliver_confidence(h, 0, false);
         return VNECT_OK;
     });
 }
@@ -733,6 +742,43 @@ int vnect_track_box(vnect_handle* h, int stream, int32_t* rect4)
         std::vector<TrackState> ts(1);
         HIPCK(h, hipMemcpy(&ts[0], h->d_track + stream, sizeof(TrackState), hipMemcpyDeviceToHost));
         rect4[0] = ts[0].x, rect4[1] = ts[0].y, rect4[2] = ts[0].uw, rect4[3] = ts[0].uh;
+        return VNECT_OK;
+    });
+}
+
+// ---- per-joint confidence and the loss rule of a tracked stream (ABI v7, additive; CONFIDENCE.md) ---------------------------------------
+int vnect_result_confidence(vnect_handle* h, double* confidence21, int32_t* lost_out)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !confidence21) return h ? fail(h, VNECT_E_ARG, "vnect_result_confidence: bad argument") : VNECT_E_ARG;
+        if (!h->have_conf) return fail(h, VNECT_E_STATE, "vnect_result_confidence: no frame has been delivered on this handle yet");
+        memcpy(confidence21, h->last_conf, sizeof h->last_conf);
+        if (lost_out) *lost_out = h->last_lost;
+        return VNECT_OK;
+    });
+}
+
+int vnect_track_policy(vnect_handle* h, int stream, double min_confidence, int min_joints, int action)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_policy: tracking on a pyramid-sharded handle is not supported");
+        if (h->stream_batch == 2 || !h->bplans.empty())
+            return fail(h, VNECT_E_ARG, "vnect_track_policy: tracking on a handle with the two-stream batch is not supported");
+        if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+        if (min_joints < 1 || min_joints > NJ) return fail(h, VNECT_E_ARG, "vnect_track_policy: min_joints must be 1 .. 21");
+        if (action < TRACK_LOST_OFF || action > TRACK_LOST_RESET) return fail(h, VNECT_E_ARG, "vnect_track_policy: action must be 0 (off), 1 (hold) or 2 (reset)");
+        if (min_confidence != min_confidence) return fail(h, VNECT_E_ARG, "vnect_track_policy: min_confidence is NaN");
+        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_track_policy before vnect_finalize");
+        Stream& sm = h->streams[stream];
+        // the box stage of a tracked frame in flight reads the rule whenever it runs: no change under it
+        if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+            return fail(h, VNECT_E_STATE, "vnect_track_policy: the stream has a tracked frame in flight: collect it first");
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        // (an untracked frame of the stream may still be in flight, and so may other streams' frames: none of them reads this rule)
+        const TrackPolicy p{min_confidence, min_joints, action};
+        HIPCK(h, hipMemcpy(h->d_policy + stream, &p, sizeof p, hipMemcpyHostToDevice));
+        sm.policy = p;
         return VNECT_OK;
     });
 }

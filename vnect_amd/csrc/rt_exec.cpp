@@ -93,19 +93,30 @@ int run_argmax(Plan* h)
 }
 
 // filters + read-off; results go straight to `out` (a device-mapped pinned host slot)
-int run_joints(Plan* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
+int run_joints(Plan* h, const FrameDyn& dyn, JointsOut* out, ConfOut* conf, int stream, const FrameParams* fp, double* conf_dev)
 {
     const vnect_handle* o = h->owner;
-    HIPCK(h, launch_joints(h->d_part, maps_of(h), o->mgeo, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st));
+    HIPCK(h, launch_joints(h->d_part, maps_of(h), o->mgeo, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st, conf, conf_dev));
     return VNECT_OK;
 }
 
 // both in one launch (post.hip: post_kernel): takes the frame's arguments by value, so it runs behind the graph, not inside it
-int run_post(Plan* h, const FrameDyn& dyn, JointsOut* out, int stream, const FrameParams* fp)
+int run_post(Plan* h, const FrameDyn& dyn, JointsOut* out, ConfOut* conf, int stream, const FrameParams* fp, double* conf_dev)
 {
     const vnect_handle* o = h->owner;
-    HIPCK(h, launch_post(maps_of(h), o->mgeo, h->d_part, h->d_ticket, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st));
+    HIPCK(h, launch_post(maps_of(h), o->mgeo, h->d_part, h->d_ticket, o->d_fb + stream, fp ? fp : h->d_fp, dyn, o->cfg.numpy_promotion, out, h->st, conf,
+                         conf_dev));
     return VNECT_OK;
+}
+
+// vnect_result_confidence's values are taken when a frame is DELIVERED, from that frame's own ring slot: with frames in flight they belong
+// to the collected frame, not to the newest one (whose joints stage may be writing another slot meanwhile)
+void deliver_confidence(vnect_handle* h, int ring, bool tracked)
+{
+    const ConfOut& c = h->h_conf[ring];
+    memcpy(h->last_conf, c.conf, sizeof h->last_conf);
+    h->last_lost = tracked ? c.lost : 0;
+    h->have_conf = true;
 }
 
 // gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the pinned frame when
@@ -348,11 +359,16 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     const bool box_tail = tk && L->post_merged && !getenv("VNECT_TRACK_BOX_LAUNCH");
     if (box_tail) {
         HIPCK(h, launch_post_track(maps_of(L), h->mgeo, L->d_part, L->d_ticket, h->d_fb + stream, h->d_track + stream, dyn, h->cfg.numpy_promotion,
-                                   e.out_dev, h->h_tout_dev + ring, L->st));
+                                   e.out_dev, h->h_tout_dev + ring, L->st, h->h_conf_dev + ring, h->d_policy + stream));
     } else {
+        // (a box kernel of its own takes the confidences from device memory, not from the ring slot: the joints stage leaves them in both)
         const FrameParams* tfp = tk ? &h->d_track[stream].fp : nullptr;
-        if ((rc = L->post_merged ? run_post(L, dyn, e.out_dev, stream, tfp) : run_joints(L, dyn, e.out_dev, stream, tfp))) return rc;
-        if (tk) HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st));
+        double* cdev = tk ? h->d_conf + (size_t)stream * NJ : nullptr;
+        if ((rc = L->post_merged ? run_post(L, dyn, e.out_dev, h->h_conf_dev + ring, stream, tfp, cdev)
+                                 : run_joints(L, dyn, e.out_dev, h->h_conf_dev + ring, stream, tfp, cdev)))
+            return rc;
+        if (tk)
+            HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st, cdev, h->d_policy + stream, h->h_conf_dev + ring));
     }
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
     HIPCK(h, hipEventRecord(e.done, L->st));
@@ -416,6 +432,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     }
     if (j2) memcpy(j2, e.out->j2d, sizeof(double) * NJ * 2);
     if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
+    deliver_confidence(h, ring, e.tracked);
     if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
     if (h->profiling && !e.batch) {
         float frame_ms = 0;
@@ -819,6 +836,7 @@ int prime(vnect_handle* h)
     h->slots[ps] = vnect_handle::SlotInfo();
     const int rf = reset_filters_impl(h);  // (sets h->err itself when it fails)
     for (Stream& sm : h->streams) sm = Stream{};  // (no crop buffer to lose yet: tracking begins on a finalized handle, and this runs inside vnect_finalize)
+    h->have_conf = false;  // (the grey frames' confidences are nobody's result: vnect_result_confidence starts at the caller's first delivery)
     for (Plan* l : h->lanes) l->fp_dev_valid = false;  // (the next frame uploads its own geometry)
     for (Plan* b : h->bplans) b->fp_dev_valid = b->fp_dev2_valid = false;
     const bool serious = rc == VNECT_E_HIP || rc == VNECT_E_INTERNAL || rc == VNECT_E_COMM;
@@ -885,7 +903,7 @@ int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots,
         // the filters are a chain within a stream: wait for its previous frame if that one ran on another lane and may be in flight
         if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L) HIPCK(h, hipStreamWaitEvent(b->st, h->ring[sm.seq % RING].done, 0));
         HIPCK(h, launch_post(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + streams[k], k ? b->d_fp2 : b->d_fp, dyn[k], h->cfg.numpy_promotion,
-                             e.out_dev, b->st));
+                             e.out_dev, b->st, h->h_conf_dev + (h->seq_submit + k) % RING));
         HIPCK(h, hipEventRecord(e.done, b->st));
     }
     for (int k = 0; k < 2; k++) {  // every launch of the batch has been accepted: commit

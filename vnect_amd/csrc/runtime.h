@@ -155,6 +155,7 @@ struct Stream {
     unsigned track_seq = 0;
     uint8_t* track_buf = nullptr;  // the stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
     size_t track_cap = 0;          // waits for this frame's box kernel, which runs after everything that reads the crop)
+    TrackPolicy policy{0.0, 1, TRACK_LOST_OFF};  // the host's copy of d_policy[stream] (vnect_track_policy; survives vnect_track_begin)
 };
 
 }  // namespace rt
@@ -205,6 +206,15 @@ struct vnect_handle : Plan {
     TrackState* d_track = nullptr;  // [VNECT_MAX_STREAMS]: per stream the next crop and its geometry on the device
     TrackOut* h_tout = nullptr;     // pinned, device-mapped, [RING]: rect_used + status of every tracked frame in flight
     TrackOut* h_tout_dev = nullptr;
+    // per-joint confidence (CONFIDENCE.md): every frame's joints stage writes its ring slot's ConfOut beside its JointsOut
+    ConfOut* h_conf = nullptr;      // pinned, device-mapped, [RING]
+    ConfOut* h_conf_dev = nullptr;
+    double* d_conf = nullptr;       // [VNECT_MAX_STREAMS][NJ], device: a tracked frame's confidences for a box kernel launched behind its
+                                    // joints stage (VNECT_TRACK_BOX_LAUNCH=1, VNECT_NO_POST_MERGE=1); a stream's frames run one behind the other
+    TrackPolicy* d_policy = nullptr;  // [VNECT_MAX_STREAMS]: the streams' loss rules as the box stage reads them
+    double last_conf[NJ] = {};      // vnect_result_confidence: the frame most recently delivered, copied out of its own ring slot then
+    int last_lost = 0;
+    bool have_conf = false;
 #if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
     // test build only (make testhooks; tests/test_gpu_track_maps.py): vnect_test_maps_override's maps on the device, RING + 1 buffers taken in
     // turn (a frame in flight keeps reading the one it was enqueued with), and the stream the uploads run on
@@ -329,8 +339,10 @@ int run_network(Plan* p, bool timed, bool stem_done = false);
 int sync_geometry(Plan* p, const FrameParams& fp, int which = 0);  // which 1: a batch's second stream (d_fp2)
 int run_pre(Plan* p, const FrameDyn& dyn, bool timed = false, bool want_batch = false);
 int run_argmax(Plan* p);
-int run_joints(Plan* p, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);  // fp: d_fp
-int run_post(Plan* p, const FrameDyn& dyn, JointsOut* out, int stream = 0, const FrameParams* fp = nullptr);
+// conf: the frame's ConfOut (device address of its ring slot's); conf_dev: nullptr, or where a box kernel behind this reads the confidences
+int run_joints(Plan* p, const FrameDyn& dyn, JointsOut* out, ConfOut* conf, int stream = 0, const FrameParams* fp = nullptr, double* conf_dev = nullptr);  // fp: d_fp
+int run_post(Plan* p, const FrameDyn& dyn, JointsOut* out, ConfOut* conf, int stream = 0, const FrameParams* fp = nullptr, double* conf_dev = nullptr);
+void deliver_confidence(vnect_handle* h, int ring, bool tracked);  // a frame has been delivered from ring slot `ring`: vnect_result_confidence's values
 int check_time(vnect_handle* h, const Stream& s, double t2d, double t3d);
 void commit_time(Stream& s, double t2d, double t3d);
 int reset_filters_impl(vnect_handle* h, int stream = -1);  // -1: every stream

@@ -45,11 +45,18 @@ hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, 
 // thread per table entry.  A frame whose own crop was refused (its joints stage skipped, post_kernel's xfail test) keeps the stream
 // stopped: the next frame is refused too, until vnect_track_begin.
 constexpr int BOX_THREADS = 384;
-__global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __restrict__ ts, JointsOut* out, TrackOut* tout, unsigned xseq)
+// The loss rule (trackbox.h) takes the frame's confidences from DEVICE memory (conf_dev: the joints stage in front of this launch left
+// them there as well as in the ring slot), requested up front with the state and the policy.
+__global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __restrict__ ts, JointsOut* out, TrackOut* tout, unsigned xseq,
+                                                                const double* __restrict__ conf_dev, const TrackPolicy* __restrict__ polp,
+                                                                ConfOut* cf)
 {
     __shared__ double j2[NJ * 2];
+    __shared__ double cl[NJ];
     const int t = threadIdx.x;
     const TrackNow c = track_now(ts);
+    const TrackPolicy pol = track_policy_now(polp);
+    if (conf_dev && t < NJ) cl[t] = conf_dev[t];
     __syncthreads();  // (every thread has read the state before thread 0 overwrites it)
     if (c.status != SQ_OK) {
         track_refused(ts, c, tout, xseq);
@@ -61,12 +68,14 @@ __global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __re
         j2[t] = v;
     }
     __syncthreads();
-    track_box_stage(ts, c, j2, tout, xseq);
+    track_box_stage(ts, c, j2, tout, xseq, conf_dev ? cl : nullptr, pol, cf);
 }
 
-hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st)
+hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st, const double* conf_dev,
+                            const TrackPolicy* pol, ConfOut* conf)
 {
-    hipLaunchKernelGGL(track_box_kernel, dim3(1), dim3(BOX_THREADS), 0, st, ts, out, tout, xseq);
+    if (!conf_dev != !pol || (conf && !conf_dev)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(track_box_kernel, dim3(1), dim3(BOX_THREADS), 0, st, ts, out, tout, xseq, conf_dev, pol, conf);
     return hipGetLastError();
 }
 

@@ -143,6 +143,73 @@ int tp_box(int n, const uint8_t* states, const double* joints, const uint32_t* x
     return 0;
 }
 
+// The box stage with a loss rule (launch_track_box's policy form; CONFIDENCE.md; tests/test_gpu_conf_track_kernels.py) over n cases: tp_box's arrays plus conf (n x 21 doubles,
+// any value: NaN and infinities are confidences like any other) and the rule of every case -- min_conf (n), min_joints (n, 1 .. 21),
+// action (n, 0 .. 2).  The confidences and the rule lie in device memory, as the runtime's do.  ConfOut and ts->fp of every case hold the
+// garbage byte before its launch.  Out: tp_box's three arrays and verdict (n x 2 ints: lost, confident).
+int tp_box_policy(int n, const uint8_t* states, const double* joints, const uint32_t* xseq, const double* conf, const double* min_conf,
+                  const int32_t* min_joints, const int32_t* action, uint8_t* states_out, int32_t* tout, double* joints_out, int32_t* verdict,
+                  int32_t* err)
+{
+    struct PolicyCase {
+        double conf[NJ];
+        TrackPolicy pol;
+        ConfOut co;
+    };
+    if (n < 1) return 0;
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        TrackState s;
+        memcpy(&s, states + (size_t)i * sizeof(TrackState), sizeof s);
+        err[i] = TP_OK;
+        if (s.status < SQ_OK || s.status > SQ_LONG) err[i] = TP_E_STATE;
+        if (min_joints[i] < 1 || min_joints[i] > NJ || action[i] < TRACK_LOST_OFF || action[i] > TRACK_LOST_RESET || min_conf[i] != min_conf[i]) err[i] = TP_E_STATE;
+        for (int k = 0; k < NJ * 2; k++) {
+            const double v = joints[(size_t)i * NJ * 2 + k];
+            if (!(fabs(v) < 1e9)) err[i] = TP_E_JOINTS;
+        }
+        bad += err[i] != TP_OK;
+    }
+    if (bad) return bad;
+    Dev D;
+    TP_HIP(hipStreamCreate(&D.st));
+    const int CH = 4096;
+    const int m_max = n < CH ? n : CH;
+    std::vector<BoxCase> hb(m_max);
+    std::vector<PolicyCase> hp(m_max);
+    BoxCase* db = nullptr;
+    PolicyCase* dp = nullptr;
+    TP_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
+    TP_HIP(D.alloc((void**)&dp, hp.size() * sizeof(PolicyCase)));
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int m = n - c0 < CH ? n - c0 : CH;
+        memset(hb.data(), 0, (size_t)m * sizeof(BoxCase));
+        for (int i = 0; i < m; i++) {
+            memcpy(&hb[i].ts, states + (size_t)(c0 + i) * sizeof(TrackState), sizeof(TrackState));
+            memset(&hb[i].ts.fp, GARBAGE, sizeof(FrameParams));
+            memcpy(hb[i].jo.j2d, joints + (size_t)(c0 + i) * NJ * 2, sizeof hb[i].jo.j2d);
+            memset(&hb[i].to, GARBAGE, sizeof(TrackOut));
+            memcpy(hp[i].conf, conf + (size_t)(c0 + i) * NJ, sizeof hp[i].conf);
+            hp[i].pol = TrackPolicy{min_conf[c0 + i], min_joints[c0 + i], action[c0 + i]};
+            memset(&hp[i].co, GARBAGE, sizeof(ConfOut));
+        }
+        TP_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
+        TP_HIP(hipMemcpyAsync(dp, hp.data(), (size_t)m * sizeof(PolicyCase), hipMemcpyHostToDevice, D.st));
+        for (int i = 0; i < m; i++)
+            TP_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st, dp[i].conf, &dp[i].pol, &dp[i].co));
+        TP_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
+        TP_HIP(hipMemcpyAsync(hp.data(), dp, (size_t)m * sizeof(PolicyCase), hipMemcpyDeviceToHost, D.st));
+        TP_HIP(hipStreamSynchronize(D.st));
+        for (int i = 0; i < m; i++) {
+            memcpy(states_out + (size_t)(c0 + i) * sizeof(TrackState), &hb[i].ts, sizeof(TrackState));
+            memcpy(tout + (size_t)(c0 + i) * 6, &hb[i].to, sizeof(TrackOut));
+            memcpy(joints_out + (size_t)(c0 + i) * NJ * 2, hb[i].jo.j2d, sizeof hb[i].jo.j2d);
+            verdict[(size_t)(c0 + i) * 2] = hp[i].co.lost, verdict[(size_t)(c0 + i) * 2 + 1] = hp[i].co.confident;
+        }
+    }
+    return 0;
+}
+
 // The crop copy (launch_frame_copy_track) of n states' crops out of ONE pinned (H, W, 3) frame whose rows are `stride` bytes apart
 // (frame: (H - 1) * stride + 3 W bytes).  The pinned buffer's capacity is that size rounded up to 4, and its end is the kernel's
 // src_end.  Every case has its own destination of dst_cap bytes, pre-filled, with a pre-filled guard on both sides: dst_out gets

@@ -22,19 +22,40 @@ __device__ __forceinline__ void track_refused(TrackState* ts, const TrackNow& c,
         ts->fail = xseq + 1;
     }
 }
+// the stream's loss rule as a frame's box stage reads it, with the state, before anything else (pol == nullptr: off)
+__device__ __forceinline__ TrackPolicy track_policy_now(const TrackPolicy* pol)
+{
+    return pol ? *pol : TrackPolicy{0.0, 1, TRACK_LOST_OFF};
+}
 // j2: the frame's 21 x 2 joints in FRAME coordinates, in LDS (every thread's write of them behind a barrier).  Every thread calls this.
-__device__ __forceinline__ void track_box_stage(TrackState* ts, const TrackNow& c, const double* j2, TrackOut* tout, unsigned xseq)
+// The loss rule (CONFIDENCE.md): conf -- the frame's NJ confidences, in LDS like j2, or nullptr (no rule) --, pol the stream's policy;
+// cf (or nullptr) gets the verdict.  confident = #{j : conf[j] >= min_confidence} (a NaN or -inf confidence never counts),
+// lost = action != OFF && confident < min_joints.  HOLD: the state stays as it is, every byte -- the next frame is cropped with this
+// frame's crop (x, y, w, h, uw, uh and the geometry; fail is 0, since this frame ran).  RESET: the box rule's result is replaced by an
+// empty rect, which box_fallback turns into the whole frame; everything behind it (crop_head / crop_entry, a refusal) is the usual path.
+__device__ __forceinline__ void track_box_stage(TrackState* ts, const TrackNow& c, const double* j2, TrackOut* tout, unsigned xseq,
+                                                const double* conf = nullptr, const TrackPolicy pol = TrackPolicy{0.0, 1, TRACK_LOST_OFF},
+                                                ConfOut* cf = nullptr)
 {
     __shared__ int rect[4];
+    __shared__ int lost_action;
     const int t = threadIdx.x;
+    // (threads 0 .. NJ - 1 are in thread 0's wave: its ballot holds all 21 verdicts)
+    const unsigned long long sure = conf ? __ballot(t < NJ && conf[t] >= pol.min_confidence) : 0ull;
     if (t == 0) {
+        const int confident = __popcll(sure);
+        const int lost = conf && pol.action != TRACK_LOST_OFF && confident < pol.min_joints;
+        if (cf) cf->lost = lost, cf->confident = confident;
+        lost_action = lost ? pol.action : TRACK_LOST_OFF;
         int r[4];
         box_update(j2, c.W, c.H, r);
+        if (lost && pol.action == TRACK_LOST_RESET) r[0] = 0, r[1] = 0, r[2] = 0, r[3] = 0;
         box_fallback(c.W, c.H, r);
         rect[0] = r[0], rect[1] = r[1], rect[2] = r[2], rect[3] = r[3];
         tout->rect[0] = c.x, tout->rect[1] = c.y, tout->rect[2] = c.uw, tout->rect[3] = c.uh, tout->status = SQ_OK;
     }
     __syncthreads();
+    if (lost_action == TRACK_LOST_HOLD) return;  // (uniform)
     const int cw = rect[2], ch = rect[3];
     SqHead g = {};
     const int status = crop_head(ch, cw, &g);

@@ -123,12 +123,14 @@ class VNectEstimator:
             raise ValueError("alpha should be in (0.0, 1.0]: timestamp earlier than the previous one") from e
         raise e
 
-    def postprocess(self, maps, timestamp=None, scaler=1.0, offset_x=0, offset_y=0):
+    def postprocess(self, maps, timestamp=None, scaler=1.0, offset_x=0, offset_y=0, return_confidence=False):
+        """``return_confidence=True`` (additive; CONFIDENCE.md): a third value, the (21,) float64 per-joint confidences."""
         t2d, t3d = self._stamps(timestamp)
         try:
-            return self._h.postprocess(maps, t2d, t3d, scaler, offset_x, offset_y)
+            res = self._h.postprocess(maps, t2d, t3d, scaler, offset_x, offset_y)
         except _native.VnectError as e:
             self._raise_like_reference(e)
+        return res + (self._h.result_confidence()[0],) if return_confidence else res
 
     def forward(self, batch):
         """sess.run equivalent (src/estimator.py:100-104): (S,368,368,3) -> (S,46,46,84)."""
@@ -156,7 +158,7 @@ class VNectEstimator:
             raise ValueError("rect= is for pixel_format='nv12' (a BGR caller slices the frame)")
         return pixel_format == "nv12"
 
-    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None):
+    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None, return_confidence=False):
         """``pixel_format="nv12"`` (additive): ``img_input`` is a 2-D uint8 array of ``H * 3 // 2`` rows -- H rows of Y, the interleaved
         U, V plane from row H on; row-strided views are fine -- converted to BGR on the device (NV12.md).  ``rect=(x, y, w, h)``: only
         that crop, as ``frame[y:y + h, x:x + w]`` of the converted frame; the joints are in crop coordinates.
@@ -164,7 +166,10 @@ class VNectEstimator:
         A frame already in DEVICE memory (additive; DEVICE_FRAMES.md): any object with ``__cuda_array_interface__`` -- a uint8 (H, W, 3)
         torch tensor on the GPU with any positive strides (packed, ``chw.permute(1, 2, 0)``, ``bgra[..., :3]``, any slice), read where it
         lies; ``pixel_format="rgb"`` for RGB order, ``"nv12"`` for an (H * 3 // 2, W) array or a ``(y, uv)`` pair.  ``stream=``: the
-        integer handle of the stream that wrote it (default: torch's current stream if torch is imported, else the default stream)."""
+        integer handle of the stream that wrote it (default: torch's current stream if torch is imported, else the default stream).
+
+        ``return_confidence=True`` (additive; CONFIDENCE.md): a third value, a fresh (21,) float64 array -- per joint the height of its
+        heat-map's peak, the value of the element ``np.argmax`` picks in ``src/utils.py:169-172``."""
         t0 = time.time()
         t2d, t3d = self._stamps(timestamp)
         device = _native.is_device_array(img_input)
@@ -178,6 +183,8 @@ class VNectEstimator:
             self._raise_like_reference(e)
         if self.verbose:
             print('FPS: {:>2.2f}'.format(1 / max(time.time() - t0, 1e-9)))
+        if return_confidence:
+            return joints_2d, joints_3d, self._h.result_confidence()[0]
         return joints_2d, joints_3d
 
     # -- pipelined use (additive; the reference's loop is strictly one frame at a time) --------------------------------
@@ -202,9 +209,10 @@ class VNectEstimator:
             self._raise_like_reference(e)
         self._submitted += 1
 
-    def collect(self):
-        """(joints_2d, joints_3d) of the oldest frame in flight."""
-        return self._h.collect()
+    def collect(self, return_confidence=False):
+        """(joints_2d, joints_3d) of the oldest frame in flight; ``return_confidence=True``: and that frame's (21,) confidences."""
+        res = self._h.collect()
+        return res + (self._h.result_confidence()[0],) if return_confidence else res
 
     def frame_buffer(self, height, width, index=0, pixel_format="bgr"):
         """Additive: a (height, width, 3) uint8 array in PINNED host memory (two exist, ``index`` 0 / 1).  Capture into it

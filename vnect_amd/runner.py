@@ -49,18 +49,46 @@ def bbox_update(joints_2d, W_img, H_img):
     return [x, y, w, h]
 
 
-def init_box(estimator, frame, timestamp=None):
+def lost_rule(lost):
+    """``lost=(min_confidence, min_joints, "hold" | "reset")`` of the tracking loops as (threshold, count, action) -- or None.  The rule
+    (CONFIDENCE.md): a frame is lost when fewer than ``min_joints`` of its 21 confidences are >= ``min_confidence``."""
+    if lost is None:
+        return None
+    min_confidence, min_joints, action = lost
+    min_confidence, min_joints = float(min_confidence), int(min_joints)
+    if action not in ("hold", "reset"):
+        raise ValueError("lost=(min_confidence, min_joints, action): action must be 'hold' or 'reset'")
+    if not 1 <= min_joints <= 21:
+        raise ValueError("lost=(min_confidence, min_joints, action): min_joints must be 1 .. 21")
+    if min_confidence != min_confidence:
+        raise ValueError("lost=(min_confidence, min_joints, action): min_confidence is NaN")
+    return min_confidence, min_joints, action
+
+
+def is_lost(confidence, min_confidence, min_joints):
+    """The loss rule on the host: fewer than min_joints confidences reach min_confidence (NaN and -inf never do)."""
+    return int(np.count_nonzero(np.asarray(confidence) >= min_confidence)) < min_joints
+
+
+def init_box(estimator, frame, timestamp=None, min_confidence=None, min_joints=1):
     """Person-box initialiser without cv2's HOG detector (SURVEY 8 f-row 3; the reference: src/hog_box.py:25-58).
 
     The reference asks a HOG people detector for a rectangle and falls back to the whole frame when it finds nobody
     (hog_box.py:28-29).  Here the network itself proposes the box: one pass over the whole frame (that fallback
     rectangle), then the tracking loop's own box arithmetic on the joints it found (run_estimator_ps.py:96-107).  The
     pass is a probe: the estimator's filters are reset afterwards, so the first tracked frame is still an unfiltered one
-    as in the reference.  Returns (x, y, w, h).
+    as in the reference.  Returns (x, y, w, h).  ``min_confidence`` (additive; CONFIDENCE.md): when the probe pass is "lost" -- fewer
+    than ``min_joints`` confidences reach it: nobody is there to box -- the whole frame.
     """
     H_img, W_img = frame.shape[:2]
-    joints_2d, _ = estimator(frame, timestamp=timestamp)
-    estimator.reset()
+    if min_confidence is None:
+        joints_2d, _ = estimator(frame, timestamp=timestamp)
+        estimator.reset()
+    else:
+        joints_2d, _, conf = estimator(frame, timestamp=timestamp, return_confidence=True)
+        estimator.reset()
+        if is_lost(conf, *lost_rule((min_confidence, min_joints, "reset"))[:2]):
+            return [0, 0, W_img, H_img]
     x, y, w, h = bbox_update(joints_2d, W_img, H_img)
     if w < 1 or h < 1:
         return [0, 0, W_img, H_img]
@@ -81,8 +109,12 @@ def _nv12_checks(pixel_format, transpose, source=None):
     return pixel_format == "nv12"
 
 
-def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_format="bgr"):
+def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_format="bgr", confidence=False, lost=None):
     """run_estimator_ps.py:80-109 without capture / drawing.  Yields (joints_2d, joints_3d, rect_used).
+
+    Additive (CONFIDENCE.md): ``lost=(min_confidence, min_joints, "hold" | "reset")`` -- behind the box update, a frame with fewer than
+    min_joints confidences >= min_confidence keeps its own crop for the next frame (hold) or hands it the whole frame (reset);
+    ``confidence=True`` yields (joints_2d, joints_3d, rect_used, confidence (21,) float64, lost flag).
 
     frames: iterable of uint8 BGR arrays of one size; rect: initial (x, y, w, h), default the full frame;
     transpose: the reference's `T` option (np.rot90(frame, 3)); timestamps: optional iterable for reproducible
@@ -91,6 +123,8 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
     """
     ts = iter(timestamps) if timestamps is not None else None
     nv12 = _nv12_checks(pixel_format, transpose)
+    rule = lost_rule(lost)
+    want_conf = confidence or rule is not None
     for frame in frames:
         if transpose:
             frame = np.rot90(frame, 3)
@@ -103,18 +137,27 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
         if w < 1 or h < 1:  # a degenerate box (all joints on one pixel): fall back to the whole frame
             x, y, w, h = rect = [0, 0, W_img, H_img]
         t = next(ts) if ts is not None else None
+        kw = {"return_confidence": True} if want_conf else {}
         if nv12:                                   # the device converts and crops: the rect goes along instead of a slice
-            joints_2d, joints_3d = estimator(frame, timestamp=t, pixel_format="nv12", rect=[x, y, w, h])
+            res = estimator(frame, timestamp=t, pixel_format="nv12", rect=[x, y, w, h], **kw)
         else:
-            joints_2d, joints_3d = estimator(frame[y:y + h, x:x + w, :], timestamp=t)
+            res = estimator(frame[y:y + h, x:x + w, :], timestamp=t, **kw)
+        joints_2d, joints_3d = res[:2]
         joints_2d[:, 0] += y
         joints_2d[:, 1] += x
         used = [x, y, w, h]
         rect = bbox_update(joints_2d, W_img, H_img)
-        yield joints_2d, joints_3d, used
+        gone = rule is not None and is_lost(res[2], rule[0], rule[1])
+        if gone:                                   # the loss rule: this frame's crop again, or the whole frame
+            rect = list(used) if rule[2] == "hold" else [0, 0, W_img, H_img]
+        if confidence:
+            yield joints_2d, joints_3d, used, res[2], int(gone)
+        else:
+            yield joints_2d, joints_3d, used
 
 
-def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr"):
+def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
+                    confidence=False, lost=None):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -124,23 +167,28 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     ``__cuda_array_interface__``; ``pixel_format`` may then be "rgb" as well), read where they lie when the frame runs and held until it
     is collected (no ``transpose``).  ``stream``: which of the handle's video streams (its filter bank).
     ``rect`` must start inside the frame (``track`` would slice from outside it); one that runs past the far edges is cropped as
-    ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight."""
-    for _, j2, j3, used in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
-                                                None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format):
-        yield j2, j3, used
+    ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight.
+    ``confidence`` / ``lost``: as in ``track``; the rule runs on the device (vnect_track_policy)."""
+    for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
+                                    None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost):
+        yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr"):
+                         pixel_format="bgr", confidence=False, lost=None):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
     ``pixel_format="nv12"``: every frame is an (H * 3 // 2, W) NV12 array; the device converts the crop's rows as it reads them out of
-    the pinned buffer (or, ``source="resident"``, the whole frame on upload)."""
+    the pinned buffer (or, ``source="resident"``, the whole frame on upload).
+    ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
+    afterwards); ``confidence=True`` appends
+    (confidence, lost flag) to every tuple."""
     from collections import deque
 
     from . import _native
     nv12 = _nv12_checks(pixel_format, transpose, source)
+    rule = lost_rule(lost)
     if source not in ("pinned", "resident", "device"):
         raise ValueError("source must be 'pinned', 'resident' or 'device'")
     device = source == "device"
@@ -173,6 +221,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             pending[i] = prep(f)
             H, W = size_of(pending[i])
             h.track_begin(streams[i], H, W, rects[i])
+            if rule is not None:
+                h.track_policy(streams[i], *rule)
     flat = []
     if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
         nbytes = max([p.size for p in pending if p is not None] + [3])
@@ -191,6 +241,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             estimator._raise_like_reference(e)
         finally:
             held.pop(k, None)
+        if confidence:                          # (of the frame just delivered: taken from its own result slot)
+            return (video_of[s], j2, j3, used) + h.result_confidence()
         return video_of[s], j2, j3, used
 
     # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
@@ -251,6 +303,13 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             except _native.VnectError:
                 pass
         held.clear()
+        if rule is not None:                    # nothing is in flight any more: the streams' rule is off again
+            for i in range(n):
+                if pending[i] is not None:
+                    try:
+                        h.track_policy(streams[i], 0.0, 1, "off")
+                    except _native.VnectError:
+                        pass
 
 
 def synthetic_stream(stream, n_frames, height=368, width=368, smooth=True):
