@@ -38,6 +38,10 @@ def cpu_lib():
         L.ingest_walk.argtypes = [u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p, i64p]
         L.ingest_walk.restype = C.c_int64
+        L.ingest_store_walk.argtypes = [C.c_int, C.c_int, u8p, u8p]
+        L.ingest_store_walk.restype = C.c_int64
+        L.ingest_store_byte.argtypes = [C.c_int64]
+        L.ingest_store_byte.restype = C.c_uint8
         _CPU = L
     return _CPU
 

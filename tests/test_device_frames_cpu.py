@@ -128,6 +128,28 @@ def test_a_wrong_mask_or_permute_would_be_noticed():
     assert np.argwhere(a != b).tolist() == [[1, 7, 2]]
 
 
+def test_store_rule_at_the_row_starts_of_the_nv12_copies():
+    """The store rule driven alone, as nv12_strip drives it: the row's first group starts 0, 3, 6 or 9 bytes in front of the row (NV12 counts
+    its groups in frame columns: 3 (x & 3)), every destination phase 0..3, widths 1 .. two waves' span + 1.  The groups' bytes are synthetic,
+    a function of the byte's row index: every byte of the row is written exactly once with its value, and nothing outside the row."""
+    L = dr.cpu_lib()
+    _, wave, _, _ = dr.kernel_spans()
+    value = np.array([L.ingest_store_byte(t) for t in range(3 * (2 * wave + 1))], np.uint8)
+    assert len(set(value[:12].tolist())) == 12 and value[0] == (12 * 37) % 251     # (neighbouring bytes differ: a shifted store shows)
+    for w in range(1, 2 * wave + 2):
+        n = 3 * w
+        for lead in (0, 3, 6, 9):
+            for phase in range(4):
+                dst = _aligned(phase + n + 64, 0)
+                dst[...] = 0xC7
+                hits = np.zeros(n, np.uint8)
+                assert L.ingest_store_walk(w, lead, _p(dst[phase:]), _p(hits)) == 0, (w, lead, phase)
+                assert np.array_equal(dst[phase:phase + n], value[:n]), (w, lead, phase, np.nonzero(dst[phase:phase + n] != value[:n])[0][:8])
+                assert np.all(hits == 1), (w, lead, phase, np.nonzero(hits != 1)[0][:8])
+                assert np.all(dst[:phase] == 0xC7) and np.all(dst[phase + n:] == 0xC7), (w, lead, phase)
+    assert L.ingest_store_walk(4, 2, _p(dst), None) == -1 and L.ingest_store_walk(4, 12, _p(dst), None) == -1
+
+
 def test_sanitizer_sweep_is_a_standalone_program():
     """-fsanitize=address,undefined build of the same walk behind its own main, the sources in exactly sized heap blocks (a load outside
     the allocation is the sanitizer's finding).  Built (sanitizer runtimes linked statically) and run here, on the CPU, in the environment

@@ -189,6 +189,11 @@ def _ptr(a, t):
     return a.ctypes.data_as(t)
 
 
+def _rect4(rect):
+    """rect (x, y, w, h) or None -> the const int32_t* argument (ctypes keeps the array alive for the call)"""
+    return None if rect is None else _ptr(np.asarray([int(v) for v in rect], np.int32), _i32p)
+
+
 class Handle:
     """Thin RAII wrapper over vnect_handle; every method maps 1:1 to a C entry point."""
 
@@ -264,15 +269,17 @@ class Handle:
         self._ck(lib().vnect_forward(self._h, _ptr(batch, _f32p), n, _ptr(out, _f32p)))
         return out
 
+    def _preprocessed(self, ck, fn, *args, want_batch=True):
+        """fn(handle, *args, batch_out, scaler, offset_x, offset_y), checked by ck -> (batch or None, scaler, [offset_x, offset_y])"""
+        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
+        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
+        ck(fn(self._h, *args, _ptr(batch, _f32p) if want_batch else None, C.byref(scaler), C.byref(ox), C.byref(oy)))
+        return batch, scaler.value, [ox.value, oy.value]
+
     def preprocess(self, img, want_batch=True):
         img = _as_frame(img)
         H, W = img.shape[:2]
-        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
-        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
-        self._ck(lib().vnect_preprocess(self._h, _ptr(img, _u8p), H, W, img.strides[0],
-                                        _ptr(batch, _f32p) if want_batch else None, C.byref(scaler), C.byref(ox),
-                                        C.byref(oy)))
-        return batch, scaler.value, [ox.value, oy.value]
+        return self._preprocessed(self._ck, lib().vnect_preprocess, _ptr(img, _u8p), H, W, img.strides[0], want_batch=want_batch)
 
     def postprocess(self, maps, t2d, t3d, scaler=1.0, offset_x=0, offset_y=0):
         maps = np.ascontiguousarray(maps, dtype=np.float32)
@@ -367,8 +374,7 @@ class Handle:
     # -- tracking on the device (vnect_track_begin ...): runner.track's crop box kept on the GPU -------------------------------------
     def track_begin(self, stream, H, W, rect=None):
         """Stream `stream` tracks (H, W) frames from now on, starting at rect (x, y, w, h); None: the whole frame."""
-        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
-        self._ck(lib().vnect_track_begin(self._h, stream, int(H), int(W), None if r is None else _ptr(r, _i32p)))
+        self._ck(lib().vnect_track_begin(self._h, stream, int(H), int(W), _rect4(rect)))
 
     def submit_tracked(self, stream, slot, t2d, t3d):
         """The stream's next frame, the whole frame in resident slot `slot`; the device crops it with the stream's box."""
@@ -420,25 +426,17 @@ class Handle:
         if rect is None:
             self._ck(lib().vnect_upload_frame_nv12(self._h, slot, y, ys, uv, uvs, H, W))
         else:
-            r = np.asarray([int(v) for v in rect], np.int32)
-            self._ck(lib().vnect_upload_frame_nv12_rect(self._h, slot, y, ys, uv, uvs, H, W, _ptr(r, _i32p)))
+            self._ck(lib().vnect_upload_frame_nv12_rect(self._h, slot, y, ys, uv, uvs, H, W, _rect4(rect)))
 
     def infer_nv12(self, nv12, t2d, t3d, rect=None):
         y, ys, uv, uvs, H, W = _as_nv12(nv12)
-        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
         j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
-        self._ck(lib().vnect_infer_nv12(self._h, y, ys, uv, uvs, H, W, None if r is None else _ptr(r, _i32p), t2d, t3d,
-                                        _ptr(j2, _f64p), _ptr(j3, _f32p)))
+        self._ck(lib().vnect_infer_nv12(self._h, y, ys, uv, uvs, H, W, _rect4(rect), t2d, t3d, _ptr(j2, _f64p), _ptr(j3, _f32p)))
         return j2, j3
 
     def preprocess_nv12(self, nv12, rect=None, want_batch=True):
         y, ys, uv, uvs, H, W = _as_nv12(nv12)
-        r = None if rect is None else np.asarray([int(v) for v in rect], np.int32)
-        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
-        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
-        self._ck(lib().vnect_preprocess_nv12(self._h, y, ys, uv, uvs, H, W, None if r is None else _ptr(r, _i32p),
-                                             _ptr(batch, _f32p) if want_batch else None, C.byref(scaler), C.byref(ox), C.byref(oy)))
-        return batch, scaler.value, [ox.value, oy.value]
+        return self._preprocessed(self._ck, lib().vnect_preprocess_nv12, y, ys, uv, uvs, H, W, _rect4(rect), want_batch=want_batch)
 
     def submit_tracked_pinned_nv12(self, stream, index, y_stride, uv_offset, uv_stride, t2d, t3d):
         """The stream's next frame, the whole NV12 frame in pinned buffer `index` (Y plane at its start, UV plane `uv_offset` bytes in)."""
@@ -460,11 +458,7 @@ class Handle:
         return j2, j3
 
     def preprocess_device(self, frame, stream=None, want_batch=True):
-        batch = np.empty((self.net_images, 368, 368, 3), np.float32) if want_batch else None
-        scaler, ox, oy = C.c_double(), C.c_int32(), C.c_int32()
-        self._ck_device(lib().vnect_preprocess_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(batch, _f32p) if want_batch else None,
-                                                      C.byref(scaler), C.byref(ox), C.byref(oy)))
-        return batch, scaler.value, [ox.value, oy.value]
+        return self._preprocessed(self._ck_device, lib().vnect_preprocess_device, C.byref(frame), _stream_arg(stream), want_batch=want_batch)
 
     def submit_tracked_device(self, stream, frame, t2d, t3d, producer=None):
         """The stream's next frame, the whole frame in device memory (`frame`: a DeviceFrame without a rect).  The buffer is read when the

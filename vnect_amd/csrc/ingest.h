@@ -96,28 +96,29 @@ VNECT_HD void ingest_pack(int form, int order, const uint32_t* v, uint32_t* P)
     P[2] = b[8] | b[9] << 8 | b[10] << 16 | b[11] << 24;
 }
 
-// The DESTINATION.  A group's 12 bytes land at byte t0 = 12 G of a packed row of `row` = 3 w bytes that starts at any alignment; e = the
-// alignment of the group's first byte (the same for every group of a row).  The lane's WINDOW is the four aligned dwords from 4 bytes *
-// floor: dword k holds bytes of the lane's dwords k - 1 and k (ingest_window_dword; k = 0: the previous lane's last dword, `prev`).
-// Bit j of the mask: the lane writes byte j of its window.  The rules are those of copy_row_any_align and nv12_store_row:
+// The DESTINATION.  A group's 12 bytes land at byte t0 of a packed row of `row` = 3 w bytes that starts at any alignment: t0 = 12 G where
+// groups are counted from the crop's first column (the device-frame copies), 12 G - 3 x where they are counted in frame columns (the NV12
+// copies: the row's first group starts 0, 3, 6 or 9 bytes in front of the row).  e = the alignment of the group's first byte (the same for
+// every group of a row).  The lane's WINDOW is the four aligned dwords from 4 bytes * floor: dword k holds bytes of the lane's dwords
+// k - 1 and k (ingest_window_dword; k = 0: the previous lane's last dword, `prev`).
+// Bit j of the mask: the lane writes byte j of its window.  The rules are those of copy_row_any_align:
 //   bytes in front of the group's own (j < e) are the previous lane's, written here when the lane holds them (`head`: e == 0, or not lane 0
 //   of its wave); the window's last dword, the lane's last e bytes, is written only when no lane behind this one in the wave writes it as
 //   ITS dword 0 (`tail`: the wave's last lane or the row's last group); nothing outside [0, row) is written.  A dword whose four bits are set is one
 //   whole store; the first and last dword of a row and the dword two waves share come out as byte stores.
 VNECT_HD unsigned ingest_dst_mask(long long t0, int e, long long row, bool head, bool tail)
 {
-    unsigned m = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int j = 0; j < 16; j++) {
-        const int sbyte = j - e;                    // byte of the group (negative: the previous group's)
-        const long long t = t0 + sbyte;
-        if (sbyte >= 12 || t < 0 || t >= row) continue;
-        if (j < 12 ? (sbyte >= 0 || head) : tail) m |= 1u << j;
-    }
-    return m;
+    // Window byte j is byte j - e of the group (negative: the previous group's), row byte t0 + j - e.  Each rule bounds j from one side,
+    // so the lane's bytes are ONE run [lo, hi): from the previous group's bytes (head) or its own first, up to its dword 2's end or (tail)
+    // its own last byte, cut to the row
+    long long lo = head ? 0 : e, hi = tail ? 12 + e : 12;
+    if (e - t0 > lo) lo = e - t0;                   // row byte 0
+    if (row - t0 + e < hi) hi = row - t0 + e;       // row byte `row`
+    if (hi <= lo) return 0u;                        // (0 <= lo and hi <= 15 from here)
+    return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
+// the common lane, known without the mask: every byte of window dwords 0 .. 2 and nothing behind them (the mask is 0xfff there)
+VNECT_HD bool ingest_dst_inner(long long t0, int e, long long row, bool head, bool tail) { return head && !tail && t0 - e >= 0 && t0 - e + 12 <= row; }
 VNECT_HD uint32_t ingest_window_dword(const uint32_t* P, uint32_t prev, int e, int k)
 {
     const uint32_t lo = k == 0 ? prev : P[k - 1], hi = k < 3 ? P[k] : 0u;

@@ -2,8 +2,9 @@
 // Built with plain g++ (`make -C vnect_amd/csrc ingest`).  ingest_walk goes through a crop the way the kernels of post.hip do -- row by
 // row, wave by wave, 64 lanes at a time, the shuffles as array look-ups -- with the SAME functions for the loads, the permute and the
 // destination masks, so the window arithmetic is held to a plain gather without a GPU, and the lowest and highest byte it loads are
-// reported.  With -DINGEST_SWEEP_MAIN (`make ... ingest_sweep_asan`, -fsanitize=address,undefined) the same file is a stand-alone program
-// whose sources sit in exactly sized heap blocks: a load outside the allocation is the sanitizer's finding.
+// reported.  ingest_store_walk drives the store rule alone, from the row starts the NV12 copies have.  With -DINGEST_SWEEP_MAIN
+// (`make ... ingest_sweep_asan`, -fsanitize=address,undefined) the same file is a stand-alone program whose sources sit in exactly sized
+// heap blocks: a load outside the allocation is the sanitizer's finding.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,6 +36,28 @@ void put(Walk& W, uintptr_t addr, uint8_t v)
     }
     W.dst[off] = v;
     if (W.hits && W.hits[off] < 255) W.hits[off]++;
+}
+
+// The stores of one wave, as ingest_store_row (post.hip) runs them: lane `lane` holds the 12 bytes P[lane] of group Gw + lane, which land at
+// byte 12 G - lead of the packed row of `row` bytes at `drow`.  lead 0: groups counted from the crop's first column (ingest_row); 3, 6 or 9:
+// the row's first group starts that many bytes in front of the row (nv12_strip: groups counted in frame columns, lead = 3 (x & 3)).
+void store_wave(Walk& W, uint8_t* drow, long long row, int lead, int Gw, int G1, const uint32_t (*P)[3])
+{
+    for (int lane = 0; lane < 64; lane++) {
+        const int G = Gw + lane;
+        if (G > G1) break;
+        const uint32_t prev = P[lane > 0 ? lane - 1 : 0][2];  // __shfl_up(.., 1)
+        const long long t0 = 12LL * G - lead;
+        const uintptr_t E = (uintptr_t)((long long)(uintptr_t)drow + t0);
+        const int e = (int)(E & 3);
+        const bool head = e == 0 || lane > 0, tail = e != 0 && (lane == 63 || G == G1);
+        const unsigned m = ingest_dst_inner(t0, e, row, head, tail) ? 0xfffu : ingest_dst_mask(t0, e, row, head, tail);
+        for (int k = 0; k < 4; k++) {
+            const uint32_t q = ingest_window_dword(P[lane], prev, e, k);
+            for (int b = 0; b < 4; b++)
+                if (m & (1u << (4 * k + b))) put(W, E - (unsigned)e + 4u * k + b, (uint8_t)(q >> (8 * b)));
+        }
+    }
 }
 
 // one row of the crop, as ingest_row + ingest_store_row (post.hip) run it
@@ -69,20 +92,7 @@ void walk_row(Walk& W, int form, int order, uintptr_t origin, long long sy, long
             }
             ingest_pack(form, order, v, P[lane]);
         }
-        for (int lane = 0; lane < 64; lane++) {
-            const int G = Gw + lane;
-            if (G > G1) break;
-            const uint32_t prev = P[lane > 0 ? lane - 1 : 0][2];  // __shfl_up(.., 1)
-            const long long t0 = 12LL * G;
-            const uintptr_t E = (uintptr_t)drow + (unsigned long long)t0;
-            const int e = (int)(E & 3);
-            const unsigned m = ingest_dst_mask(t0, e, 3LL * w, e == 0 || lane > 0, e != 0 && (lane == 63 || G == G1));
-            for (int k = 0; k < 4; k++) {
-                const uint32_t q = ingest_window_dword(P[lane], prev, e, k);
-                for (int b = 0; b < 4; b++)
-                    if (m & (1u << (4 * k + b))) put(W, E - (unsigned)e + 4u * k + b, (uint8_t)(q >> (8 * b)));
-            }
-        }
+        store_wave(W, drow, 3LL * w, 0, Gw, G1, P);
     }
 }
 
@@ -133,6 +143,29 @@ int64_t ingest_walk(const uint8_t* base, int64_t size, int64_t data_off, int H, 
     return Wk.stray;
 }
 
+// The store rule alone, as the NV12 copies drive it: one packed row of w pixels at `dst` (any alignment) whose first group starts `lead`
+// (0, 3, 6 or 9) bytes in front of the row.  Every byte a group holds is synthetic, ingest_store_byte of its row byte index (bytes in front
+// of the row and behind it have indices outside [0, 3 w): none of them may be stored).  hits (3 w bytes, or null) as in ingest_walk.
+// Returns the number of stores outside the row's 3 w bytes, or -1 for arguments nv12_strip cannot produce.
+uint8_t ingest_store_byte(int64_t t) { return (uint8_t)(((t + 12) * 37) % 251); }
+
+int64_t ingest_store_walk(int w, int lead, uint8_t* dst, uint8_t* hits)
+{
+    if (!dst || w < 1 || lead < 0 || lead > 9 || lead % 3) return -1;
+    Walk Wk = {0, 0, {~(uintptr_t)0, 0}, dst, 3LL * w, hits, 0};
+    const int G1 = (lead / 3 + w - 1) >> 2;
+    for (int Gw = 0; Gw <= G1; Gw += 64) {
+        uint32_t P[64][3];
+        for (int lane = 0; lane < 64; lane++)
+            for (int k = 0; k < 3; k++) {
+                P[lane][k] = 0;
+                for (int b = 0; b < 4; b++) P[lane][k] |= (uint32_t)ingest_store_byte(12LL * (Gw + lane) - lead + 4 * k + b) << (8 * b);
+            }
+        store_wave(Wk, dst, 3LL * w, lead, Gw, G1, P);
+    }
+    return Wk.stray;
+}
+
 }  // extern "C"
 
 #ifdef INGEST_SWEEP_MAIN
@@ -179,6 +212,18 @@ int main()
                         }
                         free(src);
                     }
+    // the store rule alone at NV12's row starts: lead 0, 3, 6, 9 x destination phase 0..3 x the same widths
+    for (int w : widths)
+        for (int lead = 0; lead < 12; lead += 3)
+            for (int ph = 0; ph < 4; ph++) {
+                const long long n = 3LL * w;
+                uint8_t* blk = (uint8_t*)malloc((size_t)(ph + n));
+                std::vector<uint8_t> hits((size_t)n, 0);
+                bad += ingest_store_walk(w, lead, blk + ph, hits.data()) != 0;
+                for (long long i = 0; i < n; i++) bad += blk[ph + i] != ingest_store_byte(i), bad += hits[(size_t)i] != 1;
+                free(blk);
+                walks++;
+            }
     printf("ingest sweep: %lld walks, %lld mismatches\n", walks, bad);
     return bad ? 1 : 0;
 }

@@ -179,6 +179,50 @@ hipError_t launch_frame_copy(const uint8_t* src_dev, uint8_t* dst, int H, int ro
 }
 
 // ---------------------------------------------------------------------------------------------
+// The store rule of the NV12 and the device-frame copies below: a lane's 12 converted bytes P -> a packed row of `row` bytes whose first
+// byte is `drow`, at any alignment.  t0: row byte index of the group's byte 0 (negative where the group starts in front of the row).  The
+// masks are ingest.h's (ingest_dst_mask; walked on the host by ingest_capi.cpp): whole dwords where the lane owns all four bytes, all
+// three at once where it owns twelve, byte stores at the row's ends and at the dword two waves share.
+__device__ __forceinline__ void ingest_store_row(uint8_t* drow, long long row, long long t0, int G, int G1, const unsigned* P)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned prev = (unsigned)__shfl_up((int)P[2], 1);  // (every lane of the wave is here: the callers branch wave-uniformly)
+    if (G > G1) return;
+    const uintptr_t E = (uintptr_t)((long long)(uintptr_t)drow + t0);
+    const int e = (int)(E & 3);
+    unsigned* const E0 = (unsigned*)(E - (unsigned)e);
+    const bool head = e == 0 || lane > 0, tail = e != 0 && (lane == 63 || G == G1);
+    typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+    const u32x3 q3 = {ingest_window_dword(P, prev, e, 0), ingest_window_dword(P, prev, e, 1), ingest_window_dword(P, prev, e, 2)};
+    if (ingest_dst_inner(t0, e, row, head, tail)) {  // (most lanes of most rows: they leave before the mask is worked out)
+        *(u32x3*)E0 = q3;
+        return;
+    }
+    const unsigned m = ingest_dst_mask(t0, e, row, head, tail);
+    if ((m & 0xfffu) == 0xfffu) {
+        *(u32x3*)E0 = q3;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const unsigned q = ingest_window_dword(P, prev, e, k), mk = (m >> (4 * k)) & 15u;
+            if (mk == 15u) {
+                E0[k] = q;
+                continue;
+            }
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if (mk & (1u << b)) ((uint8_t*)E0)[4 * k + b] = (uint8_t)(q >> (8 * b));
+        }
+    }
+    if (m >> 12) {
+        const unsigned q = ingest_window_dword(P, prev, e, 3);
+#pragma unroll
+        for (int b = 0; b < 3; b++)
+            if (m & (1u << (12 + b))) ((uint8_t*)E0)[12 + b] = (uint8_t)(q >> (8 * b));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The same copies from an NV12 frame (vnect_infer_nv12 / vnect_submit_tracked_pinned_nv12): the conversion to BGR (nv12.h: OpenCV's
 // integers) happens inside the read of the pinned buffer, so 1.5 bytes per pixel cross PCIe instead of 3 and everything behind the
 // slot sees the BGR frame it always saw.  The rules of the copies above hold:
@@ -206,51 +250,6 @@ __device__ __forceinline__ unsigned nv12_load(uintptr_t a, const Nv12Src& s, boo
             if (a + j >= lo && a + j < end) v |= (unsigned)(*(const uint8_t*)(a + j)) << (8 * j);
     }
     return v;
-}
-// the four bytes at byte `sh` of the dword pair (hi, lo)
-__device__ __forceinline__ unsigned nv12_funnel(unsigned hi, unsigned lo, int sh) { return (unsigned)((((unsigned long long)hi << 32) | lo) >> (8 * sh)); }
-// one packed destination row of the strip: P = the lane's 12 converted bytes, `drow` the row's first byte
-__device__ __forceinline__ void nv12_store_row(uint8_t* drow, int x, int w, int G, int G1, const unsigned* P)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned prev = (unsigned)__shfl_up((int)P[2], 1);  // (every lane of the wave is here: the callers branch wave-uniformly)
-    if (G > G1) return;
-    const long long t0 = 12LL * G - 3LL * x;        // row byte index of the group's byte 0 (negative for pixels in front of the crop)
-    const long long row = 3LL * w;
-    const uintptr_t E = (uintptr_t)((long long)(uintptr_t)drow + t0);
-    const int e = (int)(E & 3);                     // (the same for every group of the row: 12 G is a multiple of 4)
-    unsigned* const E0 = (unsigned*)(E - (unsigned)e);
-    const unsigned Q[4] = {nv12_funnel(P[0], prev, 4 - e), nv12_funnel(P[1], P[0], 4 - e), nv12_funnel(P[2], P[1], 4 - e), nv12_funnel(0u, P[2], 4 - e)};
-    const bool head = e == 0 || lane > 0;           // bytes in front of the group's byte 0 are the previous lane's, held through the shuffle
-    const bool tail = e != 0 && (lane == 63 || G == G1);  // nobody behind this lane in the wave writes dword 3
-    bool whole[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) whole[k] = t0 + 4 * k - e >= 0 && t0 + 4 * k - e + 4 <= row && (k > 0 || head);
-    if (whole[0] && whole[1] && whole[2]) {
-        typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
-        *(u32x3*)E0 = u32x3{Q[0], Q[1], Q[2]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            if (whole[k]) {
-                E0[k] = Q[k];
-                continue;
-            }
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int sbyte = 4 * k + b - e;    // byte of the group (negative: the previous group's)
-                const long long t = t0 + sbyte;
-                if (t >= 0 && t < row && (sbyte >= 0 || head)) ((uint8_t*)E0)[4 * k + b] = (uint8_t)(Q[k] >> (8 * b));
-            }
-        }
-    }
-    if (tail) {
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-            const long long t = t0 + 12 + b - e;
-            if (b < e && t >= 0 && t < row) ((uint8_t*)E0)[12 + b] = (uint8_t)(Q[3] >> (8 * b));
-        }
-    }
 }
 // strip `strip` (counted from the crop's first chroma row) of the crop (x, y, w, h): rows 2 cr, 2 cr + 1 of the frame where they lie in it
 __device__ __forceinline__ void nv12_strip(const Nv12Src& s, int x, int y, int w, int h, uint8_t* __restrict__ dst, int strip)
@@ -284,7 +283,7 @@ __device__ __forceinline__ void nv12_strip(const Nv12Src& s, int x, int y, int w
         v[i] = lo[i];
         if (on[i] && sh) {
             const unsigned next = (unsigned)__shfl_down((int)lo[i], 1);
-            v[i] = nv12_funnel(self_hi ? hi[i] : next, lo[i], sh);
+            v[i] = ingest_funnel(self_hi ? hi[i] : next, lo[i], sh);
         }
     }
 #pragma unroll
@@ -292,7 +291,7 @@ __device__ __forceinline__ void nv12_strip(const Nv12Src& s, int x, int y, int w
         if (!row_on[rr]) continue;
         unsigned P[3];
         nv12_quad(v[1 + rr], v[0], P);
-        nv12_store_row(dst + (unsigned long long)(r0 + rr - y) * (3ull * (unsigned)w), x, w, G, G1, P);
+        ingest_store_row(dst + (unsigned long long)(r0 + rr - y) * (3ull * (unsigned)w), 3LL * w, 12LL * G - 3LL * x, G, G1, P);
     }
 }
 __global__ __launch_bounds__(256) void nv12_copy_kernel(const Nv12Src s, int x, int y, int w, int h, uint8_t* __restrict__ dst, int strip_base)
@@ -336,39 +335,6 @@ hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_
 // groups, a workgroup four waves; grid = (ceil(groups / 256), rows), workgroups past the crop leave at once.  The crop's origin is folded
 // into `origin` (pixel (x, y), channel 0).  Loads stay inside [s.lo, s.end), the caller's allocation; bytes outside the crop's 3 w h are
 // never stored.
-__device__ __forceinline__ void ingest_store_row(uint8_t* drow, long long row, int G, int G1, const unsigned* P)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned prev = (unsigned)__shfl_up((int)P[2], 1);  // (every lane of the wave is here: the callers branch wave-uniformly)
-    if (G > G1) return;
-    const long long t0 = 12LL * G;
-    const uintptr_t E = (uintptr_t)drow + (unsigned long long)t0;
-    const int e = (int)(E & 3);
-    unsigned* const E0 = (unsigned*)(E - (unsigned)e);
-    const unsigned m = ingest_dst_mask(t0, e, row, e == 0 || lane > 0, e != 0 && (lane == 63 || G == G1));
-    if ((m & 0xfffu) == 0xfffu) {
-        typedef unsigned u32x3 __attribute__((ext_vector_type(3), aligned(4)));
-        *(u32x3*)E0 = u32x3{ingest_window_dword(P, prev, e, 0), ingest_window_dword(P, prev, e, 1), ingest_window_dword(P, prev, e, 2)};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const unsigned q = ingest_window_dword(P, prev, e, k), mk = (m >> (4 * k)) & 15u;
-            if (mk == 15u) {
-                E0[k] = q;
-                continue;
-            }
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if (mk & (1u << b)) ((uint8_t*)E0)[4 * k + b] = (uint8_t)(q >> (8 * b));
-        }
-    }
-    if (m >> 12) {
-        const unsigned q = ingest_window_dword(P, prev, e, 3);
-#pragma unroll
-        for (int b = 0; b < 3; b++)
-            if (m & (1u << (12 + b))) ((uint8_t*)E0)[12 + b] = (uint8_t)(q >> (8 * b));
-    }
-}
 // row `y` of the crop whose pixel (0, 0) is `origin`, w pixels wide -> dst + y * 3 w
 template <int FORM, int ORDER>
 __device__ __forceinline__ void ingest_row(const IngestSrc& s, const uint8_t* origin, int w, int y, uint8_t* __restrict__ dst)
@@ -409,7 +375,7 @@ __device__ __forceinline__ void ingest_row(const IngestSrc& s, const uint8_t* or
     }
     unsigned P[3];
     ingest_pack(FORM, ORDER, v, P);
-    ingest_store_row(dst + (unsigned long long)y * (3ull * (unsigned)w), 3LL * w, G, G1, P);
+    ingest_store_row(dst + (unsigned long long)y * (3ull * (unsigned)w), 3LL * w, 12LL * G, G, G1, P);
 }
 template <int FORM, int ORDER>
 __global__ __launch_bounds__(256) void ingest_copy_kernel(const IngestSrc s, const uint8_t* origin, int w, int row_base, uint8_t* __restrict__ dst)

@@ -1,5 +1,5 @@
 // rt_abi.cpp -- the extern "C" entry points of include/vnect_abi.h (which cites the reference lines each one replaces): argument and
-// state checks, device selection, and the guard that lets no C++ exception cross the boundary.  The work is in rt_plan / rt_exec / rt_comm.
+// state checks, device selection, and the guard that lets no C++ exception cross the boundary.  The work is in rt_plan / rt_exec / rt_ingest / rt_comm.
 #include "runtime.h"
 
 namespace vnect {
@@ -7,6 +7,97 @@ namespace rt {
 thread_local std::string g_create_error = "";
 }  // namespace rt
 }  // namespace vnect
+
+// gen_input_batch of the frame in slot 0 (vnect_preprocess, vnect_preprocess_nv12)
+static int preprocess_slot0(vnect_handle* h, float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y)
+{
+    FrameParams fp;
+    int rc;
+    if ((rc = squarify_params(h, h->slots[0].H, h->slots[0].W, &fp))) return rc;
+    FrameDyn dyn{};
+    dyn.row_stride = h->slots[0].stride, dyn.frame = h->frames;
+    if ((rc = sync_geometry(h, fp))) return rc;
+    if ((rc = run_pre(h, dyn, false, true))) return rc;
+    if (batch_out) {
+        const long long npix = (long long)h->Snet * BOX * BOX;
+        HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
+        HIPCK(h, hipMemcpyAsync(batch_out, h->in3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCK(h, hipStreamSynchronize(h->st));
+    if (scaler) *scaler = fp.scaler;
+    if (offset_x) *offset_x = fp.offx;
+    if (offset_y) *offset_y = fp.offy;
+    return VNECT_OK;
+}
+
+// ---- The four operations a frame source takes part in: upload, infer, preprocess, tracked submit.  `resolve(FrameSrc*)` is the source's
+// resolver (rt_ingest.cpp) over the entry point's arguments.  The order everywhere: state, then the source's validation, then what changes
+// state.
+// finalized (or, where that serves, preprocess_only), nothing in flight; selects the device
+static int idle(vnect_handle* h, const char* who, bool pre_only_serves)
+{
+    if (!h->finalized && !(pre_only_serves && h->pre_only)) return fail(h, VNECT_E_STATE, std::string(who) + " before vnect_finalize");
+    if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
+    HIPCK(h, hipSetDevice(h->cfg.device));
+    return VNECT_OK;
+}
+
+static int tracked_ok(vnect_handle* h, int stream)
+{
+    if (!h->finalized) return fail(h, VNECT_E_STATE, "inference before vnect_finalize");
+    if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
+    if (!h->streams[stream].track_on) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
+    if (h->streams[stream].track_stopped) return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
+    return VNECT_OK;
+}
+
+// the frame into `slot`; done with the caller's buffer on return
+template <class R>
+static int upload_from(vnect_handle* h, int slot, const char* who, R&& resolve)
+{
+    if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, std::string(who) + ": bad frame slot");
+    HIPCK(h, hipSetDevice(h->cfg.device));
+    FrameSrc src;
+    int rc = resolve(&src);
+    return rc ? rc : ingest_sync(h, slot, src);
+}
+
+// the frame through slot 0, synchronously.  Nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the
+// stream ingest() copies on; the result is back when this returns, so the copy has long read the caller's buffer
+template <class R>
+static int infer_from(vnect_handle* h, const char* who, double t2d, double t3d, double* j2, float* j3, R&& resolve)
+{
+    int rc = idle(h, who, false);
+    if (rc) return rc;
+    FrameSrc src;
+    if ((rc = resolve(&src))) return rc;
+    if ((rc = ingest(h, 0, src))) return rc;
+    return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+}
+
+template <class R>
+static int preprocess_from(vnect_handle* h, const char* who, float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y, R&& resolve)
+{
+    int rc = idle(h, who, true);
+    if (rc) return rc;
+    FrameSrc src;
+    if ((rc = resolve(&src))) return rc;
+    if ((rc = ingest_sync(h, 0, src))) return rc;
+    return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
+}
+
+// the stream's next tracked frame: the whole frame in `slot`, or (slot -1) where the resolver says
+template <class R>
+static int submit_tracked_from(vnect_handle* h, int stream, int slot, double t2d, double t3d, R&& resolve)
+{
+    int rc = tracked_ok(h, stream);
+    if (rc) return rc;
+    HIPCK(h, hipSetDevice(h->cfg.device));
+    FrameSrc src;
+    if ((rc = resolve(&src))) return rc;
+    int ring;
+    return enqueue_frame(h, slot, t2d, t3d, &ring, stream, &src);
+}
 
 // =====================================================================================================
 extern "C" {
@@ -302,38 +393,14 @@ int vnect_forward(vnect_handle* h, const float* batch, int num_images, float* ou
     });
 }
 
-// gen_input_batch of the frame in slot 0 (vnect_preprocess, vnect_preprocess_nv12)
-static int preprocess_slot0(vnect_handle* h, float* batch_out, double* scaler, int32_t* offset_x, int32_t* offset_y)
-{
-    FrameParams fp;
-    int rc;
-    if ((rc = squarify_params(h, h->slots[0].H, h->slots[0].W, &fp))) return rc;
-    FrameDyn dyn{};
-    dyn.row_stride = h->slots[0].stride, dyn.frame = h->frames;
-    if ((rc = sync_geometry(h, fp))) return rc;
-    if ((rc = run_pre(h, dyn, false, true))) return rc;
-    if (batch_out) {
-        const long long npix = (long long)h->Snet * BOX * BOX;
-        HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
-        HIPCK(h, hipMemcpyAsync(batch_out, h->in3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCK(h, hipStreamSynchronize(h->st));
-    if (scaler) *scaler = fp.scaler;
-    if (offset_x) *offset_x = fp.offx;
-    if (offset_y) *offset_y = fp.offy;
-    return VNECT_OK;
-}
-
 int vnect_preprocess(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, float* batch_out,
                      double* scaler, int32_t* offset_x, int32_t* offset_y)
 {
     return guarded(&h, [&]() -> int {
         if (!h || !bgr) return VNECT_E_ARG;
-        if (!h->finalized && !h->pre_only) return fail(h, VNECT_E_STATE, "vnect_preprocess before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        int rc = upload_frame_impl(h, 0, bgr, H, W, row_stride);
+        int rc = idle(h, "vnect_preprocess", true);
         if (rc) return rc;
+        if ((rc = upload_frame_impl(h, 0, bgr, H, W, row_stride))) return rc;  // (the pageable, synchronous copy: rt_ingest.cpp)
         return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
     });
 }
@@ -465,14 +532,7 @@ int vnect_infer(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_s
 {
     return guarded(&h, [&]() -> int {
         if (!h || !bgr || !j2 || !j3) return VNECT_E_ARG;
-        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_infer before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        // nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the stream stage_frame copies on
-        static const bool sync_copy = getenv("VNECT_INFER_SYNC_COPY") != nullptr;
-        int rc = sync_copy ? upload_frame_impl(h, 0, bgr, H, W, row_stride) : stage_frame(h, 0, bgr, H, W, row_stride);
-        if (rc) return rc;
-        return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+        return infer_from(h, "vnect_infer", t2d, t3d, j2, j3, [&](FrameSrc* s) { return resolve_host_bgr(h, bgr, H, W, row_stride, s); });
     });
 }
 
@@ -681,25 +741,11 @@ int vnect_track_begin(vnect_handle* h, int stream, int H, int W, const int32_t* 
     });
 }
 
-static int tracked_ok(vnect_handle* h, int stream)
-{
-    if (!h->finalized) return fail(h, VNECT_E_STATE, "inference before vnect_finalize");
-    if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
-    if (!h->streams[stream].track_on) return fail(h, VNECT_E_STATE, "stream is not tracking: call vnect_track_begin first");
-    if (h->streams[stream].track_stopped) return fail(h, VNECT_E_STATE, "tracking of this stream stopped at a refused crop: call vnect_track_begin");
-    return VNECT_OK;
-}
-
 int vnect_submit_tracked(vnect_handle* h, int stream, int slot, double t2d, double t3d)
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        int rc = tracked_ok(h, stream);
-        if (rc) return rc;
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        TrackedSrc tk;
-        int ring;
-        return enqueue_frame(h, slot, t2d, t3d, &ring, stream, &tk);
+        return submit_tracked_from(h, stream, slot, t2d, t3d, [](FrameSrc*) { return VNECT_OK; });  // (a FrameSrc is born SRC_SLOT)
     });
 }
 
@@ -707,17 +753,9 @@ int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, i
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        int rc = tracked_ok(h, stream);
-        if (rc) return rc;
-        if (buffer_index < 0 || buffer_index > 1 || !h->stage[buffer_index]) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: no such pinned buffer (vnect_frame_buffer)");
-        const int H = h->streams[stream].track_H, W = h->streams[stream].track_W;
-        if (row_stride < (int64_t)W * 3 || (size_t)(H - 1) * (size_t)row_stride + (size_t)W * 3 > h->stage_cap[buffer_index])
-            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned: the frame does not fit the pinned buffer at this row stride");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        TrackedSrc tk;
-        tk.pinned_dev = h->stage_dev[buffer_index], tk.pinned_end = h->stage_dev[buffer_index] + h->stage_cap[buffer_index], tk.stride = row_stride;
-        int ring;
-        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+        return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
+            return resolve_pinned_bgr(h, "vnect_submit_tracked_pinned", buffer_index, h->streams[stream].track_H, h->streams[stream].track_W, row_stride, s);
+        });
     });
 }
 
@@ -788,8 +826,8 @@ int vnect_upload_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        return upload_nv12_impl(h, slot, y, y_stride, uv, uv_stride, H, W, nullptr, "vnect_upload_frame_nv12");
+        return upload_from(h, slot, "vnect_upload_frame_nv12",
+                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12", y, y_stride, uv, uv_stride, H, W, nullptr, s); });
     });
 }
 
@@ -798,8 +836,8 @@ int vnect_upload_frame_nv12_rect(vnect_handle* h, int slot, const uint8_t* y, in
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        return upload_nv12_impl(h, slot, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_upload_frame_nv12_rect");
+        return upload_from(h, slot, "vnect_upload_frame_nv12_rect",
+                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12_rect", y, y_stride, uv, uv_stride, H, W, rect4, s); });
     });
 }
 
@@ -808,13 +846,8 @@ int vnect_infer_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const 
 {
     return guarded(&h, [&]() -> int {
         if (!h || !y || !uv || !j2 || !j3) return VNECT_E_ARG;
-        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_infer_nv12 before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        // nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the stream the conversion runs on
-        int rc = stage_frame_nv12(h, 0, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_infer_nv12");
-        if (rc) return rc;
-        return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+        return infer_from(h, "vnect_infer_nv12", t2d, t3d, j2, j3,
+                          [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_infer_nv12", y, y_stride, uv, uv_stride, H, W, rect4, s); });
     });
 }
 
@@ -823,12 +856,8 @@ int vnect_preprocess_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, c
 {
     return guarded(&h, [&]() -> int {
         if (!h || !y || !uv) return VNECT_E_ARG;
-        if (!h->finalized && !h->pre_only) return fail(h, VNECT_E_STATE, "vnect_preprocess_nv12 before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        int rc = upload_nv12_impl(h, 0, y, y_stride, uv, uv_stride, H, W, rect4, "vnect_preprocess_nv12");
-        if (rc) return rc;
-        return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
+        return preprocess_from(h, "vnect_preprocess_nv12", batch_out, scaler, offset_x, offset_y,
+                               [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_preprocess_nv12", y, y_stride, uv, uv_stride, H, W, rect4, s); });
     });
 }
 
@@ -837,23 +866,10 @@ int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_ind
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        int rc = tracked_ok(h, stream);
-        if (rc) return rc;
-        if (buffer_index < 0 || buffer_index > 1 || !h->stage[buffer_index])
-            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: no such pinned buffer (vnect_frame_buffer)");
-        const int H = h->streams[stream].track_H, W = h->streams[stream].track_W;
-        if ((H | W) & 1) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: an NV12 frame needs even W and H (vnect_track_begin gave odd ones)");
-        if (y_stride < (int64_t)W || uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: y_stride and uv_stride must be at least W");
-        const size_t y_span = (size_t)(H - 1) * (size_t)y_stride + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)uv_stride + (size_t)W;
-        if (uv_offset < 0 || (size_t)uv_offset < y_span) return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: the UV plane overlaps the Y plane");
-        if ((size_t)uv_offset + uv_span > h->stage_cap[buffer_index])
-            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_pinned_nv12: the planes run past the pinned buffer at these strides");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        TrackedSrc tk;
-        tk.pinned_dev = tk.pinned_lo = h->stage_dev[buffer_index], tk.pinned_end = h->stage_dev[buffer_index] + h->stage_cap[buffer_index], tk.stride = y_stride;
-        tk.nv12 = true, tk.uv_dev = h->stage_dev[buffer_index] + uv_offset, tk.uv_stride = uv_stride;
-        int ring;
-        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+        return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
+            return resolve_pinned_nv12(h, "vnect_submit_tracked_pinned_nv12", buffer_index, h->streams[stream].track_H, h->streams[stream].track_W, y_stride,
+                                       uv_offset, uv_stride, s);
+        });
     });
 }
 
@@ -862,12 +878,8 @@ int vnect_upload_frame_device(vnect_handle* h, int slot, const vnect_device_fram
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "vnect_upload_frame_device: bad frame slot");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        DeviceFrame f;
-        int rc = check_device_frame(h, frame, producer_stream, "vnect_upload_frame_device", true, &f);
-        if (rc) return rc;
-        return upload_device_impl(h, slot, f);
+        return upload_from(h, slot, "vnect_upload_frame_device",
+                           [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_upload_frame_device", true, s); });
     });
 }
 
@@ -875,16 +887,8 @@ int vnect_infer_device(vnect_handle* h, const vnect_device_frame* frame, void* p
 {
     return guarded(&h, [&]() -> int {
         if (!h || !j2 || !j3) return VNECT_E_ARG;
-        if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_infer_device before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        DeviceFrame f;
-        int rc = check_device_frame(h, frame, producer_stream, "vnect_infer_device", true, &f);
-        if (rc) return rc;
-        // nothing is in flight, so the frame will run on the first lane's stream (enqueue_frame), the stream the copy runs on.  The result
-        // is back when this returns, so the copy has long read the caller's buffer
-        if ((rc = stage_frame_device(h, 0, f))) return rc;
-        return vnect_infer_resident(h, 0, t2d, t3d, j2, j3);
+        return infer_from(h, "vnect_infer_device", t2d, t3d, j2, j3,
+                          [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_infer_device", true, s); });
     });
 }
 
@@ -893,14 +897,8 @@ int vnect_preprocess_device(vnect_handle* h, const vnect_device_frame* frame, vo
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        if (!h->finalized && !h->pre_only) return fail(h, VNECT_E_STATE, "vnect_preprocess_device before vnect_finalize");
-        if (h->seq_submit != h->seq_collect) return fail(h, VNECT_E_STATE, "frames in flight");
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        DeviceFrame f;
-        int rc = check_device_frame(h, frame, producer_stream, "vnect_preprocess_device", true, &f);
-        if (rc) return rc;
-        if ((rc = upload_device_impl(h, 0, f))) return rc;
-        return preprocess_slot0(h, batch_out, scaler, offset_x, offset_y);
+        return preprocess_from(h, "vnect_preprocess_device", batch_out, scaler, offset_x, offset_y,
+                               [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_preprocess_device", true, s); });
     });
 }
 
@@ -908,17 +906,13 @@ int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_
 {
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
-        int rc = tracked_ok(h, stream);
-        if (rc) return rc;
-        HIPCK(h, hipSetDevice(h->cfg.device));
-        DeviceFrame f;
-        if ((rc = check_device_frame(h, frame, producer_stream, "vnect_submit_tracked_device", false, &f))) return rc;
-        if (f.H != h->streams[stream].track_H || f.W != h->streams[stream].track_W)
-            return fail(h, VNECT_E_ARG, "vnect_submit_tracked_device: the frame is not of the size vnect_track_begin gave for this stream");
-        TrackedSrc tk;
-        tk.pinned_dev = f.nv12 ? f.nv.y : f.ing.data, tk.dev = &f;
-        int ring;
-        return enqueue_frame(h, -1, t2d, t3d, &ring, stream, &tk);
+        return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
+            int rc = check_device_frame(h, frame, producer_stream, "vnect_submit_tracked_device", false, s);
+            if (rc) return rc;
+            if (s->H != h->streams[stream].track_H || s->W != h->streams[stream].track_W)
+                return fail(h, VNECT_E_ARG, "vnect_submit_tracked_device: the frame is not of the size vnect_track_begin gave for this stream");
+            return (int)VNECT_OK;
+        });
     });
 }
 

@@ -1,6 +1,6 @@
 // rt_exec.cpp -- running frames on a plan: launch sequences, the hipGraph and its profiling twin, lane choice, video streams, submit /
-// collect, host -> device staging, the warm start.  One call of VNectEstimator.__call__ (/root/reference/src/estimator.py:97-142)
-// is enqueue_frame + collect_impl.
+// collect, the warm start.  One call of VNectEstimator.__call__ (the reference's src/estimator.py:97-142) is enqueue_frame +
+// collect_impl.  (How a frame gets into a slot, or a tracked frame's description to enqueue_frame: rt_ingest.cpp.)
 #include "runtime.h"
 
 namespace vnect {
@@ -119,24 +119,23 @@ void deliver_confidence(vnect_handle* h, int ring, bool tracked)
     h->have_conf = true;
 }
 
-// gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the pinned frame when
-// the frame lies in one), the pyramid from it, and on a stem_mode 2 lane the stem from the batch tensor (the host does not know whether
+// gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the frame when that
+// lies outside the slots), the pyramid from it, and on a stem_mode 2 lane the stem from the batch tensor (the host does not know whether
 // the crop's squarify step is a copy, which the stem's frame form needs; the results are the same bit for bit)
-static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn& dyn, const TrackedSrc& tk, bool timed)
+static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn& dyn, const FrameSrc& src, bool timed)
 {
     TrackState* ts = h->d_track + stream;
     const Stream& sm = h->streams[stream];
-    if (tk.dev) {  // the frame lies in the caller's device memory: this lane's stream waits for its producer, then copies the crop's rows
-        int rc = wait_for_producer(h, tk.dev->producer, L->st);
-        if (rc) return rc;
-        if (tk.dev->nv12) HIPCK(h, launch_nv12_copy_track(ts, tk.dev->nv, sm.track_buf, sm.track_H, sm.track_W, L->st));
-        else HIPCK(h, launch_ingest_copy_track(ts, tk.dev->ing, sm.track_buf, sm.track_H, sm.track_W, L->st));
-    } else if (tk.pinned_dev && tk.nv12) {
-        const Nv12Src src = {tk.pinned_dev, tk.stride, tk.uv_dev, tk.uv_stride, tk.pinned_lo, tk.pinned_end};
-        HIPCK(h, launch_nv12_copy_track(ts, src, sm.track_buf, sm.track_H, sm.track_W, L->st));
-    } else if (tk.pinned_dev)
-        HIPCK(h, launch_frame_copy_track(ts, tk.pinned_dev, sm.track_buf, sm.track_H, sm.track_W, tk.stride, tk.pinned_end, L->st));
-    HIPCK(h, launch_pyramid_track(ts, dyn, tk.pinned_dev != nullptr, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
+    // a frame outside the slots: this lane's stream waits for its producer, then copies the crop's rows (packed) into the stream's buffer
+    int rc = wait_for_producer(h, src.producer, L->st);
+    if (rc) return rc;
+    switch (src.where) {
+    case SRC_SLOT: break;
+    case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy_track(ts, src.bgr.data, sm.track_buf, sm.track_H, sm.track_W, src.bgr.stride, src.bgr.end, L->st)); break;
+    case SRC_NV12: HIPCK(h, launch_nv12_copy_track(ts, src.nv, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
+    case SRC_DEVICE: HIPCK(h, launch_ingest_copy_track(ts, src.ing, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
+    }
+    HIPCK(h, launch_pyramid_track(ts, dyn, src.where != SRC_SLOT, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
     if (L->stem_mode == 2) {
         StemArgs a = stamped(L, L->stem, L->l_conv1, timed);
         a.from_frame = 0;
@@ -281,15 +280,16 @@ static Plan* pick_lane(vnect_handle* h, bool timed)
 static bool replays(const vnect_handle* h, const Plan* p) { return p->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect); }
 
 // enqueue one frame from a resident slot; results land in its ring entry's slot.  `tk`: a tracked frame (vnect_submit_tracked*) -- its crop and
-// geometry are the stream's state on the device, the frame is the whole one (in `slot`, or in a pinned buffer: then slot is -1)
-int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream, const TrackedSrc* tk)
+// geometry are the stream's state on the device, the frame is the whole one (in `slot`, or outside the slots where tk says: then slot is -1)
+int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream, const FrameSrc* tk)
 {
+    const bool from_slot = !tk || tk->where == SRC_SLOT;
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
     if (stream != 0 && h->sharded) return fail(h, VNECT_E_ARG, "a pyramid-sharded handle serves one stream");
-    if (!(tk && tk->pinned_dev) && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0))
+    if (from_slot && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0))
         return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
     Stream& sm = h->streams[stream];
-    if (tk && !tk->pinned_dev && (h->slots[slot].H != sm.track_H || h->slots[slot].W != sm.track_W))
+    if (tk && from_slot && (h->slots[slot].H != sm.track_H || h->slots[slot].W != sm.track_W))
         return fail(h, VNECT_E_ARG, "the slot's frame is not of the size vnect_track_begin gave for this stream");
     if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
     if (h->sharded && !comm_ready(h))  // refuse before any filter / timestamp state changes
@@ -303,7 +303,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     InFlight& e = h->ring[ring];
     FrameDyn dyn{};
     dyn.t2d = t2d, dyn.t3d = t3d;
-    if (tk && tk->pinned_dev) {
+    if (!from_slot) {
         dyn.frame = sm.track_buf;  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
     } else {
         dyn.row_stride = h->slots[slot].stride;
@@ -491,274 +491,6 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         h->tim.net_ms += last > first ? (double)(last - first) * 1e-5 : 0;  // first conv start .. last conv end
         h->tim.conv_ms += conv_ms;                                       // sum of conv kernel durations
     }
-    return VNECT_OK;
-}
-
-// pinned staging buffer i with room for `bytes` (grows in 1-MiB steps; a grown buffer moves, so nothing may be in flight)
-int ensure_stage(vnect_handle* h, int i, size_t bytes)
-{
-    if (h->stage_cap[i] >= bytes) return VNECT_OK;
-    HIPCK(h, hipStreamSynchronize(h->st));
-    if (h->stage[i]) HIPCK(h, hipHostFree(h->stage[i]));
-    h->stage[i] = nullptr, h->stage_cap[i] = 0;
-    const size_t cap = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    HIPCK(h, hipHostMalloc((void**)&h->stage[i], cap, hipHostMallocMapped));
-    HIPCK(h, hipHostGetDevicePointer((void**)&h->stage_dev[i], h->stage[i], 0));
-    h->stage_cap[i] = cap;
-    return VNECT_OK;
-}
-
-// vnect_infer: the frame goes to slot `slot` through pinned memory, asynchronously on the handle's stream (the caller runs the frame
-// on that stream next).  The copy is a kernel reading the pinned buffer over PCIe (post.hip: frame_copy_kernel; VNECT_INFER_DMA=1: the
-// copy engine instead, hipMemcpyAsync).  VNECT_INFER_SYNC_COPY=1: the round-4 form (a synchronous pageable hipMemcpy2D), for A/B runs.
-int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride)
-{
-    if (!bgr || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
-    if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return fail(h, VNECT_E_ARG, "bad frame geometry");
-    if ((size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes) return fail(h, VNECT_E_ARG, "frame larger than max_frame_bytes");
-    const size_t row = (size_t)W * 3, span = (size_t)(H - 1) * (size_t)row_stride + row;
-    const uint8_t *src = nullptr, *src_dev = nullptr, *src_end = nullptr;  // src_end: end of the pinned buffer, as the device addresses it
-    size_t src_stride = (size_t)row_stride;
-    for (int i = 0; i < 2 && !src; i++)  // already in pinned memory (a crop of a frame the caller captured into vnect_frame_buffer)?
-        if (h->stage[i] && bgr >= h->stage[i] && bgr + span <= h->stage[i] + h->stage_cap[i])
-            src = bgr, src_dev = h->stage_dev[i] + (bgr - h->stage[i]), src_end = h->stage_dev[i] + h->stage_cap[i];
-    if (!src) {
-        const int i = 2;
-        int rc = ensure_stage(h, i, (size_t)H * row);
-        if (rc) return rc;
-        if ((size_t)row_stride == row) memcpy(h->stage[i], bgr, (size_t)H * row);
-        else
-            for (int y = 0; y < H; y++) memcpy(h->stage[i] + (size_t)y * row, bgr + (size_t)y * (size_t)row_stride, row);
-        src = h->stage[i], src_dev = h->stage_dev[i], src_stride = row, src_end = h->stage_dev[i] + h->stage_cap[i];
-    }
-    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    static const bool dma = getenv("VNECT_INFER_DMA") != nullptr;
-    if (!dma) HIPCK(h, launch_frame_copy(src_dev, dst, H, (int)row, (long long)src_stride, src_end, h->st));
-    else if (src_stride == row) HIPCK(h, hipMemcpyAsync(dst, src, (size_t)H * row, hipMemcpyHostToDevice, h->st));
-    else HIPCK(h, hipMemcpy2DAsync(dst, row, src, src_stride, row, H, hipMemcpyHostToDevice, h->st));
-    h->slots[slot].H = H, h->slots[slot].W = W, h->slots[slot].stride = (long long)row;
-    return VNECT_OK;
-}
-
-// `slot` is about to be overwritten with a frame of `bytes` BGR bytes
-static int claim_slot(vnect_handle* h, int slot, size_t bytes)
-{
-    if (h->pre_only && bytes > h->pre_frame_cap) {  // the one slot of a pre-processing-only handle grows with its frames
-        HIPCK(h, hipStreamSynchronize(h->st));
-        if (h->frames) {
-            HIPCK(h, hipFree(h->frames));
-            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->frames));
-            h->frames = nullptr, h->pre_frame_cap = 0;
-        }
-        int rc = dev_alloc(h, &h->frames, bytes);
-        if (rc) return rc;
-        h->pre_frame_cap = bytes;
-    }
-    // a frame still being read by an in-flight inference must not be overwritten: wait for that inference only (frames in
-    // other slots keep running, so a pipelined caller uploads frame k+1 while frames k and k-1 compute)
-    const long long q = h->slots[slot].last_use;
-    if (q >= (long long)h->seq_collect) HIPCK(h, hipEventSynchronize(h->ring[q % RING].done));
-    return VNECT_OK;
-}
-
-// ---- NV12 frames (vnect_infer_nv12 and its kin) ------------------------------------------------------------------------------------------
-// stage_frame's rules with NV12 on the source side: planes inside one of the caller's pinned buffers are read where they lie, anything
-// else is first copied by the CPU into the internal stage (1.5 bytes per pixel: Y rows W apart, the UV plane directly behind); the
-// conversion is the copy kernel's (post.hip: nv12_copy_kernel), on the handle's stream, in front of the frame.  With a rect only the crop
-// is converted and lands at the slot's origin -- what stage_frame does for a BGR crop cut out of a pinned buffer; a rect that runs past the
-// frame's far edges crops what numpy slicing crops.  Every refusal comes before anything changes.
-int stage_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                     const int32_t* rect4, const char* who, hipStream_t st)
-{
-    const std::string w_ = std::string(who) + ": ";
-    if (!y || !uv || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, w_ + "bad frame slot or plane pointer");
-    if (H < 2 || W < 2 || ((H | W) & 1)) return fail(h, VNECT_E_ARG, w_ + "an NV12 frame needs even W and H (>= 2)");
-    if (y_stride < (int64_t)W || uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, w_ + "y_stride and uv_stride must be at least W");
-    const size_t y_span = (size_t)(H - 1) * (size_t)y_stride + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)uv_stride + (size_t)W;
-    if (y < uv + uv_span && uv < y + y_span) return fail(h, VNECT_E_ARG, w_ + "the UV plane overlaps the Y plane");
-    int r[4] = {0, 0, W, H};
-    if (rect4) {
-        for (int k = 0; k < 4; k++) r[k] = rect4[k];
-        if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H) return fail(h, VNECT_E_ARG, w_ + "the rect's origin must lie inside the frame");
-        if (r[2] < 1 || r[3] < 1) return fail(h, VNECT_E_ARG, w_ + "the rect must be at least one pixel wide and high");
-        r[2] = std::min(r[2], W - r[0]), r[3] = std::min(r[3], H - r[1]);
-    }
-    if ((size_t)r[2] * r[3] * 3 > (size_t)h->cfg.max_frame_bytes)
-        return fail(h, VNECT_E_ARG, w_ + "frame larger than max_frame_bytes (the slot holds BGR: 3 bytes per pixel)");
-    Nv12Src src{};
-    for (int i = 0; i < 2 && !src.y; i++) {  // already in pinned memory (a decoder's surface captured into vnect_frame_buffer)?
-        const uint8_t *lo = h->stage[i], *end = lo ? lo + h->stage_cap[i] : nullptr;
-        const bool y_in = lo && y >= lo && y < end, uv_in = lo && uv >= lo && uv < end;
-        if (!y_in && !uv_in) continue;
-        if (!y_in || !uv_in || y + y_span > end || uv + uv_span > end)
-            return fail(h, VNECT_E_ARG, w_ + "the planes run past the pinned buffer they start in");
-        src = {h->stage_dev[i] + (y - lo), (long long)y_stride, h->stage_dev[i] + (uv - lo), (long long)uv_stride, h->stage_dev[i], h->stage_dev[i] + h->stage_cap[i]};
-    }
-    if (!src.y) {
-        // only what the crop needs: its Y rows from the even row at or above its first, and the chroma rows under them, as a frame of
-        // its own (rows W apart, the UV plane directly behind); the rect moves up by the rows left out
-        const int i = 2, y0 = r[1] & ~1, rows = (r[1] + r[3] - y0 + 1) & ~1;   // (y0 + rows <= H: H is even)
-        const size_t plane = (size_t)rows * W;
-        int rc = ensure_stage(h, i, plane + plane / 2);
-        if (rc) return rc;
-        for (int q = 0; q < rows; q++) memcpy(h->stage[i] + (size_t)q * W, y + (size_t)(y0 + q) * (size_t)y_stride, (size_t)W);
-        for (int q = 0; q < rows / 2; q++) memcpy(h->stage[i] + plane + (size_t)q * W, uv + (size_t)(y0 / 2 + q) * (size_t)uv_stride, (size_t)W);
-        src = {h->stage_dev[i], (long long)W, h->stage_dev[i] + plane, (long long)W, h->stage_dev[i], h->stage_dev[i] + h->stage_cap[i]};
-        r[1] -= y0;
-    }
-    int rc = claim_slot(h, slot, (size_t)r[2] * r[3] * 3);
-    if (rc) return rc;
-    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    HIPCK(h, launch_nv12_copy(src, r[0], r[1], r[2], r[3], dst, st ? st : h->st));
-    h->slots[slot].H = r[3], h->slots[slot].W = r[2], h->slots[slot].stride = 3LL * r[2];
-    return VNECT_OK;
-}
-
-// vnect_upload_frame_nv12 / vnect_preprocess_nv12: the same, and done when it returns (vnect_upload_frame's copy is synchronous as well).
-// The conversion runs on a stream of its own, not on lane 0's: like vnect_upload_frame's blocking copy it waits only for the slot's last
-// reader (claim_slot), so a pipelined caller uploads frame k + 1 while frame k computes.  (The internal stage is free again on return,
-// and vnect_infer_nv12, its other user, runs only with nothing in flight.)
-int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                     const int32_t* rect4, const char* who)
-{
-    if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
-    int rc = stage_frame_nv12(h, slot, y, y_stride, uv, uv_stride, H, W, rect4, who, h->upload_st);
-    if (rc) return rc;
-    HIPCK(h, hipStreamSynchronize(h->upload_st));
-    return VNECT_OK;
-}
-
-// ---- frames in the caller's DEVICE memory (vnect_infer_device and its kin) ---------------------------------------------------------------
-// `p` must be device memory of the handle's device as this process's HIP runtime knows it; [*lo, *end) = the allocation it lies in
-static int device_range(vnect_handle* h, const void* p, const std::string& w_, const char* what, const uint8_t** lo, const uint8_t** end)
-{
-    static const char* advice =
-        ": device-frame entry points take hipMalloc'ed memory of the handle's device only -- pass host memory to vnect_infer / vnect_upload_frame "
-        "(vnect_infer_nv12 / vnect_upload_frame_nv12 for NV12); a pointer of another HIP runtime in this process means nothing to this one "
-        "(torch ships its own libamdhip64: import torch BEFORE vnect_amd, so that the process holds one runtime)";
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // (an unknown pointer is the caller's mistake, not a sticky error of the handle)
-        return fail(h, VNECT_E_ARG, w_ + what + " is not memory this process's HIP runtime allocated" + advice);
-    }
-    if (at.type != hipMemoryTypeDevice || at.isManaged) return fail(h, VNECT_E_ARG, w_ + what + " is host or managed memory, not device memory" + advice);
-    if (at.device != h->cfg.device) return fail(h, VNECT_E_ARG, w_ + what + " lies on another device than the handle's" + advice);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base || !size) {
-        (void)hipGetLastError();
-        return fail(h, VNECT_E_ARG, w_ + "hipMemGetAddressRange does not know the allocation " + what + " points into" + advice);
-    }
-    *lo = (const uint8_t*)base, *end = (const uint8_t*)base + size;
-    if ((const uint8_t*)p < *lo || (const uint8_t*)p >= *end) return fail(h, VNECT_E_ARG, w_ + what + " lies outside the allocation the runtime reports for it");
-    return VNECT_OK;
-}
-
-int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, DeviceFrame* out)
-{
-    const std::string w_ = std::string(who) + ": ";
-    if (!f) return fail(h, VNECT_E_ARG, w_ + "no frame descriptor");
-    if (f->struct_size != (int32_t)sizeof(vnect_device_frame)) return fail(h, VNECT_E_ARG, w_ + "vnect_device_frame::struct_size is not sizeof(vnect_device_frame)");
-    if (f->format != VNECT_PIX_BGR && f->format != VNECT_PIX_RGB && f->format != VNECT_PIX_NV12)
-        return fail(h, VNECT_E_ARG, w_ + "format must be VNECT_PIX_BGR, VNECT_PIX_RGB or VNECT_PIX_NV12");
-    const bool nv12 = f->format == VNECT_PIX_NV12;
-    const int H = f->H, W = f->W;
-    if (!f->data || (nv12 && !f->uv)) return fail(h, VNECT_E_ARG, w_ + "null frame pointer");
-    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return fail(h, VNECT_E_ARG, w_ + "bad frame geometry");
-    size_t span = 0, uv_span = 0;
-    if (nv12) {  // the rules of stage_frame_nv12
-        if (H < 2 || W < 2 || ((H | W) & 1)) return fail(h, VNECT_E_ARG, w_ + "an NV12 frame needs even W and H (>= 2)");
-        if (f->stride_y < (int64_t)W || f->uv_stride < (int64_t)W) return fail(h, VNECT_E_ARG, w_ + "stride_y and uv_stride must be at least W");
-        if (f->stride_y > ((int64_t)1 << 32) || f->uv_stride > ((int64_t)1 << 32)) return fail(h, VNECT_E_ARG, w_ + "stride out of range");
-        span = (size_t)(H - 1) * (size_t)f->stride_y + (size_t)W, uv_span = (size_t)(H / 2 - 1) * (size_t)f->uv_stride + (size_t)W;
-        const uint8_t *y = (const uint8_t*)f->data, *uv = (const uint8_t*)f->uv;
-        if (y < uv + uv_span && uv < y + span) return fail(h, VNECT_E_ARG, w_ + "the UV plane overlaps the Y plane");
-    } else {
-        if (f->stride_y < 1 || f->stride_x < 1 || f->stride_c < 1) return fail(h, VNECT_E_ARG, w_ + "strides must be positive (flip or broadcast on the device first)");
-        if (f->stride_y > ((int64_t)1 << 32) || f->stride_x > ((int64_t)1 << 32) || f->stride_c > ((int64_t)1 << 36)) return fail(h, VNECT_E_ARG, w_ + "stride out of range");
-        span = (size_t)ingest_span(H, W, f->stride_y, f->stride_x, f->stride_c);
-    }
-    int r[4] = {0, 0, W, H};
-    if (f->has_rect) {
-        if (!allow_rect) return fail(h, VNECT_E_ARG, w_ + "a tracked frame takes no rect: the crop is the stream's box on the device");
-        for (int k = 0; k < 4; k++) r[k] = f->rect[k];
-        if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H) return fail(h, VNECT_E_ARG, w_ + "the rect's origin must lie inside the frame");
-        if (r[2] < 1 || r[3] < 1) return fail(h, VNECT_E_ARG, w_ + "the rect must be at least one pixel wide and high");
-        r[2] = std::min(r[2], W - r[0]), r[3] = std::min(r[3], H - r[1]);
-    }
-    if (allow_rect && (size_t)r[2] * r[3] * 3 > (size_t)h->cfg.max_frame_bytes)
-        return fail(h, VNECT_E_ARG, w_ + "frame larger than max_frame_bytes (the slot holds BGR: 3 bytes per pixel)");
-    const uint8_t *lo = nullptr, *end = nullptr, *uv_lo = nullptr, *uv_end = nullptr;
-    int rc = device_range(h, f->data, w_, "data", &lo, &end);
-    if (rc) return rc;
-    if ((size_t)(end - (const uint8_t*)f->data) < span)
-        return fail(h, VNECT_E_ARG, w_ + "the frame's last byte lies past the end of the allocation `data` points into (at these strides)");
-    if (nv12) {
-        if ((rc = device_range(h, f->uv, w_, "uv", &uv_lo, &uv_end))) return rc;
-        if ((size_t)(uv_end - (const uint8_t*)f->uv) < uv_span) return fail(h, VNECT_E_ARG, w_ + "the UV plane's last byte lies past the end of the allocation `uv` points into");
-    }
-    DeviceFrame d;
-    d.nv12 = nv12, d.H = H, d.W = W, d.producer = producer_stream;
-    for (int k = 0; k < 4; k++) d.r[k] = r[k];
-    if (nv12) {
-        d.nv = {(const uint8_t*)f->data, (long long)f->stride_y, (const uint8_t*)f->uv, (long long)f->uv_stride, lo, end};
-        d.nv.uv_lo = uv_lo, d.nv.uv_end = uv_end, d.nv.any_bounds = 1;
-    } else {
-        d.ing = {(const uint8_t*)f->data, (long long)f->stride_y, (long long)f->stride_x, (long long)f->stride_c, lo, end,
-                 f->format == VNECT_PIX_RGB ? INGEST_RGB : INGEST_BGR};
-    }
-    *out = d;
-    return VNECT_OK;
-}
-
-// `consumer` waits for what has been enqueued on the producer's stream so far; the host does not
-int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer)
-{
-    if (producer_stream == VNECT_STREAM_SYNCED) return VNECT_OK;
-    if (!h->producer_ev) HIPCK(h, hipEventCreateWithFlags(&h->producer_ev, hipEventDisableTiming));
-    HIPCK(h, hipEventRecord(h->producer_ev, (hipStream_t)producer_stream));  // (NULL: HIP's default stream)
-    HIPCK(h, hipStreamWaitEvent(consumer, h->producer_ev, 0));
-    return VNECT_OK;
-}
-
-int stage_frame_device(vnect_handle* h, int slot, const DeviceFrame& f, hipStream_t st)
-{
-    if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
-    int rc = claim_slot(h, slot, (size_t)f.r[2] * f.r[3] * 3);
-    if (rc) return rc;
-    if (!st) st = h->st;
-    if ((rc = wait_for_producer(h, f.producer, st))) return rc;
-    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    if (f.nv12) HIPCK(h, launch_nv12_copy(f.nv, f.r[0], f.r[1], f.r[2], f.r[3], dst, st));
-    else HIPCK(h, launch_ingest_copy(f.ing, f.H, f.W, f.r[0], f.r[1], f.r[2], f.r[3], dst, st));
-    h->slots[slot].H = f.r[3], h->slots[slot].W = f.r[2], h->slots[slot].stride = 3LL * f.r[2];
-    return VNECT_OK;
-}
-
-// vnect_upload_frame_device / vnect_preprocess_device: done with the caller's buffer on return.  On upload_st, like upload_nv12_impl: it
-// waits only for the slot's last reader (claim_slot) and for the producer
-int upload_device_impl(vnect_handle* h, int slot, const DeviceFrame& f)
-{
-    if (slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
-    if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
-    int rc = stage_frame_device(h, slot, f, h->upload_st);
-    if (rc) return rc;
-    HIPCK(h, hipStreamSynchronize(h->upload_st));
-    return VNECT_OK;
-}
-
-int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride)
-{
-    if (!bgr || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
-    if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return fail(h, VNECT_E_ARG, "bad frame geometry");
-    if ((size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes) return fail(h, VNECT_E_ARG, "frame larger than max_frame_bytes");
-    int rc = claim_slot(h, slot, (size_t)H * W * 3);
-    if (rc) return rc;
-    uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    HIPCK(h, hipMemcpy2D(dst, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, H, hipMemcpyHostToDevice));
-    h->slots[slot].H = H, h->slots[slot].W = W, h->slots[slot].stride = (long long)W * 3;
     return VNECT_OK;
 }
 

@@ -1,10 +1,12 @@
 // runtime.h -- internal header of the host runtime of libvnect_hip.so (not part of the ABI: include/vnect_abi.h is).
-// The runtime is four translation units along its seams (round 6; one 2 300-line file before):
-//   rt_plan.cpp  weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables,
-//                the further plans built from lane 0's (lanes, batched plans)
-//   rt_exec.cpp  running frames: launch sequences, hipGraph, lanes, streams, submit / collect, staging, warm start, roctx ranges
-//   rt_comm.cpp  the pyramid exchange: RCCL (dlopen'ed) and peer writes, vnect_comm_*
-//   rt_abi.cpp   the extern "C" entry points of include/vnect_abi.h (argument checks, device selection, the no-exception guard)
+// The runtime is five translation units along its seams:
+//   rt_plan.cpp    weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables,
+//                  the further plans built from lane 0's (lanes, batched plans)
+//   rt_exec.cpp    running frames: launch sequences, hipGraph, lanes, streams, submit / collect, warm start, roctx ranges
+//   rt_ingest.cpp  frames into slots: one resolver per source (host BGR, host NV12, device memory, a pinned buffer by index) that validates
+//                  the caller's frame into a FrameSrc, the pinned staging buffers, and ingest(), the one way from a FrameSrc into a slot
+//   rt_comm.cpp    the pyramid exchange: RCCL (dlopen'ed) and peer writes, vnect_comm_*
+//   rt_abi.cpp     the extern "C" entry points of include/vnect_abi.h (argument checks, device selection, the no-exception guard)
 #pragma once
 #include <dlfcn.h>
 #include <link.h>
@@ -182,15 +184,14 @@ struct vnect_handle : Plan {
     std::vector<Plan*> bplans;  // two video streams per launch: the batched plan once per lane, bplans[i] on lanes[i]'s stream
     // pre/post
     uint8_t* frames = nullptr;  // num_frame_slots * max_frame_bytes
-    // vnect_infer's way from host memory to slot 0: pinned (page-locked) buffers.  [0], [1] are the caller's capture buffers
-    // (vnect_frame_buffer; they only move when the caller asks for a larger one): a frame that lies inside one of them is copied to the
-    // device straight from there.  Any other pointer is first copied into [2] by the CPU (grown on demand; vnect_infer is synchronous,
-    // so one suffices).  The device copy is asynchronous on the frame's stream: nothing synchronises between it and the frame's first kernel.
+    // A host frame's way to a slot: pinned (page-locked) buffers.  [0], [1] are the caller's capture buffers (vnect_frame_buffer; they
+    // only move when the caller asks for a larger one): a frame that lies inside one of them is copied to the device straight from there.
+    // Any other pointer is first copied into [2] by the CPU (grown on demand; its users are synchronous, so one suffices).
     uint8_t* stage[3] = {};
     uint8_t* stage_dev[3] = {};  // the same buffers as the device addresses them (hipHostMallocMapped)
     size_t stage_cap[3] = {};
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
-    hipStream_t upload_st = nullptr;  // vnect_upload_frame_nv12's conversion kernel (made on first use): not a lane's compute stream
+    hipStream_t upload_st = nullptr;  // ingest_sync's copy kernel (made on first use): not a lane's compute stream
     hipEvent_t producer_ev = nullptr; // a device frame's producer stream -> the stream that ingests it (wait_for_producer; made on first use)
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
     std::vector<SlotInfo> slots;
@@ -348,51 +349,50 @@ void commit_time(Stream& s, double t2d, double t3d);
 int reset_filters_impl(vnect_handle* h, int stream = -1);  // -1: every stream
 void roctx_load();
 int build_graph(Plan* p);
-// a validated vnect_device_frame (check_device_frame): what the ingest kernels take, the crop clipped to the frame
-struct DeviceFrame {
-    bool nv12 = false;
-    IngestSrc ing{};          // BGR / RGB
-    Nv12Src nv{};             // NV12: both planes with their allocations' bounds
+// A validated frame as the copy kernels address it: what a resolver of rt_ingest.cpp makes of the caller's arguments, what ingest() puts
+// into a slot and what a tracked submit (enqueue_frame) cuts the stream's crop out of
+enum FrameWhere {
+    SRC_SLOT,        // a resident slot (vnect_submit_tracked; nothing to copy)
+    SRC_PINNED_BGR,  // BGR rows in pinned host memory: a caller's buffer (vnect_frame_buffer) or the internal stage
+    SRC_NV12,        // NV12 planes, in pinned host memory or in the caller's device memory (they differ in the bounds of `nv` and in `producer`)
+    SRC_DEVICE       // BGR / RGB at any strides in the caller's device memory
+};
+struct PinnedBgr {
+    const uint8_t* data;  // the frame's first byte as the device addresses it
+    long long stride;     // its row stride
+    const uint8_t* end;   // end of the pinned buffer it lies in
+};
+struct FrameSrc {
+    FrameWhere where = SRC_SLOT;
     int H = 0, W = 0;
-    int r[4] = {0, 0, 0, 0};  // (x, y, w, h)
-    void* producer = nullptr; // the producer's stream as the caller gave it
+    int r[4] = {0, 0, 0, 0};  // the crop (x, y, w, h), clipped to the frame (a tracked frame: the whole frame)
+    PinnedBgr bgr{};          // the kernel argument block of its kind: SRC_PINNED_BGR,
+    Nv12Src nv{};             // SRC_NV12,
+    IngestSrc ing{};          // SRC_DEVICE
+    void* producer = VNECT_STREAM_SYNCED;  // a device frame's producer stream as the caller gave it; every host source is synced
 };
-// a tracked frame (vnect_submit_tracked*): the whole frame in a resident slot (pinned_dev == nullptr) or in a pinned buffer
-struct TrackedSrc {
-    const uint8_t* pinned_dev = nullptr;  // the frame as the device addresses it
-    const uint8_t* pinned_end = nullptr;  // end of its pinned buffer
-    long long stride = 0;                 // its row stride
-    // an NV12 frame (vnect_submit_tracked_pinned_nv12): pinned_dev is the Y plane (rows `stride` apart), converted to BGR by the copy
-    bool nv12 = false;
-    const uint8_t* uv_dev = nullptr;      // the interleaved U, V plane
-    long long uv_stride = 0;
-    const uint8_t* pinned_lo = nullptr;   // start of the pinned buffer
-    // a frame in the caller's DEVICE memory (vnect_submit_tracked_device): pinned_dev is its first byte, everything else is here
-    const DeviceFrame* dev = nullptr;
-};
-int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const TrackedSrc* tk = nullptr);
+// tk: a tracked frame (vnect_submit_tracked*) -- in `slot` (SRC_SLOT) or where tk says (slot is -1 then)
+int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const FrameSrc* tk = nullptr);
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
 int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4);
-int ensure_stage(vnect_handle* h, int i, size_t bytes);
-int stage_frame(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
-int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
-// an NV12 frame (Y rows y_stride apart, U/V rows uv_stride apart), or its crop rect4 = (x, y, w, h), converted to BGR on its way into
-// `slot` by a kernel on the handle's stream (asynchronous, like stage_frame); upload_nv12_impl also waits for it (like upload_frame_impl)
-int stage_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                     const int32_t* rect4, const char* who, hipStream_t st = nullptr);  // st: nullptr = the handle's stream
-int upload_nv12_impl(vnect_handle* h, int slot, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                     const int32_t* rect4, const char* who);
-// Frames in the caller's device memory (vnect_infer_device and its kin).  check_device_frame validates everything -- the descriptor, the
-// pointers (device memory of the handle's device, the frame's span inside its allocation), the rect, the slot's room -- and changes
-// nothing; stage_frame_device makes `st` (nullptr: the handle's stream) wait for the producer and launches the copy (asynchronous, like
-// stage_frame); upload_device_impl runs it on upload_st and waits for it (like upload_nv12_impl)
-int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, DeviceFrame* out);
-int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer);
-int stage_frame_device(vnect_handle* h, int slot, const DeviceFrame& f, hipStream_t st = nullptr);
-int upload_device_impl(vnect_handle* h, int slot, const DeviceFrame& f);
 int prime(vnect_handle* h);
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 int forward_batch(vnect_handle* h, const float* batch, float* out);
+
+// ---- rt_ingest.cpp -------------------------------------------------------------------------------------------------------------
+// The resolvers: each validates everything and refuses with the entry point's name (`who`) in front; the host ones then copy a pageable
+// frame into the internal stage.  Nothing else changes.
+int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, FrameSrc* out);
+int resolve_host_nv12(vnect_handle* h, const char* who, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
+                      const int32_t* rect4, FrameSrc* out);  // rect4: nullptr, or the crop (x, y, w, h)
+int resolve_pinned_bgr(vnect_handle* h, const char* who, int index, int H, int W, int64_t row_stride, FrameSrc* out);
+int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int W, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, FrameSrc* out);
+int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, FrameSrc* out);
+int ingest(vnect_handle* h, int slot, const FrameSrc& src, hipStream_t st = nullptr);  // asynchronous on st (nullptr: the handle's stream)
+int ingest_sync(vnect_handle* h, int slot, const FrameSrc& src);                       // on upload_st, done on return
+int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
+int ensure_stage(vnect_handle* h, int i, size_t bytes);
+int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);
