@@ -9,6 +9,9 @@ Sharpness: over elements with y != 0, the fraction where gpu == RNE_fp16(float32
 does not carry over: fp16's half ulp is 8x closer to the fp32 accumulation error, so a correct launch sits on the other side of a rounding
 midpoint 8x as often -- the CPU stand-in of tests/test_fp16_bounds_cpu.py measures 0.9962 at the lowest -- while a truncating or bf16-rounding
 store lands near 1/2.
+Overflow (FP16.md): the store rounds to nearest even, so a result of magnitude 65 520 or more is stored as +-inf.  check_overflow gates a
+tensor that holds such results: with b the larger of the two tiers' bounds, elements with |y| > 65 520 + b must be +-inf of y's sign,
+elements with |y| < 65 520 - b finite and within both bounds; the band between, where a correct launch may land on either side, is left out.
 """
 import numpy as np
 
@@ -18,6 +21,7 @@ from tests.layer_ref import TABLE, _nhwc, _ratio, _t64, maxpool_same
 UH = 2.0 ** -11
 SUB = 2.0 ** -25
 MATCH_FLOOR_F16 = 0.995
+F16_INF = 65520.0   # the midpoint between fp16's largest finite value, 65 504, and 2^16: it and everything beyond rounds to infinity
 
 
 def round_f16(a):
@@ -55,6 +59,24 @@ def check_tensor(name, gpu, r, f16_out):
         match = float(np.mean(gpu[nz] == round_f16(y[nz].astype(np.float32)))) if nz.any() else 1.0
     ok = rig <= 1.0 and cal <= 1.0 and (match is None or match >= MATCH_FLOOR_F16)
     return dict(tensor=name, rig=rig, cal=cal, match=match, ok=ok)
+
+
+def check_overflow(name, gpu, r):
+    """The overflow rule on one tensor of an fp16 handle (reference r): counts of the elements beyond, inside and below the band around
+    65 520, of those above 2^15, and whether the rule holds (ok)."""
+    y = r["y"]
+    assert gpu.shape == y.shape, (name, gpu.shape, y.shape)
+    rig_b, cal_b = bounds(r, True)
+    b = np.maximum(rig_b, cal_b)
+    over, under = np.abs(y) > F16_INF + b, np.abs(y) < F16_INF - b
+    with np.errstate(invalid="ignore"):
+        d = np.abs(gpu.astype(np.float64) - y)
+    inf_ok = bool(np.array_equal(gpu[over], np.where(y[over] > 0, np.inf, -np.inf).astype(np.float32)))
+    finite_ok = bool(np.all(np.isfinite(gpu[under])))
+    rig, cal = (_ratio(d[under], x[under]) for x in (rig_b, cal_b)) if finite_ok else (float("inf"), float("inf"))
+    return dict(tensor=name, over=int(over.sum()), band=int((~over & ~under).sum()), large=int((np.abs(y) > 2.0 ** 15).sum()),
+                stored_inf=int(np.isinf(gpu).sum()), inf_ok=inf_ok, finite_ok=finite_ok, rig=rig, cal=cal,
+                ok=inf_ok and finite_ok and rig <= 1.0 and cal <= 1.0)
 
 
 def check_all(acts, weights, batch, stem=False, table=TABLE):

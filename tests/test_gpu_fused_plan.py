@@ -156,6 +156,12 @@ def test_default_plans_are_unchanged(weights):
 
 @pytest.mark.parametrize("cid,prec,S,env,paper", CONFIGS, ids=[c[0] for c in CONFIGS])
 def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, monkeypatch, cid, prec, S, env, paper):
+    fused_equals_plain(weights, monkeypatch, cid, prec, S, env, paper, RESULTS, "fused_plan.json")
+
+
+def fused_equals_plain(weights, monkeypatch, cid, prec, S, env, paper, results, logname=None):
+    """The body of the test above, for any weights (tests/test_gpu_weight_families.py runs it on its families): every tensor the seam plan
+    stores equals the plain plan's, and the plain plan passes the per-element float64 gate.  Returns the plain plan's rows."""
     import oracle
     from tests import helpers, layer_ref_f16
     n = _native()
@@ -251,10 +257,12 @@ def test_every_stored_tensor_of_the_fused_plan_equals_the_plain_plans(weights, m
                 if L["M"] and L["tile_m"] == 64 and L["tile_n"] in (32, 64) and L["name"] != "conv1":
                     split.update(layer_ref.launch_tensors(L["name"], table=table))
         rows = layer_ref.check_all(acts, weights, prec, batch, split_tensors=split, table=table)
-    RESULTS[cid] = dict(prec=prec, scales=scales, env=env, paper_res2c=paper, fused_launches=names, stored=order, pinned=sorted(absorbed),
+    results[cid] = dict(prec=prec, scales=scales, env=env, paper_res2c=paper, fused_launches=names, stored=order, pinned=sorted(absorbed),
                         equal=order if approx_at is None else order[:approx_at], worst_of_max=dict(forward=worst_fwd, infer=worst_inf),
                         plain_rows=rows)
-    _log("fused_plan.json", RESULTS)
+    if logname:
+        _log(logname, results)
     assert len(rows) == len(table)
     bad = [r for r in rows if not r["ok"]]
     assert not bad, bad[:4]
+    return rows

@@ -46,6 +46,15 @@ WIRING_FAULTS = {
     "wiring_crossed": ("res2c_branch2b", "fp32", False),
 }
 
+# Faults that no tensor notices under synthetic_weights() -- they need weights the default family never draws -- and that fail on exactly
+# their own tensor under a family of tests/weight_families.py (tests/test_weight_families_cpu.py asserts both halves):
+# fault -> (tensor, precision, family).  (a) the BN epilogue multiplies by |scale| (the default gamma is positive), (b) an output
+# channel whose filter is all zeros is skipped together with its bias and comes out 0 (the default weights have no zero filter)
+FAMILY_FAULTS = {
+    "bn_abs": ("res5c_branch2a_feat", "fp32", "signed_bn"),
+    "dead_skip": ("res3b_branch2a", "bf16", "dead"),
+}
+
 
 # The fused launches of the one-scale bf16 product plan (h.layers() names; VNECT_FORCE_CHAIN gives fp32 the wide chains too), and the
 # stem in its PAIR form
@@ -94,12 +103,13 @@ def _low_channel(y):
 
 def device_forward(weights, batch, prec, fault=None, fused=False, paper=False):
     """Every tensor of TABLE (paper: of TABLE_PAPER; name -> NHWC float32 numpy) as a device with fp32 accumulation computes it; fault: a
-    key of FAULTS or of WIRING_FAULTS.  fused: as the launches of FUSED_LAUNCHES (FUSED_LAUNCHES_PAPER) and the PAIR stem compute them --
+    key of FAULTS, of WIRING_FAULTS or of FAMILY_FAULTS.  fused: as the launches of FUSED_LAUNCHES (FUSED_LAUNCHES_PAPER) and the PAIR stem compute them --
     the tensors of HIDDEN stay on chip and are not returned; fault: a key of FUSED_FAULTS (FUSED_FAULTS_PAPER)."""
     bf = prec == "bf16"
     lw = layer_ref.layer_weights(weights, prec)
     faults = ((FUSED_FAULTS_PAPER if paper else FUSED_FAULTS) if fused else
-              {k: v for k, v in WIRING_FAULTS.items() if v[2] == paper} if fault in WIRING_FAULTS else FAULTS)
+              {k: v for k, v in WIRING_FAULTS.items() if v[2] == paper} if fault in WIRING_FAULTS else
+              FAMILY_FAULTS if fault in FAMILY_FAULTS else FAULTS)
     assert fault is None or fault in faults, (fault, fused, paper)
     target = faults[fault][0] if fault else None
     # the graph the device runs: the asked wiring's table, but for the two wiring faults
@@ -186,6 +196,9 @@ def device_forward(weights, batch, prec, fault=None, fused=False, paper=False):
                 v = v + s
             if relu:
                 v = F.relu(v)
+            if fault == "dead_skip" and name == target:   # the columns of all-zero filters: not computed, bias and all
+                v = v.clone()
+                v[:, (wt.reshape(wt.shape[0], -1) != 0).sum(1) == 0] = 0
             if fault == "channel" and name == target:
                 ch = _low_channel(v)
                 info.update(channel=ch, ch_max=float(v[:, ch].abs().max()), layer_max=float(v.abs().max()))
@@ -197,6 +210,8 @@ def device_forward(weights, batch, prec, fault=None, fused=False, paper=False):
             d2 = F.conv_transpose2d(x, f32(lw["res5c_branch2a/kernel"]).permute(3, 2, 0, 1), stride=2, padding=1)
             d1 = F.conv_transpose2d(x, f32(lw["res5c_branch1a/kernel"]).permute(3, 2, 0, 1), stride=2, padding=1)
             bias, scale, shift = (f32(v).view(1, -1, 1, 1) for v in layer_ref.fold_bn(lw))
+            if fault == "bn_abs":
+                scale = scale.abs()
             bn = F.relu((d2 + bias) * scale + shift)
             deltas = _rne_bf16(d1) if bf else d1
             dx, dy, dz = deltas[:, 0:21], deltas[:, 21:42], deltas[:, 42:63]

@@ -7,32 +7,11 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tests import helpers
+from tests.weight_families import family as variant  # the one definition of the weight families
 from vnect_amd import _native
-from vnect_amd.weights import synthetic_weights, MASTER_SEED
+from vnect_amd.weights import MASTER_SEED
 
 SCALES = [1.0, 0.8, 0.6]
-
-
-def variant(kind, seed):
-    w = synthetic_weights(seed)
-    rng = np.random.RandomState(seed % (2 ** 31))
-    if kind == "channel_scales":      # every conv's output channels rescaled by 2^U(-2, 2): activations of very different magnitude per channel
-        for k in list(w):
-            if k.endswith("/weights"):
-                s = (2.0 ** rng.uniform(-2, 2, size=w[k].shape[-1])).astype(np.float32)
-                s /= np.sqrt(np.mean(s ** 2))                       # keep the layer's overall gain
-                w[k] = w[k] * s
-    elif kind == "heavy_tails":       # a few large weights per filter (cubed uniform, renormalised to the same variance)
-        for k in list(w):
-            if k.endswith("/weights") or k.endswith("/kernel"):
-                a = w[k].astype(np.float64)
-                b = a ** 3
-                w[k] = (b * (a.std() / max(b.std(), 1e-30))).astype(np.float32)
-    elif kind == "big_biases":
-        for k in list(w):
-            if k.endswith("/biases"):
-                w[k] = w[k] * 8.0
-    return w
 
 
 def maps(handle, batch):

@@ -3,7 +3,7 @@
       (a) synchronous frames, (c) three frames deep on three lanes;
   (2) per-layer kernel time of a profiled frame, fp16 against bf16 (profiling twin stamps, mean of 20 frames, vnect_get_layer_info);
   (3) final-map error against the fp32 handle, bf16 and fp16, over the nine weight sets of profiles/r06_bf16_gate_spread.txt
-      (tools/bf16_gate_spread.py: variant) on a smooth and a noise frame -- what tests/test_gpu_fp16.py's EPS16 is set from;
+      (tests/weight_families.py: family) on a smooth and a noise frame -- what tests/test_gpu_fp16.py's EPS16 is set from;
   (4) the largest |activation| of every weight family (fp32 handle, every readable tensor): where fp16's range (65 504) would show first.
     python3 tools/fp16_rate.py > profiles/fp16_rate.txt"""
 import os
@@ -13,9 +13,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 
-from bf16_gate_spread import variant  # noqa: E402
 from stream_batch_rate import deep_single, layer_table, sync_single  # noqa: E402
 from tests import helpers, layer_ref  # noqa: E402
+from tests.weight_families import family as variant  # noqa: E402
 from vnect_amd import _native  # noqa: E402
 from vnect_amd.weights import MASTER_SEED, synthetic_weights  # noqa: E402
 
