@@ -326,6 +326,43 @@ int vnect_preprocess_device(vnect_handle* h, const vnect_device_frame* frame, vo
                             int32_t* offset_x, int32_t* offset_y);
 int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d);
 
+/* ABI v7, additive.  The skeleton and the crop rectangle drawn into a frame in DEVICE memory (OVERLAY.md).  The reference's frame loop
+ * draws into the frame it has just estimated (run_estimator_ps.py:92-94: utils.draw_limbs_2d, src/utils.py:222-243 -- an ellipse of
+ * half-axes (length / 2, 3) per limb, then the crop rectangle, thickness 4) with cv2 on the host; these entry points draw the same shapes
+ * with one kernel launch into a vnect_device_frame, by an exact rule of this project's own (vnect_amd/csrc/overlay.h: float64 multiplies,
+ * adds and compares only, so the host, numpy and the device agree bit for bit; cv2 itself rounds the angle to whole degrees and cannot be
+ * pinned here).  Every layout vnect_device_frame describes is written where it lies: packed 3-byte, packed 4-byte (the fourth byte is
+ * never written), planar, any positive strides, BGR or RGB order; NV12 gets Y per pixel and a 2 x 2 block's chroma sample if any of its
+ * four pixels is drawn (the rect's colour wins), the colours converted once by BT.601 limited range in 8-bit integer arithmetic.  A pixel
+ * that no shape covers is not written, nor is any byte that is no pixel of the frame.
+ * The style, a vnect_overlay_style -- NULL: the reference's colours and parents, no threshold: limb_bgr / rect_bgr, 0 .. 255 each; min_confidence: a
+ * limb is left out when the confidence of either of its joints lies below it (NaN: no threshold); parents[i] (with has_parents; 0 .. 20):
+ * the joint limb i joins joint i to -- a joint that is its own parent has no limb.
+ * vnect_draw_device: joints_2d (21 x 2 float64 [row, col] in the target's coordinates; non-finite or beyond 2^20: its limbs are left out),
+ * confidence21 (or NULL: no threshold applies), rect4 = (x, y, w, h) or NULL (no rectangle) into `target`.  `stream` is a producer_stream:
+ * the draw is ordered behind what has been enqueued there (NULL: HIP's default stream; VNECT_STREAM_SYNCED: wait for nothing).  Returns
+ * when the draw is done.  Works on a preprocess_only handle and before vnect_finalize too.  VNECT_E_ARG, before anything is written: what
+ * vnect_upload_frame_device refuses of a frame (a host pointer, a last byte outside the allocation, ...); target->has_rect; a parent
+ * outside 0 .. 20; a rect with w < 1 or h < 1; a colour outside 0 .. 255; a wrong struct_size.
+ * vnect_submit_tracked_device_draw: vnect_submit_tracked_device, plus one overlay launch on the frame's stream behind its box stage and in
+ * front of its completion: `frame` itself is drawn into, as cv2 draws into the reference's `frame` -- with the frame's own joints in frame
+ * coordinates, the rect it was cropped with and (with a threshold) its confidences, all read on the device; a frame whose crop was refused
+ * is not drawn.  THE BUFFER IS WRITTEN UNTIL THE FRAME HAS BEEN COLLECTED: keep it alive and read it only after vnect_collect_tracked has
+ * delivered the frame, which is annotated then.  Joints, rects, confidences and filter states are bit-identical to
+ * vnect_submit_tracked_device; its refusals and rollback are that call's, plus the style's (checked before anything changes). */
+typedef struct vnect_overlay_style {
+    int32_t struct_size;     /* = sizeof(vnect_overlay_style) */
+    int32_t limb_bgr[3];     /* (49, 22, 122): src/utils.py:236 */
+    int32_t rect_bgr[3];     /* (60, 66, 207): src/utils.py:241 */
+    double min_confidence;
+    int32_t parents[VNECT_JOINTS];
+    int32_t has_parents;     /* 0: the reference's (src/estimator.py joint_parents) */
+} vnect_overlay_style;
+int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* joints_2d, const double* confidence21,
+                      const int32_t* rect4, const vnect_overlay_style* style);
+int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                                     const vnect_overlay_style* style);
+
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
  * per call, :84).  Values travel as float64; values_are_f32 = 1 says they are numpy float32 scalars -- what the reference

@@ -60,6 +60,35 @@ class DeviceFrame(C.Structure):
                 ("uv_stride", C.c_int64), ("has_rect", C.c_int32), ("rect", C.c_int32 * 4)]
 
 
+LIMB_BGR, RECT_BGR = (49, 22, 122), (60, 66, 207)   # the reference's colours (src/utils.py:236, 241)
+
+
+class OverlayStyle(C.Structure):
+    """vnect_overlay_style: colours, confidence threshold and parents of a draw (include/vnect_abi.h; OVERLAY.md)."""
+    _fields_ = [("struct_size", C.c_int32), ("limb_bgr", C.c_int32 * 3), ("rect_bgr", C.c_int32 * 3), ("min_confidence", C.c_double),
+                ("parents", C.c_int32 * 21), ("has_parents", C.c_int32)]
+
+
+def overlay_style(min_confidence=None, colors=None, parents=None):
+    """The OverlayStyle of a draw.  min_confidence None: no threshold; colors: None, or (limb_bgr, rect_bgr) -- either may be None for the
+    reference's; parents: None for the reference's joint_parents, or 21 joint indices."""
+    s = OverlayStyle()
+    s.struct_size = C.sizeof(OverlayStyle)
+    limb, rect = (None, None) if colors is None else colors
+    for k in range(3):
+        s.limb_bgr[k] = int((LIMB_BGR if limb is None else limb)[k])
+        s.rect_bgr[k] = int((RECT_BGR if rect is None else rect)[k])
+    s.min_confidence = float("nan") if min_confidence is None else float(min_confidence)
+    if parents is not None:
+        parents = [int(v) for v in parents]
+        if len(parents) != 21:
+            raise ValueError("parents must name one joint for each of the 21 joints")
+        s.has_parents = 1
+        for k, v in enumerate(parents):
+            s.parents[k] = v
+    return s
+
+
 class DeviceFrameError(VnectError, ValueError):
     """VNECT_E_ARG of a device-frame entry point: the frame as given cannot be read (a ValueError, like every refused argument)."""
 
@@ -122,6 +151,9 @@ SYMBOLS = {
     "vnect_infer_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double, _f64p, _f32p]),
     "vnect_preprocess_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, _f32p, _f64p, _i32p, _i32p]),
     "vnect_submit_tracked_device": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double]),
+    "vnect_draw_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, _f64p, _f64p, _i32p, C.POINTER(OverlayStyle)]),
+    "vnect_submit_tracked_device_draw": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
+                                                   C.POINTER(OverlayStyle)]),
 }
 
 
@@ -135,6 +167,8 @@ NV12PROBE_LIB = os.path.join(_HERE, "lib", "libvnect_nv12probe.so")       # post
 NV12_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_nv12.so")             # g++'s build of csrc/nv12.h (tests only; no GPU code)
 INGESTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_ingestprobe.so")   # post.o + track.o behind csrc/ingest_probe.hip (tests only)
 INGEST_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_ingest.so")         # g++'s build of csrc/ingest.h (tests only; no GPU code)
+OVERLAYPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_overlayprobe.so") # overlay.o behind csrc/overlay_probe.hip (tests only)
+OVERLAY_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_overlay.so")       # g++'s build of csrc/overlay.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -151,6 +185,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "nv12probe", "nv12"], stdout=subprocess.DEVNULL)
     # the device-frame copies' probe (tests/test_gpu_device_ingest_kernels.py) and g++'s build of their lane windows (tests/test_device_frames_cpu.py)
     subprocess.check_call(["make", "-C", src, "ingestprobe", "ingest"], stdout=subprocess.DEVNULL)
+    # the overlay's probe (tests/test_gpu_overlay_kernels.py) and g++'s build of the drawing rule (tests/test_overlay_cpu.py)
+    subprocess.check_call(["make", "-C", src, "overlayprobe", "overlay"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -464,6 +500,27 @@ class Handle:
         """The stream's next frame, the whole frame in device memory (`frame`: a DeviceFrame without a rect).  The buffer is read when the
         frame runs: keep it alive and untouched until the frame has been collected."""
         self._ck_device(lib().vnect_submit_tracked_device(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d))
+
+    # -- the overlay: skeleton and crop rectangle drawn into a frame in device memory (include/vnect_abi.h; OVERLAY.md) -------------------
+    def draw_device(self, frame, joints_2d, rect=None, confidence=None, style=None, stream=None):
+        """vnect_draw_device: draws into `frame` (a DeviceFrame without a rect); done on return."""
+        j2 = np.ascontiguousarray(joints_2d, dtype=np.float64)
+        if j2.shape != (21, 2):
+            raise ValueError("joints_2d must be (21, 2)")
+        cf = None
+        if confidence is not None:
+            cf = np.ascontiguousarray(confidence, dtype=np.float64)
+            if cf.shape != (21,):
+                raise ValueError("confidence must be (21,)")
+        self._ck_device(lib().vnect_draw_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(j2, _f64p),
+                                                None if cf is None else _ptr(cf, _f64p), _rect4(rect),
+                                                None if style is None else C.byref(style)))
+
+    def submit_tracked_device_draw(self, stream, frame, t2d, t3d, producer=None, style=None):
+        """submit_tracked_device, and the frame is annotated in place with its own joints and crop rect by the time it is collected: the
+        buffer is WRITTEN until then."""
+        self._ck_device(lib().vnect_submit_tracked_device_draw(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d,
+                                                               None if style is None else C.byref(style)))
 
     def read_frame(self, slot):
         """The (H, W, 3) BGR frame resident slot `slot` holds (a debugging read)."""

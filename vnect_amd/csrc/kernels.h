@@ -343,6 +343,15 @@ hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsi
 hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
                              int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf = nullptr, const TrackPolicy* pol = nullptr);
 
+// ---- the overlay (overlay.hip; vnect_draw_device / vnect_submit_tracked_device_draw; OVERLAY.md) -----------------------------------
+// utils.draw_limbs_2d (src/utils.py:222-243; run_estimator_ps.py:92-94) into a frame in device memory, by the rule of overlay.h.  One
+// launch; the grid is fixed by the frame's size.  jo / to (both or neither) and co: the tracked form -- joints in frame coordinates,
+// rect_used + status and (with a threshold in `in`) confidences are read from a frame's result-ring slot, which the box stage in front of
+// this launch filled; a frame whose status is not SQ_OK is not drawn.  Otherwise they come from `in`.  The parents always come from `in`.
+struct OverlayTarget;
+struct OverlayInput;
+hipError_t launch_overlay(const OverlayTarget& t, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
+
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);
 

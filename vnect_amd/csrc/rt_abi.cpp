@@ -916,6 +916,35 @@ int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_
     });
 }
 
+int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                                     const vnect_overlay_style* style)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
+            static const char* who = "vnect_submit_tracked_device_draw";
+            OverlayTarget t;
+            OverlayInput in;
+            int rc = check_draw(h, who, frame, producer_stream, style, &t, &in, s);
+            if (rc) return rc;
+            if (s->H != h->streams[stream].track_H || s->W != h->streams[stream].track_W)
+                return fail(h, VNECT_E_ARG, std::string(who) + ": the frame is not of the size vnect_track_begin gave for this stream");
+            s->draw = true, s->draw_target = t, s->draw_in = in;
+            return (int)VNECT_OK;
+        });
+    });
+}
+
+int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* joints_2d, const double* confidence21,
+                      const int32_t* rect4, const vnect_overlay_style* style)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return draw_device_impl(h, target, stream, joints_2d, confidence21, rect4, style);
+    });
+}
+
 int vnect_read_frame(vnect_handle* h, int slot, uint8_t* out, int64_t capacity, int32_t* hw2)
 {
     return guarded(&h, [&]() -> int {

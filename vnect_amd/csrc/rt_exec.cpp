@@ -370,6 +370,9 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
         if (tk)
             HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st, cdev, h->d_policy + stream, h->h_conf_dev + ring));
     }
+    // run_estimator_ps.py:92-94: the frame itself annotated with its own joints and the rect it was cropped with, read from its ring slot
+    if (tk && tk->draw)
+        HIPCK(h, launch_overlay(tk->draw_target, tk->draw_in, e.out_dev, h->h_tout_dev + ring, tk->draw_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
     HIPCK(h, hipEventRecord(e.done, L->st));
     // only now: every launch of the frame has been accepted

@@ -1,10 +1,11 @@
 // runtime.h -- internal header of the host runtime of libvnect_hip.so (not part of the ABI: include/vnect_abi.h is).
-// The runtime is five translation units along its seams:
+// The runtime is six translation units along its seams:
 //   rt_plan.cpp    weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables,
 //                  the further plans built from lane 0's (lanes, batched plans)
 //   rt_exec.cpp    running frames: launch sequences, hipGraph, lanes, streams, submit / collect, warm start, roctx ranges
 //   rt_ingest.cpp  frames into slots: one resolver per source (host BGR, host NV12, device memory, a pinned buffer by index) that validates
 //                  the caller's frame into a FrameSrc, the pinned staging buffers, and ingest(), the one way from a FrameSrc into a slot
+//   rt_draw.cpp    frames out: the overlay drawn into a caller's device frame (overlay.h), on its own or as the tail of a tracked frame
 //   rt_comm.cpp    the pyramid exchange: RCCL (dlopen'ed) and peer writes, vnect_comm_*
 //   rt_abi.cpp     the extern "C" entry points of include/vnect_abi.h (argument checks, device selection, the no-exception guard)
 #pragma once
@@ -29,6 +30,7 @@
 #include "hostplan.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "overlay.h"
 
 namespace vnect {
 namespace rt {
@@ -370,6 +372,10 @@ struct FrameSrc {
     Nv12Src nv{};             // SRC_NV12,
     IngestSrc ing{};          // SRC_DEVICE
     void* producer = VNECT_STREAM_SYNCED;  // a device frame's producer stream as the caller gave it; every host source is synced
+    // a tracked device frame that is also drawn into (vnect_submit_tracked_device_draw): one overlay launch behind its box stage
+    bool draw = false;
+    OverlayTarget draw_target{};
+    OverlayInput draw_in{};  // the style: parents, threshold (joints, rect and confidences are read from the ring slot)
 };
 // tk: a tracked frame (vnect_submit_tracked*) -- in `slot` (SRC_SLOT) or where tk says (slot is -1 then)
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const FrameSrc* tk = nullptr);
@@ -393,6 +399,13 @@ int ingest_sync(vnect_handle* h, int slot, const FrameSrc& src);                
 int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
 int ensure_stage(vnect_handle* h, int i, size_t bytes);
 int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consumer);
+
+// ---- rt_draw.cpp ---------------------------------------------------------------------------------------------------------------
+// validates a draw's target (check_device_frame; a rect is refused) and style, and describes them; src_out (may be null): the frame as a source
+int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style, OverlayTarget* t,
+               OverlayInput* in, FrameSrc* src_out);
+int draw_device_impl(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* j2d, const double* conf, const int32_t* rect4,
+                     const vnect_overlay_style* style);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);

@@ -214,6 +214,19 @@ class VNectEstimator:
         res = self._h.collect()
         return res + (self._h.result_confidence()[0],) if return_confidence else res
 
+    def draw(self, frame, joints_2d, rect=None, confidence=None, pixel_format="bgr", min_confidence=None, colors=None, stream=None):
+        """Additive (OVERLAY.md): the reference's ``utils.draw_limbs_2d`` (src/utils.py:222-243; run_estimator_ps.py:92-94) on a frame in
+        DEVICE memory -- anything with ``__cuda_array_interface__``, in every layout the estimator reads (``pixel_format`` "bgr", "rgb" or
+        "nv12") -- drawn IN PLACE by one kernel launch, and returned.  ``joints_2d``: (21, 2) [row, col] in the frame's coordinates;
+        ``rect``: (x, y, w, h) or None; ``min_confidence`` with ``confidence`` (21,): limbs with an end below it are left out;
+        ``colors``: (limb_bgr, rect_bgr), either None for the reference's.  The pixels are those of ``render.draw_limbs_2d_exact``."""
+        if not _native.is_device_array(frame):
+            raise ValueError("draw() takes a frame in device memory; render.draw_limbs_2d_exact draws into host arrays")
+        self._format(pixel_format, None, True)
+        style = _native.overlay_style(min_confidence, colors, self.joint_parents)
+        self._h.draw_device(_native.device_frame(frame, pixel_format), joints_2d, rect, confidence, style, stream)
+        return frame
+
     def frame_buffer(self, height, width, index=0, pixel_format="bgr"):
         """Additive: a (height, width, 3) uint8 array in PINNED host memory (two exist, ``index`` 0 / 1).  Capture into it
         (``cap.read(buf)``, ``buf[...] = frame``) and pass it -- or a crop of it, as the tracking loop does -- to the estimator: the

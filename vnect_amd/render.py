@@ -35,6 +35,76 @@ def draw_limbs_2d(img, joints_2d, limb_parents, rect):
     return _back(pil)
 
 
+def _limb_half_axis(L2):
+    """The largest integer a >= 0 with 4 a^2 <= L2: int(length / 2) of src/utils.py:233, independent of how sqrt rounds."""
+    a = np.floor(np.sqrt(L2) * 0.5)
+    if 4.0 * a * a > L2:
+        a -= 1.0
+    if 4.0 * (a + 1.0) * (a + 1.0) <= L2:
+        a += 1.0
+    return a
+
+
+def draw_limbs_2d_exact(img, joints_2d, limb_parents, rect, pixel_format="bgr", confidence=None, min_confidence=None, colors=None,
+                        inplace=False):
+    """``draw_limbs_2d`` by the exact rule the device draws with (OVERLAY.md; vnect_amd/csrc/overlay.h): pixel-identical to
+    ``VNectEstimator.draw`` and to the frames ``track_on_device(..., draw=True)`` leaves.  A limb is the ellipse of half-axes
+    (a, 3) along it (src/utils.py:232-235) tested per pixel in float64 -- no angle, hence no rounding of it to whole degrees as in
+    cv2.ellipse2Poly: alike, not identical, to the reference's picture -- and the rectangle is a band of thickness 4 (:241), drawn over
+    the limbs.  ``img``: a uint8 (H, W, 3) host array, any strides; ``pixel_format`` "bgr" or "rgb"; ``rect`` (x, y, w, h) or None;
+    ``min_confidence`` with ``confidence`` (21,): limbs with an end below it are left out; ``colors``: (limb_bgr, rect_bgr), either None
+    for the reference's.  Returns an annotated copy, or with ``inplace=True`` draws into ``img`` itself and returns it."""
+    if pixel_format not in ("bgr", "rgb"):
+        raise ValueError("pixel_format must be 'bgr' or 'rgb'")
+    out = img if inplace else np.array(img, copy=True)
+    if out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 3:
+        raise ValueError("frame must be a uint8 (H, W, 3) array")
+    H, W = out.shape[:2]
+    limb, box = (None, None) if colors is None else colors
+    limb = tuple(int(v) for v in (LIMB_BGR if limb is None else limb))
+    box = tuple(int(v) for v in (RECT_BGR if box is None else box))
+    if pixel_format == "rgb":
+        limb, box = limb[::-1], box[::-1]
+    j = np.asarray(joints_2d, np.float64)
+    thr = None if (min_confidence is None or confidence is None or np.isnan(min_confidence)) else float(min_confidence)
+    with np.errstate(all="ignore"):
+        for i, parent in enumerate(limb_parents):
+            parent = int(parent)
+            if not 0 <= parent < len(j):
+                raise ValueError("a parent must be a joint")
+            r1, c1, r2, c2 = (float(v) for v in (j[i, 0], j[i, 1], j[parent, 0], j[parent, 1]))
+            if not all(abs(v) <= 2.0 ** 20 for v in (r1, c1, r2, c2)):   # (NaN and +-inf fail the comparison)
+                continue
+            if thr is not None and (confidence[i] < thr or confidence[parent] < thr):
+                continue
+            dr, dc = np.float64(r1 - r2), np.float64(c1 - c2)
+            L2 = dr * dr + dc * dc
+            a = _limb_half_axis(L2)
+            if a < 1.0:
+                continue
+            cr, cc = float(np.rint((r1 + r2) * 0.5)), float(np.rint((c1 + c2) * 0.5))
+            m = max(a, 3.0)                                               # no pixel further than this from the centre can be inside
+            ya, yb = int(max(0.0, cr - m)), int(min(H - 1.0, cr + m))
+            xa, xb = int(max(0.0, cc - m)), int(min(W - 1.0, cc + m))
+            if yb < ya or xb < xa:
+                continue
+            u = (np.arange(ya, yb + 1, dtype=np.float64) - cr)[:, None]
+            v = (np.arange(xa, xb + 1, dtype=np.float64) - cc)[None, :]
+            s_, t_ = u * dr + v * dc, u * dc - v * dr
+            aa = a * a
+            inside = (s_ * s_) * 9.0 + (t_ * t_) * aa <= (aa * 9.0) * L2
+            out[ya:yb + 1, xa:xb + 1][inside] = limb
+    if rect is not None:
+        x0, y0, w, h = (int(v) for v in rect)
+        if w < 1 or h < 1:
+            raise ValueError("the rect must be at least one pixel wide and high")
+        ys, xs = np.arange(H)[:, None], np.arange(W)[None, :]
+        outer = (xs >= x0 - 2) & (xs <= x0 + w + 1) & (ys >= y0 - 2) & (ys <= y0 + h + 1)
+        inner = (xs >= x0 + 2) & (xs <= x0 + w - 3) & (ys >= y0 + 2) & (ys <= y0 + h - 3)
+        out[outer & ~inner] = box
+    return out
+
+
 def draw_limbs_3d(joints_3d, joint_parents, size=400, extent=500.0):
     """Orthographic front view of the 21x3 joints in mm (the reference's plot limits are +-500): uint8 BGR (size, size, 3)."""
     from PIL import Image, ImageDraw

@@ -157,7 +157,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
 
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
-                    confidence=False, lost=None):
+                    confidence=False, lost=None, draw=False):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -168,14 +168,17 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     is collected (no ``transpose``).  ``stream``: which of the handle's video streams (its filter bank).
     ``rect`` must start inside the frame (``track`` would slice from outside it); one that runs past the far edges is cropped as
     ``track`` crops it.  However the loop ends -- a refused crop, the caller's ``break``, an exception -- nothing stays in flight.
-    ``confidence`` / ``lost``: as in ``track``; the rule runs on the device (vnect_track_policy)."""
+    ``confidence`` / ``lost``: as in ``track``; the rule runs on the device (vnect_track_policy).
+    ``draw`` (``source="device"`` only; OVERLAY.md): True, or an ``_native.overlay_style(...)`` -- every frame is annotated IN PLACE with its
+    own joints and the rect it was cropped with (run_estimator_ps.py:92-94) by the time it is yielded; the results are those of
+    ``draw=False``, bit for bit."""
     for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
-                                    None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost):
+                                    None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw):
         yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr", confidence=False, lost=None):
+                         pixel_format="bgr", confidence=False, lost=None, draw=False):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
@@ -183,10 +186,16 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     the pinned buffer (or, ``source="resident"``, the whole frame on upload).
     ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
     afterwards); ``confidence=True`` appends
-    (confidence, lost flag) to every tuple."""
+    (confidence, lost flag) to every tuple.
+    ``draw``: as in ``track_on_device``."""
     from collections import deque
 
     from . import _native
+    if draw is not False and draw is not None and source != "device":
+        raise ValueError("draw= annotates frames in device memory: it needs source='device'")
+    style = None
+    if draw is not False and draw is not None:
+        style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
     nv12 = _nv12_checks(pixel_format, transpose, source)
     rule = lost_rule(lost)
     if source not in ("pinned", "resident", "device"):
@@ -258,7 +267,10 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 H, W = size_of(frame)
                 try:
                     if device:
-                        h.submit_tracked_device(streams[i], frame, t2d, t3d, frame._producer)
+                        if style is not None:
+                            h.submit_tracked_device_draw(streams[i], frame, t2d, t3d, frame._producer, style)
+                        else:
+                            h.submit_tracked_device(streams[i], frame, t2d, t3d, frame._producer)
                         held[count] = frame
                     elif source == "pinned":
                         b = count % 2                  # a frame captured into this buffer already (the view itself) is not copied
