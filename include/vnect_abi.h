@@ -363,6 +363,25 @@ int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* s
 int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
                                      const vnect_overlay_style* style);
 
+/* Orientation (ABI v7, additive; ORIENTATION.md).  The reference's loop has a `T` option for a camera that is mounted sideways: it turns
+ * every frame with np.rot90(frame, 3) before the crop (run_estimator_ps.py:57-62, 81-85; commented out beside it, an np.transpose
+ * variant).  Here the turn happens on the device, inside the copy that brings the crop into the slot, so only the crop moves.
+ * An orientation is a code o in 0 .. 7: the oriented picture of a stored (H, W) frame f is
+ *     g = np.rot90(f, o & 3);  if o & 4: g = g[:, ::-1]
+ * (0: as stored, the default; 3: the reference's T; 7: its np.transpose variant; 6: upside down; 4: a mirror).  Its size is (H, W) for an
+ * even o & 3 and (W, H) for an odd one.
+ * vnect_set_orientation sets the code for every frame SUBMITTED FROM NOW ON, through every entry point that takes a frame: vnect_infer,
+ * vnect_upload_frame, vnect_preprocess, their _nv12 / _nv12_rect / _device kin, and -- through the stream, below -- the tracked submits.
+ * Frames already in flight keep theirs.  The entry points keep taking the frame as it is STORED (H, W and the strides describe memory);
+ * everything else the caller gives or gets is in ORIENTED coordinates: rects, the tracked box, vnect_track_begin's (H, W), rect_used,
+ * joints_2d, and what vnect_draw_device draws.  Every result is bit-identical to the same entry point given the contiguous oriented copy
+ * of the frame (NV12: of the converted BGR frame; the chroma of an oriented pixel is that of the stored pixel it comes from).
+ * A resident slot holds the oriented frame from its upload on.  A tracked stream remembers the code in force at its vnect_track_begin and
+ * its submits use that one, so two videos with different orientations can share a handle; a stored frame whose oriented size is not the
+ * track's is refused as a wrong size is.  Works on a preprocess_only handle and before vnect_finalize.  VNECT_E_ARG: a code outside
+ * 0 .. 7; a pyramid-sharded handle.  Under a code other than 0, an NV12 draw target is refused with VNECT_E_ARG. */
+int vnect_set_orientation(vnect_handle* h, int orientation);
+
 /* Replaces VNectEstimator.joint_filter(joints, dim) (src/estimator.py:83-95) on its own: the handle's 2-D (dim 2: 21x2)
  * or 3-D (dim 3: 21x3) OneEuro bank applied to caller-supplied joints at timestamp t (the reference reads time.time() once
  * per call, :84).  Values travel as float64; values_are_f32 = 1 says they are numpy float32 scalars -- what the reference

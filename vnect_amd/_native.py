@@ -154,6 +154,7 @@ SYMBOLS = {
     "vnect_draw_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, _f64p, _f64p, _i32p, C.POINTER(OverlayStyle)]),
     "vnect_submit_tracked_device_draw": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
                                                    C.POINTER(OverlayStyle)]),
+    "vnect_set_orientation": (C.c_int, [_H, C.c_int]),
 }
 
 
@@ -169,6 +170,8 @@ INGESTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_ingestprobe.so")   # post
 INGEST_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_ingest.so")         # g++'s build of csrc/ingest.h (tests only; no GPU code)
 OVERLAYPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_overlayprobe.so") # overlay.o behind csrc/overlay_probe.hip (tests only)
 OVERLAY_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_overlay.so")       # g++'s build of csrc/overlay.h (tests only; no GPU code)
+ORIENTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_orientprobe.so")   # orient.o behind csrc/orient_probe.hip (tests only)
+ORIENT_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_orient.so")         # g++'s build of csrc/orient.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -187,6 +190,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "ingestprobe", "ingest"], stdout=subprocess.DEVNULL)
     # the overlay's probe (tests/test_gpu_overlay_kernels.py) and g++'s build of the drawing rule (tests/test_overlay_cpu.py)
     subprocess.check_call(["make", "-C", src, "overlayprobe", "overlay"], stdout=subprocess.DEVNULL)
+    # the oriented copies' probe (tests/test_gpu_orient_kernels.py) and g++'s build of their tile walk (tests/test_orient_cpu.py)
+    subprocess.check_call(["make", "-C", src, "orientprobe", "orient"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -257,6 +262,7 @@ class Handle:
         rc = L.vnect_create(C.byref(cfg), C.byref(h))
         self._h = h if h.value else None
         self.num_scales = len(scales)
+        self.orientation = 0  # the code the handle holds (set_orientation keeps it: the C ABI has no getter)
         self.net_images = 1 if pyramid is not None else len(scales)
         if rc:
             msg = L.vnect_last_error(self._h).decode()
@@ -441,6 +447,12 @@ class Handle:
         conf, lost = np.empty(21, np.float64), C.c_int32(0)
         self._ck(lib().vnect_result_confidence(self._h, _ptr(conf, _f64p), C.byref(lost)))
         return conf, int(lost.value)
+
+    def set_orientation(self, orientation):
+        """vnect_set_orientation: how the frames submitted from now on are stored -- code 0 .. 7, the picture is np.rot90(frame, code & 3),
+        mirrored when code & 4 (ORIENTATION.md)"""
+        self._ck(lib().vnect_set_orientation(self._h, int(orientation)))
+        self.orientation = int(orientation)
 
     def track_policy(self, stream, min_confidence, min_joints, action):
         """The stream's loss rule: action 0 / "off", 1 / "hold", 2 / "reset" (LOST_ACTIONS)."""
@@ -696,7 +708,7 @@ def _cai(x, ndim, what):
             n *= v
     strides = tuple(int(v) for v in strides)
     if any(v < 1 for v in strides):
-        raise ValueError("%s has a zero or negative stride %r: flip or broadcast it on the device first (.contiguous())" % (what, strides))
+        raise ValueError("%s has a zero or negative stride %r: pass a flipped frame as it is stored, with orientation= (ORIENTATION.md); broadcast on the device first (.contiguous())" % (what, strides))
     ptr = d["data"][0]
     if not ptr:
         raise ValueError("%s has a null data pointer" % what)

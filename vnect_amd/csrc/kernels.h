@@ -333,6 +333,13 @@ hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev,
 hipError_t launch_nv12_copy_track(const TrackState* ts, const Nv12Src& s, uint8_t* dst, int H, int W, hipStream_t st);
 // the same out of an (H, W) frame in device memory (H <= 65535)
 hipError_t launch_ingest_copy_track(const TrackState* ts, const IngestSrc& s, uint8_t* dst, int H, int W, hipStream_t st, int force_generic = 0);
+// The oriented copies (orient.hip; orient.h; ORIENTATION.md): the crop (x, y, w, h) -- in ORIENTED coordinates -- of an (H, W) frame that is
+// stored rotated / mirrored by code o (1 .. 7; 0 stays with the copies above) -> `dst`, rows packed 3 w bytes apart, BGR.  One source
+// block for every form: pinned or device BGR / RGB at any strides, NV12 in one or two allocations.
+struct OrientSrc;
+hipError_t launch_orient_copy(const OrientSrc& s, int o, int H, int W, int x, int y, int w, int h, uint8_t* dst, hipStream_t st);
+// the same with the rect from the stream's state; grid sized for the whole oriented frame
+hipError_t launch_orient_copy_track(const TrackState* ts, const OrientSrc& s, int o, int H, int W, uint8_t* dst, hipStream_t st);
 // behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
 // its geometry to `ts`.  conf_dev: the frame's NJ confidences in device memory (launch_post / launch_joints left them there), pol: the
 // stream's loss rule (device memory), conf: the frame's ConfOut, which gets lost / confident -- all three or none (no rule: today's loop)

@@ -51,6 +51,10 @@ static int tracked_ok(vnect_handle* h, int stream)
     return VNECT_OK;
 }
 
+// the size of the frames a tracked stream is given, as they are STORED: vnect_track_begin's (H, W) is the oriented picture's
+static int stored_H(const Stream& sm) { return (sm.orient & 1) ? sm.track_W : sm.track_H; }
+static int stored_W(const Stream& sm) { return (sm.orient & 1) ? sm.track_H : sm.track_W; }
+
 // the frame into `slot`; done with the caller's buffer on return
 template <class R>
 static int upload_from(vnect_handle* h, int slot, const char* who, R&& resolve)
@@ -532,7 +536,7 @@ int vnect_infer(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_s
 {
     return guarded(&h, [&]() -> int {
         if (!h || !bgr || !j2 || !j3) return VNECT_E_ARG;
-        return infer_from(h, "vnect_infer", t2d, t3d, j2, j3, [&](FrameSrc* s) { return resolve_host_bgr(h, bgr, H, W, row_stride, s); });
+        return infer_from(h, "vnect_infer", t2d, t3d, j2, j3, [&](FrameSrc* s) { return resolve_host_bgr(h, bgr, H, W, row_stride, h->orient, s); });
     });
 }
 
@@ -754,7 +758,8 @@ int vnect_submit_tracked_pinned(vnect_handle* h, int stream, int buffer_index, i
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
-            return resolve_pinned_bgr(h, "vnect_submit_tracked_pinned", buffer_index, h->streams[stream].track_H, h->streams[stream].track_W, row_stride, s);
+            const Stream& sm = h->streams[stream];  // (the buffer holds the frame as it is stored: the track's size turned back)
+            return resolve_pinned_bgr(h, "vnect_submit_tracked_pinned", buffer_index, stored_H(sm), stored_W(sm), row_stride, sm.orient, s);
         });
     });
 }
@@ -827,7 +832,7 @@ int vnect_upload_frame_nv12(vnect_handle* h, int slot, const uint8_t* y, int64_t
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return upload_from(h, slot, "vnect_upload_frame_nv12",
-                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12", y, y_stride, uv, uv_stride, H, W, nullptr, s); });
+                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12", y, y_stride, uv, uv_stride, H, W, nullptr, h->orient, s); });
     });
 }
 
@@ -837,7 +842,7 @@ int vnect_upload_frame_nv12_rect(vnect_handle* h, int slot, const uint8_t* y, in
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return upload_from(h, slot, "vnect_upload_frame_nv12_rect",
-                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12_rect", y, y_stride, uv, uv_stride, H, W, rect4, s); });
+                           [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_upload_frame_nv12_rect", y, y_stride, uv, uv_stride, H, W, rect4, h->orient, s); });
     });
 }
 
@@ -847,7 +852,7 @@ int vnect_infer_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, const 
     return guarded(&h, [&]() -> int {
         if (!h || !y || !uv || !j2 || !j3) return VNECT_E_ARG;
         return infer_from(h, "vnect_infer_nv12", t2d, t3d, j2, j3,
-                          [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_infer_nv12", y, y_stride, uv, uv_stride, H, W, rect4, s); });
+                          [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_infer_nv12", y, y_stride, uv, uv_stride, H, W, rect4, h->orient, s); });
     });
 }
 
@@ -857,7 +862,7 @@ int vnect_preprocess_nv12(vnect_handle* h, const uint8_t* y, int64_t y_stride, c
     return guarded(&h, [&]() -> int {
         if (!h || !y || !uv) return VNECT_E_ARG;
         return preprocess_from(h, "vnect_preprocess_nv12", batch_out, scaler, offset_x, offset_y,
-                               [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_preprocess_nv12", y, y_stride, uv, uv_stride, H, W, rect4, s); });
+                               [&](FrameSrc* s) { return resolve_host_nv12(h, "vnect_preprocess_nv12", y, y_stride, uv, uv_stride, H, W, rect4, h->orient, s); });
     });
 }
 
@@ -867,8 +872,9 @@ int vnect_submit_tracked_pinned_nv12(vnect_handle* h, int stream, int buffer_ind
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
-            return resolve_pinned_nv12(h, "vnect_submit_tracked_pinned_nv12", buffer_index, h->streams[stream].track_H, h->streams[stream].track_W, y_stride,
-                                       uv_offset, uv_stride, s);
+            const Stream& sm = h->streams[stream];
+            return resolve_pinned_nv12(h, "vnect_submit_tracked_pinned_nv12", buffer_index, stored_H(sm), stored_W(sm), y_stride, uv_offset, uv_stride,
+                                       sm.orient, s);
         });
     });
 }
@@ -879,7 +885,7 @@ int vnect_upload_frame_device(vnect_handle* h, int slot, const vnect_device_fram
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return upload_from(h, slot, "vnect_upload_frame_device",
-                           [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_upload_frame_device", true, s); });
+                           [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_upload_frame_device", true, h->orient, s); });
     });
 }
 
@@ -888,7 +894,7 @@ int vnect_infer_device(vnect_handle* h, const vnect_device_frame* frame, void* p
     return guarded(&h, [&]() -> int {
         if (!h || !j2 || !j3) return VNECT_E_ARG;
         return infer_from(h, "vnect_infer_device", t2d, t3d, j2, j3,
-                          [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_infer_device", true, s); });
+                          [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_infer_device", true, h->orient, s); });
     });
 }
 
@@ -898,7 +904,7 @@ int vnect_preprocess_device(vnect_handle* h, const vnect_device_frame* frame, vo
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return preprocess_from(h, "vnect_preprocess_device", batch_out, scaler, offset_x, offset_y,
-                               [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_preprocess_device", true, s); });
+                               [&](FrameSrc* s) { return check_device_frame(h, frame, producer_stream, "vnect_preprocess_device", true, h->orient, s); });
     });
 }
 
@@ -907,9 +913,10 @@ int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_
     return guarded(&h, [&]() -> int {
         if (!h) return VNECT_E_ARG;
         return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
-            int rc = check_device_frame(h, frame, producer_stream, "vnect_submit_tracked_device", false, s);
+            const Stream& sm = h->streams[stream];
+            int rc = check_device_frame(h, frame, producer_stream, "vnect_submit_tracked_device", false, sm.orient, s);
             if (rc) return rc;
-            if (s->H != h->streams[stream].track_H || s->W != h->streams[stream].track_W)
+            if (s->H != stored_H(sm) || s->W != stored_W(sm))
                 return fail(h, VNECT_E_ARG, "vnect_submit_tracked_device: the frame is not of the size vnect_track_begin gave for this stream");
             return (int)VNECT_OK;
         });
@@ -925,9 +932,10 @@ int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_de
             static const char* who = "vnect_submit_tracked_device_draw";
             OverlayTarget t;
             OverlayInput in;
-            int rc = check_draw(h, who, frame, producer_stream, style, &t, &in, s);
+            const Stream& sm = h->streams[stream];
+            int rc = check_draw(h, who, frame, producer_stream, style, sm.orient, &t, &in, s);
             if (rc) return rc;
-            if (s->H != h->streams[stream].track_H || s->W != h->streams[stream].track_W)
+            if (s->H != stored_H(sm) || s->W != stored_W(sm))
                 return fail(h, VNECT_E_ARG, std::string(who) + ": the frame is not of the size vnect_track_begin gave for this stream");
             s->draw = true, s->draw_target = t, s->draw_in = in;
             return (int)VNECT_OK;
@@ -942,6 +950,18 @@ int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* s
         if (!h) return VNECT_E_ARG;
         HIPCK(h, hipSetDevice(h->cfg.device));
         return draw_device_impl(h, target, stream, joints_2d, confidence21, rect4, style);
+    });
+}
+
+// ---- orientation (additive; ORIENTATION.md): frames that are stored rotated / mirrored, turned inside the crop's copy (orient.hip) ------
+int vnect_set_orientation(vnect_handle* h, int orientation)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (!orient_ok(orientation)) return fail(h, VNECT_E_ARG, "vnect_set_orientation: the orientation is a code 0 .. 7 (np.rot90 by code & 3, mirrored when code & 4)");
+        if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_set_orientation: orientation on a pyramid-sharded handle is not supported");
+        h->orient = orientation;  // (a frame in flight has been copied, or carries its own code: nothing of it reads this)
+        return VNECT_OK;
     });
 }
 

@@ -34,14 +34,16 @@ static int style_in(vnect_handle* h, const char* who, const vnect_overlay_style*
 }
 
 // Validates the target and the style and describes both; changes nothing
-int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style, OverlayTarget* t,
+int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style, int orient, OverlayTarget* t,
                OverlayInput* in, FrameSrc* src_out)
 {
     if (f && f->struct_size == (int32_t)sizeof(vnect_device_frame) && f->has_rect)
         return refuse(h, who, "the target takes no rect: the whole frame is drawn into");
     FrameSrc d;
-    int rc = check_device_frame(h, f, stream, who, false, &d);
+    int rc = check_device_frame(h, f, stream, who, false, orient, &d);
     if (rc) return rc;
+    if (orient && d.where == SRC_NV12)
+        return refuse(h, who, "an NV12 target cannot be drawn into under an orientation other than 0 (oriented chroma addressing is not supported)");
     memset(t, 0, sizeof *t);
     memset(in, 0, sizeof *in);
     t->H = d.H, t->W = d.W;
@@ -50,6 +52,18 @@ int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, vo
         t->uv = const_cast<uint8_t*>(d.nv.uv), t->uv_stride = d.nv.uv_stride;
     } else {
         t->data = const_cast<uint8_t*>(d.ing.data), t->sy = d.ing.stride_y, t->sx = d.ing.stride_x, t->sc = d.ing.stride_c;
+        if (orient) {
+            // joints and rect are in oriented coordinates: the overlay gets the oriented VIEW of the stored frame -- oriented pixel (i, j)
+            // is stored pixel orient_map(i, j), which is linear in (i, j): the origin's address, and the steps along i and j as strides
+            // (signed; overlay.h addresses with signed long long throughout)
+            int r0, c0, ri, ci, rj, cj;
+            orient_size(orient, d.H, d.W, &t->H, &t->W);
+            orient_map(orient, d.H, d.W, 0, 0, &r0, &c0);
+            orient_map(orient, d.H, d.W, t->H > 1 ? 1 : 0, 0, &ri, &ci);
+            orient_map(orient, d.H, d.W, 0, t->W > 1 ? 1 : 0, &rj, &cj);
+            const long long sy = d.ing.stride_y, sx = d.ing.stride_x;
+            t->data += r0 * sy + c0 * sx, t->sy = (ri - r0) * sy + (ci - c0) * sx, t->sx = (rj - r0) * sy + (cj - c0) * sx;
+        }
     }
     if ((rc = style_in(h, who, style, f->format, t, in))) return rc;
     if (src_out) *src_out = d;
@@ -64,7 +78,7 @@ int draw_device_impl(vnect_handle* h, const vnect_device_frame* target, void* st
     if (!j2d) return refuse(h, who, "no joints");
     OverlayTarget t;
     OverlayInput in;
-    int rc = check_draw(h, who, target, stream, style, &t, &in, nullptr);
+    int rc = check_draw(h, who, target, stream, style, h->orient, &t, &in, nullptr);
     if (rc) return rc;
     if (rect4) {
         if (rect4[2] < 1 || rect4[3] < 1) return refuse(h, who, "the rect must be at least one pixel wide and high");

@@ -129,11 +129,15 @@ static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn&
     // a frame outside the slots: this lane's stream waits for its producer, then copies the crop's rows (packed) into the stream's buffer
     int rc = wait_for_producer(h, src.producer, L->st);
     if (rc) return rc;
-    switch (src.where) {
-    case SRC_SLOT: break;
-    case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy_track(ts, src.bgr.data, sm.track_buf, sm.track_H, sm.track_W, src.bgr.stride, src.bgr.end, L->st)); break;
-    case SRC_NV12: HIPCK(h, launch_nv12_copy_track(ts, src.nv, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
-    case SRC_DEVICE: HIPCK(h, launch_ingest_copy_track(ts, src.ing, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
+    if (src.orient && src.where != SRC_SLOT) {  // stored rotated / mirrored: the crop (oriented coordinates) through the oriented copy
+        HIPCK(h, launch_orient_copy_track(ts, orient_src_of(src), src.orient, src.H, src.W, sm.track_buf, L->st));
+    } else {
+        switch (src.where) {
+        case SRC_SLOT: break;
+        case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy_track(ts, src.bgr.data, sm.track_buf, sm.track_H, sm.track_W, src.bgr.stride, src.bgr.end, L->st)); break;
+        case SRC_NV12: HIPCK(h, launch_nv12_copy_track(ts, src.nv, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
+        case SRC_DEVICE: HIPCK(h, launch_ingest_copy_track(ts, src.ing, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
+        }
     }
     HIPCK(h, launch_pyramid_track(ts, dyn, src.where != SRC_SLOT, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
     if (L->stem_mode == 2) {
@@ -708,7 +712,7 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
     }
     HIPCK(h, hipMemcpyAsync(h->d_track + stream, &t, sizeof(TrackState), hipMemcpyHostToDevice, h->st));
     HIPCK(h, hipStreamSynchronize(h->st));
-    sm.track_on = true, sm.track_stopped = false, sm.track_H = H, sm.track_W = W, sm.track_seq = 1;
+    sm.track_on = true, sm.track_stopped = false, sm.track_H = H, sm.track_W = W, sm.track_seq = 1, sm.orient = h->orient;
     return VNECT_OK;
 }
 

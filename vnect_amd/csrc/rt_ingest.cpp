@@ -73,15 +73,17 @@ int ensure_stage(vnect_handle* h, int i, size_t bytes)
 // ---- host BGR (vnect_infer, vnect_submit_tracked_pinned) ------------------------------------------------------------------------------------
 // A frame that lies inside one of the caller's pinned buffers (a frame captured there, or a crop of it) is read where it lies; any other
 // pointer is first copied by the CPU into the internal stage, rows packed -- behind the last refusal.
-int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, FrameSrc* out)
+int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, int orient, FrameSrc* out)
 {
     if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return refuse(h, nullptr, "bad frame geometry");
     FrameSrc f;
-    int rc = clip_rect(h, nullptr, nullptr, H, W, f.r);
+    int Ho, Wo;
+    orient_size(orient, H, W, &Ho, &Wo);
+    int rc = clip_rect(h, nullptr, nullptr, Ho, Wo, f.r);
     if (rc) return rc;
     const size_t row = (size_t)W * 3;
     int i = pinned_view(h, bgr, (size_t)(H - 1) * (size_t)row_stride + row);
-    f.where = SRC_PINNED_BGR, f.H = H, f.W = W;
+    f.where = SRC_PINNED_BGR, f.H = H, f.W = W, f.orient = orient;
     if (i >= 0) {
         f.bgr = {pinned_dev(h, i, bgr), (long long)row_stride, pinned_end(h, i)};
     } else {
@@ -97,13 +99,14 @@ int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t 
 }
 
 // the whole (H, W) frame at the start of pinned buffer `index`, rows row_stride apart
-int resolve_pinned_bgr(vnect_handle* h, const char* who, int index, int H, int W, int64_t row_stride, FrameSrc* out)
+int resolve_pinned_bgr(vnect_handle* h, const char* who, int index, int H, int W, int64_t row_stride, int orient, FrameSrc* out)
 {
     if (index < 0 || index > 1 || !h->stage[index]) return refuse(h, who, "no such pinned buffer (vnect_frame_buffer)");
     if (row_stride < (int64_t)W * 3 || pinned_view(h, h->stage[index], (size_t)(H - 1) * (size_t)row_stride + (size_t)W * 3) != index)
         return refuse(h, who, "the frame does not fit the pinned buffer at this row stride");
     FrameSrc f;
-    f.where = SRC_PINNED_BGR, f.H = H, f.W = W, f.r[2] = W, f.r[3] = H;
+    f.where = SRC_PINNED_BGR, f.H = H, f.W = W, f.orient = orient;
+    orient_size(orient, H, W, &f.r[3], &f.r[2]);
     f.bgr = {h->stage_dev[index], (long long)row_stride, pinned_end(h, index)};
     *out = f;
     return VNECT_OK;
@@ -123,7 +126,7 @@ static int nv12_pinned(vnect_handle* h, const char* who, const uint8_t* y, int64
 }
 
 int resolve_host_nv12(vnect_handle* h, const char* who, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                      const int32_t* rect4, FrameSrc* out)
+                      const int32_t* rect4, int orient, FrameSrc* out)
 {
     if (!y || !uv) return refuse(h, who, "null plane pointer");
     size_t y_span, uv_span;
@@ -131,27 +134,41 @@ int resolve_host_nv12(vnect_handle* h, const char* who, const uint8_t* y, int64_
     int rc;
     if ((rc = nv12_planes(h, who, H, W, y_stride, uv_stride, &y_span, &uv_span))) return rc;
     if ((rc = nv12_apart(h, who, y, y_span, uv, uv_span))) return rc;
-    if ((rc = clip_rect(h, who, rect4, H, W, f.r))) return rc;
+    int Ho, Wo;
+    orient_size(orient, H, W, &Ho, &Wo);
+    if ((rc = clip_rect(h, who, rect4, Ho, Wo, f.r))) return rc;
     if ((rc = nv12_pinned(h, who, y, y_stride, y_span, uv, uv_stride, uv_span, &f))) return rc;
-    f.where = SRC_NV12, f.H = H, f.W = W;
+    f.where = SRC_NV12, f.H = H, f.W = W, f.orient = orient;
     if (!f.nv.y) {
         // pageable planes: the CPU copies what the crop needs into the internal stage -- its Y rows from the even row at or above its
         // first, and the chroma rows under them, as a frame of its own (rows W apart, the UV plane directly behind; 1.5 bytes per
         // pixel); the rect moves up by the rows left out
-        const int i = 2, y0 = f.r[1] & ~1, rows = (f.r[1] + f.r[3] - y0 + 1) & ~1;   // (y0 + rows <= H: H is even)
+        // (an oriented frame: the stored rows of the crop's stored rectangle, orient_src_rect; the staged frame is then `rows` high, and the
+        // crop, which stays in oriented coordinates, moves by the rows left out as they lie in the oriented picture)
+        int sr[4] = {f.r[0], f.r[1], f.r[2], f.r[3]};
+        if (orient) orient_src_rect(orient, H, W, f.r[0], f.r[1], f.r[2], f.r[3], sr);
+        const int i = 2, y0 = sr[1] & ~1, rows = (sr[1] + sr[3] - y0 + 1) & ~1;   // (y0 + rows <= H: H is even)
         const size_t plane = (size_t)rows * W;
         if ((rc = ensure_stage(h, i, plane + plane / 2))) return rc;
         for (int q = 0; q < rows; q++) memcpy(h->stage[i] + (size_t)q * W, y + (size_t)(y0 + q) * (size_t)y_stride, (size_t)W);
         for (int q = 0; q < rows / 2; q++) memcpy(h->stage[i] + plane + (size_t)q * W, uv + (size_t)(y0 / 2 + q) * (size_t)uv_stride, (size_t)W);
         f.nv = {h->stage_dev[i], (long long)W, h->stage_dev[i] + plane, (long long)W, h->stage_dev[i], pinned_end(h, i)};
-        f.r[1] -= y0;
+        if (!orient) f.r[1] -= y0;
+        else {
+            // the staged frame is the stored rows y0 .. y0 + rows - 1: the crop's first pixel keeps its stored column and lies y0 rows
+            // higher, and the crop starts where that stored pixel lies in the STAGED frame's oriented picture
+            int r0, c0;
+            orient_map(orient, H, W, f.r[1], f.r[0], &r0, &c0);
+            orient_unmap(orient, rows, W, r0 - y0, c0, &f.r[1], &f.r[0]);
+            f.H = rows;
+        }
     }
     *out = f;
     return VNECT_OK;
 }
 
 // the whole (H, W) NV12 frame in pinned buffer `index`: the Y plane at its start, the UV plane uv_offset bytes in
-int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int W, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, FrameSrc* out)
+int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int W, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, int orient, FrameSrc* out)
 {
     if (index < 0 || index > 1 || !h->stage[index]) return refuse(h, who, "no such pinned buffer (vnect_frame_buffer)");
     size_t y_span, uv_span;
@@ -161,7 +178,8 @@ int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int 
     const uint8_t *y = h->stage[index], *uv = y + std::max<int64_t>(uv_offset, 0);  // (an offset in front of the buffer's start counts as 0: it overlaps)
     if ((rc = nv12_apart(h, who, y, y_span, uv, uv_span))) return rc;
     if ((rc = nv12_pinned(h, who, y, y_stride, y_span, uv, uv_stride, uv_span, &f))) return rc;
-    f.where = SRC_NV12, f.H = H, f.W = W, f.r[2] = W, f.r[3] = H;
+    f.where = SRC_NV12, f.H = H, f.W = W, f.orient = orient;
+    orient_size(orient, H, W, &f.r[3], &f.r[2]);
     *out = f;
     return VNECT_OK;
 }
@@ -198,7 +216,7 @@ static int device_range(vnect_handle* h, const void* p, const char* who, const c
 
 // Validates everything -- the descriptor, the rect, the slot's room, the pointers (device memory of the handle's device, the frame's span
 // inside its allocation) -- and changes nothing.  allow_rect false: a tracked frame (no rect, and no slot whose room matters)
-int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, FrameSrc* out)
+int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, int orient, FrameSrc* out)
 {
     if (!f) return refuse(h, who, "no frame descriptor");
     if (f->struct_size != (int32_t)sizeof(vnect_device_frame)) return refuse(h, who, "vnect_device_frame::struct_size is not sizeof(vnect_device_frame)");
@@ -216,13 +234,15 @@ int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* produ
         if (f->stride_y > ((int64_t)1 << 32) || f->uv_stride > ((int64_t)1 << 32)) return refuse(h, who, "stride out of range");
         if ((rc = nv12_apart(h, who, data, span, uv, uv_span))) return rc;
     } else {
-        if (f->stride_y < 1 || f->stride_x < 1 || f->stride_c < 1) return refuse(h, who, "strides must be positive (flip or broadcast on the device first)");
+        if (f->stride_y < 1 || f->stride_x < 1 || f->stride_c < 1) return refuse(h, who, "strides must be positive (a flipped or rotated frame: pass it as it is stored and say how with vnect_set_orientation; broadcast on the device first)");
         if (f->stride_y > ((int64_t)1 << 32) || f->stride_x > ((int64_t)1 << 32) || f->stride_c > ((int64_t)1 << 36)) return refuse(h, who, "stride out of range");
         span = (size_t)ingest_span(H, W, f->stride_y, f->stride_x, f->stride_c);
     }
     FrameSrc d;
     if (f->has_rect && !allow_rect) return refuse(h, who, "a tracked frame takes no rect: the crop is the stream's box on the device");
-    if (allow_rect && (rc = clip_rect(h, who, f->has_rect ? f->rect : nullptr, H, W, d.r))) return rc;
+    int Ho, Wo;
+    orient_size(orient, H, W, &Ho, &Wo);
+    if (allow_rect && (rc = clip_rect(h, who, f->has_rect ? f->rect : nullptr, Ho, Wo, d.r))) return rc;
     const uint8_t *lo = nullptr, *end = nullptr, *uv_lo = nullptr, *uv_end = nullptr;
     if ((rc = device_range(h, data, who, "data", &lo, &end))) return rc;
     if ((size_t)(end - data) < span)
@@ -231,8 +251,8 @@ int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* produ
         if ((rc = device_range(h, uv, who, "uv", &uv_lo, &uv_end))) return rc;
         if ((size_t)(uv_end - uv) < uv_span) return refuse(h, who, "the UV plane's last byte lies past the end of the allocation `uv` points into");
     }
-    d.where = nv12 ? SRC_NV12 : SRC_DEVICE, d.H = H, d.W = W, d.producer = producer_stream;
-    if (!allow_rect) d.r[2] = W, d.r[3] = H;
+    d.where = nv12 ? SRC_NV12 : SRC_DEVICE, d.H = H, d.W = W, d.orient = orient, d.producer = producer_stream;
+    if (!allow_rect) d.r[2] = Wo, d.r[3] = Ho;
     if (nv12) {
         d.nv = {data, (long long)f->stride_y, uv, (long long)f->uv_stride, lo, end};
         d.nv.uv_lo = uv_lo, d.nv.uv_end = uv_end, d.nv.any_bounds = 1;
@@ -241,6 +261,25 @@ int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* produ
     }
     *out = d;
     return VNECT_OK;
+}
+
+// the source block of the oriented copies: pinned BGR is packed-3 in mapped memory, NV12 keeps its one or two allocations
+OrientSrc orient_src_of(const FrameSrc& f)
+{
+    OrientSrc s{};
+    s.order = INGEST_BGR;
+    if (f.where == SRC_PINNED_BGR) {
+        // (a pinned buffer starts on a multiple of 4 in front of the frame: the aligned dword that holds the frame's first byte lies in it)
+        s.p0 = f.bgr.data, s.sy = f.bgr.stride, s.sx = 3, s.sc = 1, s.form = INGEST_PACKED3;
+        s.lo0 = (const uint8_t*)((uintptr_t)f.bgr.data & ~(uintptr_t)3), s.end0 = f.bgr.end;
+    } else if (f.where == SRC_NV12) {
+        s.p0 = f.nv.y, s.p1 = f.nv.uv, s.sy = f.nv.y_stride, s.sx = 1, s.sc = f.nv.uv_stride, s.form = ORIENT_NV12;
+        s.lo0 = f.nv.lo, s.end0 = f.nv.end, s.lo1 = f.nv.uv_lo ? f.nv.uv_lo : f.nv.lo, s.end1 = f.nv.uv_lo ? f.nv.uv_end : f.nv.end;
+    } else {
+        s.p0 = f.ing.data, s.sy = f.ing.stride_y, s.sx = f.ing.stride_x, s.sc = f.ing.stride_c, s.order = f.ing.order;
+        s.form = ingest_form(s.sx, s.sc), s.lo0 = f.ing.lo, s.end0 = f.ing.end;
+    }
+    return s;
 }
 
 // ---- into the slot ------------------------------------------------------------------------------------------------------------------------
@@ -286,11 +325,16 @@ int ingest(vnect_handle* h, int slot, const FrameSrc& f, hipStream_t st)
     if (!st) st = h->st;
     if ((rc = wait_for_producer(h, f.producer, st))) return rc;
     uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    switch (f.where) {
-    case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy(f.bgr.data, dst, f.H, 3 * f.W, f.bgr.stride, f.bgr.end, st)); break;
-    case SRC_NV12: HIPCK(h, launch_nv12_copy(f.nv, f.r[0], f.r[1], f.r[2], f.r[3], dst, st)); break;
-    case SRC_DEVICE: HIPCK(h, launch_ingest_copy(f.ing, f.H, f.W, f.r[0], f.r[1], f.r[2], f.r[3], dst, st)); break;
-    case SRC_SLOT: return fail(h, VNECT_E_INTERNAL, "ingest: a resident slot is no source");
+    if (f.orient) {  // a frame stored rotated / mirrored: one oriented copy for every source (orient.hip)
+        if (f.where == SRC_SLOT) return fail(h, VNECT_E_INTERNAL, "ingest: a resident slot is no source");
+        HIPCK(h, launch_orient_copy(orient_src_of(f), f.orient, f.H, f.W, f.r[0], f.r[1], f.r[2], f.r[3], dst, st));
+    } else {
+        switch (f.where) {
+        case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy(f.bgr.data, dst, f.H, 3 * f.W, f.bgr.stride, f.bgr.end, st)); break;
+        case SRC_NV12: HIPCK(h, launch_nv12_copy(f.nv, f.r[0], f.r[1], f.r[2], f.r[3], dst, st)); break;
+        case SRC_DEVICE: HIPCK(h, launch_ingest_copy(f.ing, f.H, f.W, f.r[0], f.r[1], f.r[2], f.r[3], dst, st)); break;
+        case SRC_SLOT: return fail(h, VNECT_E_INTERNAL, "ingest: a resident slot is no source");
+        }
     }
     h->slots[slot].H = f.r[3], h->slots[slot].W = f.r[2], h->slots[slot].stride = 3LL * f.r[2];
     return VNECT_OK;
@@ -314,6 +358,11 @@ int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int 
     if (!bgr || slot < 0 || slot >= (int)h->slots.size()) return fail(h, VNECT_E_ARG, "bad frame slot");
     if (H < 1 || W < 1 || row_stride < (int64_t)W * 3) return fail(h, VNECT_E_ARG, "bad frame geometry");
     if ((size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes) return fail(h, VNECT_E_ARG, "frame larger than max_frame_bytes");
+    if (h->orient) {  // stored rotated / mirrored: through the stage and the oriented copy, done on return like the copy below
+        FrameSrc f;
+        int rc = resolve_host_bgr(h, bgr, H, W, row_stride, h->orient, &f);
+        return rc ? rc : ingest_sync(h, slot, f);
+    }
     int rc = claim_slot(h, slot, (size_t)H * W * 3);
     if (rc) return rc;
     uint8_t* dst = h->frames + (size_t)slot * h->cfg.max_frame_bytes;

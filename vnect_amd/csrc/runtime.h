@@ -30,6 +30,7 @@
 #include "hostplan.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "orient.h"
 #include "overlay.h"
 
 namespace vnect {
@@ -155,7 +156,8 @@ struct Stream {
     long long seq = -1;
     Plan* lane = nullptr;
     bool track_on = false, track_stopped = false;
-    int track_H = 0, track_W = 0;
+    int track_H = 0, track_W = 0;  // the ORIENTED frame's size
+    int orient = 0;                // the orientation in force at vnect_track_begin: every tracked submit of the stream uses it
     unsigned track_seq = 0;
     uint8_t* track_buf = nullptr;  // the stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
     size_t track_cap = 0;          // waits for this frame's box kernel, which runs after everything that reads the crop)
@@ -173,6 +175,7 @@ struct vnect_handle : Plan {
     vnect_config cfg{};
     std::string err;
     bool finalized = false;
+    int orient = 0;         // vnect_set_orientation: how the frames submitted from now on are stored (orient.h; 0: as they are shown)
     bool pre_only = false;  // vnect_config::preprocess_only: the input batch buffer and the resize tables, nothing else
     bool x3 = false;    // VNECT_FP32_SPLIT: fp32 tensors; the 64x64-tile layers multiply on the bf16 pipe by three-way splits (conv.hip, X3)
     std::map<std::string, HostArray> weights;
@@ -366,8 +369,9 @@ struct PinnedBgr {
 };
 struct FrameSrc {
     FrameWhere where = SRC_SLOT;
-    int H = 0, W = 0;
-    int r[4] = {0, 0, 0, 0};  // the crop (x, y, w, h), clipped to the frame (a tracked frame: the whole frame)
+    int H = 0, W = 0;         // the frame as it is STORED
+    int orient = 0;           // orient.h's code: the picture is np.rot90(frame, orient & 3), mirrored when orient & 4
+    int r[4] = {0, 0, 0, 0};  // the crop (x, y, w, h) in ORIENTED coordinates, clipped to the oriented frame (a tracked frame: all of it)
     PinnedBgr bgr{};          // the kernel argument block of its kind: SRC_PINNED_BGR,
     Nv12Src nv{};             // SRC_NV12,
     IngestSrc ing{};          // SRC_DEVICE
@@ -388,12 +392,14 @@ int forward_batch(vnect_handle* h, const float* batch, float* out);
 // ---- rt_ingest.cpp -------------------------------------------------------------------------------------------------------------
 // The resolvers: each validates everything and refuses with the entry point's name (`who`) in front; the host ones then copy a pageable
 // frame into the internal stage.  Nothing else changes.
-int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, FrameSrc* out);
+// (H, W and the strides describe memory; `orient` is the code the frame is stored under, rects are in oriented coordinates)
+int resolve_host_bgr(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, int orient, FrameSrc* out);
 int resolve_host_nv12(vnect_handle* h, const char* who, const uint8_t* y, int64_t y_stride, const uint8_t* uv, int64_t uv_stride, int H, int W,
-                      const int32_t* rect4, FrameSrc* out);  // rect4: nullptr, or the crop (x, y, w, h)
-int resolve_pinned_bgr(vnect_handle* h, const char* who, int index, int H, int W, int64_t row_stride, FrameSrc* out);
-int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int W, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, FrameSrc* out);
-int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, FrameSrc* out);
+                      const int32_t* rect4, int orient, FrameSrc* out);  // rect4: nullptr, or the crop (x, y, w, h)
+int resolve_pinned_bgr(vnect_handle* h, const char* who, int index, int H, int W, int64_t row_stride, int orient, FrameSrc* out);
+int resolve_pinned_nv12(vnect_handle* h, const char* who, int index, int H, int W, int64_t y_stride, int64_t uv_offset, int64_t uv_stride, int orient, FrameSrc* out);
+int check_device_frame(vnect_handle* h, const vnect_device_frame* f, void* producer_stream, const char* who, bool allow_rect, int orient, FrameSrc* out);
+OrientSrc orient_src_of(const FrameSrc& f);  // the frame as the oriented copies (orient.hip) address it
 int ingest(vnect_handle* h, int slot, const FrameSrc& src, hipStream_t st = nullptr);  // asynchronous on st (nullptr: the handle's stream)
 int ingest_sync(vnect_handle* h, int slot, const FrameSrc& src);                       // on upload_st, done on return
 int upload_frame_impl(vnect_handle* h, int slot, const uint8_t* bgr, int H, int W, int64_t row_stride);
@@ -402,7 +408,7 @@ int wait_for_producer(vnect_handle* h, void* producer_stream, hipStream_t consum
 
 // ---- rt_draw.cpp ---------------------------------------------------------------------------------------------------------------
 // validates a draw's target (check_device_frame; a rect is refused) and style, and describes them; src_out (may be null): the frame as a source
-int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style, OverlayTarget* t,
+int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style, int orient, OverlayTarget* t,
                OverlayInput* in, FrameSrc* src_out);
 int draw_device_impl(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* j2d, const double* conf, const int32_t* rect4,
                      const vnect_overlay_style* style);

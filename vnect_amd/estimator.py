@@ -28,7 +28,7 @@ class VNectEstimator:
     joint_parents = [16, 15, 1, 2, 3, 1, 5, 6, 14, 8, 9, 14, 11, 12, 14, 14, 1, 4, 7, 10, 13]
 
     def __init__(self, scales=None, weights=None, seed=MASTER_SEED, device=0, precision="fp32", paper_res2c=False,
-                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1):
+                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1, orientation=0):
         if verbose:
             print('Initializing VNect Estimator...')
         # src/estimator.py:32; "for faster loops, use less scales e.g. [1], [1, 0.7]"
@@ -45,6 +45,7 @@ class VNectEstimator:
                          numpy_promotion={"legacy": 0, "nep50": 1}[numpy_promotion], lanes=lanes)
         self._submitted = 0
         self._weights = weights
+        self._orientation = self._check_orientation(orientation)
         self._h = None
         self._open()
         self.verbose = verbose
@@ -57,6 +58,32 @@ class VNectEstimator:
         self._h = _native.Handle(self._scales, **self._cfg)
         self._h.set_weights(self._weights)
         self._h.finalize()
+        self._orient(None)
+
+    # -- orientation (additive; ORIENTATION.md): frames that are STORED rotated / mirrored ------------------------------
+    @staticmethod
+    def _check_orientation(o):
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not 0 <= int(o) <= 7:
+            raise ValueError("orientation must be a code 0 .. 7: the picture is np.rot90(frame, code & 3), mirrored when code & 4")
+        return int(o)
+
+    @property
+    def orientation(self):
+        """How the frames this estimator is given are stored: code 0 .. 7, the picture is ``np.rot90(frame, code & 3)``, mirrored
+        (``[:, ::-1]``) when ``code & 4``.  3 is the reference's ``T`` option (run_estimator_ps.py:57-62, 81-85).  Rects, boxes and
+        joints are in the picture's coordinates; the turn happens on the device, inside the crop's copy."""
+        return self._orientation
+
+    @orientation.setter
+    def orientation(self, value):
+        self._orientation = self._check_orientation(value)
+        self._orient(None)
+
+    def _orient(self, orientation):
+        """the handle's orientation for the call at hand: `orientation`, or (None) the estimator's; set only when it differs"""
+        o = self._orientation if orientation is None else self._check_orientation(orientation)
+        if o != self._h.orientation:      # (the handle remembers what it was last given, whoever gave it)
+            self._h.set_orientation(o)
 
     # `self.scales` is a plain attribute in the reference; assigning it re-plans the pyramid
     @property
@@ -78,7 +105,7 @@ class VNectEstimator:
         return self._h
 
     @staticmethod
-    def gen_input_batch(img_input, box_size, scales, _handle=None):
+    def gen_input_batch(img_input, box_size, scales, _handle=None, orientation=None):
         """src/estimator.py:70-81 on the device.  Returns (batch (S,368,368,3) f32, scaler, [offset_x, offset_y])."""
         if box_size != 368:
             raise ValueError("box_size is fixed at 368 by the network")
@@ -89,11 +116,19 @@ class VNectEstimator:
             h = _native.Handle(list(scales), preprocess_only=True)
         else:
             h.set_scales(scales)
+        # orientation (additive; ORIENTATION.md): the batch of the oriented picture.  None: the code the handle holds (a handle of its
+        # own: 0); a given handle is left with the code it was found with
+        found = h.orientation
+        o = found if orientation is None else VNectEstimator._check_orientation(orientation)
         try:
+            if o != found:
+                h.set_orientation(o)
             return h.preprocess(img_input)
         finally:
             if own:
                 h.close()
+            elif o != found:
+                h.set_orientation(found)
 
     def joint_filter(self, joints, dim=2, timestamp=None):
         """src/estimator.py:83-95: the estimator's 2-D (``dim=2``) or 3-D OneEuro bank applied to ``joints`` IN PLACE; returns
@@ -158,7 +193,7 @@ class VNectEstimator:
             raise ValueError("rect= is for pixel_format='nv12' (a BGR caller slices the frame)")
         return pixel_format == "nv12"
 
-    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None, return_confidence=False):
+    def __call__(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None, return_confidence=False, orientation=None):
         """``pixel_format="nv12"`` (additive): ``img_input`` is a 2-D uint8 array of ``H * 3 // 2`` rows -- H rows of Y, the interleaved
         U, V plane from row H on; row-strided views are fine -- converted to BGR on the device (NV12.md).  ``rect=(x, y, w, h)``: only
         that crop, as ``frame[y:y + h, x:x + w]`` of the converted frame; the joints are in crop coordinates.
@@ -169,11 +204,15 @@ class VNectEstimator:
         integer handle of the stream that wrote it (default: torch's current stream if torch is imported, else the default stream).
 
         ``return_confidence=True`` (additive; CONFIDENCE.md): a third value, a fresh (21,) float64 array -- per joint the height of its
-        heat-map's peak, the value of the element ``np.argmax`` picks in ``src/utils.py:169-172``."""
+        heat-map's peak, the value of the element ``np.argmax`` picks in ``src/utils.py:169-172``.
+
+        ``orientation=`` (additive; ORIENTATION.md): the code this frame is stored under (default: the estimator's ``orientation``);
+        ``rect`` and the joints are in the oriented picture's coordinates."""
         t0 = time.time()
         t2d, t3d = self._stamps(timestamp)
         device = _native.is_device_array(img_input)
         nv12 = self._format(pixel_format, rect, device)
+        self._orient(orientation)
         try:
             if device:
                 joints_2d, joints_3d = self._h.infer_device(_native.device_frame(img_input, pixel_format, rect), t2d, t3d, stream)
@@ -188,7 +227,7 @@ class VNectEstimator:
         return joints_2d, joints_3d
 
     # -- pipelined use (additive; the reference's loop is strictly one frame at a time) --------------------------------
-    def submit(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None):
+    def submit(self, img_input, timestamp=None, pixel_format="bgr", rect=None, stream=None, orientation=None):
         """Queue a frame and return at once; at most ``max(lanes, 2)`` may be in flight.  With ``lanes=2`` / ``3`` the frames
         overlap on the GPU (+29 % frames/s for one video stream at three lanes -- `pipelined_frames_per_s_per_gpu` against `value` in
         profiles/r06_bench_line.json -- at the price of their latency); ``collect()`` returns
@@ -197,6 +236,7 @@ class VNectEstimator:
         slot = self._submitted % 4
         device = _native.is_device_array(img_input)
         nv12 = self._format(pixel_format, rect, device)
+        self._orient(orientation)    # (frames already in flight keep theirs: their slots hold the oriented frame)
         try:
             if device:  # (the upload is done with the caller's buffer when it returns)
                 self._h.upload_frame_device(slot, _native.device_frame(img_input, pixel_format, rect), stream)
@@ -214,7 +254,8 @@ class VNectEstimator:
         res = self._h.collect()
         return res + (self._h.result_confidence()[0],) if return_confidence else res
 
-    def draw(self, frame, joints_2d, rect=None, confidence=None, pixel_format="bgr", min_confidence=None, colors=None, stream=None):
+    def draw(self, frame, joints_2d, rect=None, confidence=None, pixel_format="bgr", min_confidence=None, colors=None, stream=None,
+             orientation=None):
         """Additive (OVERLAY.md): the reference's ``utils.draw_limbs_2d`` (src/utils.py:222-243; run_estimator_ps.py:92-94) on a frame in
         DEVICE memory -- anything with ``__cuda_array_interface__``, in every layout the estimator reads (``pixel_format`` "bgr", "rgb" or
         "nv12") -- drawn IN PLACE by one kernel launch, and returned.  ``joints_2d``: (21, 2) [row, col] in the frame's coordinates;
@@ -223,6 +264,7 @@ class VNectEstimator:
         if not _native.is_device_array(frame):
             raise ValueError("draw() takes a frame in device memory; render.draw_limbs_2d_exact draws into host arrays")
         self._format(pixel_format, None, True)
+        self._orient(orientation)    # joints and rect are in the oriented picture's coordinates (an NV12 target: orientation 0 only)
         style = _native.overlay_style(min_confidence, colors, self.joint_parents)
         self._h.draw_device(_native.device_frame(frame, pixel_format), joints_2d, rect, confidence, style, stream)
         return frame

@@ -95,21 +95,41 @@ def init_box(estimator, frame, timestamp=None, min_confidence=None, min_joints=1
     return [x, y, w, h]
 
 
+def orient_view(frame, orientation):
+    """The oriented picture of a stored frame as a numpy view (ORIENTATION.md): np.rot90 by ``orientation & 3``, mirrored when
+    ``orientation & 4``.  3 is the reference's ``T`` (run_estimator_ps.py:57-62, 81-85), 7 its commented np.transpose variant."""
+    g = np.rot90(frame, orientation & 3)
+    return g[:, ::-1] if orientation & 4 else g
+
+
+def _orientations(estimator, orientation, n, transpose):
+    """one code 0 .. 7 per video, from one code or a sequence of n -- None: the estimator's own (``VNectEstimator(orientation=)``; an
+    estimator without one: 0); not together with transpose"""
+    if orientation is None:
+        orientation = getattr(estimator, "orientation", 0)
+    codes = [orientation] * n if isinstance(orientation, (int, np.integer)) and not isinstance(orientation, bool) else list(orientation)
+    if len(codes) != n or any(isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not 0 <= int(o) <= 7 for o in codes):
+        raise ValueError("orientation must be a code 0 .. 7 (or one per video): np.rot90 by code & 3, mirrored when code & 4")
+    if transpose and any(codes):
+        raise ValueError("transpose=True is orientation=3: pass one of the two, not transpose together with a non-zero orientation")
+    return [int(o) for o in codes]
+
+
 def _nv12_checks(pixel_format, transpose, source=None):
     if source == "device":  # frames in device memory (DEVICE_FRAMES.md): 'rgb' exists there, rotating does not
         if pixel_format not in ("bgr", "rgb", "nv12"):
             raise ValueError("pixel_format must be 'bgr', 'rgb' or 'nv12'")
         if transpose:
-            raise ValueError("transpose=True is not supported with source='device': rotate the frame on the device before passing it")
+            raise ValueError("transpose=True is not supported with source='device': use orientation=3, which turns the crop on the device")
         return pixel_format == "nv12"
     if pixel_format not in ("bgr", "nv12"):
         raise ValueError("pixel_format must be 'bgr' or 'nv12'")
     if pixel_format == "nv12" and transpose:
-        raise ValueError("transpose=True is not supported with pixel_format='nv12': rotate the two planes before passing the frame")
+        raise ValueError("transpose=True is not supported with pixel_format='nv12': use orientation=3, which turns the crop on the device")
     return pixel_format == "nv12"
 
 
-def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_format="bgr", confidence=False, lost=None):
+def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_format="bgr", confidence=False, lost=None, orientation=None):
     """run_estimator_ps.py:80-109 without capture / drawing.  Yields (joints_2d, joints_3d, rect_used).
 
     Additive (CONFIDENCE.md): ``lost=(min_confidence, min_joints, "hold" | "reset")`` -- behind the box update, a frame with fewer than
@@ -120,17 +140,28 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
     transpose: the reference's `T` option (np.rot90(frame, 3)); timestamps: optional iterable for reproducible
     filtering (default wall clock, like the reference); pixel_format="nv12": the frames are (H * 3 // 2, W) NV12 arrays, converted
     and cropped on the device (no transpose).
+    orientation (additive; ORIENTATION.md): the code 0 .. 7 the frames are stored under -- the picture is ``orient_view(frame, code)``;
+    3 is ``transpose=True``; None (the default): the estimator's own ``orientation``.  A BGR frame is turned as a numpy view, like
+    ``transpose``, and the estimator is called under code 0; an NV12 frame is turned on the device.  Rects and joints are in the
+    picture's coordinates.
     """
     ts = iter(timestamps) if timestamps is not None else None
     nv12 = _nv12_checks(pixel_format, transpose)
+    orientation = _orientations(estimator, orientation, 1, transpose)[0]
+    own = getattr(estimator, "orientation", 0)
+    call_code = orientation if nv12 else 0     # what the estimator itself still has to turn
     rule = lost_rule(lost)
     want_conf = confidence or rule is not None
     for frame in frames:
         if transpose:
             frame = np.rot90(frame, 3)
+        elif orientation and not nv12:
+            frame = orient_view(frame, orientation)
         H_img, W_img = frame.shape[:2]
         if nv12:                                   # (H * 3 // 2, W): Y rows, then the U, V rows
             H_img = H_img * 2 // 3
+            if orientation & 1:                    # (the picture of a quarter-turned frame)
+                H_img, W_img = W_img, H_img
         if rect is None:
             rect = [0, 0, W_img, H_img]
         x, y, w, h = rect
@@ -138,6 +169,8 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
             x, y, w, h = rect = [0, 0, W_img, H_img]
         t = next(ts) if ts is not None else None
         kw = {"return_confidence": True} if want_conf else {}
+        if call_code != own:                       # (said only where it differs from the estimator's own: any callable serves otherwise)
+            kw["orientation"] = call_code
         if nv12:                                   # the device converts and crops: the rect goes along instead of a slice
             res = estimator(frame, timestamp=t, pixel_format="nv12", rect=[x, y, w, h], **kw)
         else:
@@ -157,7 +190,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
 
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
-                    confidence=False, lost=None, draw=False):
+                    confidence=False, lost=None, draw=False, orientation=None):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -171,14 +204,17 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     ``confidence`` / ``lost``: as in ``track``; the rule runs on the device (vnect_track_policy).
     ``draw`` (``source="device"`` only; OVERLAY.md): True, or an ``_native.overlay_style(...)`` -- every frame is annotated IN PLACE with its
     own joints and the rect it was cropped with (run_estimator_ps.py:92-94) by the time it is yielded; the results are those of
-    ``draw=False``, bit for bit."""
+    ``draw=False``, bit for bit.
+    ``orientation`` (ORIENTATION.md): the code 0 .. 7 the frames are stored under, from every source (None: the estimator's own); the crop
+    is turned on the device."""
     for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
-                                    None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw):
+                                    None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw,
+                                    orientation):
         yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr", confidence=False, lost=None, draw=False):
+                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
@@ -187,7 +223,9 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
     afterwards); ``confidence=True`` appends
     (confidence, lost flag) to every tuple.
-    ``draw``: as in ``track_on_device``."""
+    ``draw``: as in ``track_on_device``.
+    ``orientation``: one code for all videos or one per video (ORIENTATION.md; None: the estimator's own): every stream keeps the code its track began with, so
+    videos with different orientations share the handle; the estimator's own orientation is back in force afterwards."""
     from collections import deque
 
     from . import _native
@@ -197,6 +235,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     if draw is not False and draw is not None:
         style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
     nv12 = _nv12_checks(pixel_format, transpose, source)
+    codes = _orientations(estimator, orientation, len(videos), transpose)
     rule = lost_rule(lost)
     if source not in ("pinned", "resident", "device"):
         raise ValueError("source must be 'pinned', 'resident' or 'device'")
@@ -229,7 +268,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
         if f is not None:
             pending[i] = prep(f)
             H, W = size_of(pending[i])
-            h.track_begin(streams[i], H, W, rects[i])
+            estimator._orient(codes[i])        # the stream keeps the code in force now; H, W: the picture's
+            h.track_begin(streams[i], W if codes[i] & 1 else H, H if codes[i] & 1 else W, rects[i])
             if rule is not None:
                 h.track_policy(streams[i], *rule)
     flat = []
@@ -285,6 +325,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                             h.submit_tracked_pinned(streams[i], b, W * 3, t2d, t3d)
                     else:
                         slot = count % nslots
+                        estimator._orient(codes[i])    # (the slot holds the oriented frame from its upload on)
                         if nv12:
                             h.upload_frame_nv12(slot, frame)
                         else:
@@ -315,6 +356,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             except _native.VnectError:
                 pass
         held.clear()
+        estimator._orient(None)                 # the estimator's own orientation again
         if rule is not None:                    # nothing is in flight any more: the streams' rule is off again
             for i in range(n):
                 if pending[i] is not None:
