@@ -363,6 +363,52 @@ int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* s
 int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
                                      const vnect_overlay_style* style);
 
+/* ABI v7, additive.  The preview: the annotated frame scaled for display, computed on the device (PREVIEW.md).  The reference's frame loop
+ * draws into a copy of the frame and scales that copy to 1024 pixels on its longer side before it shows it (run_estimator_ps.py:94-96:
+ * frame_draw = utils.draw_limbs_2d(frame.copy(), ..); frame_draw = utils.img_scale(frame_draw, 1024 / max(W_img, H_img)); cv2.imshow).
+ * One kernel launch reads the frame where it lies -- every layout vnect_device_frame describes, under the orientation in force --, applies
+ * the overlay's rule (vnect_amd/csrc/overlay.h, in the BGR domain) to every source tap and writes cv2.resize(.., fx = fy = factor,
+ * INTER_LINEAR) of the annotated picture in cv2's own 11-bit fixed point (vnect_amd/csrc/preview.h).  THE FRAME IS NEVER WRITTEN.
+ * vnect_preview_spec: factor -- 0: the reference's 1024.0 / max(W, H) of the oriented picture; out_format -- VNECT_PIX_BGR or VNECT_PIX_RGB,
+ * packed 3 bytes per pixel; draw_frame -- vnect_submit_tracked_device_preview only: the frame itself is annotated too.
+ * vnect_preview_size (run_estimator_ps.py:94-96: the size cv2.resize gives the displayed picture): out_hw = (rows, columns) =
+ * (cv_round(Hp factor), cv_round(Wp factor)), half to even, of the frame's oriented picture (Hp, Wp) under the orientation in force.
+ * Arithmetic only: the frame's pointers are not looked at; works before vnect_finalize and on a preprocess_only handle.
+ * vnect_preview_device (run_estimator_ps.py:94-96): the preview of `frame` into `out`, rows out_pitch >= 3 * columns bytes apart; no byte
+ * outside the 3 * columns bytes of each row is written.  joints_2d (21 x 2 float64 [row, col], oriented coordinates), confidence21, rect4
+ * and style are vnect_draw_device's, each may be NULL (no joints and no rect: the plain scaled picture).  `out` is device memory of the
+ * handle's device (the kernel writes it; its last byte must lie inside its allocation) or host memory, pinned or pageable (the library
+ * stages and copies).  The launch is ordered behind producer_stream as in vnect_draw_device and runs on the handle's upload stream; the
+ * preview is complete on return.  Needs no weights.  VNECT_E_ARG, before anything is launched or written: a factor that is negative, NaN
+ * or infinite; an output side that rounds to 0 or exceeds VNECT_PREVIEW_MAX; everything vnect_draw_device refuses of a frame (but an NV12
+ * frame under an orientation is accepted: it is only read) or a style; frame->has_rect; draw_frame; an out_format other than the two; an
+ * output that overlaps the frame; out_pitch < 3 * columns; an `out` that is neither such device memory nor host memory.
+ * vnect_submit_tracked_device_preview (run_estimator_ps.py:94-96 inside the tracked loop): vnect_submit_tracked_device, plus one preview
+ * launch on the frame's lane stream behind its box stage -- joints in frame coordinates, rect_used, status and (with a threshold)
+ * confidences are read from the frame's result-ring slot on the device -- plus the preview's copy to the host, both in front of the
+ * frame's completion.  The preview lands in a pinned host buffer the handle owns, one per result-ring slot; the buffers are sized at the
+ * first such submit and re-sized (for a larger preview) only while nothing is in flight: VNECT_E_STATE otherwise.  With spec->draw_frame
+ * the overlay launch of vnect_submit_tracked_device_draw follows the preview launch on the same stream: the preview reads the clean frame
+ * and the frame is then annotated in place as that call leaves it; this order is part of the contract.  A frame whose crop was refused
+ * has no preview.  Joints, rects, confidences, filter states, refusals and rollback are those of vnect_submit_tracked_device, bit for
+ * bit, plus the style's and the spec's (checked before anything changes).
+ * vnect_result_preview (run_estimator_ps.py:94-96): the preview of the frame most recently delivered by vnect_collect_tracked -- *data,
+ * hw = (rows, columns), *pitch = 3 * columns -- valid until the next submit on the handle; hw = (0, 0) and *data = NULL if that frame
+ * has none. */
+#define VNECT_PREVIEW_MAX 4096
+typedef struct vnect_preview_spec {
+    int32_t struct_size;  /* = sizeof(vnect_preview_spec) */
+    double factor;        /* 0: 1024.0 / max(Wp, Hp) */
+    int32_t out_format;   /* VNECT_PIX_BGR | VNECT_PIX_RGB */
+    int32_t draw_frame;   /* 0 */
+} vnect_preview_spec;
+int vnect_preview_size(vnect_handle* h, const vnect_device_frame* frame, const vnect_preview_spec* spec, int32_t out_hw[2]);
+int vnect_preview_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, const double* joints_2d, const double* confidence21,
+                         const int32_t* rect4, const vnect_overlay_style* style, const vnect_preview_spec* spec, void* out, int64_t out_pitch);
+int vnect_submit_tracked_device_preview(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                                        const vnect_overlay_style* style, const vnect_preview_spec* spec);
+int vnect_result_preview(vnect_handle* h, const uint8_t** data, int32_t hw[2], int64_t* pitch);
+
 /* Orientation (ABI v7, additive; ORIENTATION.md).  The reference's loop has a `T` option for a camera that is mounted sideways: it turns
  * every frame with np.rot90(frame, 3) before the crop (run_estimator_ps.py:57-62, 81-85; commented out beside it, an np.transpose
  * variant).  Here the turn happens on the device, inside the copy that brings the crop into the slot, so only the crop moves.

@@ -89,6 +89,26 @@ def overlay_style(min_confidence=None, colors=None, parents=None):
     return s
 
 
+PREVIEW_MAX = 4096   # VNECT_PREVIEW_MAX: an output side of a preview at most
+
+
+class PreviewSpec(C.Structure):
+    """vnect_preview_spec: factor, output channel order and draw_frame of a preview (include/vnect_abi.h; PREVIEW.md)."""
+    _fields_ = [("struct_size", C.c_int32), ("factor", C.c_double), ("out_format", C.c_int32), ("draw_frame", C.c_int32)]
+
+
+def preview_spec(factor=None, out_format="bgr", draw_frame=False):
+    """The PreviewSpec of a preview.  factor None (or 0): the reference's 1024 / the picture's longer side; out_format "bgr" or "rgb"."""
+    if out_format not in ("bgr", "rgb"):
+        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    s = PreviewSpec()
+    s.struct_size = C.sizeof(PreviewSpec)
+    s.factor = 0.0 if factor is None else float(factor)
+    s.out_format = PIX_RGB if out_format == "rgb" else PIX_BGR
+    s.draw_frame = int(bool(draw_frame))
+    return s
+
+
 class DeviceFrameError(VnectError, ValueError):
     """VNECT_E_ARG of a device-frame entry point: the frame as given cannot be read (a ValueError, like every refused argument)."""
 
@@ -155,6 +175,12 @@ SYMBOLS = {
     "vnect_submit_tracked_device_draw": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
                                                    C.POINTER(OverlayStyle)]),
     "vnect_set_orientation": (C.c_int, [_H, C.c_int]),
+    "vnect_preview_size": (C.c_int, [_H, C.POINTER(DeviceFrame), C.POINTER(PreviewSpec), _i32p]),
+    "vnect_preview_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, _f64p, _f64p, _i32p, C.POINTER(OverlayStyle),
+                                       C.POINTER(PreviewSpec), C.c_void_p, C.c_int64]),
+    "vnect_submit_tracked_device_preview": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
+                                                      C.POINTER(OverlayStyle), C.POINTER(PreviewSpec)]),
+    "vnect_result_preview": (C.c_int, [_H, C.POINTER(_u8p), _i32p, C.POINTER(C.c_int64)]),
 }
 
 
@@ -172,6 +198,8 @@ OVERLAYPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_overlayprobe.so") # over
 OVERLAY_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_overlay.so")       # g++'s build of csrc/overlay.h (tests only; no GPU code)
 ORIENTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_orientprobe.so")   # orient.o behind csrc/orient_probe.hip (tests only)
 ORIENT_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_orient.so")         # g++'s build of csrc/orient.h (tests only; no GPU code)
+PREVIEWPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_previewprobe.so") # preview.o behind csrc/preview_probe.hip (tests only)
+PREVIEW_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_preview.so")       # g++'s build of csrc/preview.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -192,6 +220,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "overlayprobe", "overlay"], stdout=subprocess.DEVNULL)
     # the oriented copies' probe (tests/test_gpu_orient_kernels.py) and g++'s build of their tile walk (tests/test_orient_cpu.py)
     subprocess.check_call(["make", "-C", src, "orientprobe", "orient"], stdout=subprocess.DEVNULL)
+    # the preview's probe (tests/test_gpu_preview_kernels.py) and g++'s build of its tile walk (tests/test_preview_cpu.py)
+    subprocess.check_call(["make", "-C", src, "previewprobe", "preview"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -533,6 +563,44 @@ class Handle:
         buffer is WRITTEN until then."""
         self._ck_device(lib().vnect_submit_tracked_device_draw(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d,
                                                                None if style is None else C.byref(style)))
+
+    # -- the preview: the annotated frame scaled for display, computed on the device (include/vnect_abi.h; PREVIEW.md) ------------------
+    def preview_size(self, frame, spec):
+        """vnect_preview_size: (rows, columns) of the preview of `frame` (a DeviceFrame; only its H and W count) under the orientation in force."""
+        hw = (C.c_int32 * 2)()
+        self._ck_device(lib().vnect_preview_size(self._h, C.byref(frame), C.byref(spec), hw))
+        return int(hw[0]), int(hw[1])
+
+    def preview_device(self, frame, spec, out, out_pitch, joints_2d=None, rect=None, confidence=None, style=None, stream=None):
+        """vnect_preview_device: the preview of `frame` (a DeviceFrame without a rect) into the memory at address `out` (device or host),
+        rows out_pitch bytes apart; done on return.  The frame is not written."""
+        j2 = cf = None
+        if joints_2d is not None:
+            j2 = np.ascontiguousarray(joints_2d, dtype=np.float64)
+            if j2.shape != (21, 2):
+                raise ValueError("joints_2d must be (21, 2)")
+        if confidence is not None:
+            cf = np.ascontiguousarray(confidence, dtype=np.float64)
+            if cf.shape != (21,):
+                raise ValueError("confidence must be (21,)")
+        self._ck_device(lib().vnect_preview_device(self._h, C.byref(frame), _stream_arg(stream), None if j2 is None else _ptr(j2, _f64p),
+                                                   None if cf is None else _ptr(cf, _f64p), _rect4(rect),
+                                                   None if style is None else C.byref(style), C.byref(spec), C.c_void_p(int(out)), int(out_pitch)))
+
+    def submit_tracked_device_preview(self, stream, frame, t2d, t3d, producer=None, style=None, spec=None):
+        """submit_tracked_device, and the frame's preview (annotated with its own joints and crop rect, scaled) is computed on the device
+        and delivered with it: result_preview() after collect_tracked().  spec.draw_frame: the frame is annotated in place too."""
+        spec = preview_spec() if spec is None else spec
+        self._ck_device(lib().vnect_submit_tracked_device_preview(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d,
+                                                                  None if style is None else C.byref(style), C.byref(spec)))
+
+    def result_preview(self):
+        """vnect_result_preview: the (dh, dw, 3) preview of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
+        data, hw, pitch = _u8p(), (C.c_int32 * 2)(), C.c_int64()
+        self._ck(lib().vnect_result_preview(self._h, C.byref(data), hw, C.byref(pitch)))
+        if hw[0] < 1 or hw[1] < 1:
+            return None
+        return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
 
     def read_frame(self, slot):
         """The (H, W, 3) BGR frame resident slot `slot` holds (a debugging read)."""

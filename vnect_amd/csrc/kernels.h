@@ -359,6 +359,13 @@ struct OverlayTarget;
 struct OverlayInput;
 hipError_t launch_overlay(const OverlayTarget& t, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
 
+// ---- the preview (preview.hip; vnect_preview_device; PREVIEW.md) ---------------------------------------------------------------------
+// run_estimator_ps.py:94-96: the annotated frame scaled for display, by the rule of preview.h.  One launch; the grid is fixed by the
+// output's size.  The frame is read, never written; the scaled packed picture goes to a.out.  jo / to / co: as in launch_overlay; a frame
+// whose status is not SQ_OK writes nothing.
+struct PreviewArgs;
+hipError_t launch_preview(const PreviewArgs& a, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
+
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);
 

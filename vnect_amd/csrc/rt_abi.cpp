@@ -281,6 +281,8 @@ void vnect_destroy(vnect_handle* h)
         if (h->xopened[r] && h->xpeer[r]) hipIpcCloseMemHandle(h->xpeer[r]);
     if (h->h_xstatus) hipHostFree(h->h_xstatus);
     if (h->h_tout) hipHostFree(h->h_tout);
+    for (int i = 0; i < RING; i++)
+        if (h->pv_host[i]) hipHostFree(h->pv_host[i]);  // (pv_dev: dev_allocs)
     if (h->h_conf) hipHostFree(h->h_conf);
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
@@ -943,6 +945,35 @@ int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_de
     });
 }
 
+// run_estimator_ps.py:94-96 inside the tracked loop: the frame's preview computed behind its box stage, delivered with the frame
+int vnect_submit_tracked_device_preview(vnect_handle* h, int stream, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                                        const vnect_overlay_style* style, const vnect_preview_spec* spec)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        return submit_tracked_from(h, stream, -1, t2d, t3d, [&](FrameSrc* s) {
+            static const char* who = "vnect_submit_tracked_device_preview";
+            const Stream& sm = h->streams[stream];
+            int rc = check_tracked_preview(h, who, frame, producer_stream, style, spec, sm.orient, s);
+            if (rc) return rc;
+            if (s->H != stored_H(sm) || s->W != stored_W(sm))
+                return fail(h, VNECT_E_ARG, std::string(who) + ": the frame is not of the size vnect_track_begin gave for this stream");
+            return (int)VNECT_OK;
+        });
+    });
+}
+
+int vnect_result_preview(vnect_handle* h, const uint8_t** data, int32_t hw[2], int64_t* pitch)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !data || !hw || !pitch) return h ? fail(h, VNECT_E_ARG, "vnect_result_preview: bad argument") : VNECT_E_ARG;
+        hw[0] = h->last_pv_h, hw[1] = h->last_pv_w;
+        *data = h->last_pv_ring >= 0 ? h->pv_host[h->last_pv_ring] : nullptr;
+        *pitch = 3LL * h->last_pv_w;
+        return VNECT_OK;
+    });
+}
+
 int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* joints_2d, const double* confidence21,
                       const int32_t* rect4, const vnect_overlay_style* style)
 {
@@ -950,6 +981,25 @@ int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* s
         if (!h) return VNECT_E_ARG;
         HIPCK(h, hipSetDevice(h->cfg.device));
         return draw_device_impl(h, target, stream, joints_2d, confidence21, rect4, style);
+    });
+}
+
+// ---- the preview (additive; PREVIEW.md; run_estimator_ps.py:94-96): the annotated frame scaled for display, one launch of preview.hip --
+int vnect_preview_size(vnect_handle* h, const vnect_device_frame* frame, const vnect_preview_spec* spec, int32_t out_hw[2])
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !out_hw) return VNECT_E_ARG;
+        return preview_size_impl(h, frame, spec, out_hw);
+    });
+}
+
+int vnect_preview_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, const double* joints_2d, const double* confidence21,
+                         const int32_t* rect4, const vnect_overlay_style* style, const vnect_preview_spec* spec, void* out, int64_t out_pitch)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return preview_device_impl(h, frame, producer_stream, joints_2d, confidence21, rect4, style, spec, out, out_pitch);
     });
 }
 

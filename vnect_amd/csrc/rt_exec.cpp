@@ -374,6 +374,14 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
         if (tk)
             HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st, cdev, h->d_policy + stream, h->h_conf_dev + ring));
     }
+    // run_estimator_ps.py:94-96: the frame's preview -- annotated with its own joints and rect_used, read from its ring slot, and scaled --
+    // into the slot's device buffer and on to its pinned host buffer; in front of the overlay launch, so that it reads the clean frame
+    if (tk && tk->preview) {
+        PreviewArgs a = tk->pv;
+        a.out = h->pv_dev[ring], a.pitch = 3LL * a.g.dw;
+        HIPCK(h, launch_preview(a, tk->pv_in, e.out_dev, h->h_tout_dev + ring, tk->pv_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
+        HIPCK(h, hipMemcpyAsync(h->pv_host[ring], h->pv_dev[ring], 3 * (size_t)a.g.dw * a.g.dh, hipMemcpyDeviceToHost, L->st));
+    }
     // run_estimator_ps.py:92-94: the frame itself annotated with its own joints and the rect it was cropped with, read from its ring slot
     if (tk && tk->draw)
         HIPCK(h, launch_overlay(tk->draw_target, tk->draw_in, e.out_dev, h->h_tout_dev + ring, tk->draw_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
@@ -381,6 +389,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     HIPCK(h, hipEventRecord(e.done, L->st));
     // only now: every launch of the frame has been accepted
     e.stream = stream, e.unit = h->unit_submit++, e.batch = false, e.prof = nullptr, e.tracked = tk != nullptr;
+    e.pv_h = tk && tk->preview ? tk->pv.g.dh : 0, e.pv_w = tk && tk->preview ? tk->pv.g.dw : 0;
     e.before = sm.t;  // (a tracked frame's refused crop rolls back)
     commit_time(sm, t2d, t3d);
     sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
@@ -424,6 +433,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         return fail(h, VNECT_E_COMM, "pyramid exchange: a peer's maps did not arrive within the bound (ranks out of step?); "
                                      "destroy the handles of every rank and reconnect");
     }
+    h->last_pv_ring = -1, h->last_pv_h = h->last_pv_w = 0;  // (a frame whose crop was refused has no preview)
     if (stream_out) *stream_out = e.stream;
     if (rect_out)
         for (int k = 0; k < 4; k++) rect_out[k] = e.tracked ? h->h_tout[ring].rect[k] : -1;
@@ -440,6 +450,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     if (j2) memcpy(j2, e.out->j2d, sizeof(double) * NJ * 2);
     if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
     deliver_confidence(h, ring, e.tracked);
+    if (e.tracked && e.pv_h) h->last_pv_ring = ring, h->last_pv_h = e.pv_h, h->last_pv_w = e.pv_w;
     if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
     if (h->profiling && !e.batch) {
         float frame_ms = 0;

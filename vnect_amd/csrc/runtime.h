@@ -32,6 +32,7 @@
 #include "kernels.h"
 #include "orient.h"
 #include "overlay.h"
+#include "preview.h"
 
 namespace vnect {
 namespace rt {
@@ -144,6 +145,7 @@ struct InFlight {
     bool batch = false;           // the entry is a frame of a batch (the handle's own profiling figures skip it)
     Plan* prof = nullptr;         // a profiled batch's plan, on the ring entry of its last frame (collect reads its layer times)
     bool tracked = false;
+    int pv_h = 0, pv_w = 0;        // a tracked frame that carries a preview (vnect_submit_tracked_device_preview): its size; 0: none
     TimeState before{};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
 };
 
@@ -196,6 +198,14 @@ struct vnect_handle : Plan {
     uint8_t* stage_dev[3] = {};  // the same buffers as the device addresses them (hipHostMallocMapped)
     size_t stage_cap[3] = {};
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
+    uint8_t* preview_stage = nullptr;  // vnect_preview_device with a host `out`: the kernel's packed output, copied out from here (grown on demand)
+    size_t preview_stage_cap = 0;
+    // tracked previews (vnect_submit_tracked_device_preview): per result-ring slot a device buffer the kernel writes and a pinned host buffer
+    // its copy lands in, all pv_cap bytes; sized at the first such submit and re-sized only while nothing is in flight
+    uint8_t* pv_dev[RING] = {};
+    uint8_t* pv_host[RING] = {};
+    size_t pv_cap = 0;
+    int last_pv_ring = -1, last_pv_h = 0, last_pv_w = 0;  // the preview of the frame vnect_collect_tracked delivered last (vnect_result_preview)
     hipStream_t upload_st = nullptr;  // ingest_sync's copy kernel (made on first use): not a lane's compute stream
     hipEvent_t producer_ev = nullptr; // a device frame's producer stream -> the stream that ingests it (wait_for_producer; made on first use)
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
@@ -380,6 +390,11 @@ struct FrameSrc {
     bool draw = false;
     OverlayTarget draw_target{};
     OverlayInput draw_in{};  // the style: parents, threshold (joints, rect and confidences are read from the ring slot)
+    // a tracked device frame that carries a preview (vnect_submit_tracked_device_preview): one preview launch behind its box stage (and in
+    // front of its overlay launch, so that it reads the clean frame) into the ring slot's device buffer, and that buffer's copy to the host
+    bool preview = false;
+    PreviewArgs pv{};        // everything but `out` and `pitch`, which are the ring slot's
+    OverlayInput pv_in{};    // the style
 };
 // tk: a tracked frame (vnect_submit_tracked*) -- in `slot` (SRC_SLOT) or where tk says (slot is -1 then)
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const FrameSrc* tk = nullptr);
@@ -412,6 +427,15 @@ int check_draw(vnect_handle* h, const char* who, const vnect_device_frame* f, vo
                OverlayInput* in, FrameSrc* src_out);
 int draw_device_impl(vnect_handle* h, const vnect_device_frame* target, void* stream, const double* j2d, const double* conf, const int32_t* rect4,
                      const vnect_overlay_style* style);
+
+// the preview (vnect_preview_size / vnect_preview_device; preview.h)
+int preview_size_impl(vnect_handle* h, const vnect_device_frame* f, const vnect_preview_spec* spec, int32_t* out_hw);
+int preview_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stream, const double* j2d, const double* conf, const int32_t* rect4,
+                        const vnect_overlay_style* style, const vnect_preview_spec* spec, void* out, int64_t out_pitch);
+
+// a tracked submit's preview: validates frame (as check_draw does when `style_too`), style and spec, sizes the ring's preview buffers, fills s->pv
+int check_tracked_preview(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style,
+                          const vnect_preview_spec* spec, int orient, FrameSrc* s);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);

@@ -269,6 +269,39 @@ class VNectEstimator:
         self._h.draw_device(_native.device_frame(frame, pixel_format), joints_2d, rect, confidence, style, stream)
         return frame
 
+    def preview(self, frame, joints_2d=None, rect=None, confidence=None, min_confidence=None, colors=None, pixel_format="bgr", factor=None,
+                out=None, out_format="bgr", stream=None, orientation=None):
+        """Additive (PREVIEW.md): the picture the reference shows (run_estimator_ps.py:94-96: ``draw_limbs_2d`` into ``frame.copy()``, then
+        ``img_scale`` to 1024 on the longer side) of a frame in DEVICE memory -- anything ``draw`` takes -- computed by one kernel launch
+        that reads the frame where it lies and NEVER writes it.  ``joints_2d`` / ``rect`` None: no limbs / no rectangle; ``factor`` None:
+        1024 / the oriented picture's longer side; ``out_format`` "bgr" or "rgb".  Returns a fresh (dh, dw, 3) uint8 numpy array -- or, with
+        ``out`` (a device array with ``__cuda_array_interface__``: (dh, dw, 3) uint8, unit channel stride, 3-byte pixel stride), fills it
+        and returns it.  The pixels are those of ``render.preview_exact``."""
+        if not _native.is_device_array(frame):
+            raise ValueError("preview() takes a frame in device memory; render.preview_exact computes the same picture from host arrays")
+        self._format(pixel_format, None, True)
+        self._orient(orientation)    # joints and rect are in the oriented picture's coordinates
+        style = _native.overlay_style(min_confidence, colors, self.joint_parents)
+        spec = _native.preview_spec(factor, out_format)
+        f = _native.device_frame(frame, pixel_format)
+        dh, dw = self._h.preview_size(f, spec)
+        if out is None:
+            res = np.empty((dh, dw, 3), np.uint8)
+            self._h.preview_device(f, spec, res.ctypes.data, 3 * dw, joints_2d, rect, confidence, style, stream)
+            return res
+        ptr, shape, strides = _native._cai(out, 3, "out")
+        if shape != (dh, dw, 3) or strides[2] != 1 or strides[1] != 3 or strides[0] < 3 * dw:
+            raise ValueError("out must be a uint8 (%d, %d, 3) device array with unit channel stride and 3-byte pixel stride" % (dh, dw))
+        self._h.preview_device(f, spec, ptr, strides[0], joints_2d, rect, confidence, style, stream)
+        return out
+
+    def preview_size(self, H, W, factor=None, orientation=None):
+        """Additive (PREVIEW.md): (rows, columns) of ``preview``'s result for a stored (H, W) frame (an NV12 frame: its picture's H, W)."""
+        self._orient(orientation)
+        f = _native.DeviceFrame()
+        f.struct_size, f.H, f.W = _native.C.sizeof(_native.DeviceFrame), int(H), int(W)
+        return self._h.preview_size(f, _native.preview_spec(factor))
+
     def frame_buffer(self, height, width, index=0, pixel_format="bgr"):
         """Additive: a (height, width, 3) uint8 array in PINNED host memory (two exist, ``index`` 0 / 1).  Capture into it
         (``cap.read(buf)``, ``buf[...] = frame``) and pass it -- or a crop of it, as the tracking loop does -- to the estimator: the

@@ -105,6 +105,100 @@ def draw_limbs_2d_exact(img, joints_2d, limb_parents, rect, pixel_format="bgr", 
     return out
 
 
+PREVIEW_MAX = 4096   # an output side at most (include/vnect_abi.h: VNECT_PREVIEW_MAX)
+
+
+def _preview_geom(H, W, factor=None):
+    """(rows, columns, the factor used) of an (H, W) picture scaled by ``factor`` as cv2.resize(.., (0, 0), fx=f, fy=f) sizes it: cv_round(H f),
+    cv_round(W f), half to even.  ``factor`` None or 0: the reference's 1024.0 / max(W, H) (run_estimator_ps.py:95).  Raises ValueError
+    for what the device refuses: a negative or non-finite factor, a side that rounds to 0 or exceeds PREVIEW_MAX."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("the picture must be at least one pixel wide and high")
+    f = 0.0 if factor is None else float(factor)
+    if not (0.0 <= f <= 1.7e308):
+        raise ValueError("the factor must be finite and not negative")
+    if f == 0.0:
+        f = 1024.0 / float(max(W, H))
+    dhf, dwf = H * f, W * f
+    if not (dhf < 1e6 and dwf < 1e6):
+        raise ValueError("an output side exceeds %d" % PREVIEW_MAX)
+    dh, dw = int(np.rint(dhf)), int(np.rint(dwf))
+    if dh < 1 or dw < 1:
+        raise ValueError("an output side rounds to 0")
+    if dh > PREVIEW_MAX or dw > PREVIEW_MAX:
+        raise ValueError("an output side exceeds %d" % PREVIEW_MAX)
+    return dh, dw, f
+
+
+def _resize_axis(dsize, ssize, scale, x_axis):
+    """cv2's per-axis INTER_LINEAR table (vnect_amd/csrc/axis.h): taps s0, s1, the 11-bit coefficients and the x axis's edge flag."""
+    fx = ((np.arange(dsize, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    fl = np.floor(fx)
+    fr = (fx - fl).astype(np.float32)
+    s = fl.astype(np.int64)
+    if x_axis:
+        fr = np.where(s < 0, np.float32(0), fr)
+        s = np.maximum(s, 0)
+        edge = s + 1 >= ssize
+        fr = np.where(s >= ssize - 1, np.float32(0), fr).astype(np.float32)
+        s0 = np.minimum(s, ssize - 1)
+        s1 = np.minimum(s0 + 1, ssize - 1)
+    else:
+        edge = np.zeros(dsize, bool)
+        s0, s1 = np.clip(s, 0, ssize - 1), np.clip(s + 1, 0, ssize - 1)
+    c0 = np.clip(np.rint((np.float32(1) - fr) * np.float32(2048)), -32768, 32767).astype(np.int64)
+    c1 = np.clip(np.rint(fr * np.float32(2048)), -32768, 32767).astype(np.int64)
+    return s0, s1, c0, c1, edge
+
+
+def resize_u8_exact(img, f):
+    """cv2.resize(img, (0, 0), fx=f, fy=f, interpolation=cv2.INTER_LINEAR) of a uint8 (H, W) or (H, W, C) array in the 8-bit path's own
+    11-bit fixed point (PREVIEW.md; vnect_amd/csrc/preview.h), in numpy: the arithmetic the pyramid and the preview kernel use on the
+    device.  Equal sizes in both axes are a copy."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError("resize_u8_exact takes a uint8 (H, W) or (H, W, C) array")
+    H, W = img.shape[:2]
+    dh, dw, f = _preview_geom(H, W, f)
+    if dh == H and dw == W:
+        return np.array(img, copy=True)
+    scale = 1.0 / f
+    x0, x1, a0, a1, edge = _resize_axis(dw, W, scale, True)
+    y0, y1, b0, b1, _ = _resize_axis(dh, H, scale, False)
+    src = img.astype(np.int64).reshape(H, W, -1)
+    a0, a1, edge = a0[None, :, None], a1[None, :, None], edge[None, :, None]
+
+    def row(y):
+        top = src[y]
+        return np.where(edge, top[:, x0] * 2048, top[:, x0] * a0 + top[:, x1] * a1)
+
+    r0, r1 = row(y0), row(y1)
+    out = (((b0[:, None, None] * (r0 >> 4)) >> 16) + ((b1[:, None, None] * (r1 >> 4)) >> 16) + 2) >> 2
+    return out.astype(np.uint8).reshape((dh, dw) + img.shape[2:])
+
+
+def preview_exact(img, joints_2d, parents, rect, factor=None, out_format="bgr", confidence=None, min_confidence=None, colors=None):
+    """The reference's display picture (run_estimator_ps.py:94-96: ``draw_limbs_2d`` into a copy, then ``img_scale`` to 1024 on the
+    longer side) by the exact rule the device computes it with (PREVIEW.md): pixel-identical to ``VNectEstimator.preview``.  ``img``: the
+    uint8 (H, W, 3) BGR picture as it is looked at (an oriented frame: turned first); ``joints_2d`` None: no limbs; ``rect`` None: no
+    rectangle; ``factor`` None: 1024 / the longer side; ``out_format`` "bgr" or "rgb".  The other arguments are
+    ``draw_limbs_2d_exact``'s.  Returns a fresh (dh, dw, 3) array; ``img`` is not changed."""
+    if out_format not in ("bgr", "rgb"):
+        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("frame must be a uint8 (H, W, 3) array")
+    _preview_geom(img.shape[0], img.shape[1], factor)
+    if joints_2d is None and rect is None:
+        a = img
+    else:
+        j = np.full((21, 2), np.nan) if joints_2d is None else joints_2d
+        a = draw_limbs_2d_exact(img, j, parents, rect, confidence=confidence, min_confidence=min_confidence, colors=colors)
+    out = resize_u8_exact(a, factor)
+    return np.ascontiguousarray(out[:, :, ::-1]) if out_format == "rgb" else out
+
+
 def draw_limbs_3d(joints_3d, joint_parents, size=400, extent=500.0):
     """Orthographic front view of the 21x3 joints in mm (the reference's plot limits are +-500): uint8 BGR (size, size, 3)."""
     from PIL import Image, ImageDraw

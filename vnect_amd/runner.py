@@ -190,7 +190,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
 
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
-                    confidence=False, lost=None, draw=False, orientation=None):
+                    confidence=False, lost=None, draw=False, orientation=None, preview=False):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -206,15 +206,19 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     own joints and the rect it was cropped with (run_estimator_ps.py:92-94) by the time it is yielded; the results are those of
     ``draw=False``, bit for bit.
     ``orientation`` (ORIENTATION.md): the code 0 .. 7 the frames are stored under, from every source (None: the estimator's own); the crop
-    is turned on the device."""
+    is turned on the device.
+    ``preview`` (``source="device"`` only; PREVIEW.md): True (the reference's 1024 on the longer side), a factor, or an
+    ``_native.preview_spec(...)`` -- every yielded tuple gets the frame's display picture appended (run_estimator_ps.py:94-96: the frame
+    annotated with its own joints and ``rect_used``, scaled; a fresh (dh, dw, 3) array, or None for a frame without one), computed on
+    the device; the frame is not written unless ``draw`` is given too, and then the preview is that of the clean frame."""
     for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
                                     None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw,
-                                    orientation):
+                                    orientation, preview):
         yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None):
+                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None, preview=False):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
@@ -223,7 +227,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
     afterwards); ``confidence=True`` appends
     (confidence, lost flag) to every tuple.
-    ``draw``: as in ``track_on_device``.
+    ``draw``, ``preview``: as in ``track_on_device``.
     ``orientation``: one code for all videos or one per video (ORIENTATION.md; None: the estimator's own): every stream keeps the code its track began with, so
     videos with different orientations share the handle; the estimator's own orientation is back in force afterwards."""
     from collections import deque
@@ -234,6 +238,16 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     style = None
     if draw is not False and draw is not None:
         style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
+    spec = None
+    if preview is not False and preview is not None:
+        if source != "device":
+            raise ValueError("preview= scales frames in device memory: it needs source='device'")
+        if isinstance(preview, _native.PreviewSpec):
+            spec = _native.preview_spec(preview.factor, "rgb" if preview.out_format == _native.PIX_RGB else "bgr", style is not None)
+        else:
+            spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
+        if style is None:
+            style = _native.overlay_style(parents=estimator.joint_parents)
     nv12 = _nv12_checks(pixel_format, transpose, source)
     codes = _orientations(estimator, orientation, len(videos), transpose)
     rule = lost_rule(lost)
@@ -290,9 +304,12 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             estimator._raise_like_reference(e)
         finally:
             held.pop(k, None)
+        res = (video_of[s], j2, j3, used)
         if confidence:                          # (of the frame just delivered: taken from its own result slot)
-            return (video_of[s], j2, j3, used) + h.result_confidence()
-        return video_of[s], j2, j3, used
+            res += h.result_confidence()
+        if spec is not None:                    # (likewise: the pinned buffer of its ring slot, copied before the next submit)
+            res += (h.result_preview(),)
+        return res
 
     # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
     # collected and dropped, so the estimator is usable at once afterwards (runner.track leaves nothing in flight either)
@@ -307,7 +324,9 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 H, W = size_of(frame)
                 try:
                     if device:
-                        if style is not None:
+                        if spec is not None:
+                            h.submit_tracked_device_preview(streams[i], frame, t2d, t3d, frame._producer, style, spec)
+                        elif style is not None:
                             h.submit_tracked_device_draw(streams[i], frame, t2d, t3d, frame._producer, style)
                         else:
                             h.submit_tracked_device(streams[i], frame, t2d, t3d, frame._producer)
