@@ -409,6 +409,52 @@ int vnect_submit_tracked_device_preview(vnect_handle* h, int stream, const vnect
                                         const vnect_overlay_style* style, const vnect_preview_spec* spec);
 int vnect_result_preview(vnect_handle* h, const uint8_t** data, int32_t hw[2], int64_t* pitch);
 
+/* ABI v7, additive.  The person detector in front of the loop (HOG.md).  The reference finds its first crop box with OpenCV's HOG people
+ * detector (src/hog_box.py:24-33: cv2.HOGDescriptor(), setSVMDetector(cv2.HOGDescriptor_getDefaultPeopleDetector()),
+ * detectMultiScale(img)), takes the biggest rectangle and inflates it (src/hog_box.py:37-58).  Here the detection runs on the device, by
+ * the rule of vnect_amd/csrc/hog.h: a pyramid of the oriented picture in cv2's 8-bit INTER_LINEAR, gamma-corrected gradients, 9-bin votes,
+ * 16 x 16 block histograms with L2-Hys, a 64 x 128 window's 3780-element descriptor against the detector vector, groupRectangles on the
+ * host.  NOTHING is pinned against cv2 (HOG.md lists what a holder of cv2 should compare first); the detector vector is an INPUT, in the
+ * layout cv2.HOGDescriptor_getDefaultPeopleDetector() returns.
+ * vnect_hog_set_detector (src/hog_box.py:26): n = 3781 floats, rho last, or 3780 with rho 0.  VNECT_E_ARG: any other n, a NaN or an
+ * infinite entry.  The handle keeps a copy.
+ * vnect_hog_spec: detectMultiScale's parameters (src/hog_box.py:28 passes none: the defaults); a zero field means its default --
+ * hit_threshold 0, win_stride 8 x 8, scale0 1.05, final_threshold 2.0, nlevels 64, max_hits 65536.  spec NULL: all defaults.
+ * vnect_hog_levels (src/hog_box.py:28): the pyramid of the frame's oriented picture under the orientation in force -- *n_out levels,
+ * hw_out[2 n] = (rows, columns), scales_out[n], the first `capacity` of them (each array may be NULL).  Arithmetic only: the frame's
+ * pointers are not looked at.
+ * vnect_hog_detect_device (src/hog_box.py:28): the grouped detections of `frame` -- rects4[4 i] = (x, y, w, h) in oriented picture
+ * coordinates, weights[i] the largest score of the group -- the first `capacity` of them; *count_out is the full count, also above
+ * capacity.  Three launches on the handle's upload stream cover all levels; they are ordered behind producer_stream as in
+ * vnect_preview_device, the frame is only read, and the call is done on return.  The workspace belongs to the handle and grows on demand.
+ * vnect_hog_detect (src/hog_box.py:28): the same for a host BGR frame, rows row_stride >= 3 * W bytes apart, under the orientation in
+ * force; the frame is copied to the device first.
+ * All of these work before vnect_finalize and on a preprocess_only handle.  VNECT_E_STATE: no detector set.  VNECT_E_ARG, before anything
+ * is launched: frame->has_rect; strides that are not positive multiples of 8; scale0 <= 1; NaN or infinite thresholds; nlevels outside
+ * 1 .. 64; a negative max_hits or capacity; a picture side above VNECT_HOG_MAX_SIDE; a pyramid-sharded handle; everything
+ * vnect_preview_device refuses of a frame.  A picture smaller than the window in either axis is no error: no level, no detection, no
+ * launch.  More than max_hits windows at or above hit_threshold fail the call (VNECT_E_STATE, "raise hit_threshold"): nothing is returned
+ * and nothing is written out of bounds. */
+#define VNECT_HOG_MAX_SIDE 4096
+#define VNECT_HOG_DETECTOR_SIZE 3781
+typedef struct vnect_hog_spec {
+    int32_t struct_size;     /* = sizeof(vnect_hog_spec) */
+    double hit_threshold;    /* 0 */
+    int32_t win_stride_x;    /* 0: 8 */
+    int32_t win_stride_y;    /* 0: 8 */
+    double scale0;           /* 0: 1.05 */
+    double final_threshold;  /* 0: 2.0 */
+    int32_t nlevels;         /* 0: 64 */
+    int32_t max_hits;        /* 0: 65536 */
+} vnect_hog_spec;
+int vnect_hog_set_detector(vnect_handle* h, const float* w, int n);
+int vnect_hog_levels(vnect_handle* h, const vnect_device_frame* frame, const vnect_hog_spec* spec, int32_t* n_out, int32_t* hw_out, double* scales_out,
+                     int capacity);
+int vnect_hog_detect_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, const vnect_hog_spec* spec, int32_t* rects4,
+                            double* weights, int capacity, int32_t* count_out);
+int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
+                     int capacity, int32_t* count_out);
+
 /* Orientation (ABI v7, additive; ORIENTATION.md).  The reference's loop has a `T` option for a camera that is mounted sideways: it turns
  * every frame with np.rot90(frame, 3) before the crop (run_estimator_ps.py:57-62, 81-85; commented out beside it, an np.transpose
  * variant).  Here the turn happens on the device, inside the copy that brings the crop into the slot, so only the crop moves.

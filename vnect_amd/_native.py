@@ -109,6 +109,30 @@ def preview_spec(factor=None, out_format="bgr", draw_frame=False):
     return s
 
 
+HOG_DETECTOR_SIZE, HOG_MAX_SIDE = 3781, 4096   # VNECT_HOG_DETECTOR_SIZE, VNECT_HOG_MAX_SIDE
+
+
+class HogSpec(C.Structure):
+    """vnect_hog_spec: detectMultiScale's parameters; a zero field means its default (include/vnect_abi.h; HOG.md)."""
+    _fields_ = [("struct_size", C.c_int32), ("hit_threshold", C.c_double), ("win_stride_x", C.c_int32), ("win_stride_y", C.c_int32),
+                ("scale0", C.c_double), ("final_threshold", C.c_double), ("nlevels", C.c_int32), ("max_hits", C.c_int32)]
+
+
+def hog_spec(hit_threshold=0.0, win_stride=(8, 8), scale0=1.05, final_threshold=2.0, nlevels=64, max_hits=65536):
+    """The HogSpec of a detection, cv2.HOGDescriptor.detectMultiScale's names and defaults (win_stride is (x, y))."""
+    s = HogSpec()
+    s.struct_size = C.sizeof(HogSpec)
+    s.hit_threshold, s.scale0, s.final_threshold = float(hit_threshold), float(scale0), float(final_threshold)
+    s.win_stride_x, s.win_stride_y = int(win_stride[0]), int(win_stride[1])
+    s.nlevels, s.max_hits = int(nlevels), int(max_hits)
+    # a zero means "the default" in the C structure: what the caller wrote as 0 where 0 is not the default must be refused, not replaced
+    if s.win_stride_x == 0 or s.win_stride_y == 0 or s.scale0 == 0.0 or s.nlevels == 0 or s.max_hits == 0:
+        raise ValueError("win_stride, scale0, nlevels and max_hits must not be 0")
+    if s.final_threshold == 0.0:
+        s.final_threshold = 0.5   # (below 1: the hits ungrouped, as 0 means in cv2)
+    return s
+
+
 class DeviceFrameError(VnectError, ValueError):
     """VNECT_E_ARG of a device-frame entry point: the frame as given cannot be read (a ValueError, like every refused argument)."""
 
@@ -181,6 +205,10 @@ SYMBOLS = {
     "vnect_submit_tracked_device_preview": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
                                                       C.POINTER(OverlayStyle), C.POINTER(PreviewSpec)]),
     "vnect_result_preview": (C.c_int, [_H, C.POINTER(_u8p), _i32p, C.POINTER(C.c_int64)]),
+    "vnect_hog_set_detector": (C.c_int, [_H, _f32p, C.c_int]),
+    "vnect_hog_levels": (C.c_int, [_H, C.POINTER(DeviceFrame), C.POINTER(HogSpec), _i32p, _i32p, _f64p, C.c_int]),
+    "vnect_hog_detect_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
+    "vnect_hog_detect": (C.c_int, [_H, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
 }
 
 
@@ -200,6 +228,8 @@ ORIENTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_orientprobe.so")   # orie
 ORIENT_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_orient.so")         # g++'s build of csrc/orient.h (tests only; no GPU code)
 PREVIEWPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_previewprobe.so") # preview.o behind csrc/preview_probe.hip (tests only)
 PREVIEW_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_preview.so")       # g++'s build of csrc/preview.h (tests only; no GPU code)
+HOGPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_hogprobe.so")         # hog.o behind csrc/hog_probe.hip (tests only)
+HOG_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_hog.so")               # g++'s build of csrc/hog.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -222,6 +252,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "orientprobe", "orient"], stdout=subprocess.DEVNULL)
     # the preview's probe (tests/test_gpu_preview_kernels.py) and g++'s build of its tile walk (tests/test_preview_cpu.py)
     subprocess.check_call(["make", "-C", src, "previewprobe", "preview"], stdout=subprocess.DEVNULL)
+    # the detector's probe (tests/test_gpu_hog_kernels.py) and g++'s build of its walk (tests/test_hog_cpu.py)
+    subprocess.check_call(["make", "-C", src, "hogprobe", "hog"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -601,6 +633,43 @@ class Handle:
         if hw[0] < 1 or hw[1] < 1:
             return None
         return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
+
+    # -- the person detector: HOG + linear SVM over a pyramid, on the device (include/vnect_abi.h; HOG.md) ------------------------------
+    def hog_set_detector(self, w):
+        """vnect_hog_set_detector: 3781 floats, rho last (cv2.HOGDescriptor_getDefaultPeopleDetector()'s layout), or 3780 with rho 0."""
+        a = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
+        rc = lib().vnect_hog_set_detector(self._h, _ptr(a, _f32p), int(a.size))
+        if rc == E_ARG:
+            raise DeviceFrameError(rc, lib().vnect_last_error(self._h).decode())
+        self._ck(rc)
+
+    def hog_levels(self, frame, spec=None):
+        """vnect_hog_levels: ((n, 2) int32 level sizes (rows, columns), (n,) float64 scales) of `frame` (a DeviceFrame; only H and W count)."""
+        n, hw, sc = C.c_int32(0), np.zeros((64, 2), np.int32), np.zeros(64, np.float64)
+        self._ck_device(lib().vnect_hog_levels(self._h, C.byref(frame), None if spec is None else C.byref(spec), C.byref(n), _ptr(hw, _i32p),
+                                               _ptr(sc, _f64p), 64))
+        return hw[:n.value].copy(), sc[:n.value].copy()
+
+    def _hog_out(self, call, capacity):
+        """call(rects pointer, weights pointer, capacity, count) -> ((n, 4) int32 rects [x, y, w, h], (n,) float64 weights), all of them"""
+        while True:
+            rects, ws, cnt = np.zeros((max(capacity, 1), 4), np.int32), np.zeros(max(capacity, 1), np.float64), C.c_int32(0)
+            self._ck_device(call(_ptr(rects, _i32p), _ptr(ws, _f64p), capacity, C.byref(cnt)))
+            if cnt.value <= capacity:
+                return rects[:cnt.value].copy(), ws[:cnt.value].copy()
+            capacity = cnt.value
+
+    def hog_detect_device(self, frame, spec=None, stream=None, capacity=256):
+        """vnect_hog_detect_device: the grouped detections of `frame` (a DeviceFrame without a rect); done on return."""
+        sp, st = None if spec is None else C.byref(spec), _stream_arg(stream)
+        return self._hog_out(lambda r, w, cap, cnt: lib().vnect_hog_detect_device(self._h, C.byref(frame), st, sp, r, w, cap, cnt), capacity)
+
+    def hog_detect(self, img, spec=None, capacity=256):
+        """vnect_hog_detect: the grouped detections of a host BGR frame."""
+        img = _as_frame(img)
+        H, W = img.shape[:2]
+        sp = None if spec is None else C.byref(spec)
+        return self._hog_out(lambda r, w, cap, cnt: lib().vnect_hog_detect(self._h, _ptr(img, _u8p), H, W, img.strides[0], sp, r, w, cap, cnt), capacity)
 
     def read_frame(self, slot):
         """The (H, W, 3) BGR frame resident slot `slot` holds (a debugging read)."""

@@ -366,6 +366,30 @@ hipError_t launch_overlay(const OverlayTarget& t, const OverlayInput& in, const 
 struct PreviewArgs;
 hipError_t launch_preview(const PreviewArgs& a, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
 
+// ---- the person detector (hog.hip; vnect_hog_detect_device; HOG.md) --------------------------------------------------------------------
+// hog_box.py:24-33: HOG + linear SVM over a pyramid of the oriented picture, by the rule of hog.h.  Three launches cover all levels through
+// the level table `lv` (device memory, p.n entries): votes (the level images are computed inside it), block histograms + L2-Hys, window
+// scores.  Everything the launches write is workspace the caller owns: votes / bins [p.npix], blocks [p.nblk * 36], hits [max_hits] and
+// one counter, which ends as the number of windows that cleared hit_threshold -- only the first max_hits of them are stored.  scores
+// (may be null): every window's score [p.nwin].  `stages`: bit 0 votes, bit 1 blocks, bit 2 windows (the product passes 7).
+struct HogSrc;
+struct HogPlan;
+struct HogLevel;
+struct HogTables;
+struct HogHit;
+struct HogDev {
+    const HogLevel* lv;
+    const HogTables* tab;
+    const float* det;  // 3781 floats, rho last
+    float2* votes;
+    uint8_t* bins;
+    float* blocks;
+    HogHit* hits;
+    unsigned* count;
+    float* scores;
+};
+hipError_t launch_hog(const HogSrc& a, const HogPlan& p, const HogDev& d, double hit_threshold, int max_hits, int stages, hipStream_t st);
+
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);
 

@@ -1004,6 +1004,45 @@ int vnect_preview_device(vnect_handle* h, const vnect_device_frame* frame, void*
 }
 
 // ---- orientation (additive; ORIENTATION.md): frames that are stored rotated / mirrored, turned inside the crop's copy (orient.hip) ------
+// ---- the person detector (additive; HOG.md; src/hog_box.py:24-33): HOG + linear SVM over a pyramid, three launches of hog.hip ----------
+int vnect_hog_set_detector(vnect_handle* h, const float* w, int n)  // hog_box.py:26
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return hog_set_detector_impl(h, w, n);
+    });
+}
+
+int vnect_hog_levels(vnect_handle* h, const vnect_device_frame* frame, const vnect_hog_spec* spec, int32_t* n_out, int32_t* hw_out, double* scales_out,
+                     int capacity)  // hog_box.py:28
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        return hog_levels_impl(h, frame, spec, n_out, hw_out, scales_out, capacity);
+    });
+}
+
+int vnect_hog_detect_device(vnect_handle* h, const vnect_device_frame* frame, void* producer_stream, const vnect_hog_spec* spec, int32_t* rects4,
+                            double* weights, int capacity, int32_t* count_out)  // hog_box.py:28
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return hog_detect_device_impl(h, frame, producer_stream, spec, rects4, weights, capacity, count_out);
+    });
+}
+
+int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
+                     int capacity, int32_t* count_out)  // hog_box.py:28
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return hog_detect_host_impl(h, bgr, H, W, row_stride, spec, rects4, weights, capacity, count_out);
+    });
+}
+
 int vnect_set_orientation(vnect_handle* h, int orientation)
 {
     return guarded(&h, [&]() -> int {

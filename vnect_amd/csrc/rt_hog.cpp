@@ -1,0 +1,185 @@
+// rt_hog.cpp -- the person detector behind the C ABI (vnect_hog_set_detector / vnect_hog_levels / vnect_hog_detect_device /
+// vnect_hog_detect; src/hog_box.py:24-33).  The frame is validated by the device-frame resolver of rt_ingest.cpp and read where it lies,
+// as the preview reads it; the spec becomes hog.h's level table, from which the handle's workspace is sized; three launches of hog.hip
+// cover all levels; the hits come back, are put in the order (level, y, x) and grouped on the host (hog.h: hog_group).  A refusal
+// changes nothing and launches nothing.
+#include "runtime.h"
+
+namespace vnect {
+namespace rt {
+
+static int refuse(vnect_handle* h, const char* who, const char* what) { return fail(h, VNECT_E_ARG, std::string(who) + ": " + what); }
+
+// the spec (nullptr: all defaults) with its defaults filled in
+static int spec_in(vnect_handle* h, const char* who, const vnect_hog_spec* s, HogSpec* out)
+{
+    vnect_hog_spec z;
+    memset(&z, 0, sizeof z);
+    if (s) {
+        if (s->struct_size != (int32_t)sizeof(vnect_hog_spec)) return refuse(h, who, "vnect_hog_spec::struct_size is not sizeof(vnect_hog_spec)");
+        z = *s;
+    }
+    if (z.win_stride_x < 0 || z.win_stride_y < 0 || z.nlevels < 0 || z.max_hits < 0) return refuse(h, who, "a negative field in vnect_hog_spec");
+    const int rc = hog_spec(z.hit_threshold, z.win_stride_x, z.win_stride_y, z.scale0, z.final_threshold, z.nlevels, z.max_hits, out);
+    return rc == HOG_OK ? VNECT_OK : refuse(h, who, hog_refusal(rc));
+}
+
+static int common_in(vnect_handle* h, const char* who, bool need_detector)
+{
+    if (h->sharded) return refuse(h, who, "the detector on a pyramid-sharded handle is not supported");
+    if (need_detector && h->hog_det.empty()) return fail(h, VNECT_E_STATE, std::string(who) + ": no detector set: call vnect_hog_set_detector first");
+    return VNECT_OK;
+}
+
+int hog_set_detector_impl(vnect_handle* h, const float* w, int n)
+{
+    static const char* who = "vnect_hog_set_detector";
+    int rc0 = common_in(h, who, false);
+    if (rc0) return rc0;
+    std::vector<float> d;
+    if (!hog_detector(w, n, &d)) return refuse(h, who, "the detector is 3781 finite floats, rho last (or 3780: rho 0)");
+    if (!h->hog_det_dev) {
+        int rc = dev_alloc(h, &h->hog_det_dev, d.size());
+        if (rc) return rc;
+    }
+    if (h->upload_st) HIPCK(h, hipStreamSynchronize(h->upload_st));
+    HIPCK(h, hipMemcpy(h->hog_det_dev, d.data(), d.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->hog_det.swap(d);
+    return VNECT_OK;
+}
+
+int hog_levels_impl(vnect_handle* h, const vnect_device_frame* f, const vnect_hog_spec* spec, int32_t* n_out, int32_t* hw_out, double* scales_out, int capacity)
+{
+    static const char* who = "vnect_hog_levels";
+    int rc = common_in(h, who, false);
+    if (rc) return rc;
+    if (!f) return refuse(h, who, "no frame descriptor");
+    if (f->struct_size != (int32_t)sizeof(vnect_device_frame)) return refuse(h, who, "vnect_device_frame::struct_size is not sizeof(vnect_device_frame)");
+    if (f->H < 1 || f->W < 1 || f->H > (1 << 24) || f->W > (1 << 24)) return refuse(h, who, "bad frame geometry");
+    if (!n_out || capacity < 0) return refuse(h, who, "bad argument");
+    HogSpec sp;
+    if ((rc = spec_in(h, who, spec, &sp))) return rc;
+    std::vector<HogPlan> pv(1);
+    if ((rc = hog_plan(h->orient, f->H, f->W, sp, &pv[0]))) return refuse(h, who, hog_refusal(rc));
+    *n_out = pv[0].n;
+    for (int n = 0; n < pv[0].n && n < capacity; n++) {
+        if (hw_out) hw_out[2 * n] = pv[0].lv[n].h, hw_out[2 * n + 1] = pv[0].lv[n].w;
+        if (scales_out) scales_out[n] = pv[0].lv[n].s;
+    }
+    return VNECT_OK;
+}
+
+// workspace buffer i with room for `need` bytes
+static int grow(vnect_handle* h, int i, size_t need)
+{
+    if (need <= h->hog_cap[i]) return VNECT_OK;
+    if (h->upload_st) HIPCK(h, hipStreamSynchronize(h->upload_st));
+    if (h->hog_buf[i]) {
+        HIPCK(h, hipFree(h->hog_buf[i]));
+        h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->hog_buf[i]));
+        h->hog_buf[i] = nullptr, h->hog_cap[i] = 0;
+    }
+    int rc = dev_alloc(h, &h->hog_buf[i], need);
+    if (rc) return rc;
+    h->hog_cap[i] = need;
+    return VNECT_OK;
+}
+
+// the detection of a validated source on upload_st; `stream`: what the launches wait for
+static int detect(vnect_handle* h, const char* who, const HogSrc& a, const HogSpec& sp, void* stream, int32_t* rects4, double* weights, int capacity, int32_t* count_out)
+{
+    std::vector<HogPlan> pv(1);
+    HogPlan& p = pv[0];
+    int rc = hog_plan(a.o, a.H, a.W, sp, &p);
+    if (rc) return refuse(h, who, hog_refusal(rc));
+    if (!p.n) {  // a picture smaller than the window: no level, no detection, no launch
+        *count_out = 0;
+        return VNECT_OK;
+    }
+    if (!h->hog_tab) {
+        HogTables t;
+        hog_tables(&t);
+        if ((rc = dev_alloc(h, &h->hog_tab, 1))) return rc;
+        HIPCK(h, hipMemcpy(h->hog_tab, &t, sizeof t, hipMemcpyHostToDevice));
+        if ((rc = dev_alloc(h, &h->hog_lv, HOG_MAX_LEVELS))) return rc;
+    }
+    if ((rc = grow(h, 0, sizeof(float2) * (size_t)p.npix)) || (rc = grow(h, 1, (size_t)p.npix)) || (rc = grow(h, 2, sizeof(float) * HOG_BLOCK_LEN * (size_t)p.nblk)) ||
+        (rc = grow(h, 3, sizeof(HogHit) * (size_t)sp.max_hits)) || (rc = grow(h, 4, 256)))
+        return rc;
+    if (!h->upload_st) HIPCK(h, hipStreamCreateWithFlags(&h->upload_st, hipStreamNonBlocking));
+    if ((rc = wait_for_producer(h, stream, h->upload_st))) return rc;
+    HIPCK(h, hipMemcpyAsync(h->hog_lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice, h->upload_st));
+    const HogDev d{h->hog_lv, h->hog_tab, h->hog_det_dev, (float2*)h->hog_buf[0], h->hog_buf[1], (float*)h->hog_buf[2], (HogHit*)h->hog_buf[3],
+                   (unsigned*)h->hog_buf[4], nullptr};
+    HIPCK(h, launch_hog(a, p, d, sp.hit_threshold, sp.max_hits, 7, h->upload_st));
+    unsigned count = 0;
+    HIPCK(h, hipMemcpyAsync(&count, d.count, sizeof count, hipMemcpyDeviceToHost, h->upload_st));
+    HIPCK(h, hipStreamSynchronize(h->upload_st));
+    if (count > (unsigned)sp.max_hits)
+        return fail(h, VNECT_E_STATE, std::string(who) + ": " + std::to_string(count) + " windows reached hit_threshold, more than max_hits (" + std::to_string(sp.max_hits) +
+                                          "): raise hit_threshold (or max_hits)");
+    std::vector<HogHit> hits(count);
+    if (count) HIPCK(h, hipMemcpy(hits.data(), d.hits, sizeof(HogHit) * count, hipMemcpyDeviceToHost));
+    std::vector<HogRect> rects;
+    std::vector<double> ws;
+    hog_hit_rects(p, hits, &rects, &ws);
+    hog_group(rects, ws, (int)sp.final_threshold);
+    for (size_t i = 0; i < rects.size() && (int)i < capacity; i++) {
+        if (rects4) rects4[4 * i] = rects[i].x, rects4[4 * i + 1] = rects[i].y, rects4[4 * i + 2] = rects[i].w, rects4[4 * i + 3] = rects[i].h;
+        if (weights) weights[i] = ws[i];
+    }
+    *count_out = (int32_t)rects.size();
+    return VNECT_OK;
+}
+
+int hog_detect_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stream, const vnect_hog_spec* spec, int32_t* rects4, double* weights, int capacity,
+                           int32_t* count_out)
+{
+    static const char* who = "vnect_hog_detect_device";
+    int rc = common_in(h, who, true);
+    if (rc) return rc;
+    if (!count_out || capacity < 0 || (capacity > 0 && (!rects4 || !weights))) return refuse(h, who, "bad output arguments");
+    if (f && f->struct_size == (int32_t)sizeof(vnect_device_frame) && f->has_rect) return refuse(h, who, "the frame takes no rect: the whole picture is searched");
+    HogSpec sp;
+    if ((rc = spec_in(h, who, spec, &sp))) return rc;
+    FrameSrc d;
+    if ((rc = check_device_frame(h, f, stream, who, false, h->orient, &d))) return rc;
+    int Hp, Wp;
+    orient_size(h->orient, d.H, d.W, &Hp, &Wp);
+    if (Hp > HOG_MAX_SIDE || Wp > HOG_MAX_SIDE) return refuse(h, who, hog_refusal(HOG_E_SIDE));
+    HogSrc a;
+    memset(&a, 0, sizeof a);
+    a.src = orient_src_of(d), a.o = h->orient, a.H = d.H, a.W = d.W;
+    return detect(h, who, a, sp, stream, rects4, weights, capacity, count_out);
+}
+
+int hog_detect_host_impl(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
+                         int capacity, int32_t* count_out)
+{
+    static const char* who = "vnect_hog_detect";
+    int rc = common_in(h, who, true);
+    if (rc) return rc;
+    if (!count_out || capacity < 0 || (capacity > 0 && (!rects4 || !weights))) return refuse(h, who, "bad output arguments");
+    if (!bgr || H < 1 || W < 1 || row_stride < (int64_t)W * 3) return refuse(h, who, "bad frame geometry");
+    HogSpec sp;
+    if ((rc = spec_in(h, who, spec, &sp))) return rc;
+    int Hp, Wp;
+    orient_size(h->orient, H, W, &Hp, &Wp);
+    if (Hp > HOG_MAX_SIDE || Wp > HOG_MAX_SIDE) return refuse(h, who, hog_refusal(HOG_E_SIDE));
+    if (Hp < HOG_WIN_H || Wp < HOG_WIN_W) {  // no level: nothing to copy either
+        *count_out = 0;
+        return VNECT_OK;
+    }
+    // the frame's rows to the device, packed: the pageable, synchronous copy vnect_upload_frame makes
+    const size_t row = (size_t)W * 3;
+    if ((rc = grow(h, 5, row * (size_t)H))) return rc;
+    HIPCK(h, hipMemcpy2D(h->hog_buf[5], row, bgr, (size_t)row_stride, row, (size_t)H, hipMemcpyHostToDevice));
+    HogSrc a;
+    memset(&a, 0, sizeof a);
+    a.src = preview_source(false, false, h->hog_buf[5], nullptr, (long long)row, 3, 1, 0);
+    a.o = h->orient, a.H = H, a.W = W;
+    return detect(h, who, a, sp, VNECT_STREAM_SYNCED, rects4, weights, capacity, count_out);
+}
+
+}  // namespace rt
+}  // namespace vnect

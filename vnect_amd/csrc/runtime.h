@@ -33,6 +33,7 @@
 #include "orient.h"
 #include "overlay.h"
 #include "preview.h"
+#include "hog.h"
 
 namespace vnect {
 namespace rt {
@@ -206,6 +207,14 @@ struct vnect_handle : Plan {
     uint8_t* pv_host[RING] = {};
     size_t pv_cap = 0;
     int last_pv_ring = -1, last_pv_h = 0, last_pv_w = 0;  // the preview of the frame vnect_collect_tracked delivered last (vnect_result_preview)
+    // the person detector (rt_hog.cpp; hog.h): the detector as given (3781 floats, rho last) and on the device, the host-built tables and the
+    // level table on the device, the workspace of the three launches and a host frame's device copy -- each grown on demand, never shrunk
+    std::vector<float> hog_det;
+    float* hog_det_dev = nullptr;
+    HogTables* hog_tab = nullptr;
+    HogLevel* hog_lv = nullptr;
+    uint8_t* hog_buf[6] = {};   // votes, bins, blocks, hits, the counter, a host frame's copy
+    size_t hog_cap[6] = {};
     hipStream_t upload_st = nullptr;  // ingest_sync's copy kernel (made on first use): not a lane's compute stream
     hipEvent_t producer_ev = nullptr; // a device frame's producer stream -> the stream that ingests it (wait_for_producer; made on first use)
     struct SlotInfo { int H = 0, W = 0; long long stride = 0; long long last_use = -1; };  // last_use: sequence number of the last frame that reads this slot
@@ -436,6 +445,15 @@ int preview_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stre
 // a tracked submit's preview: validates frame (as check_draw does when `style_too`), style and spec, sizes the ring's preview buffers, fills s->pv
 int check_tracked_preview(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style,
                           const vnect_preview_spec* spec, int orient, FrameSrc* s);
+
+// ---- rt_hog.cpp ----------------------------------------------------------------------------------------------------------------
+// the person detector (vnect_hog_*; hog.h; HOG.md)
+int hog_set_detector_impl(vnect_handle* h, const float* w, int n);
+int hog_levels_impl(vnect_handle* h, const vnect_device_frame* f, const vnect_hog_spec* spec, int32_t* n_out, int32_t* hw_out, double* scales_out, int capacity);
+int hog_detect_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stream, const vnect_hog_spec* spec, int32_t* rects4, double* weights, int capacity,
+                           int32_t* count_out);
+int hog_detect_host_impl(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
+                         int capacity, int32_t* count_out);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);

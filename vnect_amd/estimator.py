@@ -28,7 +28,7 @@ class VNectEstimator:
     joint_parents = [16, 15, 1, 2, 3, 1, 5, 6, 14, 8, 9, 14, 11, 12, 14, 14, 1, 4, 7, 10, 13]
 
     def __init__(self, scales=None, weights=None, seed=MASTER_SEED, device=0, precision="fp32", paper_res2c=False,
-                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1, orientation=0):
+                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1, orientation=0, hog_detector=None):
         if verbose:
             print('Initializing VNect Estimator...')
         # src/estimator.py:32; "for faster loops, use less scales e.g. [1], [1, 0.7]"
@@ -46,6 +46,7 @@ class VNectEstimator:
         self._submitted = 0
         self._weights = weights
         self._orientation = self._check_orientation(orientation)
+        self._hog_detector = None if hog_detector is None else np.array(hog_detector, dtype=np.float32).reshape(-1)
         self._h = None
         self._open()
         self.verbose = verbose
@@ -59,6 +60,8 @@ class VNectEstimator:
         self._h.set_weights(self._weights)
         self._h.finalize()
         self._orient(None)
+        if self._hog_detector is not None:
+            self._h.hog_set_detector(self._hog_detector)
 
     # -- orientation (additive; ORIENTATION.md): frames that are STORED rotated / mirrored ------------------------------
     @staticmethod
@@ -301,6 +304,32 @@ class VNectEstimator:
         f = _native.DeviceFrame()
         f.struct_size, f.H, f.W = _native.C.sizeof(_native.DeviceFrame), int(H), int(W)
         return self._h.preview_size(f, _native.preview_spec(factor))
+
+    # -- the person detector (additive; HOG.md): the reference's HOGBox (src/hog_box.py:24-33) on the device -------------
+    def set_hog_detector(self, detector):
+        """The linear SVM of ``detect_people``: 3781 floats, rho last -- the array ``cv2.HOGDescriptor_getDefaultPeopleDetector()``
+        returns, flattened -- or 3780 with rho 0.  Kept across a re-plan of the scales."""
+        det = np.array(detector, dtype=np.float32).reshape(-1)
+        self._h.hog_set_detector(det)
+        self._hog_detector = det
+
+    def detect_people(self, frame, detector=None, pixel_format="bgr", stream=None, orientation=None, **spec):
+        """Additive (HOG.md): ``cv2.HOGDescriptor().detectMultiScale(frame)`` (src/hog_box.py:28) computed on the device by the rule of
+        vnect_amd/csrc/hog.h -> (rects (n, 4) int32 [x, y, w, h] in the oriented picture's coordinates, weights (n,) float64).
+        ``frame``: a host uint8 (H, W, 3) BGR array, or a frame in device memory as the estimator itself takes it (``pixel_format``
+        "bgr", "rgb" or "nv12"; ``stream`` its producer).  ``detector``: set (and kept) before the call.  ``spec``: detectMultiScale's
+        ``hit_threshold``, ``win_stride`` (x, y), ``scale0``, ``final_threshold``, ``nlevels``, and ``max_hits``."""
+        if detector is not None:
+            self.set_hog_detector(detector)
+        sp = _native.hog_spec(**spec)
+        device = _native.is_device_array(frame)
+        self._format(pixel_format, None, device)
+        if not device and pixel_format != "bgr":
+            raise ValueError("detect_people takes a host frame as BGR; an NV12 frame is read in device memory")
+        self._orient(orientation)
+        if device:
+            return self._h.hog_detect_device(_native.device_frame(frame, pixel_format), sp, stream)
+        return self._h.hog_detect(frame, sp)
 
     def frame_buffer(self, height, width, index=0, pixel_format="bgr"):
         """Additive: a (height, width, 3) uint8 array in PINNED host memory (two exist, ``index`` 0 / 1).  Capture into it

@@ -7,6 +7,8 @@
   the joints, for any iterable of frames (synthetic streams on the GPU box; there is no camera / ffmpeg).
 * ``init_box``  -- the person-box initialiser: the reference's HOG detector (``src/hog_box.py``) replaced by one pass of
   the network over the whole frame and the loop's own box arithmetic.
+* ``hog_box``   -- the reference's initialiser itself (``src/hog_box.py:26-31``): the HOG people detector on the device (HOG.md), the
+  largest detection through ``cal_rect``; ``track(lost=(c, n, "detect"))`` calls it for the frame behind a lost one.
 The capture, drawing and 3-D plotting of the reference stay out of scope.
 """
 import numpy as np
@@ -49,14 +51,18 @@ def bbox_update(joints_2d, W_img, H_img):
     return [x, y, w, h]
 
 
-def lost_rule(lost):
+def lost_rule(lost, detect=False):
     """``lost=(min_confidence, min_joints, "hold" | "reset")`` of the tracking loops as (threshold, count, action) -- or None.  The rule
-    (CONFIDENCE.md): a frame is lost when fewer than ``min_joints`` of its 21 confidences are >= ``min_confidence``."""
+    (CONFIDENCE.md): a frame is lost when fewer than ``min_joints`` of its 21 confidences are >= ``min_confidence``.  ``detect``: the
+    host loop's third action, "detect" (HOG.md), is allowed too."""
     if lost is None:
         return None
     min_confidence, min_joints, action = lost
     min_confidence, min_joints = float(min_confidence), int(min_joints)
-    if action not in ("hold", "reset"):
+    if action == "detect" and not detect:
+        raise ValueError("lost=(min_confidence, min_joints, 'detect') runs the person detector on the host's side of the loop: "
+                         "use runner.track (the device loops take 'hold' or 'reset')")
+    if action not in ("hold", "reset") + (("detect",) if detect else ()):
         raise ValueError("lost=(min_confidence, min_joints, action): action must be 'hold' or 'reset'")
     if not 1 <= min_joints <= 21:
         raise ValueError("lost=(min_confidence, min_joints, action): min_joints must be 1 .. 21")
@@ -93,6 +99,34 @@ def init_box(estimator, frame, timestamp=None, min_confidence=None, min_joints=1
     if w < 1 or h < 1:
         return [0, 0, W_img, H_img]
     return [x, y, w, h]
+
+
+def cal_rect(rect, H, W):
+    """HOGBox.cal_rect (src/hog_box.py:48-58), term by term: the detection (x, y, w, h) grown by 40 % of the frame's width and 20 % of
+    its height -- half of each on either side, ``int()`` truncation as there -- and clamped to the (H, W) frame."""
+    x, y, w, h = (int(v) for v in rect)
+    offset_w = int(0.4 / 2 * W)                      # hog_box.py:53
+    offset_h = int(0.2 / 2 * H)                      # hog_box.py:54
+    x0, y0 = max(x - offset_w, 0), max(y - offset_h, 0)
+    return [x0, y0, min(x + w + offset_w, W) - x0, min(y + h + offset_h, H) - y0]
+
+
+def hog_box(estimator, frame, pixel_format="bgr", orientation=None, stream=None, **spec):
+    """``HOGBox.__call__`` without its window (src/hog_box.py:26-31): the person detector over the frame
+    (``estimator.detect_people``; HOG.md), the detection of the largest area -- the first of equals, as ``np.argmax`` picks it --
+    through ``cal_rect``; the whole frame when nobody is found.  Returns [x, y, w, h] in the oriented picture's coordinates."""
+    from . import _native
+    rects, _ = estimator.detect_people(frame, pixel_format=pixel_format, orientation=orientation, stream=stream, **spec)
+    if _native.is_device_array(frame):
+        f = _native.device_frame(frame, pixel_format)
+        H, W = int(f.H), int(f.W)
+    else:
+        H, W = frame.shape[:2]
+    if (estimator.orientation if orientation is None else orientation) & 1:
+        H, W = W, H
+    if not len(rects):
+        return [0, 0, W, H]
+    return cal_rect(rects[int(np.argmax(rects[:, 2].astype(np.int64) * rects[:, 3]))], H, W)
 
 
 def orient_view(frame, orientation):
@@ -134,6 +168,8 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
     Additive (CONFIDENCE.md): ``lost=(min_confidence, min_joints, "hold" | "reset")`` -- behind the box update, a frame with fewer than
     min_joints confidences >= min_confidence keeps its own crop for the next frame (hold) or hands it the whole frame (reset);
+    "detect" (HOG.md; this loop only): the next frame's box is ``hog_box`` of the lost frame -- the reference's detector in the place of
+    the whole frame; the estimator needs a detector (``set_hog_detector``);
     ``confidence=True`` yields (joints_2d, joints_3d, rect_used, confidence (21,) float64, lost flag).
 
     frames: iterable of uint8 BGR arrays of one size; rect: initial (x, y, w, h), default the full frame;
@@ -150,7 +186,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
     orientation = _orientations(estimator, orientation, 1, transpose)[0]
     own = getattr(estimator, "orientation", 0)
     call_code = orientation if nv12 else 0     # what the estimator itself still has to turn
-    rule = lost_rule(lost)
+    rule = lost_rule(lost, detect=True)
     want_conf = confidence or rule is not None
     for frame in frames:
         if transpose:
@@ -181,8 +217,11 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
         used = [x, y, w, h]
         rect = bbox_update(joints_2d, W_img, H_img)
         gone = rule is not None and is_lost(res[2], rule[0], rule[1])
-        if gone:                                   # the loss rule: this frame's crop again, or the whole frame
-            rect = list(used) if rule[2] == "hold" else [0, 0, W_img, H_img]
+        if gone:                                   # the loss rule: this frame's crop again, the whole frame, or where the detector finds someone
+            if rule[2] == "detect":
+                rect = hog_box(estimator, frame, pixel_format, call_code)
+            else:
+                rect = list(used) if rule[2] == "hold" else [0, 0, W_img, H_img]
         if confidence:
             yield joints_2d, joints_3d, used, res[2], int(gone)
         else:
