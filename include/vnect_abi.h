@@ -455,6 +455,57 @@ int vnect_hog_detect_device(vnect_handle* h, const vnect_device_frame* frame, vo
 int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
                      int capacity, int32_t* count_out);
 
+/* ABI v7, additive.  The 3-D view (VIEW3D.md).  The reference's frame loop shows a second picture per frame: it puts joints_3d into
+ * q_joints (run_estimator_ps.py:90, 124-126) and a second process plots the skeleton with matplotlib (src/utils.py:272-304: axes limits
+ * -500 .. 500, view_init(-90, -90), one line of width 3 per limb; :317-330).  Here one launch of view3d.hip renders that picture into
+ * device memory, by the rule of vnect_amd/csrc/view3d.h -- this project's own (orthographic, round caps, no anti-aliasing, no axes):
+ * matplotlib's Agg lines cannot be pinned.
+ * vnect_view3d_spec: src/utils.py:277-280 and 289 as a structure.  A zero field or a cleared has_* flag means its default -- rows x cols 400 x 400 (each at most
+ * VNECT_VIEW3D_MAX), extent 500.0 (the axes' set_xlim/ylim/zlim(-500, 500)), view the identity (view_init(-90, -90): +x right, +y down, +z
+ * away from the camera; row-major 3 x 3, (u, v, d) = view (x, y, z)), line_width 3.0 (linewidth=3), background white, colors the ten-entry
+ * colour cycle by limb index, parents the reference's (src/estimator.py joint_parents); min_confidence as in vnect_overlay_style, NaN for
+ * none (it needs confidences); out_format VNECT_PIX_BGR or VNECT_PIX_RGB, packed 3 bytes per pixel; order 0 -- a limb of a higher index
+ * lies over one of a lower (src/utils.py:289, 298 add line 0 first) -- or 1 -- the nearer limb lies on top.  spec NULL: all defaults.
+ * vnect_view3d_device (src/utils.py:283-304): the view of joints_3d (21 x 3 float32, host memory: what vnect_infer returns) into `out`,
+ * rows out_pitch >= 3 * cols bytes apart; every pixel is written and no byte outside the 3 * cols bytes of each row is.  `out` is device
+ * memory of the handle's device (its last byte must lie inside its allocation) or host memory (the library stages and copies), as in
+ * vnect_preview_device; the call is done on return.  Needs no weights: it works before vnect_finalize, on a preprocess_only handle and
+ * on batched and sharded handles.  VNECT_E_ARG, before anything is launched or written: a wrong struct_size; rows or cols outside
+ * 1 .. VNECT_VIEW3D_MAX; out_pitch < 3 * cols; a non-finite or non-positive extent; a non-finite view entry; a line_width outside
+ * (0, 64]; a colour outside 0 .. 255; a parent outside 0 .. 20; an order or out_format outside its two values; an `out` that is neither
+ * such device memory nor host memory.
+ * vnect_track_view3d (run_estimator_ps.py:90 inside the tracked loop): a setting of tracked stream `stream`, like vnect_track_policy.
+ * While set, EVERY tracked submit on that stream -- vnect_submit_tracked, _pinned, _pinned_nv12, _device, _device_draw, _device_preview --
+ * also renders the frame's view: one launch on the frame's lane stream behind its joints stage and in front of its completion, joints_3d,
+ * status and (with a threshold) confidences read from the frame's result-ring slot on the device, then the view's copy into a pinned host
+ * buffer the handle owns, one per result-ring slot.  spec NULL turns the setting off.  VNECT_E_STATE while frames are in flight on the
+ * handle; VNECT_E_ARG for a bad stream or spec.  A frame whose crop was refused has no view.  Joints, rects, confidences and filter
+ * states of every frame are bit-identical to the same loop without the setting.
+ * vnect_result_view3d (src/utils.py:317-330: what the plot process shows): the view of the frame most recently delivered by
+ * vnect_collect_tracked -- *data, hw = (rows, cols), *pitch = 3 * cols -- valid until the next submit on the handle; hw = (0, 0) and
+ * *data = NULL if that frame has none. */
+#define VNECT_VIEW3D_MAX 2048
+typedef struct vnect_view3d_spec {
+    int32_t struct_size;        /* = sizeof(vnect_view3d_spec) */
+    int32_t rows, cols;         /* 0: 400 */
+    double extent;              /* 0: 500.0 */
+    double view[9];
+    int32_t has_view;           /* 0: the identity */
+    int32_t has_background;     /* 0: (255, 255, 255) */
+    double line_width;          /* 0: 3.0 */
+    int32_t background_bgr[3];
+    int32_t has_colors;         /* 0: the colour cycle */
+    int32_t colors_bgr[VNECT_JOINTS][3];
+    int32_t parents[VNECT_JOINTS];
+    int32_t has_parents;        /* 0: the reference's */
+    double min_confidence;
+    int32_t out_format;         /* VNECT_PIX_BGR | VNECT_PIX_RGB */
+    int32_t order;              /* 0 | 1 */
+} vnect_view3d_spec;
+int vnect_view3d_device(vnect_handle* h, const float* joints_3d, const double* confidence21, const vnect_view3d_spec* spec, void* out, int64_t out_pitch);
+int vnect_track_view3d(vnect_handle* h, int stream, const vnect_view3d_spec* spec);
+int vnect_result_view3d(vnect_handle* h, const uint8_t** data, int32_t hw[2], int64_t* pitch);
+
 /* Orientation (ABI v7, additive; ORIENTATION.md).  The reference's loop has a `T` option for a camera that is mounted sideways: it turns
  * every frame with np.rot90(frame, 3) before the crop (run_estimator_ps.py:57-62, 81-85; commented out beside it, an np.transpose
  * variant).  Here the turn happens on the device, inside the copy that brings the crop into the slot, so only the crop moves.

@@ -109,6 +109,65 @@ def preview_spec(factor=None, out_format="bgr", draw_frame=False):
     return s
 
 
+VIEW3D_MAX = 2048   # VNECT_VIEW3D_MAX: rows and columns of a 3-D view at most
+
+
+class View3dSpec(C.Structure):
+    """vnect_view3d_spec: size, scale, view, line width, colours, parents, threshold, channel order and stacking order of a 3-D view; a zero
+    field or a cleared has_* flag means its default (include/vnect_abi.h; VIEW3D.md)."""
+    _fields_ = [("struct_size", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("extent", C.c_double), ("view", C.c_double * 9),
+                ("has_view", C.c_int32), ("has_background", C.c_int32), ("line_width", C.c_double), ("background_bgr", C.c_int32 * 3),
+                ("has_colors", C.c_int32), ("colors_bgr", (C.c_int32 * 3) * 21), ("parents", C.c_int32 * 21), ("has_parents", C.c_int32),
+                ("min_confidence", C.c_double), ("out_format", C.c_int32), ("order", C.c_int32)]
+
+
+def view3d_spec(size=400, view=None, extent=500.0, line_width=3.0, background=None, colors=None, parents=None, min_confidence=None,
+                out_format="bgr", order=0):
+    """The View3dSpec of a 3-D view.  size: rows = cols, or (rows, cols); view: None (the reference's view_init(-90, -90): the identity) or a
+    3 x 3 matrix (render.view_matrix); background: None (white) or BGR; colors: None (matplotlib's cycle) or 21 BGR triples; parents: None
+    for the reference's joint_parents; min_confidence None: no threshold; out_format "bgr" or "rgb"; order 0 (a higher limb index lies on
+    top) or 1 (the nearer limb does)."""
+    if out_format not in ("bgr", "rgb"):
+        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    s = View3dSpec()
+    s.struct_size = C.sizeof(View3dSpec)
+    rows, cols = (size, size) if np.isscalar(size) else size
+    s.rows, s.cols, s.extent, s.line_width = int(rows), int(cols), float(extent), float(line_width)
+    # a zero means "the default" in the C structure: what the caller wrote as 0 where 0 is not the default must be refused, not replaced
+    if s.rows == 0 or s.cols == 0 or s.extent == 0.0 or s.line_width == 0.0:
+        raise ValueError("size, extent and line_width must not be 0")
+    if view is not None:
+        v = np.asarray(view, dtype=np.float64)
+        if v.shape != (3, 3):
+            raise ValueError("view must be a 3 x 3 matrix")
+        s.has_view = 1
+        for k, x in enumerate(v.reshape(-1)):
+            s.view[k] = float(x)
+    if background is not None:
+        s.has_background = 1
+        for k in range(3):
+            s.background_bgr[k] = int(background[k])
+    if colors is not None:
+        c = np.asarray(colors)
+        if c.shape != (21, 3):
+            raise ValueError("colors must be 21 BGR triples")
+        s.has_colors = 1
+        for i in range(21):
+            for k in range(3):
+                s.colors_bgr[i][k] = int(c[i, k])
+    if parents is not None:
+        parents = [int(v) for v in parents]
+        if len(parents) != 21:
+            raise ValueError("parents must name one joint for each of the 21 joints")
+        s.has_parents = 1
+        for k, v in enumerate(parents):
+            s.parents[k] = v
+    s.min_confidence = float("nan") if min_confidence is None else float(min_confidence)
+    s.out_format = PIX_RGB if out_format == "rgb" else PIX_BGR
+    s.order = int(order)
+    return s
+
+
 HOG_DETECTOR_SIZE, HOG_MAX_SIDE = 3781, 4096   # VNECT_HOG_DETECTOR_SIZE, VNECT_HOG_MAX_SIDE
 
 
@@ -205,6 +264,9 @@ SYMBOLS = {
     "vnect_submit_tracked_device_preview": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
                                                       C.POINTER(OverlayStyle), C.POINTER(PreviewSpec)]),
     "vnect_result_preview": (C.c_int, [_H, C.POINTER(_u8p), _i32p, C.POINTER(C.c_int64)]),
+    "vnect_view3d_device": (C.c_int, [_H, _f32p, _f64p, C.POINTER(View3dSpec), C.c_void_p, C.c_int64]),
+    "vnect_track_view3d": (C.c_int, [_H, C.c_int, C.POINTER(View3dSpec)]),
+    "vnect_result_view3d": (C.c_int, [_H, C.POINTER(_u8p), _i32p, C.POINTER(C.c_int64)]),
     "vnect_hog_set_detector": (C.c_int, [_H, _f32p, C.c_int]),
     "vnect_hog_levels": (C.c_int, [_H, C.POINTER(DeviceFrame), C.POINTER(HogSpec), _i32p, _i32p, _f64p, C.c_int]),
     "vnect_hog_detect_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
@@ -230,6 +292,8 @@ PREVIEWPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_previewprobe.so") # prev
 PREVIEW_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_preview.so")       # g++'s build of csrc/preview.h (tests only; no GPU code)
 HOGPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_hogprobe.so")         # hog.o behind csrc/hog_probe.hip (tests only)
 HOG_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_hog.so")               # g++'s build of csrc/hog.h (tests only; no GPU code)
+VIEW3DPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_view3dprobe.so")   # view3d.o behind csrc/view3d_probe.hip (tests only)
+VIEW3D_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_view3d.so")         # g++'s build of csrc/view3d.h (tests only; no GPU code)
 
 
 def build(force=False):
@@ -254,6 +318,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "previewprobe", "preview"], stdout=subprocess.DEVNULL)
     # the detector's probe (tests/test_gpu_hog_kernels.py) and g++'s build of its walk (tests/test_hog_cpu.py)
     subprocess.check_call(["make", "-C", src, "hogprobe", "hog"], stdout=subprocess.DEVNULL)
+    # the 3-D view's probe (tests/test_gpu_view3d_kernels.py) and g++'s build of its tile walk (tests/test_view3d_cpu.py)
+    subprocess.check_call(["make", "-C", src, "view3dprobe", "view3d"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -630,6 +696,34 @@ class Handle:
         """vnect_result_preview: the (dh, dw, 3) preview of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
         data, hw, pitch = _u8p(), (C.c_int32 * 2)(), C.c_int64()
         self._ck(lib().vnect_result_preview(self._h, C.byref(data), hw, C.byref(pitch)))
+        if hw[0] < 1 or hw[1] < 1:
+            return None
+        return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
+
+    # -- the 3-D view: the skeleton plot of joints_3d, rendered on the device (include/vnect_abi.h; VIEW3D.md) ---------------------------
+    def view3d_device(self, joints_3d, spec, out, out_pitch, confidence=None):
+        """vnect_view3d_device: the view of joints_3d (21, 3) into the memory at address `out` (device or host), rows out_pitch bytes apart;
+        done on return."""
+        j3 = np.ascontiguousarray(joints_3d, dtype=np.float32)
+        if j3.shape != (21, 3):
+            raise ValueError("joints_3d must be (21, 3)")
+        cf = None
+        if confidence is not None:
+            cf = np.ascontiguousarray(confidence, dtype=np.float64)
+            if cf.shape != (21,):
+                raise ValueError("confidence must be (21,)")
+        self._ck_device(lib().vnect_view3d_device(self._h, _ptr(j3, _f32p), None if cf is None else _ptr(cf, _f64p),
+                                                  None if spec is None else C.byref(spec), C.c_void_p(int(out)), int(out_pitch)))
+
+    def track_view3d(self, stream, spec):
+        """vnect_track_view3d: while set (spec a View3dSpec), every tracked submit of `stream` also renders its frame's 3-D view:
+        result_view3d() after collect_tracked().  spec None: off."""
+        self._ck_device(lib().vnect_track_view3d(self._h, stream, None if spec is None else C.byref(spec)))
+
+    def result_view3d(self):
+        """vnect_result_view3d: the (rows, cols, 3) view of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
+        data, hw, pitch = _u8p(), (C.c_int32 * 2)(), C.c_int64()
+        self._ck(lib().vnect_result_view3d(self._h, C.byref(data), hw, C.byref(pitch)))
         if hw[0] < 1 or hw[1] < 1:
             return None
         return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()

@@ -366,6 +366,14 @@ hipError_t launch_overlay(const OverlayTarget& t, const OverlayInput& in, const 
 struct PreviewArgs;
 hipError_t launch_preview(const PreviewArgs& a, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
 
+// ---- the 3-D view (view3d.hip; vnect_view3d_device, vnect_track_view3d; VIEW3D.md) ----------------------------------------------------
+// run_estimator_ps.py:90, 124-126 and src/utils.py:272-304: the skeleton plot of joints_3d, by the rule of view3d.h.  One launch; the grid
+// is fixed by the picture's size; every pixel of a.out is written once.  Two forms: j3d (63 floats) and conf (21 doubles, or nullptr
+// without a threshold) in device memory; or jo (and co) -- a result-ring slot's JointsOut::j3d and ::status and its ConfOut, read on the
+// device: a frame whose status is not 0 writes nothing.  Exactly one of j3d and jo is given.
+struct View3dArgs;
+hipError_t launch_view3d(const View3dArgs& a, const float* j3d, const double* conf, const JointsOut* jo, const ConfOut* co, hipStream_t st);
+
 // ---- the person detector (hog.hip; vnect_hog_detect_device; HOG.md) --------------------------------------------------------------------
 // hog_box.py:24-33: HOG + linear SVM over a pyramid of the oriented picture, by the rule of hog.h.  Three launches cover all levels through
 // the level table `lv` (device memory, p.n entries): votes (the level images are computed inside it), block histograms + L2-Hys, window

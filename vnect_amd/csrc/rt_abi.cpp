@@ -283,6 +283,8 @@ void vnect_destroy(vnect_handle* h)
     if (h->h_tout) hipHostFree(h->h_tout);
     for (int i = 0; i < RING; i++)
         if (h->pv_host[i]) hipHostFree(h->pv_host[i]);  // (pv_dev: dev_allocs)
+    for (int i = 0; i < RING; i++)
+        if (h->v3_host[i]) hipHostFree(h->v3_host[i]);  // (v3_dev: dev_allocs)
     if (h->h_conf) hipHostFree(h->h_conf);
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
@@ -981,6 +983,38 @@ int vnect_draw_device(vnect_handle* h, const vnect_device_frame* target, void* s
         if (!h) return VNECT_E_ARG;
         HIPCK(h, hipSetDevice(h->cfg.device));
         return draw_device_impl(h, target, stream, joints_2d, confidence21, rect4, style);
+    });
+}
+
+// ---- the 3-D view (additive; VIEW3D.md; run_estimator_ps.py:90, 124-126; src/utils.py:272-304, 317-330): one launch of view3d.hip ------
+int vnect_view3d_device(vnect_handle* h, const float* joints_3d, const double* confidence21, const vnect_view3d_spec* spec, void* out, int64_t out_pitch)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return view3d_device_impl(h, joints_3d, confidence21, spec, out, out_pitch);
+    });
+}
+
+// run_estimator_ps.py:90 inside the tracked loop: every tracked submit of the stream also renders its frame's view
+int vnect_track_view3d(vnect_handle* h, int stream, const vnect_view3d_spec* spec)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return track_view3d_impl(h, stream, spec);
+    });
+}
+
+// src/utils.py:317-330: the picture the plot process shows, of the frame delivered last
+int vnect_result_view3d(vnect_handle* h, const uint8_t** data, int32_t hw[2], int64_t* pitch)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !data || !hw || !pitch) return h ? fail(h, VNECT_E_ARG, "vnect_result_view3d: bad argument") : VNECT_E_ARG;
+        hw[0] = h->last_v3_h, hw[1] = h->last_v3_w;
+        *data = h->last_v3_ring >= 0 ? h->v3_host[h->last_v3_ring] : nullptr;
+        *pitch = 3LL * h->last_v3_w;
+        return VNECT_OK;
     });
 }
 

@@ -171,7 +171,7 @@ int check_tracked_preview(vnect_handle* h, const char* who, const vnect_device_f
 }
 
 // where `out` lies: 1 device memory of the handle's device ([*lo, *end): its allocation), 0 host memory (pinned or pageable), -1 neither
-static int out_kind(vnect_handle* h, const void* p, const uint8_t** lo, const uint8_t** end)
+int out_kind(vnect_handle* h, const void* p, const uint8_t** lo, const uint8_t** end)
 {
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);

@@ -385,11 +385,21 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // run_estimator_ps.py:92-94: the frame itself annotated with its own joints and the rect it was cropped with, read from its ring slot
     if (tk && tk->draw)
         HIPCK(h, launch_overlay(tk->draw_target, tk->draw_in, e.out_dev, h->h_tout_dev + ring, tk->draw_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
+    // run_estimator_ps.py:90 (q_joints.put(joints_3d): the 3-D plot's input): the frame's 3-D view (vnect_track_view3d) -- joints_3d, status and
+    // confidences read from its ring slot -- into the slot's device buffer and on to its pinned host buffer
+    const bool v3 = tk && sm.v3_on;
+    if (v3) {
+        View3dArgs a = sm.v3;
+        a.out = h->v3_dev[ring], a.pitch = 3LL * a.cols;
+        HIPCK(h, launch_view3d(a, nullptr, nullptr, e.out_dev, a.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
+        HIPCK(h, hipMemcpyAsync(h->v3_host[ring], h->v3_dev[ring], 3 * (size_t)a.cols * a.rows, hipMemcpyDeviceToHost, L->st));
+    }
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
     HIPCK(h, hipEventRecord(e.done, L->st));
     // only now: every launch of the frame has been accepted
     e.stream = stream, e.unit = h->unit_submit++, e.batch = false, e.prof = nullptr, e.tracked = tk != nullptr;
     e.pv_h = tk && tk->preview ? tk->pv.g.dh : 0, e.pv_w = tk && tk->preview ? tk->pv.g.dw : 0;
+    e.v3_h = v3 ? sm.v3.rows : 0, e.v3_w = v3 ? sm.v3.cols : 0;
     e.before = sm.t;  // (a tracked frame's refused crop rolls back)
     commit_time(sm, t2d, t3d);
     sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
@@ -434,6 +444,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
                                      "destroy the handles of every rank and reconnect");
     }
     h->last_pv_ring = -1, h->last_pv_h = h->last_pv_w = 0;  // (a frame whose crop was refused has no preview)
+    h->last_v3_ring = -1, h->last_v3_h = h->last_v3_w = 0;  // (nor a 3-D view)
     if (stream_out) *stream_out = e.stream;
     if (rect_out)
         for (int k = 0; k < 4; k++) rect_out[k] = e.tracked ? h->h_tout[ring].rect[k] : -1;
@@ -451,6 +462,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
     deliver_confidence(h, ring, e.tracked);
     if (e.tracked && e.pv_h) h->last_pv_ring = ring, h->last_pv_h = e.pv_h, h->last_pv_w = e.pv_w;
+    if (e.tracked && e.v3_h) h->last_v3_ring = ring, h->last_v3_h = e.v3_h, h->last_v3_w = e.v3_w;
     if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
     if (h->profiling && !e.batch) {
         float frame_ms = 0;

@@ -33,6 +33,7 @@
 #include "orient.h"
 #include "overlay.h"
 #include "preview.h"
+#include "view3d.h"
 #include "hog.h"
 
 namespace vnect {
@@ -147,6 +148,7 @@ struct InFlight {
     Plan* prof = nullptr;         // a profiled batch's plan, on the ring entry of its last frame (collect reads its layer times)
     bool tracked = false;
     int pv_h = 0, pv_w = 0;        // a tracked frame that carries a preview (vnect_submit_tracked_device_preview): its size; 0: none
+    int v3_h = 0, v3_w = 0;        // a tracked frame that carries a 3-D view (vnect_track_view3d): its size; 0: none
     TimeState before{};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
 };
 
@@ -164,6 +166,8 @@ struct Stream {
     unsigned track_seq = 0;
     uint8_t* track_buf = nullptr;  // the stream's crop copied out of a pinned buffer (one suffices: the next frame's copy
     size_t track_cap = 0;          // waits for this frame's box kernel, which runs after everything that reads the crop)
+    bool v3_on = false;            // vnect_track_view3d: every tracked submit of the stream also renders its frame's 3-D view
+    View3dArgs v3{};               // ... with these arguments (but `out` and `pitch`, which are the ring slot's)
     TrackPolicy policy{0.0, 1, TRACK_LOST_OFF};  // the host's copy of d_policy[stream] (vnect_track_policy; survives vnect_track_begin)
 };
 
@@ -207,6 +211,16 @@ struct vnect_handle : Plan {
     uint8_t* pv_host[RING] = {};
     size_t pv_cap = 0;
     int last_pv_ring = -1, last_pv_h = 0, last_pv_w = 0;  // the preview of the frame vnect_collect_tracked delivered last (vnect_result_preview)
+    // the 3-D view (rt_view.cpp; view3d.h).  vnect_view3d_device: the confidences and joints on the device (21 doubles, then 63 floats) and, for
+    // a host `out`, the kernel's packed output (grown on demand).  Tracked views (vnect_track_view3d): per result-ring slot a device buffer
+    // the kernel writes and a pinned host buffer its copy lands in, all v3_cap bytes; re-sized only while nothing is in flight
+    double* view_in = nullptr;
+    uint8_t* view_stage = nullptr;
+    size_t view_stage_cap = 0;
+    uint8_t* v3_dev[RING] = {};
+    uint8_t* v3_host[RING] = {};
+    size_t v3_cap = 0;
+    int last_v3_ring = -1, last_v3_h = 0, last_v3_w = 0;  // the view of the frame vnect_collect_tracked delivered last (vnect_result_view3d)
     // the person detector (rt_hog.cpp; hog.h): the detector as given (3781 floats, rho last) and on the device, the host-built tables and the
     // level table on the device, the workspace of the three launches and a host frame's device copy -- each grown on demand, never shrunk
     std::vector<float> hog_det;
@@ -445,6 +459,13 @@ int preview_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stre
 // a tracked submit's preview: validates frame (as check_draw does when `style_too`), style and spec, sizes the ring's preview buffers, fills s->pv
 int check_tracked_preview(vnect_handle* h, const char* who, const vnect_device_frame* f, void* stream, const vnect_overlay_style* style,
                           const vnect_preview_spec* spec, int orient, FrameSrc* s);
+
+// ---- rt_view.cpp ---------------------------------------------------------------------------------------------------------------
+// the 3-D view (vnect_view3d_device, vnect_track_view3d; view3d.h; VIEW3D.md)
+int view3d_device_impl(vnect_handle* h, const float* j3d, const double* conf, const vnect_view3d_spec* spec, void* out, int64_t out_pitch);
+int track_view3d_impl(vnect_handle* h, int stream, const vnect_view3d_spec* spec);
+// where `out` lies: 1 device memory of the handle's device ([*lo, *end): its allocation), 0 host memory (pinned or pageable), -1 neither (rt_draw.cpp)
+int out_kind(vnect_handle* h, const void* p, const uint8_t** lo, const uint8_t** end);
 
 // ---- rt_hog.cpp ----------------------------------------------------------------------------------------------------------------
 // the person detector (vnect_hog_*; hog.h; HOG.md)

@@ -305,6 +305,33 @@ class VNectEstimator:
         f.struct_size, f.H, f.W = _native.C.sizeof(_native.DeviceFrame), int(H), int(W)
         return self._h.preview_size(f, _native.preview_spec(factor))
 
+    def view3d(self, joints_3d, size=400, view=None, out=None, confidence=None, **spec):
+        """Additive (VIEW3D.md): the reference's second window -- the 3-D skeleton plot its loop feeds ``joints_3d`` through ``q_joints``
+        (run_estimator_ps.py:90, 124-126; src/utils.py:272-304) -- rendered by one kernel launch.  ``joints_3d``: (21, 3) as the estimator
+        returns it; ``size``: rows = cols, or (rows, cols); ``view``: None for the reference's ``view_init(-90, -90)``, or
+        ``render.view_matrix(elev, azim)``; ``confidence`` (21,) with ``min_confidence=``: limbs with an end below it are left out;
+        ``spec``: ``_native.view3d_spec``'s other arguments (``extent``, ``line_width``, ``background``, ``colors``, ``parents``,
+        ``min_confidence``, ``out_format``, ``order``).  Returns a fresh (rows, cols, 3) uint8 numpy array -- or, with ``out`` (a numpy array
+        or a device array with ``__cuda_array_interface__``: (rows, cols, 3) uint8, unit channel stride, 3-byte pixel stride, any row pitch:
+        a column block of a wider canvas counts), fills it and returns it.  The pixels are those of ``render.view3d_exact``."""
+        spec.setdefault("parents", self.joint_parents)
+        sp = _native.view3d_spec(size, view, **spec)
+        rows, cols = sp.rows, sp.cols
+        if out is None:
+            res = np.empty((rows, cols, 3), np.uint8)
+            self._h.view3d_device(joints_3d, sp, res.ctypes.data, 3 * cols, confidence)
+            return res
+        if _native.is_device_array(out):
+            ptr, shape, strides = _native._cai(out, 3, "out")
+        else:
+            if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.writeable:
+                raise ValueError("out must be a writeable uint8 numpy array or a device array")
+            ptr, shape, strides = out.ctypes.data, out.shape, out.strides
+        if tuple(shape) != (rows, cols, 3) or strides[2] != 1 or strides[1] != 3 or (rows > 1 and strides[0] < 3 * cols):
+            raise ValueError("out must be a uint8 (%d, %d, 3) array with unit channel stride and 3-byte pixel stride" % (rows, cols))
+        self._h.view3d_device(joints_3d, sp, ptr, strides[0] if rows > 1 else 3 * cols, confidence)
+        return out
+
     # -- the person detector (additive; HOG.md): the reference's HOGBox (src/hog_box.py:24-33) on the device -------------
     def set_hog_detector(self, detector):
         """The linear SVM of ``detect_people``: 3781 floats, rho last -- the array ``cv2.HOGDescriptor_getDefaultPeopleDetector()``

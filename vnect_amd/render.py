@@ -217,3 +217,97 @@ def draw_limbs_3d(joints_3d, joint_parents, size=400, extent=500.0):
 def save(path, img_bgr):
     """cv2.imwrite replacement (PNG / JPEG by extension)."""
     _canvas(img_bgr).save(path)
+
+
+# matplotlib's colour cycle (rcParams['axes.prop_cycle']: "tab10") as RGB; limb i of the 3-D view takes entry i % 10
+VIEW3D_CYCLE_RGB = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194),
+                    (127, 127, 127), (188, 189, 34), (23, 190, 207))
+JOINT_PARENTS = (16, 15, 1, 2, 3, 1, 5, 6, 14, 8, 9, 14, 11, 12, 14, 14, 1, 4, 7, 10, 13)   # src/estimator.py joint_parents
+
+
+def _trig_deg(deg):
+    """(cos, sin) of an angle in degrees, exact at the multiples of 90."""
+    q = float(deg) % 360.0
+    exact = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}
+    if q in exact:
+        return exact[q]
+    return float(np.cos(np.deg2rad(deg))), float(np.sin(np.deg2rad(deg)))
+
+
+def view_matrix(elev, azim):
+    """The 3 x 3 view of ``view3d`` / ``view3d_exact`` for mplot3d's ``view_init(elev, azim)`` (degrees, no roll, |elev| <= 90): row 0
+    is the screen's right, row 1 its DOWN, row 2 the direction away from the camera -- mplot3d's view axes u, -v, -w for the eye at
+    (cos e cos a, cos e sin a, sin e).  ``view_matrix(-90, -90)`` is the identity, the reference's view (src/utils.py:280)."""
+    ce, se = _trig_deg(elev)
+    ca, sa = _trig_deg(azim)
+    return np.array([[-sa, ca, 0.0], [se * ca, se * sa, -ce], [-ce * ca, -ce * sa, -se]], dtype=np.float64) + 0.0
+
+
+def view3d_exact(joints_3d, size=400, view=None, extent=500.0, line_width=3.0, background=None, colors=None, parents=None, confidence=None,
+                 min_confidence=None, out_format="bgr", order=0, out=None):
+    """The 3-D skeleton view by the exact rule the device renders with (VIEW3D.md; vnect_amd/csrc/view3d.h): pixel-identical to
+    ``VNectEstimator.view3d`` and to the views ``track_on_device(..., view3d=True)`` yields.  The reference's picture is matplotlib's
+    (src/utils.py:272-304); this is its shapes by this project's rule -- orthographic, round caps, no anti-aliasing, no axes.
+    ``joints_3d``: (21, 3) [x, y, z] in mm; the other arguments are ``_native.view3d_spec``'s.  Returns a fresh (rows, cols, 3) uint8 array, or
+    fills ``out`` (a uint8 (rows, cols, 3) host array with unit channel stride and 3-byte pixel stride) and returns it."""
+    if out_format not in ("bgr", "rgb"):
+        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    rows, cols = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    extent, w = float(extent), float(line_width)
+    if not (1 <= rows <= 2048 and 1 <= cols <= 2048):
+        raise ValueError("rows and cols must lie in 1 .. 2048")
+    if not (np.isfinite(extent) and extent > 0.0) or not (0.0 < w <= 64.0) or order not in (0, 1):
+        raise ValueError("extent must be finite and positive, line_width in (0, 64], order 0 or 1")
+    R = np.eye(3) if view is None else np.asarray(view, dtype=np.float64)
+    if R.shape != (3, 3) or not np.isfinite(R).all():
+        raise ValueError("view must be a finite 3 x 3 matrix")
+    par = [int(p) for p in (JOINT_PARENTS if parents is None else parents)]
+    if len(par) != 21 or min(par) < 0 or max(par) > 20:
+        raise ValueError("parents must name one joint, 0 .. 20, for each of the 21 joints")
+    col = np.array([c[::-1] for c in VIEW3D_CYCLE_RGB] * 3)[:21] if colors is None else np.asarray(colors)
+    bg = np.array((255, 255, 255) if background is None else background)
+    if col.shape != (21, 3) or col.min() < 0 or col.max() > 255 or bg.shape != (3,) or bg.min() < 0 or bg.max() > 255:
+        raise ValueError("21 BGR colours and a BGR background, components 0 .. 255")
+    if out_format == "rgb":
+        col, bg = col[:, ::-1], bg[::-1]
+    j = np.asarray(joints_3d, dtype=np.float32).astype(np.float64)
+    if j.shape != (21, 3):
+        raise ValueError("joints_3d must be (21, 3)")
+    k = np.float64(min(rows, cols) - 1) / (2.0 * extent)
+    cx, cy = np.float64(cols - 1) * 0.5, np.float64(rows - 1) * 0.5
+    r2 = (w * 0.5) * (w * 0.5)
+    with np.errstate(all="ignore"):
+        x, y, z = j[:, 0], j[:, 1], j[:, 2]
+        u = (R[0, 0] * x + R[0, 1] * y) + R[0, 2] * z
+        v = (R[1, 0] * x + R[1, 1] * y) + R[1, 2] * z
+        d = (R[2, 0] * x + R[2, 1] * y) + R[2, 2] * z
+        pc, pr = cx + u * k, cy + v * k
+    ok = np.isfinite(pc) & np.isfinite(pr) & (np.abs(pc) <= 2.0 ** 20) & (np.abs(pr) <= 2.0 ** 20)
+    low = np.zeros(21, bool)
+    if min_confidence is not None and confidence is not None and not np.isnan(min_confidence):
+        low = np.asarray(confidence, dtype=np.float64) < float(min_confidence)
+    best = np.full((rows, cols), -1, np.int64)        # the limb on top so far
+    bkey = np.zeros((rows, cols), np.float64)
+    Y, X = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    for i in range(21):
+        p = par[i]
+        if p == i or not (ok[i] and ok[p]) or low[i] or low[p] or (order == 1 and not (np.isfinite(d[i]) and np.isfinite(d[p]))):
+            continue
+        ex, ey = pc[p] - pc[i], pr[p] - pr[i]
+        L2 = ex * ex + ey * ey
+        wx, wy = X - pc[i], Y - pr[i]
+        t = wx * ex + wy * ey
+        qx, qy = X - pc[p], Y - pr[p]
+        c = wx * ey - wy * ex
+        inside = np.where(t <= 0.0, wx * wx + wy * wy <= r2, np.where(t >= L2, qx * qx + qy * qy <= r2, c * c <= r2 * L2))
+        key = d[i] + d[p] if order == 1 else 0.0
+        # limb i lies over what is there: order 0 -- always (a higher index); order 1 -- a smaller key, or an equal one (a higher index)
+        over = inside & ((best < 0) | (key <= bkey))
+        best[over], bkey[over] = i, key
+    pic = np.where((best >= 0)[:, :, None], col[np.maximum(best, 0)], bg[None, None, :]).astype(np.uint8)
+    if out is None:
+        return pic
+    if out.dtype != np.uint8 or out.shape != (rows, cols, 3) or out.strides[2] != 1 or out.strides[1] != 3:
+        raise ValueError("out must be a uint8 (%d, %d, 3) array with unit channel stride and 3-byte pixel stride" % (rows, cols))
+    out[...] = pic
+    return out

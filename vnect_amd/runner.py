@@ -229,7 +229,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
 
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
-                    confidence=False, lost=None, draw=False, orientation=None, preview=False):
+                    confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -249,15 +249,19 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     ``preview`` (``source="device"`` only; PREVIEW.md): True (the reference's 1024 on the longer side), a factor, or an
     ``_native.preview_spec(...)`` -- every yielded tuple gets the frame's display picture appended (run_estimator_ps.py:94-96: the frame
     annotated with its own joints and ``rect_used``, scaled; a fresh (dh, dw, 3) array, or None for a frame without one), computed on
-    the device; the frame is not written unless ``draw`` is given too, and then the preview is that of the clean frame."""
+    the device; the frame is not written unless ``draw`` is given too, and then the preview is that of the clean frame.
+    ``view3d`` (every ``source``; VIEW3D.md): True (the reference's plot: 400 x 400, view_init(-90, -90)) or an
+    ``_native.view3d_spec(...)`` -- every yielded tuple gets the frame's 3-D skeleton view appended last (run_estimator_ps.py:90,
+    124-126; src/utils.py:272-304: a fresh (rows, cols, 3) array, the picture ``render.view3d_exact`` gives for the ``joints_3d`` yielded
+    with it), rendered on the device behind the frame's joints stage; the other results are those of ``view3d=False``, bit for bit."""
     for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
                                     None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw,
-                                    orientation, preview):
+                                    orientation, preview, view3d):
         yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None, preview=False):
+                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
@@ -266,7 +270,7 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
     afterwards); ``confidence=True`` appends
     (confidence, lost flag) to every tuple.
-    ``draw``, ``preview``: as in ``track_on_device``.
+    ``draw``, ``preview``, ``view3d``: as in ``track_on_device`` (the view is the last element of every tuple).
     ``orientation``: one code for all videos or one per video (ORIENTATION.md; None: the estimator's own): every stream keeps the code its track began with, so
     videos with different orientations share the handle; the estimator's own orientation is back in force afterwards."""
     from collections import deque
@@ -287,6 +291,9 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
         if style is None:
             style = _native.overlay_style(parents=estimator.joint_parents)
+    vspec = None
+    if view3d is not False and view3d is not None:
+        vspec = view3d if isinstance(view3d, _native.View3dSpec) else _native.view3d_spec(parents=estimator.joint_parents)
     nv12 = _nv12_checks(pixel_format, transpose, source)
     codes = _orientations(estimator, orientation, len(videos), transpose)
     rule = lost_rule(lost)
@@ -325,6 +332,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             h.track_begin(streams[i], W if codes[i] & 1 else H, H if codes[i] & 1 else W, rects[i])
             if rule is not None:
                 h.track_policy(streams[i], *rule)
+            if vspec is not None:              # (nothing is in flight yet)
+                h.track_view3d(streams[i], vspec)
     flat = []
     if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
         nbytes = max([p.size for p in pending if p is not None] + [3])
@@ -348,6 +357,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             res += h.result_confidence()
         if spec is not None:                    # (likewise: the pinned buffer of its ring slot, copied before the next submit)
             res += (h.result_preview(),)
+        if vspec is not None:
+            res += (h.result_view3d(),)
         return res
 
     # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
@@ -415,6 +426,13 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 pass
         held.clear()
         estimator._orient(None)                 # the estimator's own orientation again
+        if vspec is not None:                   # nothing is in flight any more: the streams render no view again
+            for i in range(n):
+                if pending[i] is not None:
+                    try:
+                        h.track_view3d(streams[i], None)
+                    except _native.VnectError:
+                        pass
         if rule is not None:                    # nothing is in flight any more: the streams' rule is off again
             for i in range(n):
                 if pending[i] is not None:
