@@ -418,6 +418,8 @@ int vnect_result_preview(vnect_handle* h, const uint8_t** data, int32_t hw[2], i
  * layout cv2.HOGDescriptor_getDefaultPeopleDetector() returns.
  * vnect_hog_set_detector (src/hog_box.py:26): n = 3781 floats, rho last, or 3780 with rho 0.  VNECT_E_ARG: any other n, a NaN or an
  * infinite entry.  The handle keeps a copy.
+ * VNECT_E_STATE (nothing changes): a stream on which vnect_track_redetect is set has a tracked frame in flight -- its detection reads the
+ * detector whenever it runs.
  * vnect_hog_spec: detectMultiScale's parameters (src/hog_box.py:28 passes none: the defaults); a zero field means its default --
  * hit_threshold 0, win_stride 8 x 8, scale0 1.05, final_threshold 2.0, nlevels 64, max_hits 65536.  spec NULL: all defaults.
  * vnect_hog_levels (src/hog_box.py:28): the pyramid of the frame's oriented picture under the orientation in force -- *n_out levels,
@@ -454,6 +456,25 @@ int vnect_hog_detect_device(vnect_handle* h, const vnect_device_frame* frame, vo
                             double* weights, int capacity, int32_t* count_out);
 int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
                      int capacity, int32_t* count_out);
+
+/* ABI v7, additive.  Re-detection inside the device tracking loop (HOG.md, "Re-detection").  The reference finds a person with HOGBox once
+ * (src/hog_box.py:26-31) and its loop falls back to the whole frame ever after (run_estimator_ps.py:96-107); runner.track's
+ * lost=(c, n, "detect") puts the detector in the place of that fallback on the host's side of the loop.  This is the same inside the
+ * device loop: a setting of a tracked stream, like vnect_track_view3d -- NOT a fourth action of vnect_track_policy.
+ * vnect_track_redetect (src/hog_box.py:26-31, 48-58): while enable != 0, the next box of a tracked frame that the stream's loss rule
+ * (vnect_track_policy: hold or reset) declares lost is that frame's largest grouped detection through cal_rect, or the whole frame when
+ * nobody is found -- computed on the device behind the frame's box stage, by the rule of vnect_amd/csrc/hog.h, with no host wait.  `spec`
+ * (NULL: defaults) as in vnect_hog_detect_device, but max_hits defaults to 4096 and may not exceed it.  A frame with more than max_hits
+ * hits cannot fail the call as the host loop does: its next box is the whole frame and its status says overflow.  While set, the stream's
+ * frames come through vnect_submit_tracked_device, _device_draw or _device_preview; vnect_submit_tracked, _pinned and _pinned_nv12 return
+ * VNECT_E_ARG.  VNECT_E_STATE: no detector set; before vnect_finalize; a tracked frame of the stream in flight.  VNECT_E_ARG: what
+ * vnect_hog_detect_device refuses of a spec; max_hits above 4096; a picture side above VNECT_HOG_MAX_SIDE (here, or in the
+ * vnect_track_begin that brings it); a handle on which vnect_track_begin is refused.  enable == 0 switches the setting off (spec ignored).
+ * vnect_result_redetect (src/hog_box.py:28-31): the verdict on the frame vnect_collect_tracked delivered last, from its own result slot --
+ * *status 0: no detection ran (not lost, not set, or a refused crop), 1: found, 2: nobody found, 3: more than max_hits hits; rect4 (may be
+ * NULL): the chosen detection before cal_rect, zeros unless found; *hits (may be NULL): the full number of hits, 0 when none ran. */
+int vnect_track_redetect(vnect_handle* h, int stream, const vnect_hog_spec* spec, int enable);
+int vnect_result_redetect(vnect_handle* h, int32_t* status, int32_t rect4[4], int32_t* hits);
 
 /* ABI v7, additive.  The 3-D view (VIEW3D.md).  The reference's frame loop shows a second picture per frame: it puts joints_3d into
  * q_joints (run_estimator_ps.py:90, 124-126) and a second process plots the skeleton with matplotlib (src/utils.py:272-304: axes limits

@@ -169,6 +169,8 @@ def view3d_spec(size=400, view=None, extent=500.0, line_width=3.0, background=No
 
 
 HOG_DETECTOR_SIZE, HOG_MAX_SIDE = 3781, 4096   # VNECT_HOG_DETECTOR_SIZE, VNECT_HOG_MAX_SIDE
+HOG_TRACK_MAX_HITS = 4096                      # the hit budget of a re-detecting stream (vnect_track_redetect)
+REDETECT_STATUS = {0: "not run", 1: "found", 2: "nobody", 3: "overflow"}   # vnect_result_redetect's status
 
 
 class HogSpec(C.Structure):
@@ -271,6 +273,8 @@ SYMBOLS = {
     "vnect_hog_levels": (C.c_int, [_H, C.POINTER(DeviceFrame), C.POINTER(HogSpec), _i32p, _i32p, _f64p, C.c_int]),
     "vnect_hog_detect_device": (C.c_int, [_H, C.POINTER(DeviceFrame), C.c_void_p, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
     "vnect_hog_detect": (C.c_int, [_H, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
+    "vnect_track_redetect": (C.c_int, [_H, C.c_int, C.POINTER(HogSpec), C.c_int]),
+    "vnect_result_redetect": (C.c_int, [_H, _i32p, _i32p, _i32p]),
 }
 
 
@@ -291,6 +295,7 @@ ORIENT_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_orient.so")         # g++'
 PREVIEWPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_previewprobe.so") # preview.o behind csrc/preview_probe.hip (tests only)
 PREVIEW_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_preview.so")       # g++'s build of csrc/preview.h (tests only; no GPU code)
 HOGPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_hogprobe.so")         # hog.o behind csrc/hog_probe.hip (tests only)
+REDETECTPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_redetectprobe.so")  # hog.o behind csrc/redetect_probe.hip (tests only)
 HOG_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_hog.so")               # g++'s build of csrc/hog.h (tests only; no GPU code)
 VIEW3DPROBE_LIB = os.path.join(_HERE, "lib", "libvnect_view3dprobe.so")   # view3d.o behind csrc/view3d_probe.hip (tests only)
 VIEW3D_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_view3d.so")         # g++'s build of csrc/view3d.h (tests only; no GPU code)
@@ -318,6 +323,8 @@ def build(force=False):
     subprocess.check_call(["make", "-C", src, "previewprobe", "preview"], stdout=subprocess.DEVNULL)
     # the detector's probe (tests/test_gpu_hog_kernels.py) and g++'s build of its walk (tests/test_hog_cpu.py)
     subprocess.check_call(["make", "-C", src, "hogprobe", "hog"], stdout=subprocess.DEVNULL)
+    # the re-detection's probe (tests/test_gpu_redetect_kernels.py): the same hog.o behind csrc/redetect_probe.hip
+    subprocess.check_call(["make", "-C", src, "redetectprobe"], stdout=subprocess.DEVNULL)
     # the 3-D view's probe (tests/test_gpu_view3d_kernels.py) and g++'s build of its tile walk (tests/test_view3d_cpu.py)
     subprocess.check_call(["make", "-C", src, "view3dprobe", "view3d"], stdout=subprocess.DEVNULL)
     return LIB_PATH
@@ -729,6 +736,19 @@ class Handle:
         return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
 
     # -- the person detector: HOG + linear SVM over a pyramid, on the device (include/vnect_abi.h; HOG.md) ------------------------------
+    def track_redetect(self, stream, spec=None, enable=True):
+        """vnect_track_redetect: while enabled, a tracked frame of `stream` that its loss rule declares lost hands the next frame the
+        largest detection of itself through cal_rect (the whole frame when nobody is found), computed on the device (HOG.md).  spec: a
+        HogSpec (max_hits at most 4096) or None for the defaults."""
+        self._ck_device(lib().vnect_track_redetect(self._h, stream, None if spec is None else C.byref(spec), 1 if enable else 0))
+
+    def result_redetect(self):
+        """vnect_result_redetect: (status, [x, y, w, h], hits) of the frame collect_tracked delivered last -- status 0 no detection ran,
+        1 found, 2 nobody found, 3 more hits than max_hits; the rect is the chosen detection before cal_rect (zeros unless found)."""
+        st, hits, rect = C.c_int32(0), C.c_int32(0), np.zeros(4, np.int32)
+        self._ck(lib().vnect_result_redetect(self._h, C.byref(st), _ptr(rect, _i32p), C.byref(hits)))
+        return int(st.value), [int(v) for v in rect], int(hits.value)
+
     def hog_set_detector(self, w):
         """vnect_hog_set_detector: 3781 floats, rho last (cv2.HOGDescriptor_getDefaultPeopleDetector()'s layout), or 3780 with rho 0."""
         a = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))

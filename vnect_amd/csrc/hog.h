@@ -303,7 +303,7 @@ inline void hog_hit_rects(const HogPlan& p, std::vector<HogHit>& hits, std::vect
         weights->push_back((double)t.s);
     }
 }
-inline bool hog_similar(const HogRect& a, const HogRect& b)
+VNECT_HD bool hog_similar(const HogRect& a, const HogRect& b)
 {
     const double d = HOG_GROUP_EPS * ((a.w < b.w ? a.w : b.w) + (a.h < b.h ? a.h : b.h)) * 0.5;
     return abs(a.x - b.x) <= d && abs(a.y - b.y) <= d && abs(a.x + a.w - b.x - b.w) <= d && abs(a.y + a.h - b.y - b.h) <= d;
@@ -371,6 +371,216 @@ inline bool hog_detector(const float* w, int n, std::vector<float>* det)
     det->assign(w, w + n);
     if (n == HOG_DESC) det->push_back(0.f);
     return true;
+}
+
+// ---- re-detection inside the device tracking loop (vnect_track_redetect): hits -> the stream's next crop, host and device -------------------
+// THE RULE.  While re-detection is set on a tracked stream, the next box of a frame that the stream's loss rule (CONFIDENCE.md) declares
+// lost is runner.hog_box of that frame -- under "hold" as under "reset"; with the rule off no frame is ever lost.  hog_box here: the hits
+// become rectangles as hog_hit_rects makes them, are grouped as hog_group groups them, the class of the largest w * h wins -- the first of
+// equals in hog_group's class order, which is the order of the classes' lowest (level, y, x) members --, and goes through cal_rect; when no
+// class survives the box is [0, 0, W, H].  The box then takes the crop_head / crop_entry / crop_fill_head path of any box.  One stated
+// difference from the host loop: more hits than max_hits make the host loop raise; the device loop takes the whole frame and reports
+// HOG_RD_OVERFLOW.
+// hog_pick_* below are the phases of hog_pick_kernel (hog.hip), written once for the kernel's lanes and for g++'s walk of them
+// (hog_capi.cpp): `tid` of `nthr` lanes, a barrier between two phases.  A hit is one 32-bit key, level << 24 | y << 12 | x (sides are at
+// most 4096, levels at most 64): keys are unique per hit and order as (level, y, x), so sorting the keys makes the slot order the order
+// hog_hit_rects gives and nothing depends on the order in which lanes appended the hits.  Classes are the components of hog_similar, named
+// by their lowest slot: a lock-free union (compare-and-swap of a root's parent, the higher root under the lower) whose final partition and
+// names do not depend on scheduling, path halving while it runs and pointer jumping to flatten it; sums in integer atomics.
+constexpr int HOG_TRACK_MAX_HITS = 4096;  // the hit budget of a tracked stream: keys, rects and labels of one detection fit one workgroup's LDS
+constexpr int HOG_PICK_THREADS = 1024;
+enum { HOG_RD_NOT_RUN = 0, HOG_RD_FOUND = 1, HOG_RD_NOBODY = 2, HOG_RD_OVERFLOW = 3 };
+struct RedetectOut {  // per result-ring slot (device-mapped pinned host memory): vnect_result_redetect
+    int status;       // HOG_RD_*
+    int rect[4];      // the chosen detection before cal_rect; written only with HOG_RD_FOUND
+    int hits;         // the full hit count; written whenever the detection ran
+};
+
+VNECT_HD int hog_rint(double v) { return (int)rint(v); }  // cv_round on both sides: half to even in the default rounding mode
+VNECT_HD unsigned hog_key(int level, int y, int x) { return (unsigned)level << 24 | (unsigned)y << 12 | (unsigned)x; }
+// cal_rect (hog_box.py:48-58; runner.cal_rect), term by term
+VNECT_HD void hog_cal_rect(const int* r, int H, int W, int* out)
+{
+    const int ow = (int)(0.4 / 2 * (double)W), oh = (int)(0.2 / 2 * (double)H);
+    const int x0 = r[0] - ow > 0 ? r[0] - ow : 0, y0 = r[1] - oh > 0 ? r[1] - oh : 0;
+    const int x1 = r[0] + r[2] + ow < W ? r[0] + r[2] + ow : W, y1 = r[1] + r[3] + oh < H ? r[1] + r[3] + oh : H;
+    out[0] = x0, out[1] = y0, out[2] = x1 - x0, out[3] = y1 - y0;
+}
+// a class's mean field as hog_group rounds it
+VNECT_HD int hog_class_mean(int sum, int n) { return hog_rint((double)((float)sum * (1.f / (float)n))); }
+// hog_group's second drop rule: class (r1, n1) lies inside the surviving class (r2, n2)
+VNECT_HD bool hog_class_inside(const HogRect& r1, int n1, const HogRect& r2, int n2)
+{
+    const int dx = hog_rint(r2.w * HOG_GROUP_EPS), dy = hog_rint(r2.h * HOG_GROUP_EPS);
+    return r1.x >= r2.x - dx && r1.y >= r2.y - dy && r1.x + r1.w <= r2.x + r2.w + dx && r1.y + r1.h <= r2.y + r2.h + dy && (n2 > (3 > n1 ? 3 : n1) || n1 < 3);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+VNECT_HD int hog_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+VNECT_HD int hog_ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+VNECT_HD void hog_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+VNECT_HD void hog_st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+VNECT_HD int hog_cas(int* p, int cmp, int v) { return atomicCAS(p, cmp, v); }
+VNECT_HD void hog_add(int* p, int v) { atomicAdd(p, v); }
+VNECT_HD void hog_max64(unsigned long long* p, unsigned long long v) { atomicMax(p, v); }
+#else  // g++'s walk runs the lanes one after the other
+VNECT_HD int hog_ld(const int* p) { return *p; }
+VNECT_HD int hog_ld_agent(const int* p) { return *p; }
+VNECT_HD void hog_st(int* p, int v) { *p = v; }
+VNECT_HD void hog_st_agent(int* p, int v) { *p = v; }
+VNECT_HD int hog_cas(int* p, int cmp, int v)
+{
+    const int o = *p;
+    if (o == cmp) *p = v;
+    return o;
+}
+VNECT_HD void hog_add(int* p, int v) { *p += v; }
+VNECT_HD void hog_max64(unsigned long long* p, unsigned long long v)
+{
+    if (v > *p) *p = v;
+}
+#endif
+
+// What one pick works on.  a, b, c: three arrays of HOG_TRACK_MAX_HITS words in the workgroup's LDS, which change their meaning as the
+// phases go: keys / rect origins / parents, then -- per class, at its root's slot -- (w | h << 16) / (x | y << 16) / member count.
+// cls: 5 * HOG_TRACK_MAX_HITS ints of device memory (count, sum x, sum y, sum w, sum h per root), all zero between two picks.
+struct HogPick {
+    unsigned* a;
+    unsigned* b;
+    int* c;
+    int* cls;
+    const HogLevel* lv;
+    unsigned long long* best;  // (area << 12 | 4095 - root) of the winning class, 0: none
+    int n, np2, threshold;
+};
+VNECT_HD HogRect hog_pick_rect(const HogPick& m, int i)  // slot i's rectangle (phases 2 .. 5)
+{
+    const double s = m.lv[m.a[i] >> 24].s;
+    return HogRect{(int)(m.b[i] & 0xffffu), (int)(m.b[i] >> 16), hog_rint(HOG_WIN_W * s), hog_rint(HOG_WIN_H * s)};
+}
+VNECT_HD int hog_pick_find(int* parent, int i)  // the root of i; halves the path (every write is an ancestor of the slot it replaces)
+{
+    int p = hog_ld(parent + i);
+    while (p != i) {
+        const int g = hog_ld(parent + p);
+        if (g != p) hog_st(parent + i, g);
+        i = p, p = g;
+    }
+    return i;
+}
+// phase 0: the keys of the first n hits (n <= HOG_TRACK_MAX_HITS), padded to a power of two with keys behind every hit's
+VNECT_HD void hog_pick_load(const HogPick& m, const HogHit* hits, int tid, int nthr)
+{
+    for (int i = tid; i < m.np2; i += nthr) m.a[i] = i < m.n ? hog_key(hits[i].level, hits[i].y, hits[i].x) : 0xffffffffu;
+    if (tid == 0) *m.best = 0ull;
+}
+// phase 1, once per (k, j) of a bitonic sort over np2 keys: k = 2, 4 .. np2; j = k / 2, k / 4 .. 1
+VNECT_HD void hog_pick_sort_step(const HogPick& m, int k, int j, int tid, int nthr)
+{
+    for (int i = tid; i < m.np2; i += nthr) {
+        const int l = i ^ j;
+        if (l > i) {
+            const unsigned x = m.a[i], y = m.a[l];
+            if (((i & k) == 0) == (x > y)) m.a[i] = y, m.a[l] = x;
+        }
+    }
+}
+// phase 2: the rect origins (cv_round(x * s), cv_round(y * s)) and every slot its own class
+VNECT_HD void hog_pick_init(const HogPick& m, int tid, int nthr)
+{
+    for (int i = tid; i < m.n; i += nthr) {
+        const unsigned key = m.a[i];
+        const double s = m.lv[key >> 24].s;
+        m.b[i] = (unsigned)hog_rint((int)(key & 0xfffu) * s) | (unsigned)hog_rint((int)(key >> 12 & 0xfffu) * s) << 16;
+        m.c[i] = i;
+    }
+}
+// phase 3: every similar pair (i < j) joins its two classes (threshold < 1: hog_group leaves the hits as they are)
+VNECT_HD void hog_pick_union(const HogPick& m, int tid, int nthr)
+{
+    if (m.threshold < 1) return;
+    for (int i = tid; i < m.n; i += nthr) {
+        const HogRect ri = hog_pick_rect(m, i);
+        for (int j = i + 1; j < m.n; j++) {
+            if (!hog_similar(ri, hog_pick_rect(m, j))) continue;
+            int x = hog_pick_find(m.c, i), y = hog_pick_find(m.c, j);
+            while (x != y) {  // the higher root goes under the lower; a lost race moves on to that root's new parent
+                const int hi = x > y ? x : y, lo = x > y ? y : x;
+                const int old = hog_cas(m.c + hi, hi, lo);
+                if (old == hi) break;
+                x = hog_pick_find(m.c, old), y = lo;
+            }
+        }
+    }
+}
+// phase 4: pointer jumping -- every slot's parent becomes its root
+VNECT_HD void hog_pick_flatten(const HogPick& m, int tid, int nthr)
+{
+    for (int i = tid; i < m.n; i += nthr) {
+        int r = hog_ld(m.c + i);
+        for (int p = hog_ld(m.c + r); p != r; p = hog_ld(m.c + r)) r = p;
+        hog_st(m.c + i, r);
+    }
+}
+// phase 5: the class sums, integers
+VNECT_HD void hog_pick_sums(const HogPick& m, int tid, int nthr)
+{
+    for (int i = tid; i < m.n; i += nthr) {
+        const HogRect r = hog_pick_rect(m, i);
+        int* q = m.cls + m.c[i];
+        hog_add(q, 1), hog_add(q + HOG_TRACK_MAX_HITS, r.x), hog_add(q + 2 * HOG_TRACK_MAX_HITS, r.y), hog_add(q + 3 * HOG_TRACK_MAX_HITS, r.w),
+            hog_add(q + 4 * HOG_TRACK_MAX_HITS, r.h);
+    }
+}
+// phase 6: every root's mean rect and count into its own slot of the three arrays (0 members: not a root); the sums go back to zero
+VNECT_HD void hog_pick_means(const HogPick& m, int tid, int nthr)
+{
+    for (int r = tid; r < m.n; r += nthr) {
+        int* q = m.cls + r;
+        const int cnt = m.c[r] == r ? hog_ld_agent(q) : 0;
+        if (cnt) {
+            int f[4];
+            for (int k = 0; k < 4; k++) f[k] = hog_class_mean(hog_ld_agent(q + (k + 1) * HOG_TRACK_MAX_HITS), cnt);
+            m.b[r] = (unsigned)f[0] | (unsigned)f[1] << 16, m.a[r] = (unsigned)f[2] | (unsigned)f[3] << 16;
+            for (int k = 0; k < 5; k++) hog_st_agent(q + k * HOG_TRACK_MAX_HITS, 0);
+        }
+        m.c[r] = cnt;
+    }
+}
+VNECT_HD HogRect hog_pick_mean(const HogPick& m, int r) { return HogRect{(int)(m.b[r] & 0xffffu), (int)(m.b[r] >> 16), (int)(m.a[r] & 0xffffu), (int)(m.a[r] >> 16)}; }
+// phase 7: hog_group's two drop rules; of the classes that stay, the largest w * h, ties to the lowest root
+VNECT_HD void hog_pick_best(const HogPick& m, int tid, int nthr)
+{
+    for (int i = tid; i < m.n; i += nthr) {
+        const int n1 = m.c[i];
+        if (n1 == 0 || (m.threshold >= 1 && n1 <= m.threshold)) continue;
+        const HogRect r1 = hog_pick_mean(m, i);
+        int j = m.n;
+        if (m.threshold >= 1)
+            for (j = 0; j < m.n; j++) {
+                const int n2 = m.c[j];
+                if (j == i || n2 <= m.threshold) continue;
+                if (hog_class_inside(r1, n1, hog_pick_mean(m, j), n2)) break;
+            }
+        if (j == m.n) hog_max64(m.best, (unsigned long long)((long long)r1.w * r1.h) << 12 | (unsigned long long)(HOG_TRACK_MAX_HITS - 1 - i));
+    }
+}
+// phase 8 (one lane): the verdict -- `count` is the window launch's counter; next4: the stream's next box
+VNECT_HD void hog_pick_result(const HogPick& m, unsigned count, int max_hits, int H, int W, RedetectOut* out, int* next4)
+{
+    next4[0] = 0, next4[1] = 0, next4[2] = W, next4[3] = H;
+    out->hits = (int)count;
+    if (count > (unsigned)max_hits) {
+        out->status = HOG_RD_OVERFLOW;
+    } else if (*m.best == 0ull) {
+        out->status = HOG_RD_NOBODY;
+    } else {
+        const HogRect r = hog_pick_mean(m, HOG_TRACK_MAX_HITS - 1 - (int)(*m.best & 0xfffull));
+        const int d[4] = {r.x, r.y, r.w, r.h};
+        hog_cal_rect(d, H, W, next4);
+        out->rect[0] = r.x, out->rect[1] = r.y, out->rect[2] = r.w, out->rect[3] = r.h;
+        out->status = HOG_RD_FOUND;
+    }
 }
 
 }  // namespace vnect

@@ -4,11 +4,14 @@
 // normalisation and a score -- so the rule as the device runs it is held to an independent statement of it (tests/hog_ref.py) without a
 // GPU.  Loads and stores go straight to the caller's buffers: with -DHOG_SWEEP_MAIN (`make ... hog_sweep_asan`,
 // -fsanitize=address,undefined) the same file is a stand-alone program whose frames and workspaces sit in exactly sized heap blocks.
+// hog_pick_walk goes through the pick of a re-detection (hog.h: THE RULE) phase by phase, lane by lane, as hog_pick_kernel does;
+// -DREDETECT_SWEEP_MAIN (`make ... redetect_sweep_asan`) is the stand-alone program over it, hit lists in exactly sized heap blocks.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "hog.h"
@@ -230,7 +233,163 @@ int hog_group_c(int32_t* rects4, double* weights, int n, int threshold, int32_t*
     return 0;
 }
 
+// The pick of a re-detection as hog_pick_kernel (hog.hip) runs it: `nthr` lanes one after the other through every phase, a barrier
+// between two phases.  The frame is stored (H, W) under `orient`; hits3 [3 n] are the hits as the window launch left them (ANY order),
+// n = min(count, max_hits) of them; count: the launch's counter.  out6: status, the chosen rect, the hit count; next4: the stream's next
+// box.  Returns 0; -1 for arguments the runtime refuses; -3 when the class sums were not left at zero.
+int hog_pick_walk(int orient, int H, int W, double scale0, int nlevels, const int32_t* hits3, int n, int64_t count, int max_hits, int threshold, int nthr,
+                  int32_t* out6, int32_t* next4)
+{
+    HogSpec sp;
+    if (!orient_ok(orient) || H < 1 || W < 1 || hog_spec(0.0, 0, 0, scale0, 0.0, nlevels, max_hits, &sp)) return -1;
+    if (max_hits < 1 || max_hits > HOG_TRACK_MAX_HITS || nthr < 1 || count < 0 || n < 0 || n != (count < max_hits ? count : max_hits)) return -1;
+    std::vector<HogPlan> pv(1);
+    if (hog_plan(orient, H, W, sp, &pv[0])) return -1;
+    const HogPlan& p = pv[0];
+    std::vector<HogHit> hits;
+    for (int i = 0; i < n; i++) {
+        if (hits3[3 * i] < 0 || hits3[3 * i] >= p.n || hits3[3 * i + 1] < 0 || hits3[3 * i + 1] >= HOG_MAX_SIDE || hits3[3 * i + 2] < 0 || hits3[3 * i + 2] >= HOG_MAX_SIDE) return -1;
+        hits.push_back(HogHit{hits3[3 * i], hits3[3 * i + 1], hits3[3 * i + 2], 0.f});
+    }
+    std::vector<unsigned> a(HOG_TRACK_MAX_HITS), b(HOG_TRACK_MAX_HITS);
+    std::vector<int> c(HOG_TRACK_MAX_HITS), cls(5 * HOG_TRACK_MAX_HITS, 0);
+    unsigned long long best = ~0ull;
+    HogPick m{a.data(), b.data(), c.data(), cls.data(), p.lv, &best, 0, 1, threshold};
+    m.n = count > max_hits ? 0 : n;
+    while (m.np2 < m.n) m.np2 <<= 1;
+#define PICK_PHASE(call) \
+    for (int tid = 0; tid < nthr; tid++) call
+    PICK_PHASE(hog_pick_load(m, hits.data(), tid, nthr));
+    for (int k = 2; k <= m.np2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) PICK_PHASE(hog_pick_sort_step(m, k, j, tid, nthr));
+    PICK_PHASE(hog_pick_init(m, tid, nthr));
+    PICK_PHASE(hog_pick_union(m, tid, nthr));
+    PICK_PHASE(hog_pick_flatten(m, tid, nthr));
+    PICK_PHASE(hog_pick_sums(m, tid, nthr));
+    PICK_PHASE(hog_pick_means(m, tid, nthr));
+    PICK_PHASE(hog_pick_best(m, tid, nthr));
+#undef PICK_PHASE
+    RedetectOut out{};
+    int next[4];
+    hog_pick_result(m, (unsigned)count, max_hits, p.Hp, p.Wp, &out, next);
+    out6[0] = out.status, out6[5] = out.hits;
+    for (int k = 0; k < 4; k++) out6[1 + k] = out.rect[k], next4[k] = next[k];
+    for (int v : cls)
+        if (v) return -3;
+    return 0;
+}
+
+// The same verdict from the host's own pieces: hog_hit_rects, hog_group, the largest w * h (the first of equals), cal_rect
+int hog_pick_ref(int orient, int H, int W, double scale0, int nlevels, const int32_t* hits3, int n, int64_t count, int max_hits, int threshold, int32_t* out6,
+                 int32_t* next4)
+{
+    HogSpec sp;
+    if (!orient_ok(orient) || H < 1 || W < 1 || hog_spec(0.0, 0, 0, scale0, 0.0, nlevels, max_hits, &sp) || n < 0 || count < 0) return -1;
+    std::vector<HogPlan> pv(1);
+    if (hog_plan(orient, H, W, sp, &pv[0])) return -1;
+    const HogPlan& p = pv[0];
+    for (int k = 0; k < 6; k++) out6[k] = 0;
+    next4[0] = 0, next4[1] = 0, next4[2] = p.Wp, next4[3] = p.Hp;
+    out6[5] = (int32_t)count;
+    if (count > max_hits) {
+        out6[0] = HOG_RD_OVERFLOW;
+        return 0;
+    }
+    std::vector<HogHit> hits;
+    for (int i = 0; i < n; i++) {
+        if (hits3[3 * i] < 0 || hits3[3 * i] >= p.n) return -1;
+        hits.push_back(HogHit{hits3[3 * i], hits3[3 * i + 1], hits3[3 * i + 2], 0.f});
+    }
+    std::vector<HogRect> rects;
+    std::vector<double> ws;
+    hog_hit_rects(p, hits, &rects, &ws);
+    hog_group(rects, ws, threshold);
+    if (rects.empty()) {
+        out6[0] = HOG_RD_NOBODY;
+        return 0;
+    }
+    size_t at = 0;
+    for (size_t i = 1; i < rects.size(); i++)
+        if ((long long)rects[i].w * rects[i].h > (long long)rects[at].w * rects[at].h) at = i;
+    const int r[4] = {rects[at].x, rects[at].y, rects[at].w, rects[at].h};
+    int nx[4];
+    hog_cal_rect(r, p.Hp, p.Wp, nx);
+    out6[0] = HOG_RD_FOUND;
+    for (int k = 0; k < 4; k++) out6[1 + k] = r[k], next4[k] = nx[k];
+    return 0;
+}
+
 }  // extern "C"
+
+#ifdef REDETECT_SWEEP_MAIN
+// Hit lists in exactly sized heap blocks -- seeded clusters of windows over a level table, shuffled, at sizes round the lane counts and at
+// the budget's edges -- through hog_pick_walk at several lane counts, each held to hog_pick_ref.  A load outside a list or a store outside
+// the pick's arrays is the sanitizer's finding.
+int main()
+{
+    const int sizes[] = {0, 1, 2, 3, 63, 64, 65, 200, 1023, 1024, 1025, 4096, 4097};
+    const int lanes[] = {1, 64, 1000, HOG_PICK_THREADS};
+    const int frames[][3] = {{360, 640, 0}, {1080, 1920, 0}, {640, 360, 3}, {200, 264, 5}};
+    long long picks = 0, bad = 0, found = 0, nobody = 0, over = 0;
+    unsigned rng = 12345u;
+    auto next = [&]() { return rng = rng * 1664525u + 1013904223u, rng >> 8; };
+    std::vector<uint8_t> seen((size_t)1 << 30 >> 3, 0);  // one bit per key
+    std::vector<unsigned> used;
+    for (const auto& fr : frames)
+        for (int total : sizes)
+            for (int thr = 0; thr < 3; thr++) {
+                HogSpec sp;
+                hog_spec(0.0, 0, 0, 0.0, 0.0, 0, 0, &sp);
+                std::vector<HogPlan> pv(1);
+                hog_plan(fr[2], fr[0], fr[1], sp, &pv[0]);
+                const HogPlan& p = pv[0];
+                const int max_hits = total == 4097 ? HOG_TRACK_MAX_HITS : (total > 64 ? HOG_TRACK_MAX_HITS : 64 + (int)(next() % 2) * 4032);
+                const int n = total < max_hits ? total : max_hits;
+                if (n > p.nwin / 4) continue;  // (a small frame has too few windows for a long list of distinct hits)
+                int32_t* h3 = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)n + !n);
+                // clusters: a centre window and neighbours a stride or two away, on the same or the next level; keys must be unique
+                for (unsigned k : used) seen[k >> 3] = 0;
+                used.clear();
+                int filled = 0;
+                while (filled < n) {
+                    const int lv0 = (int)(next() % (unsigned)p.n);
+                    const HogLevel& L = p.lv[lv0];
+                    const int cx = (int)(next() % (unsigned)L.nwx), cy = (int)(next() % (unsigned)L.nwy), members = 1 + (int)(next() % 9);
+                    for (int q = 0; q < members && filled < n; q++) {
+                        int lv = lv0 + (int)(next() % 2);
+                        if (lv >= p.n) lv = lv0;
+                        const HogLevel& M = p.lv[lv];
+                        int wx = cx + (int)(next() % 3) - 1, wy = cy + (int)(next() % 3) - 1;
+                        wx = wx < 0 ? 0 : (wx >= M.nwx ? M.nwx - 1 : wx), wy = wy < 0 ? 0 : (wy >= M.nwy ? M.nwy - 1 : wy);
+                        const unsigned key = hog_key(lv, wy * 8, wx * 8);
+                        if (seen[key >> 3] >> (key & 7) & 1) continue;
+                        seen[key >> 3] |= (uint8_t)(1 << (key & 7)), used.push_back(key);
+                        h3[3 * filled] = lv, h3[3 * filled + 1] = wy * 8, h3[3 * filled + 2] = wx * 8, filled++;
+                    }
+                }
+                int32_t want6[6], want4[4];
+                if (hog_pick_ref(fr[2], fr[0], fr[1], 0.0, 0, h3, n, total, max_hits, thr, want6, want4)) bad++;
+                for (int nthr : lanes)
+                    for (int shuffle = 0; shuffle < 2; shuffle++) {
+                        for (int i = n - 1; i > 0 && shuffle; i--) {
+                            const int j = (int)(next() % (unsigned)(i + 1));
+                            for (int k = 0; k < 3; k++) std::swap(h3[3 * i + k], h3[3 * j + k]);
+                        }
+                        int32_t got6[6], got4[4];
+                        const int rc = hog_pick_walk(fr[2], fr[0], fr[1], 0.0, 0, h3, n, total, max_hits, thr, nthr, got6, got4);
+                        if (rc || memcmp(got6, want6, sizeof got6) || memcmp(got4, want4, sizeof got4)) {
+                            printf("redetect sweep: %dx%d code %d, %d hits, threshold %d, %d lanes: rc %d, status %d / %d\n", fr[0], fr[1], fr[2], total, thr, nthr, rc, got6[0], want6[0]);
+                            bad++;
+                        }
+                        picks++;
+                    }
+                found += want6[0] == HOG_RD_FOUND, nobody += want6[0] == HOG_RD_NOBODY, over += want6[0] == HOG_RD_OVERFLOW;
+                free(h3);
+            }
+    printf("redetect sweep: %lld picks, %lld lists found / %lld nobody / %lld overflow, %lld mismatches\n", picks, found, nobody, over, bad);
+    return (bad || !picks || !found || !nobody || !over) ? 1 : 0;
+}
+#endif
 
 #ifdef HOG_SWEEP_MAIN
 // Layouts x orientations x sizes: every frame in an exactly sized heap block (its first pixel byte at the block's first, its last at the

@@ -343,12 +343,15 @@ hipError_t launch_orient_copy_track(const TrackState* ts, const OrientSrc& s, in
 // behind the joints stage of tracked frame `xseq`: joints to frame coordinates (in `out`), rect_used + status to `tout`, the next crop and
 // its geometry to `ts`.  conf_dev: the frame's NJ confidences in device memory (launch_post / launch_joints left them there), pol: the
 // stream's loss rule (device memory), conf: the frame's ConfOut, which gets lost / confident -- all three or none (no rule: today's loop)
+// gate (here and in launch_post_track): nullptr, or the re-detection word of the stream (vnect_track_redetect): 1 when the rule calls the
+// frame lost, else 0
 hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st, const double* conf_dev = nullptr,
-                            const TrackPolicy* pol = nullptr, ConfOut* conf = nullptr);
+                            const TrackPolicy* pol = nullptr, ConfOut* conf = nullptr, int* gate = nullptr);
 // post_kernel with the same box stage as its tail (the last arriver's joints stage hands its frame-coordinate joints -- and the
 // confidences -- over in LDS).  conf: the frame's ConfOut or nullptr; pol: the stream's loss rule or nullptr (off)
 hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
-                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf = nullptr, const TrackPolicy* pol = nullptr);
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf = nullptr, const TrackPolicy* pol = nullptr,
+                             int* gate = nullptr);
 
 // ---- the overlay (overlay.hip; vnect_draw_device / vnect_submit_tracked_device_draw; OVERLAY.md) -----------------------------------
 // utils.draw_limbs_2d (src/utils.py:222-243; run_estimator_ps.py:92-94) into a frame in device memory, by the rule of overlay.h.  One
@@ -397,6 +400,22 @@ struct HogDev {
     float* scores;
 };
 hipError_t launch_hog(const HogSrc& a, const HogPlan& p, const HogDev& d, double hit_threshold, int max_hits, int stages, hipStream_t st);
+// Re-detection inside the tracked loop (vnect_track_redetect; hog.h: THE RULE).  launch_hog_gated: the same three launches WITHOUT the
+// counter reset (the caller zeroes d.count in front of them), each returning at once unless *gate (device memory; a tracked frame's box stage wrote it) is 1.  cap > 0: each launch runs at
+// most `cap` workgroups, which walk the launch's workgroup indices in a grid-stride loop -- a frame that is not lost then dispatches
+// 3 * cap empty workgroups, not the pyramid's; cap 0: the ungated kernels' grids, every workgroup leaving at once.  Gate 1: the outputs of
+// launch_hog, whatever the cap.
+constexpr int HOG_GATED_CAP = 8192;  // measured (profiles/redetect_rate.txt): gate 0 costs what 1024 costs, gate 1 what the ungated launches cost
+hipError_t launch_hog_gated(const HogSrc& a, const HogPlan& p, const HogDev& d, double hit_threshold, int max_hits, int stages, const int* gate, int cap,
+                            hipStream_t st);
+// launch_hog_pick: one workgroup behind them.  Gate 0: out->status = HOG_RD_NOT_RUN and nothing else.  Gate 1: the hits (d.hits, d.count;
+// nlev levels in d.lv) become the stream's next crop by hog.h's rule -- grouped with `threshold` (the spec's (int)final_threshold), the
+// largest class through cal_rect, or the whole frame when nobody is found or more than max_hits (<= HOG_TRACK_MAX_HITS) windows hit -- and
+// *ts gets that crop the way a box stage commits it (trackbox.h: track_box_commit, for tracked frame `xseq`); `out` gets the verdict.
+// cls: 5 * HOG_TRACK_MAX_HITS ints of device memory, zero before the first pick (every pick leaves them zero).
+struct RedetectOut;
+hipError_t launch_hog_pick(const HogDev& d, int nlev, int max_hits, int threshold, const int* gate, int* cls, TrackState* ts, unsigned xseq, RedetectOut* out,
+                           hipStream_t st);
 
 // VNectEstimator.joint_filter alone: bank `dim` of fb over NJ * dim values (float64 carriers; f32vals: they are float32 scalars)
 hipError_t launch_filter(FilterBank* fb, int dim, bool f32vals, int nep50, double t, const double* in, double* out, hipStream_t st);

@@ -935,7 +935,8 @@ template <int SMAX, bool TRACK = false>
 __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restrict__ maps, const MergeGeo geo, ArgPartial* part, unsigned* ticket,
                                                            FilterBank* fb, const FrameParams* __restrict__ fp, const FrameDyn dyn,
                                                            int nep50, JointsOut* __restrict__ out, ConfOut* __restrict__ cf, double* conf_dev,
-                                                           TrackState* ts = nullptr, TrackOut* tout = nullptr, const TrackPolicy* polp = nullptr)
+                                                           TrackState* ts = nullptr, TrackOut* tout = nullptr, const TrackPolicy* polp = nullptr,
+                                                           int* gate = nullptr)
 {
     __shared__ int last;
     if (POST_DBG == 4) return;
@@ -960,7 +961,7 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
     if constexpr (TRACK) {
         if (c.status != SQ_OK) {  // this frame's crop was refused (dyn.xfail names it): no joints stage, the stream stays stopped
             if (threadIdx.x == 0) out->status = 1;
-            track_refused(ts, c, tout, dyn.xseq);
+            track_refused(ts, c, tout, dyn.xseq, gate);
             return;
         }
         __shared__ double jf[NJ * 2];
@@ -968,7 +969,7 @@ __global__ __launch_bounds__(ARG_THREADS) void post_kernel(const float* __restri
         const int shift[2] = {c.y, c.x};
         joints_stage_wide<SMAX, true>(part, maps, geo, fb, f2, f3, pr2, pr3, scaler, off, dyn, nep50, out, cf, cl, shift, jf);
         __syncthreads();
-        track_box_stage(ts, c, jf, tout, dyn.xseq, cl, pol, cf);
+        track_box_stage(ts, c, jf, tout, dyn.xseq, cl, pol, cf, gate);
     } else {
         if (dyn.xfail && __hip_atomic_load(dyn.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == dyn.xseq) {
             if (threadIdx.x == 0) out->status = 1;  // the exchange of THIS frame timed out: stale maps, leave the filters alone
@@ -985,12 +986,12 @@ hipError_t launch_post(const float* maps, MergeGeo geo, ArgPartial* part, unsign
     return hipGetLastError();
 }
 hipError_t launch_post_track(const float* maps, MergeGeo geo, ArgPartial* part, unsigned* ticket, FilterBank* fb, TrackState* ts, FrameDyn dyn,
-                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf, const TrackPolicy* pol)
+                             int nep50, JointsOut* out, TrackOut* tout, hipStream_t st, ConfOut* conf, const TrackPolicy* pol, int* gate)
 {
     const FrameParams* fp = &ts->fp;
     double* const none = nullptr;
-    if (geo.S <= 3) hipLaunchKernelGGL((post_kernel<3, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol);
-    else hipLaunchKernelGGL((post_kernel<VNECT_MAX_S, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol);
+    if (geo.S <= 3) hipLaunchKernelGGL((post_kernel<3, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol, gate);
+    else hipLaunchKernelGGL((post_kernel<VNECT_MAX_S, true>), dim3(NJ, ARG_SLABS), dim3(ARG_THREADS), 0, st, maps, geo, part, ticket, fb, fp, dyn, nep50, out, conf, none, ts, tout, pol, gate);
     return hipGetLastError();
 }
 hipError_t launch_joints(const ArgPartial* part, const float* maps, MergeGeo geo, FilterBank* fb, const FrameParams* fp, FrameDyn dyn,

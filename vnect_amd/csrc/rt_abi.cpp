@@ -91,11 +91,16 @@ static int preprocess_from(vnect_handle* h, const char* who, float* batch_out, d
 }
 
 // the stream's next tracked frame: the whole frame in `slot`, or (slot -1) where the resolver says
+// whole_on_device: the submit form leaves the whole frame in device memory in a layout HogSrc describes -- what a stream that re-detects
+// (vnect_track_redetect) needs of every frame
 template <class R>
-static int submit_tracked_from(vnect_handle* h, int stream, int slot, double t2d, double t3d, R&& resolve)
+static int submit_tracked_from(vnect_handle* h, int stream, int slot, double t2d, double t3d, R&& resolve, bool whole_on_device = false)
 {
     int rc = tracked_ok(h, stream);
     if (rc) return rc;
+    if (h->streams[stream].rd_on && !whole_on_device)
+        return fail(h, VNECT_E_ARG, "vnect_track_redetect is set on this stream: its frames come through vnect_submit_tracked_device, _device_draw or "
+                                    "_device_preview (the detector reads the whole frame in device memory)");
     HIPCK(h, hipSetDevice(h->cfg.device));
     FrameSrc src;
     if ((rc = resolve(&src))) return rc;
@@ -286,6 +291,7 @@ void vnect_destroy(vnect_handle* h)
     for (int i = 0; i < RING; i++)
         if (h->v3_host[i]) hipHostFree(h->v3_host[i]);  // (v3_dev: dev_allocs)
     if (h->h_conf) hipHostFree(h->h_conf);
+    if (h->h_redet) hipHostFree(h->h_redet);
     for (int i = 0; i < 3; i++)
         if (h->stage[i]) hipHostFree(h->stage[i]);
     if (h->h_filt) hipHostFree(h->h_filt);
@@ -923,7 +929,7 @@ int vnect_submit_tracked_device(vnect_handle* h, int stream, const vnect_device_
             if (s->H != stored_H(sm) || s->W != stored_W(sm))
                 return fail(h, VNECT_E_ARG, "vnect_submit_tracked_device: the frame is not of the size vnect_track_begin gave for this stream");
             return (int)VNECT_OK;
-        });
+        }, true);
     });
 }
 
@@ -943,7 +949,7 @@ int vnect_submit_tracked_device_draw(vnect_handle* h, int stream, const vnect_de
                 return fail(h, VNECT_E_ARG, std::string(who) + ": the frame is not of the size vnect_track_begin gave for this stream");
             s->draw = true, s->draw_target = t, s->draw_in = in;
             return (int)VNECT_OK;
-        });
+        }, true);
     });
 }
 
@@ -961,7 +967,7 @@ int vnect_submit_tracked_device_preview(vnect_handle* h, int stream, const vnect
             if (s->H != stored_H(sm) || s->W != stored_W(sm))
                 return fail(h, VNECT_E_ARG, std::string(who) + ": the frame is not of the size vnect_track_begin gave for this stream");
             return (int)VNECT_OK;
-        });
+        }, true);
     });
 }
 
@@ -1074,6 +1080,28 @@ int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t 
         if (!h) return VNECT_E_ARG;
         HIPCK(h, hipSetDevice(h->cfg.device));
         return hog_detect_host_impl(h, bgr, H, W, row_stride, spec, rects4, weights, capacity, count_out);
+    });
+}
+
+// ---- re-detection inside the device tracking loop (additive; HOG.md; src/hog_box.py:26-31 behind run_estimator_ps.py:96-107) -------------
+int vnect_track_redetect(vnect_handle* h, int stream, const vnect_hog_spec* spec, int enable)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return track_redetect_impl(h, stream, spec, enable);
+    });
+}
+
+int vnect_result_redetect(vnect_handle* h, int32_t* status, int32_t rect4[4], int32_t* hits)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h || !status) return h ? fail(h, VNECT_E_ARG, "vnect_result_redetect: bad argument") : VNECT_E_ARG;
+        *status = h->last_redet.status;
+        if (rect4)
+            for (int k = 0; k < 4; k++) rect4[k] = h->last_redet.rect[k];
+        if (hits) *hits = h->last_redet.hits;
+        return VNECT_OK;
     });
 }
 

@@ -361,9 +361,12 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // post_kernel (the default: measured faster, TRACKING.md), or -- the two-launch post-processing, VNECT_TRACK_BOX_LAUNCH=1 (A/B, read per
     // frame) -- as a launch of its own behind it, which reads the joints back from the result ring slot
     const bool box_tail = tk && L->post_merged && !getenv("VNECT_TRACK_BOX_LAUNCH");
+    // vnect_track_redetect: the box stage also tells the detection chain behind it whether the frame is lost (the stream's gate word)
+    const bool redetect = tk && sm.rd_on;
+    int* const gate = redetect ? sm.rd_gate() : nullptr;
     if (box_tail) {
         HIPCK(h, launch_post_track(maps_of(L), h->mgeo, L->d_part, L->d_ticket, h->d_fb + stream, h->d_track + stream, dyn, h->cfg.numpy_promotion,
-                                   e.out_dev, h->h_tout_dev + ring, L->st, h->h_conf_dev + ring, h->d_policy + stream));
+                                   e.out_dev, h->h_tout_dev + ring, L->st, h->h_conf_dev + ring, h->d_policy + stream, gate));
     } else {
         // (a box kernel of its own takes the confidences from device memory, not from the ring slot: the joints stage leaves them in both)
         const FrameParams* tfp = tk ? &h->d_track[stream].fp : nullptr;
@@ -372,8 +375,12 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
                                  : run_joints(L, dyn, e.out_dev, h->h_conf_dev + ring, stream, tfp, cdev)))
             return rc;
         if (tk)
-            HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st, cdev, h->d_policy + stream, h->h_conf_dev + ring));
+            HIPCK(h, launch_track_box(h->d_track + stream, e.out_dev, h->h_tout_dev + ring, dyn.xseq, L->st, cdev, h->d_policy + stream, h->h_conf_dev + ring, gate));
     }
+    // hog_box.py:26-31 in the place of the loop's whole-frame fallback (hog.h: THE RULE): the detection of THIS frame, gated by its box
+    // stage's verdict, and the pick that turns the hits into the stream's next crop -- on the frame's stream, in front of the event the
+    // stream's next frame waits for, and in front of the overlay launch, so that the detector reads the clean frame
+    if (redetect && (rc = redetect_enqueue(h, stream, *tk, dyn.xseq, ring, L->st))) return rc;
     // run_estimator_ps.py:94-96: the frame's preview -- annotated with its own joints and rect_used, read from its ring slot, and scaled --
     // into the slot's device buffer and on to its pinned host buffer; in front of the overlay launch, so that it reads the clean frame
     if (tk && tk->preview) {
@@ -400,6 +407,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     e.stream = stream, e.unit = h->unit_submit++, e.batch = false, e.prof = nullptr, e.tracked = tk != nullptr;
     e.pv_h = tk && tk->preview ? tk->pv.g.dh : 0, e.pv_w = tk && tk->preview ? tk->pv.g.dw : 0;
     e.v3_h = v3 ? sm.v3.rows : 0, e.v3_w = v3 ? sm.v3.cols : 0;
+    e.redetect = redetect;
     e.before = sm.t;  // (a tracked frame's refused crop rolls back)
     commit_time(sm, t2d, t3d);
     sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
@@ -445,6 +453,7 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     }
     h->last_pv_ring = -1, h->last_pv_h = h->last_pv_w = 0;  // (a frame whose crop was refused has no preview)
     h->last_v3_ring = -1, h->last_v3_h = h->last_v3_w = 0;  // (nor a 3-D view)
+    h->last_redet = RedetectOut{};                          // (nor a detection)
     if (stream_out) *stream_out = e.stream;
     if (rect_out)
         for (int k = 0; k < 4; k++) rect_out[k] = e.tracked ? h->h_tout[ring].rect[k] : -1;
@@ -461,6 +470,12 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     if (j2) memcpy(j2, e.out->j2d, sizeof(double) * NJ * 2);
     if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
     deliver_confidence(h, ring, e.tracked);
+    if (e.tracked && e.redetect) {  // the frame's verdict, from its own ring slot like the confidences; what the kernel did not write reads as zero
+        const RedetectOut& r = h->h_redet[ring];
+        h->last_redet.status = r.status;
+        if (r.status != HOG_RD_NOT_RUN) h->last_redet.hits = r.hits;
+        if (r.status == HOG_RD_FOUND) memcpy(h->last_redet.rect, r.rect, sizeof r.rect);
+    }
     if (e.tracked && e.pv_h) h->last_pv_ring = ring, h->last_pv_h = e.pv_h, h->last_pv_w = e.pv_w;
     if (e.tracked && e.v3_h) h->last_v3_ring = ring, h->last_v3_h = e.v3_h, h->last_v3_w = e.v3_w;
     if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
@@ -732,6 +747,12 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
         int rc = dev_alloc(h, &sm.track_buf, need);
         if (rc) return rc;
         sm.track_cap = need;
+    }
+    // vnect_track_redetect is set on the stream: its level table and workspace for this size and orientation, now that they are known --
+    // the last step that can refuse, so a refused vnect_track_begin leaves the stream's track and its detection plan as they were
+    if (sm.rd_on) {
+        int rc = redetect_prepare(h, stream, H, W, h->orient);
+        if (rc) return rc;
     }
     HIPCK(h, hipMemcpyAsync(h->d_track + stream, &t, sizeof(TrackState), hipMemcpyHostToDevice, h->st));
     HIPCK(h, hipStreamSynchronize(h->st));

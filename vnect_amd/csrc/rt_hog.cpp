@@ -2,7 +2,8 @@
 // vnect_hog_detect; src/hog_box.py:24-33).  The frame is validated by the device-frame resolver of rt_ingest.cpp and read where it lies,
 // as the preview reads it; the spec becomes hog.h's level table, from which the handle's workspace is sized; three launches of hog.hip
 // cover all levels; the hits come back, are put in the order (level, y, x) and grouped on the host (hog.h: hog_group).  A refusal
-// changes nothing and launches nothing.
+// changes nothing and launches nothing.  vnect_track_redetect: the same detection inside the device tracking loop, on a workspace of the
+// stream's own -- gated launches and a pick kernel behind every tracked frame's box stage, nothing coming back to the host but a verdict.
 #include "runtime.h"
 
 namespace vnect {
@@ -38,6 +39,9 @@ int hog_set_detector_impl(vnect_handle* h, const float* w, int n)
     if (rc0) return rc0;
     std::vector<float> d;
     if (!hog_detector(w, n, &d)) return refuse(h, who, "the detector is 3781 finite floats, rho last (or 3780: rho 0)");
+    for (const Stream& sm : h->streams)  // (a re-detecting stream's frame in flight reads the detector whenever its chain runs)
+        if (sm.rd_on && sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+            return fail(h, VNECT_E_STATE, std::string(who) + ": a re-detecting stream has a tracked frame in flight: collect it first");
     if (!h->hog_det_dev) {
         int rc = dev_alloc(h, &h->hog_det_dev, d.size());
         if (rc) return rc;
@@ -85,6 +89,18 @@ static int grow(vnect_handle* h, int i, size_t need)
     return VNECT_OK;
 }
 
+// the host-built tables on the device (and the handle's level table), once
+static int tables_ready(vnect_handle* h)
+{
+    if (h->hog_tab) return VNECT_OK;
+    HogTables t;
+    hog_tables(&t);
+    int rc;
+    if ((rc = dev_alloc(h, &h->hog_tab, 1))) return rc;
+    HIPCK(h, hipMemcpy(h->hog_tab, &t, sizeof t, hipMemcpyHostToDevice));
+    return dev_alloc(h, &h->hog_lv, HOG_MAX_LEVELS);
+}
+
 // the detection of a validated source on upload_st; `stream`: what the launches wait for
 static int detect(vnect_handle* h, const char* who, const HogSrc& a, const HogSpec& sp, void* stream, int32_t* rects4, double* weights, int capacity, int32_t* count_out)
 {
@@ -96,13 +112,7 @@ static int detect(vnect_handle* h, const char* who, const HogSrc& a, const HogSp
         *count_out = 0;
         return VNECT_OK;
     }
-    if (!h->hog_tab) {
-        HogTables t;
-        hog_tables(&t);
-        if ((rc = dev_alloc(h, &h->hog_tab, 1))) return rc;
-        HIPCK(h, hipMemcpy(h->hog_tab, &t, sizeof t, hipMemcpyHostToDevice));
-        if ((rc = dev_alloc(h, &h->hog_lv, HOG_MAX_LEVELS))) return rc;
-    }
+    if ((rc = tables_ready(h))) return rc;
     if ((rc = grow(h, 0, sizeof(float2) * (size_t)p.npix)) || (rc = grow(h, 1, (size_t)p.npix)) || (rc = grow(h, 2, sizeof(float) * HOG_BLOCK_LEN * (size_t)p.nblk)) ||
         (rc = grow(h, 3, sizeof(HogHit) * (size_t)sp.max_hits)) || (rc = grow(h, 4, 256)))
         return rc;
@@ -179,6 +189,104 @@ int hog_detect_host_impl(vnect_handle* h, const uint8_t* bgr, int H, int W, int6
     a.src = preview_source(false, false, h->hog_buf[5], nullptr, (long long)row, 3, 1, 0);
     a.o = h->orient, a.H = H, a.W = W;
     return detect(h, who, a, sp, VNECT_STREAM_SYNCED, rects4, weights, capacity, count_out);
+}
+
+// ---- re-detection inside the device tracking loop (vnect_track_redetect; hog.h: THE RULE) ------------------------------------------------
+// buffer i of the stream's own workspace with room for `need` bytes (nothing of the stream is in flight; hipFree waits for the device)
+static int rd_grow(vnect_handle* h, Stream& sm, int i, size_t need)
+{
+    if (need <= sm.rd_bytes[i]) return VNECT_OK;
+    if (sm.rd_buf[i]) {
+        HIPCK(h, hipFree(sm.rd_buf[i]));
+        h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)sm.rd_buf[i]));
+        sm.rd_buf[i] = nullptr, sm.rd_bytes[i] = 0;
+    }
+    int rc = dev_alloc(h, &sm.rd_buf[i], need);
+    if (rc) return rc;
+    HIPCK(h, hipMemset(sm.rd_buf[i], 0, need));  // (the gate, the counter and the class sums start at zero)
+    sm.rd_bytes[i] = need;
+    return VNECT_OK;
+}
+
+int redetect_prepare(vnect_handle* h, int stream, int H, int W, int orient)
+{
+    static const char* who = "vnect_track_redetect";
+    Stream& sm = h->streams[stream];
+    const int sH = (orient & 1) ? W : H, sW = (orient & 1) ? H : W;  // the frames as they are stored
+    std::vector<HogPlan> pv(1);
+    int rc = hog_plan(orient, sH, sW, sm.rd_spec, &pv[0]);
+    if (rc) return refuse(h, who, hog_refusal(rc));
+    const HogPlan& p = pv[0];
+    if ((rc = tables_ready(h))) return rc;
+    if ((rc = rd_grow(h, sm, 0, sizeof(HogLevel) * HOG_MAX_LEVELS)) || (rc = rd_grow(h, sm, 1, sizeof(float2) * (size_t)p.npix)) || (rc = rd_grow(h, sm, 2, (size_t)p.npix)) ||
+        (rc = rd_grow(h, sm, 3, sizeof(float) * HOG_BLOCK_LEN * (size_t)p.nblk)) || (rc = rd_grow(h, sm, 4, sizeof(HogHit) * (size_t)sm.rd_spec.max_hits)) ||
+        (rc = rd_grow(h, sm, 5, 256)) || (rc = rd_grow(h, sm, 6, sizeof(int) * 5 * HOG_TRACK_MAX_HITS)))
+        return rc;
+    if (p.n) HIPCK(h, hipMemcpy(sm.rd_buf[0], p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice));
+    sm.rd_plan.swap(pv), sm.rd_o = orient, sm.rd_H = sH, sm.rd_W = sW;
+    return VNECT_OK;
+}
+
+int track_redetect_impl(vnect_handle* h, int stream, const vnect_hog_spec* spec, int enable)
+{
+    static const char* who = "vnect_track_redetect";
+    if (stream < 0 || stream >= VNECT_MAX_STREAMS) return refuse(h, who, "stream out of range");
+    if (h->sharded) return refuse(h, who, "tracking on a pyramid-sharded handle is not supported");
+    if (h->stream_batch == 2 || !h->bplans.empty()) return refuse(h, who, "tracking on a handle with the two-stream batch is not supported");
+    if (!h->finalized) return fail(h, VNECT_E_STATE, std::string(who) + " before vnect_finalize");
+    Stream& sm = h->streams[stream];
+    HogSpec sp{};
+    int rc;
+    if (enable) {
+        if ((rc = common_in(h, who, true))) return rc;
+        if ((rc = spec_in(h, who, spec, &sp))) return rc;
+        if (!spec || !spec->max_hits) sp.max_hits = HOG_TRACK_MAX_HITS;  // (the tracked default: what one workgroup's LDS groups)
+        if (sp.max_hits > HOG_TRACK_MAX_HITS) return refuse(h, who, "max_hits of a tracked stream is at most 4096");
+    }
+    // the chain of a tracked frame in flight reads the setting's workspace whenever it runs: no change under it
+    if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+        return fail(h, VNECT_E_STATE, std::string(who) + ": the stream has a tracked frame in flight: collect it first");
+    if (!enable) {
+        sm.rd_on = false;
+        return VNECT_OK;
+    }
+    if (!h->h_redet) {
+        HIPCK(h, hipHostMalloc((void**)&h->h_redet, RING * sizeof(RedetectOut), hipHostMallocMapped | hipHostMallocCoherent));
+        memset(h->h_redet, 0, RING * sizeof(RedetectOut));
+        HIPCK(h, hipHostGetDevicePointer((void**)&h->h_redet_dev, h->h_redet, 0));
+    }
+    const HogSpec before = sm.rd_spec;
+    sm.rd_spec = sp;
+    if (sm.track_on && (rc = redetect_prepare(h, stream, sm.track_H, sm.track_W, sm.orient))) {
+        sm.rd_spec = before;
+        return rc;
+    }
+    const char* cap = getenv("VNECT_REDETECT_CAP");  // (tuning: tools/redetect_rate.py measures both grid shapes)
+    sm.rd_cap = cap ? std::max(0, atoi(cap)) : HOG_GATED_CAP;
+    sm.rd_on = true;
+    return VNECT_OK;
+}
+
+int redetect_enqueue(vnect_handle* h, int stream, const FrameSrc& src, unsigned xseq, int ring, hipStream_t st)
+{
+    static const char* who = "re-detection";
+    const Stream& sm = h->streams[stream];
+    if (src.where != SRC_DEVICE && src.where != SRC_NV12) return refuse(h, who, "the frame is not whole in device memory");
+    if (sm.rd_plan.empty() || src.orient != sm.rd_o || src.H != sm.rd_H || src.W != sm.rd_W)
+        return fail(h, VNECT_E_INTERNAL, "re-detection: the stream's level table was not built for this frame");
+    const HogPlan& p = sm.rd_plan[0];
+    const HogDev d{(HogLevel*)sm.rd_buf[0], h->hog_tab, h->hog_det_dev, (float2*)sm.rd_buf[1], sm.rd_buf[2], (float*)sm.rd_buf[3], (HogHit*)sm.rd_buf[4], sm.rd_count(),
+                   nullptr};
+    HIPCK(h, hipMemsetAsync(d.count, 0, sizeof(unsigned), st));
+    if (p.n) {  // (a picture smaller than the window has no level: nobody found)
+        HogSrc a;
+        memset(&a, 0, sizeof a);
+        a.src = orient_src_of(src), a.o = src.orient, a.H = src.H, a.W = src.W;
+        HIPCK(h, launch_hog_gated(a, p, d, sm.rd_spec.hit_threshold, sm.rd_spec.max_hits, 7, sm.rd_gate(), sm.rd_cap, st));
+    }
+    HIPCK(h, launch_hog_pick(d, p.n, sm.rd_spec.max_hits, (int)sm.rd_spec.final_threshold, sm.rd_gate(), (int*)sm.rd_buf[6], h->d_track + stream, xseq,
+                             h->h_redet_dev + ring, st));
+    return VNECT_OK;
 }
 
 }  // namespace rt

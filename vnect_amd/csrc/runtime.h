@@ -149,6 +149,7 @@ struct InFlight {
     bool tracked = false;
     int pv_h = 0, pv_w = 0;        // a tracked frame that carries a preview (vnect_submit_tracked_device_preview): its size; 0: none
     int v3_h = 0, v3_w = 0;        // a tracked frame that carries a 3-D view (vnect_track_view3d): its size; 0: none
+    bool redetect = false;         // a tracked frame of a re-detecting stream (vnect_track_redetect): its ring slot's RedetectOut is its verdict
     TimeState before{};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
 };
 
@@ -169,6 +170,18 @@ struct Stream {
     bool v3_on = false;            // vnect_track_view3d: every tracked submit of the stream also renders its frame's 3-D view
     View3dArgs v3{};               // ... with these arguments (but `out` and `pitch`, which are the ring slot's)
     TrackPolicy policy{0.0, 1, TRACK_LOST_OFF};  // the host's copy of d_policy[stream] (vnect_track_policy; survives vnect_track_begin)
+    // re-detection inside the loop (vnect_track_redetect; rt_hog.cpp; hog.h: THE RULE): the setting, its spec, and -- built when the setting
+    // and the stream's frame size and orientation are both known, in vnect_track_redetect or vnect_track_begin -- the level table and a
+    // workspace of the stream's OWN (the synchronous vnect_hog_detect* calls keep using the handle's on the upload stream)
+    bool rd_on = false;
+    HogSpec rd_spec{};
+    int rd_cap = HOG_GATED_CAP;    // workgroups of a gated launch at most (VNECT_REDETECT_CAP, read when the setting is made; 0: full grids)
+    std::vector<HogPlan> rd_plan;  // one entry once built, for (rd_o, rd_H, rd_W)
+    int rd_o = -1, rd_H = 0, rd_W = 0;  // the orientation and the STORED size the plan was built for
+    uint8_t* rd_buf[7] = {};       // level table, votes, bins, blocks, hits, {counter, gate}, class sums
+    size_t rd_bytes[7] = {};
+    unsigned* rd_count() const { return (unsigned*)rd_buf[5]; }
+    int* rd_gate() const { return (int*)rd_buf[5] + 16; }
 };
 
 }  // namespace rt
@@ -251,6 +264,9 @@ struct vnect_handle : Plan {
     double* d_conf = nullptr;       // [VNECT_MAX_STREAMS][NJ], device: a tracked frame's confidences for a box kernel launched behind its
                                     // joints stage (VNECT_TRACK_BOX_LAUNCH=1, VNECT_NO_POST_MERGE=1); a stream's frames run one behind the other
     TrackPolicy* d_policy = nullptr;  // [VNECT_MAX_STREAMS]: the streams' loss rules as the box stage reads them
+    RedetectOut* h_redet = nullptr;   // pinned, device-mapped, [RING]: a re-detecting stream's frames' verdicts (made by the first vnect_track_redetect)
+    RedetectOut* h_redet_dev = nullptr;
+    RedetectOut last_redet{};         // vnect_result_redetect: the frame most recently delivered, from its own ring slot
     double last_conf[NJ] = {};      // vnect_result_confidence: the frame most recently delivered, copied out of its own ring slot then
     int last_lost = 0;
     bool have_conf = false;
@@ -475,6 +491,12 @@ int hog_detect_device_impl(vnect_handle* h, const vnect_device_frame* f, void* s
                            int32_t* count_out);
 int hog_detect_host_impl(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const vnect_hog_spec* spec, int32_t* rects4, double* weights,
                          int capacity, int32_t* count_out);
+// re-detection inside the tracked loop (vnect_track_redetect; hog.h: THE RULE)
+int track_redetect_impl(vnect_handle* h, int stream, const vnect_hog_spec* spec, int enable);
+// the stream's level table and workspace for (H, W) oriented frames under `orient`; never with a tracked frame of the stream in flight
+int redetect_prepare(vnect_handle* h, int stream, int H, int W, int orient);
+// behind tracked frame `xseq`'s box stage on `st`: the counter reset, the three gated launches and the pick kernel; the verdict goes to ring slot `ring`
+int redetect_enqueue(vnect_handle* h, int stream, const FrameSrc& src, unsigned xseq, int ring, hipStream_t st);
 
 // ---- rt_comm.cpp ---------------------------------------------------------------------------------------------------------------
 int exchange_maps(vnect_handle* h, unsigned long long seq, int ring);

@@ -49,7 +49,7 @@ constexpr int BOX_THREADS = 384;
 // them there as well as in the ring slot), requested up front with the state and the policy.
 __global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __restrict__ ts, JointsOut* out, TrackOut* tout, unsigned xseq,
                                                                 const double* __restrict__ conf_dev, const TrackPolicy* __restrict__ polp,
-                                                                ConfOut* cf)
+                                                                ConfOut* cf, int* gate)
 {
     __shared__ double j2[NJ * 2];
     __shared__ double cl[NJ];
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __re
     if (conf_dev && t < NJ) cl[t] = conf_dev[t];
     __syncthreads();  // (every thread has read the state before thread 0 overwrites it)
     if (c.status != SQ_OK) {
-        track_refused(ts, c, tout, xseq);
+        track_refused(ts, c, tout, xseq, gate);
         return;
     }
     if (t < NJ * 2) {  // run_estimator_ps.py:92-93: joints_2d[:, 0] += y; joints_2d[:, 1] += x  (float64)
@@ -68,14 +68,14 @@ __global__ __launch_bounds__(BOX_THREADS) void track_box_kernel(TrackState* __re
         j2[t] = v;
     }
     __syncthreads();
-    track_box_stage(ts, c, j2, tout, xseq, conf_dev ? cl : nullptr, pol, cf);
+    track_box_stage(ts, c, j2, tout, xseq, conf_dev ? cl : nullptr, pol, cf, gate);
 }
 
 hipError_t launch_track_box(TrackState* ts, JointsOut* out, TrackOut* tout, unsigned xseq, hipStream_t st, const double* conf_dev,
-                            const TrackPolicy* pol, ConfOut* conf)
+                            const TrackPolicy* pol, ConfOut* conf, int* gate)
 {
     if (!conf_dev != !pol || (conf && !conf_dev)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(track_box_kernel, dim3(1), dim3(BOX_THREADS), 0, st, ts, out, tout, xseq, conf_dev, pol, conf);
+    hipLaunchKernelGGL(track_box_kernel, dim3(1), dim3(BOX_THREADS), 0, st, ts, out, tout, xseq, conf_dev, pol, conf, gate);
     return hipGetLastError();
 }
 

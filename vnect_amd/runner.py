@@ -229,7 +229,7 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
 
 
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
-                    confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False):
+                    confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False, redetect=False):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
 
     Each frame goes to the device whole; the device crops it with the box it grew from the previous frame's joints, so the host submits
@@ -253,15 +253,20 @@ def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=No
     ``view3d`` (every ``source``; VIEW3D.md): True (the reference's plot: 400 x 400, view_init(-90, -90)) or an
     ``_native.view3d_spec(...)`` -- every yielded tuple gets the frame's 3-D skeleton view appended last (run_estimator_ps.py:90,
     124-126; src/utils.py:272-304: a fresh (rows, cols, 3) array, the picture ``render.view3d_exact`` gives for the ``joints_3d`` yielded
-    with it), rendered on the device behind the frame's joints stage; the other results are those of ``view3d=False``, bit for bit."""
+    with it), rendered on the device behind the frame's joints stage; the other results are those of ``view3d=False``, bit for bit.
+    ``redetect`` (``source="device"`` and a ``lost=`` rule of "hold" or "reset" only; HOG.md): True (the detector's defaults), or a dict of
+    ``detect_people``'s spec -- the next box of a lost frame is ``hog_box`` of that frame, found on the device with no host wait: with
+    "reset" the loop yields what ``track(lost=(c, n, "detect"))`` yields, bit for bit.  A frame with more than ``max_hits`` (at most 4096)
+    hits hands on the whole frame where ``track`` would raise.  With ``confidence=True`` every tuple gets the frame's re-detection
+    status appended last (0 none ran, 1 found, 2 nobody found, 3 overflow).  The estimator needs a detector (``set_hog_detector``)."""
     for res in track_many_on_device(estimator, [frames], None if rect is None else [rect], transpose,
                                     None if timestamps is None else [timestamps], ahead, source, [stream], pixel_format, confidence, lost, draw,
-                                    orientation, preview, view3d):
+                                    orientation, preview, view3d, redetect):
         yield res[1:]
 
 
 def track_many_on_device(estimator, videos, rects=None, transpose=False, timestamps=None, ahead=1, source="pinned", streams=None,
-                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False):
+                         pixel_format="bgr", confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False, redetect=False):
     """Several tracked videos on one handle, video i on stream ``streams[i]`` (default i): their frames are submitted in turn and
     overlap on the handle's lanes.  Yields (i, joints_2d, joints_3d, rect_used) in submission order; every video's sequence is what
     ``track`` yields for it alone on a handle of its own.  ``rects`` / ``timestamps``: one per video (or None).
@@ -270,7 +275,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     ``lost=(min_confidence, min_joints, "hold" | "reset")``: every video's stream gets this loss rule for the loop (and is off again
     afterwards); ``confidence=True`` appends
     (confidence, lost flag) to every tuple.
-    ``draw``, ``preview``, ``view3d``: as in ``track_on_device`` (the view is the last element of every tuple).
+    ``draw``, ``preview``, ``view3d``, ``redetect``: as in ``track_on_device`` (the view, then the re-detection status, are the last
+    elements of every tuple).
     ``orientation``: one code for all videos or one per video (ORIENTATION.md; None: the estimator's own): every stream keeps the code its track began with, so
     videos with different orientations share the handle; the estimator's own orientation is back in force afterwards."""
     from collections import deque
@@ -297,6 +303,15 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     nv12 = _nv12_checks(pixel_format, transpose, source)
     codes = _orientations(estimator, orientation, len(videos), transpose)
     rule = lost_rule(lost)
+    rspec = None
+    if redetect is not False and redetect is not None:
+        if source != "device":
+            raise ValueError("redetect= runs the detector over frames in device memory: it needs source='device'")
+        if rule is None:
+            raise ValueError("redetect= needs a lost=(min_confidence, min_joints, 'hold' | 'reset') rule: without one no frame is ever lost")
+        kw = dict(redetect) if isinstance(redetect, dict) else {}
+        kw.setdefault("max_hits", _native.HOG_TRACK_MAX_HITS)
+        rspec = _native.hog_spec(**kw)
     if source not in ("pinned", "resident", "device"):
         raise ValueError("source must be 'pinned', 'resident' or 'device'")
     device = source == "device"
@@ -330,9 +345,19 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             H, W = size_of(pending[i])
             estimator._orient(codes[i])        # the stream keeps the code in force now; H, W: the picture's
             h.track_begin(streams[i], W if codes[i] & 1 else H, H if codes[i] & 1 else W, rects[i])
+            if rspec is not None:              # (nothing is in flight yet; first: what it refuses leaves no rule behind)
+                try:
+                    h.track_redetect(streams[i], rspec, True)
+                except _native.VnectError:
+                    for k in range(i):
+                        if pending[k] is not None:
+                            h.track_redetect(streams[k], None, False)
+                            if rule is not None:
+                                h.track_policy(streams[k], 0.0, 1, "off")
+                    raise
             if rule is not None:
                 h.track_policy(streams[i], *rule)
-            if vspec is not None:              # (nothing is in flight yet)
+            if vspec is not None:
                 h.track_view3d(streams[i], vspec)
     flat = []
     if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
@@ -359,6 +384,8 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
             res += (h.result_preview(),)
         if vspec is not None:
             res += (h.result_view3d(),)
+        if rspec is not None and confidence:
+            res += (h.result_redetect()[0],)
         return res
 
     # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
@@ -431,6 +458,13 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                 if pending[i] is not None:
                     try:
                         h.track_view3d(streams[i], None)
+                    except _native.VnectError:
+                        pass
+        if rspec is not None:                   # ... and they detect nobody again
+            for i in range(n):
+                if pending[i] is not None:
+                    try:
+                        h.track_redetect(streams[i], None, False)
                     except _native.VnectError:
                         pass
         if rule is not None:                    # nothing is in flight any more: the streams' rule is off again
