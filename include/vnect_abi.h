@@ -173,7 +173,8 @@ int vnect_reset_filters_stream(vnect_handle* h, int stream);
  * form one batch of 2 S images: image i is scale i % S of the i / S-th frame.  Called before vnect_finalize: n = 1 is the default (no
  * batched plan); n = 2 makes finalize build a second launch plan for 2 S images -- the S-image plan's layers, tiles, K splits and fused
  * forms with M doubled, the same packed weights -- and gives every lane an activation arena for it.  VNECT_E_STATE after finalize or on a
- * preprocess_only handle; VNECT_E_ARG on a pyramid-sharded handle, for n outside 1 .. 2, or when 2 S > VNECT_MAX_SCALES.
+ * preprocess_only handle; VNECT_E_ARG on a pyramid-sharded handle, for n outside 1 .. 2, when 2 S > VNECT_MAX_SCALES, or (n = 2) on a
+ * people handle (vnect_set_people).
  * Pays with two or more videos per GPU, where a frame is bound by launch count (bf16); a stream's latency becomes its batch's.         */
 int vnect_set_stream_batch(vnect_handle* h, int n);
 /* n frames of DISTINCT streams from resident slots as one batch (src/estimator.py:97-142 once per stream, as the reference's per-video
@@ -475,6 +476,45 @@ int vnect_hog_detect(vnect_handle* h, const uint8_t* bgr, int H, int W, int64_t 
  * NULL): the chosen detection before cal_rect, zeros unless found; *hits (may be NULL): the full number of hits, 0 when none ran. */
 int vnect_track_redetect(vnect_handle* h, int stream, const vnect_hog_spec* spec, int enable);
 int vnect_result_redetect(vnect_handle* h, int32_t* status, int32_t rect4[4], int32_t* hits);
+
+/* ABI v7, additive.  People mode: several persons of ONE video on one handle, one submit per frame (PEOPLE.md).  The reference has no
+ * counterpart: src/hog_box.py:26-31 keeps the biggest rectangle, and run_estimator_ps.py:80-109 follows that one person.  Here person p
+ * (0 .. n-1, n <= VNECT_MAX_STREAMS) is video stream p: each person's loop is that loop -- its own filter bank, box, loss rule
+ * (vnect_track_policy) and 3-D view (vnect_track_view3d) -- and every person's results are bit for bit those of a tracked stream on a
+ * handle of its own fed the same clean frames from the same first rect.
+ * Called before vnect_finalize, with n in 1 .. VNECT_MAX_STREAMS and pair 0 or 1.  pair = 1 with n >= 2 and 2 S <= VNECT_MAX_SCALES makes
+ * finalize build the (2 S)-image launch plan per lane (as vnect_set_stream_batch(h, 2) does), and two persons' crops then go through ONE conv
+ * stack; with 2 S > VNECT_MAX_SCALES the people run singly, which is not an error.  VNECT_E_STATE after finalize or on a preprocess_only
+ * handle; VNECT_E_ARG for n or pair out of range, on a pyramid-sharded handle, and together with vnect_set_stream_batch(h, 2).
+ * On a people handle vnect_track_redetect is refused (VNECT_E_ARG: its pick takes the largest detection, which could be another person);
+ * vnect_track_begin / vnect_submit_tracked* stay legal and run one person on the S-image plan. */
+int vnect_set_people(vnect_handle* h, int n, int pair);
+/* vnect_track_begin for streams 0 .. n-1 (the start of each person's loop, run_estimator_ps.py:80-109), all or nothing: rects holds 4 n values,
+ * (x, y, w, h) per person, or is NULL for the whole frame for everyone.  The rect rules, the fallback and the refusals are
+ * vnect_track_begin's; VNECT_E_STATE while any of those streams has a frame in flight; VNECT_E_ARG for n outside 1 .. vnect_set_people's n. */
+int vnect_people_begin(vnect_handle* h, int n, int H, int W, const int32_t* rects);
+/* The next frame for persons 0 .. n-1 (one pass of run_estimator_ps.py:80-109 per person): the WHOLE frame in a resident slot, or in device
+ * memory (every format, layout and orientation vnect_submit_tracked_device accepts).  Pinned sources are not supported in people mode.
+ * A frame of n persons is ceil(n / 2) lane units on a handle with the pair plan -- persons (0, 1) and (2, 3) share a conv stack, an odd last
+ * person runs singly -- and n units without it.  Atomic, like vnect_submit_streams: that every stream tracks the submitted (H, W), that none
+ * is stopped, both timestamps for every stream (VNECT_E_TIMESTAMP / VNECT_E_TIMEORDER), that the units in flight stay within the limit
+ * (max(lanes, 2); a frame submitted while nothing is in flight is always accepted) and that the results in flight plus n stay within the
+ * result ring (8) are all checked before anything changes.
+ * style (may be NULL): as in vnect_submit_tracked_device_draw, for every person, in person order, and only after every person's crop has
+ * been read from the clean frame; the frame is written until the LAST person has been collected.
+ * preview_spec (may be NULL): the frame's ONE picture, as in vnect_submit_tracked_device_preview but with every person in it -- a tap of the
+ * annotated picture is band p over limbs p over ..., for p = n-1 down to 0, over the source pixel: n applications of the overlay's rule in
+ * person order -- computed from the clean frame before anything is drawn; a person whose crop was refused is left out.  The frame itself
+ * is drawn into only where `style` is given (draw_frame of the spec is not read); with style NULL the picture uses the reference's style.
+ * vnect_result_preview is valid after the LAST person's delivery of the frame.
+ * Results come back through vnect_collect_tracked, n deliveries in person order; vnect_result_confidence and vnect_result_view3d belong to
+ * each delivery. */
+int vnect_submit_people(vnect_handle* h, int n, int slot, double t2d, double t3d);
+int vnect_submit_people_device(vnect_handle* h, int n, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                               const vnect_overlay_style* style, const vnect_preview_spec* preview_spec);
+/* Of the people frame submitted last (each one pass of run_estimator_ps.py:80-109 per person): how many lane units it took, and how many
+ * of those were paired conv stacks. */
+int vnect_result_people(vnect_handle* h, int32_t* units_out, int32_t* paired_out);
 
 /* ABI v7, additive.  The 3-D view (VIEW3D.md).  The reference's frame loop shows a second picture per frame: it puts joints_3d into
  * q_joints (run_estimator_ps.py:90, 124-126) and a second process plots the skeleton with matplotlib (src/utils.py:272-304: axes limits

@@ -275,6 +275,12 @@ SYMBOLS = {
     "vnect_hog_detect": (C.c_int, [_H, _u8p, C.c_int, C.c_int, C.c_int64, C.POINTER(HogSpec), _i32p, _f64p, C.c_int, _i32p]),
     "vnect_track_redetect": (C.c_int, [_H, C.c_int, C.POINTER(HogSpec), C.c_int]),
     "vnect_result_redetect": (C.c_int, [_H, _i32p, _i32p, _i32p]),
+    "vnect_set_people": (C.c_int, [_H, C.c_int, C.c_int]),
+    "vnect_people_begin": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _i32p]),
+    "vnect_submit_people": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "vnect_submit_people_device": (C.c_int, [_H, C.c_int, C.POINTER(DeviceFrame), C.c_void_p, C.c_double, C.c_double,
+                                             C.POINTER(OverlayStyle), C.POINTER(PreviewSpec)]),
+    "vnect_result_people": (C.c_int, [_H, _i32p, _i32p]),
 }
 
 
@@ -375,7 +381,7 @@ class Handle:
 
     def __init__(self, scales, device=0, precision=FP32, paper_res2c=False, use_graph="auto", numpy_promotion=0,
                  max_frame_bytes=0, num_frame_slots=0, pyramid=None, keep_activations=False, lanes=1,
-                 preprocess_only=False, exchange=XCHG_RCCL, stream_batch=1):
+                 preprocess_only=False, exchange=XCHG_RCCL, stream_batch=1, people=0, pair=False):
         L = lib()
         cfg = Config()
         cfg.struct_size = C.sizeof(Config)
@@ -406,6 +412,39 @@ class Handle:
         self.stream_batch = int(stream_batch)  # 2: finalize also builds the batched plan of two streams (submit_streams)
         if self.stream_batch != 1:
             self.set_stream_batch(self.stream_batch)
+        self.people = 0          # P > 0: people mode -- persons 0 .. P-1 of one video on streams 0 .. P-1 (set_people; PEOPLE.md)
+        if people:
+            self.set_people(people, pair)
+
+    def set_people(self, n, pair=False):
+        """vnect_set_people: people mode for n persons (before finalize); pair: two persons' crops share one conv stack where 2 S <= 8."""
+        self._ck(lib().vnect_set_people(self._h, int(n), int(bool(pair))))
+        self.people, self.pair_people = int(n), bool(pair)
+
+    def people_begin(self, n, H, W, rects=None):
+        """vnect_people_begin: persons 0 .. n-1 track (H, W) frames from now on, person p from rects[p] (x, y, w, h); None: the whole frame."""
+        r = None
+        if rects is not None:
+            r = np.asarray([[int(v) for v in rect] for rect in rects], np.int32)
+            if r.shape != (int(n), 4):
+                raise ValueError("rects must hold n rects (x, y, w, h)")
+        self._ck(lib().vnect_people_begin(self._h, int(n), int(H), int(W), None if r is None else _ptr(r, _i32p)))
+
+    def submit_people(self, n, slot, t2d, t3d):
+        """vnect_submit_people: the next frame for persons 0 .. n-1, the whole frame in resident slot `slot`; n collect_tracked() deliveries."""
+        self._ck(lib().vnect_submit_people(self._h, int(n), int(slot), t2d, t3d))
+
+    def submit_people_device(self, n, frame, t2d, t3d, producer=None, style=None, spec=None):
+        """vnect_submit_people_device: the same from device memory (`frame`: a DeviceFrame without a rect, kept alive and untouched until the
+        last person has been collected); style: every person is drawn into the frame, in person order, once every crop has been read."""
+        self._ck_device(lib().vnect_submit_people_device(self._h, int(n), C.byref(frame), _stream_arg(producer), t2d, t3d,
+                                                         None if style is None else C.byref(style), None if spec is None else C.byref(spec)))
+
+    def result_people(self):
+        """vnect_result_people: (lane units, paired units) of the people frame submitted last."""
+        u, p = C.c_int32(0), C.c_int32(0)
+        self._ck(lib().vnect_result_people(self._h, C.byref(u), C.byref(p)))
+        return int(u.value), int(p.value)
 
     def set_stream_batch(self, n):
         """vnect_set_stream_batch: 2 = two video streams' frames per launch (before finalize)."""

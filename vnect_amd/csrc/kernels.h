@@ -326,6 +326,10 @@ struct TrackOut {     // per result-ring slot, device-mapped pinned host memory
 // the pyramid of a tracked frame: the crop origin (and, `packed`, the row stride of a crop copied out of a pinned buffer) from the
 // stream's state instead of FrameDyn::frame; geometry ts->fp
 hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, const ScaleTabs* tabs, void* batch4, int S, int el, hipStream_t st);
+// the same for two streams whose states are ts2[0] and ts2[1], into one (2 S, 368, 368, 4) batch: images 0 .. S-1 from (ts2[0], dyn0),
+// S .. 2 S-1 from (ts2[1], dyn1); 2 S <= VNECT_MAX_IMAGES (people mode: vnect_submit_people)
+hipError_t launch_pyramid_track_pair(const TrackState* ts2, FrameDyn dyn0, FrameDyn dyn1, int packed, const ScaleTabs* tabs, void* batch4, int S, int el,
+                                     hipStream_t st);
 // the crop's rows (rect from the stream's state) out of a pinned frame of H rows into `dst`, packed; grid sized for the whole frame
 hipError_t launch_frame_copy_track(const TrackState* ts, const uint8_t* src_dev, uint8_t* dst, int H, int W, long long stride, const uint8_t* src_end,
                                    hipStream_t st);
@@ -368,6 +372,17 @@ hipError_t launch_overlay(const OverlayTarget& t, const OverlayInput& in, const 
 // whose status is not SQ_OK writes nothing.
 struct PreviewArgs;
 hipError_t launch_preview(const PreviewArgs& a, const OverlayInput& in, const JointsOut* jo, const TrackOut* to, const ConfOut* co, hipStream_t st);
+// The people form (people mode; PEOPLE.md): the ONE picture of a frame with P persons (1 .. 4) -- band p over limbs p over ... for
+// p = P-1 down to 0 -- each person's joints, rect_used, status and confidences read from its own result-ring slot; `in` carries the style
+// only (parents, threshold).  A person whose status is not SQ_OK is left out; the picture is always written.  With P = 1 and status
+// SQ_OK it writes launch_preview's bytes.
+struct PreviewPeopleIn {
+    int P;
+    const JointsOut* jo[4];
+    const TrackOut* to[4];
+    const ConfOut* co[4];  // (all nullptr without a threshold)
+};
+hipError_t launch_preview_people(const PreviewArgs& a, const OverlayInput& in, const PreviewPeopleIn& pin, hipStream_t st);
 
 // ---- the 3-D view (view3d.hip; vnect_view3d_device, vnect_track_view3d; VIEW3D.md) ----------------------------------------------------
 // run_estimator_ps.py:90, 124-126 and src/utils.py:272-304: the skeleton plot of joints_3d, by the rule of view3d.h.  One launch; the grid

@@ -112,28 +112,66 @@ VNECT_HD void preview_tap(const PreviewArgs& a, const OverlayLimb* L, const int*
     else bgr[0] = a.col[s - 1][0], bgr[1] = a.col[s - 1][1], bgr[2] = a.col[s - 1][2];
 }
 
+// The annotation of ONE person as a tap's source: what preview_kernel and vnect_preview_device draw
+struct PreviewOne {
+    const OverlayLimb* L;
+    const int* live;
+    int nlive;
+    const OverlayBand* b;
+    VNECT_HD void tap(const PreviewArgs& a, int i, int j, int* bgr) const { preview_tap(a, L, live, nlive, *b, i, j, bgr); }
+};
+
+// The annotation of P persons of one frame (people mode; PEOPLE.md; no reference counterpart: run_estimator_ps.py:92-96 draws the one
+// person it follows): pixel (i, j) of A is band p over limbs p over ... for p = P-1 down to 0, over P's pixel -- exactly P applications of
+// overlay.h's rule in person order 0 .. P-1, each drawing over the one before.  Person p's limbs are L[p * OVERLAY_NJ ..], the survivors'
+// indices live[p * OVERLAY_NJ ..] (nlive[p] of them), its band b[p]; a person that is not drawn has nlive 0 and its band off.
+constexpr int PREVIEW_MAX_PEOPLE = 4;
+struct PreviewPeople {
+    int P;
+    const OverlayLimb* L;
+    const int* live;
+    const int* nlive;
+    const OverlayBand* b;
+    VNECT_HD void tap(const PreviewArgs& a, int i, int j, int* bgr) const
+    {
+        int s = OVERLAY_NONE;
+        for (int p = P - 1; p >= 0 && s == OVERLAY_NONE; p--) {
+            if (overlay_in_band(b[p], i, j)) s = OVERLAY_BAND;
+            for (int k = 0; k < nlive[p] && s == OVERLAY_NONE; k++)
+                if (overlay_inside(L[p * OVERLAY_NJ + live[p * OVERLAY_NJ + k]], i, j)) s = OVERLAY_LIMB;
+        }
+        if (s == OVERLAY_NONE) preview_src_pixel(a.src, a.o, a.H, a.W, i, j, bgr);
+        else bgr[0] = a.col[s - 1][0], bgr[1] = a.col[s - 1][1], bgr[2] = a.col[s - 1][2];
+    }
+};
+
 // Output pixel (dy, dx): cv2's 8-bit INTER_LINEAR as the project pins it (oracle.resize; hostplan.h: build_u8_tab + sample_u8)
-VNECT_HD void preview_pixel(const PreviewArgs& a, const OverlayLimb* L, const int* live, int nlive, const OverlayBand& b, int dy, int dx, int* bgr)
+template <class Scene>
+VNECT_HD void preview_pixel_of(const PreviewArgs& a, const Scene& sc, int dy, int dx, int* bgr)
 {
     if (a.g.copy) {
-        preview_tap(a, L, live, nlive, b, dy, dx, bgr);
+        sc.tap(a, dy, dx, bgr);
         return;
     }
     const AxE x = axis_x_at(dx, a.g.Wp, a.g.scale), y = axis_y_at(dy, a.g.Hp, a.g.scale);
     const int b0 = crop_sat((1.f - y.f) * 2048.f), b1 = crop_sat(y.f * 2048.f);
     int t0[3], t1[3], r0[3], r1[3];
-    preview_tap(a, L, live, nlive, b, y.s0, x.s0, t0);
-    preview_tap(a, L, live, nlive, b, y.s1, x.s0, t1);
+    sc.tap(a, y.s0, x.s0, t0);
+    sc.tap(a, y.s1, x.s0, t1);
     if (!x.edge) {
         const int a0 = crop_sat((1.f - x.f) * 2048.f), a1 = crop_sat(x.f * 2048.f);
         int u0[3], u1[3];
-        preview_tap(a, L, live, nlive, b, y.s0, x.s0 + 1, u0);
-        preview_tap(a, L, live, nlive, b, y.s1, x.s0 + 1, u1);
+        sc.tap(a, y.s0, x.s0 + 1, u0);
+        sc.tap(a, y.s1, x.s0 + 1, u1);
         for (int c = 0; c < 3; c++) r0[c] = t0[c] * a0 + u0[c] * a1, r1[c] = t1[c] * a0 + u1[c] * a1;
     } else {
         for (int c = 0; c < 3; c++) r0[c] = t0[c] * 2048, r1[c] = t1[c] * 2048;  // a column at or past xmax: the single tap
     }
     for (int c = 0; c < 3; c++) bgr[c] = (((b0 * (r0[c] >> 4)) >> 16) + ((b1 * (r1[c] >> 4)) >> 16) + 2) >> 2;
+}
+VNECT_HD void preview_pixel(const PreviewArgs& a, const OverlayLimb* L, const int* live, int nlive, const OverlayBand& b, int dy, int dx, int* bgr)
+{
+    preview_pixel_of(a, PreviewOne{L, live, nlive, &b}, dy, dx, bgr);
 }
 
 // The rectangle of A that the taps of output rows dy0 .. dy1 and columns dx0 .. dx1 lie in (taps are monotonic in the output index)
@@ -177,7 +215,8 @@ VNECT_HD void preview_store(uintptr_t at, const uint32_t* w, int n)
 }
 
 // One lane: output row dy, columns dx .. dx + PREVIEW_LANE_PX - 1 (those below dw)
-VNECT_HD void preview_lane(const PreviewArgs& a, const OverlayLimb* L, const int* live, int nlive, const OverlayBand& b, int dy, int dx)
+template <class Scene>
+VNECT_HD void preview_lane_of(const PreviewArgs& a, const Scene& sc, int dy, int dx)
 {
     uint32_t w[3] = {0u, 0u, 0u};
     const int npx = a.g.dw - dx < PREVIEW_LANE_PX ? a.g.dw - dx : PREVIEW_LANE_PX;
@@ -187,7 +226,7 @@ VNECT_HD void preview_lane(const PreviewArgs& a, const OverlayLimb* L, const int
     for (int p = 0; p < PREVIEW_LANE_PX; p++) {
         if (p >= npx) break;
         int c[3];
-        preview_pixel(a, L, live, nlive, b, dy, dx + p, c);
+        preview_pixel_of(a, sc, dy, dx + p, c);
         const uint32_t c0 = (uint32_t)(a.out_rgb ? c[2] : c[0]), c1 = (uint32_t)c[1], c2 = (uint32_t)(a.out_rgb ? c[0] : c[2]);
         // pixel p's bytes are 3 p, 3 p + 1, 3 p + 2 of the stream
         w[(3 * p) >> 2] |= c0 << (8 * ((3 * p) & 3));
@@ -195,6 +234,10 @@ VNECT_HD void preview_lane(const PreviewArgs& a, const OverlayLimb* L, const int
         w[(3 * p + 2) >> 2] |= c2 << (8 * ((3 * p + 2) & 3));
     }
     preview_store((uintptr_t)a.out + (unsigned long long)dy * (unsigned long long)a.pitch + 3ull * (unsigned)dx, w, 3 * npx);
+}
+VNECT_HD void preview_lane(const PreviewArgs& a, const OverlayLimb* L, const int* live, int nlive, const OverlayBand& b, int dy, int dx)
+{
+    preview_lane_of(a, PreviewOne{L, live, nlive, &b}, dy, dx);
 }
 
 // The limbs and the band of a launch as every workgroup sets them up

@@ -112,6 +112,66 @@ int preview_walk(const uint8_t* src, int64_t src_size, int64_t data_off, int64_t
     return 0;
 }
 
+// The people form (preview.h: PreviewPeople; PEOPLE.md), walked as preview_people_kernel goes: per tile every person's band and limbs
+// culled against the footprint, then the lanes.  preview_walk's arguments, but P persons (1 .. 4): j2d holds P x 42 doubles, conf P x 21
+// (or null), rects P x 4 (every person has a rect, as a tracked frame has), drawn P flags (or null: everybody; 0: the person is left
+// out, as one whose crop was refused).
+int preview_walk_people(const uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off, int format, int H, int W, int64_t sy, int64_t sx, int64_t sc,
+                        int64_t uv_stride, int orient, int P, const double* j2d, const double* conf, double min_conf, const int32_t* parents,
+                        const int32_t* rects, const int32_t* drawn, const int32_t* limb_bgr, const int32_t* rect_bgr, double factor, int out_format,
+                        uint8_t* out, int64_t out_size, int64_t out_off, int64_t out_pitch)
+{
+    PreviewArgs a;
+    memset(&a, 0, sizeof a);
+    if (P < 1 || P > PREVIEW_MAX_PEOPLE || !j2d || !rects) return -1;
+    if (!source_of(&a, src, src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, orient)) return -1;
+    if (preview_geom(orient, H, W, factor, &a.g) != PREVIEW_OK) return -1;
+    if (!out || out_off < 0 || (out_format != 0 && out_format != 1) || out_pitch < 3LL * a.g.dw) return -1;
+    if (out_off + (int64_t)(a.g.dh - 1) * out_pitch + 3LL * a.g.dw > out_size) return -1;
+    if ((uintptr_t)out < (uintptr_t)src + (uintptr_t)src_size && (uintptr_t)src < (uintptr_t)out + (uintptr_t)out_size) return -1;
+    int lc[3], rc[3], par[OVERLAY_NJ];
+    for (int k = 0; k < 3; k++) {
+        lc[k] = limb_bgr ? limb_bgr[k] : OVERLAY_LIMB_BGR[k], rc[k] = rect_bgr ? rect_bgr[k] : OVERLAY_RECT_BGR[k];
+        if (lc[k] < 0 || lc[k] > 255 || rc[k] < 0 || rc[k] > 255) return -1;
+    }
+    preview_colours(&a, lc, rc);
+    for (int i = 0; i < OVERLAY_NJ; i++) {
+        par[i] = parents ? parents[i] : OVERLAY_PARENTS[i];
+        if (par[i] < 0 || par[i] >= OVERLAY_NJ) return -1;
+    }
+    for (int p = 0; p < P; p++)
+        if (rects[4 * p + 2] < 1 || rects[4 * p + 3] < 1) return -1;
+    const bool has_conf = conf && min_conf == min_conf;
+    a.has_joints = 1, a.out = out + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
+    OverlayLimb L[PREVIEW_MAX_PEOPLE * OVERLAY_NJ];
+    for (int p = 0; p < P; p++)
+        for (int i = 0; i < OVERLAY_NJ; i++)
+            L[p * OVERLAY_NJ + i] = preview_limb_of(a, j2d + p * OVERLAY_NJ * 2, conf ? conf + p * OVERLAY_NJ : nullptr, has_conf, min_conf, par, i);
+    for (int dy0 = 0; dy0 < a.g.dh; dy0 += PREVIEW_TILE_H)
+        for (int dx0 = 0; dx0 < a.g.dw; dx0 += PREVIEW_TILE_W) {
+            const int dy1 = (dy0 + PREVIEW_TILE_H < a.g.dh ? dy0 + PREVIEW_TILE_H : a.g.dh) - 1, dx1 = (dx0 + PREVIEW_TILE_W < a.g.dw ? dx0 + PREVIEW_TILE_W : a.g.dw) - 1;
+            long long y0, y1, x0, x1;
+            preview_footprint(a.g, dy0, dy1, dx0, dx1, &y0, &y1, &x0, &x1);
+            OverlayBand band[PREVIEW_MAX_PEOPLE];
+            int live[PREVIEW_MAX_PEOPLE * OVERLAY_NJ], nlive[PREVIEW_MAX_PEOPLE];
+            for (int p = 0; p < P; p++) {
+                const bool on = !drawn || drawn[p];
+                band[p] = overlay_band(on, on ? rects[4 * p] : 0, on ? rects[4 * p + 1] : 0, on ? rects[4 * p + 2] : 0, on ? rects[4 * p + 3] : 0);
+                if (!overlay_band_near(band[p], y0, y1, x0, x1)) band[p].on = 0;
+                nlive[p] = 0;
+                for (int i = 0; i < OVERLAY_NJ && on; i++)
+                    if (overlay_limb_near(L[p * OVERLAY_NJ + i], y0, y1, x0, x1)) live[p * OVERLAY_NJ + nlive[p]++] = i;
+            }
+            const PreviewPeople scene{P, L, live, nlive, band};
+            for (int tid = 0; tid < PREVIEW_THREADS; tid++) {
+                const int dy = dy0 + tid / PREVIEW_LANES_X, dx = dx0 + (tid % PREVIEW_LANES_X) * PREVIEW_LANE_PX;
+                if (dy > dy1 || dx > dx1) continue;
+                preview_lane_of(a, scene, dy, dx);
+            }
+        }
+    return 0;
+}
+
 }  // extern "C"
 
 #ifdef PREVIEW_SWEEP_MAIN

@@ -156,6 +156,79 @@ int pp_preview(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off,
     return PP_OK;
 }
 
+// The people form (launch_preview_people; tests/test_gpu_people_kernels.py): preview_capi.cpp's preview_walk_people's arguments, with
+// `status` (P ints, SQ_OK = 0: drawn) in the place of its `drawn`, then guards as in pp_preview.  Every person's joints, rect, status and
+// confidences lie in JointsOut / TrackOut / ConfOut structures in device memory, as the runtime's ring slots do.
+int pp_preview_people(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off, int format, int H, int W, int64_t sy, int64_t sx, int64_t sc,
+                      int64_t uv_stride, int orient, int P, const double* j2d, const double* conf, double min_conf, const int32_t* parents,
+                      const int32_t* rects, const int32_t* status, const int32_t* limb_bgr, const int32_t* rect_bgr, double factor, int out_format,
+                      uint8_t* out, int64_t out_size, int64_t out_off, int64_t out_pitch, uint8_t* guards)
+{
+    if (!src || !out || !guards || !j2d || !rects || !status || P < 1 || P > PREVIEW_MAX_PEOPLE) return PP_E_ARG;
+    if (!frame_ok(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, orient)) return PP_E_ARG;
+    PreviewArgs a;
+    OverlayInput in;
+    memset(&a, 0, sizeof a);
+    memset(&in, 0, sizeof in);
+    if (preview_geom(orient, H, W, factor, &a.g) != PREVIEW_OK) return PP_E_ARG;
+    if (out_off < 0 || out_size < 1 || (out_format != 0 && out_format != 1) || out_pitch < 3LL * a.g.dw || out_pitch > (1 << 24)) return PP_E_ARG;
+    if (out_off + (int64_t)(a.g.dh - 1) * out_pitch + 3LL * a.g.dw > out_size) return PP_E_ARG;
+    int lc[3], rc[3];
+    for (int k = 0; k < 3; k++) {
+        lc[k] = limb_bgr ? limb_bgr[k] : OVERLAY_LIMB_BGR[k], rc[k] = rect_bgr ? rect_bgr[k] : OVERLAY_RECT_BGR[k];
+        if (lc[k] < 0 || lc[k] > 255 || rc[k] < 0 || rc[k] > 255) return PP_E_ARG;
+    }
+    preview_colours(&a, lc, rc);
+    for (int i = 0; i < OVERLAY_NJ; i++) {
+        in.parents[i] = parents ? parents[i] : OVERLAY_PARENTS[i];
+        if (in.parents[i] < 0 || in.parents[i] >= OVERLAY_NJ) return PP_E_ARG;
+    }
+    if (conf) in.min_conf = min_conf, in.has_conf = min_conf == min_conf;
+    for (int p = 0; p < P; p++)
+        if (rects[4 * p + 2] < 1 || rects[4 * p + 3] < 1) return PP_E_ARG;
+    Dev D;
+    PP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    uint8_t *ds = nullptr, *dout = nullptr;
+    PP_HIP(D.alloc((void**)&ds, (size_t)src_size));
+    PP_HIP(hipMemcpyAsync(ds, src, (size_t)src_size, hipMemcpyHostToDevice, D.st));
+    PP_HIP(D.alloc((void**)&dout, (size_t)out_size + 2 * GUARD));
+    PP_HIP(hipMemsetAsync(dout, GUARD_FILL, (size_t)out_size + 2 * GUARD, D.st));
+    PP_HIP(hipMemcpyAsync(dout + GUARD, out, (size_t)out_size, hipMemcpyHostToDevice, D.st));
+    a.src = preview_source(format == 2, format == 1, ds + data_off, ds + uv_off, sy, sx, sc, uv_stride);
+    a.H = H, a.W = W, a.o = orient, a.has_joints = 1;
+    a.out = dout + GUARD + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
+    std::vector<JointsOut> hjo(P);
+    std::vector<TrackOut> hto(P);
+    std::vector<ConfOut> hco(P);
+    PreviewPeopleIn pin;
+    memset(&pin, 0, sizeof pin);
+    pin.P = P;
+    JointsOut* djo = nullptr;
+    TrackOut* dto = nullptr;
+    ConfOut* dco = nullptr;
+    PP_HIP(D.alloc((void**)&djo, P * sizeof(JointsOut)));
+    PP_HIP(D.alloc((void**)&dto, P * sizeof(TrackOut)));
+    PP_HIP(D.alloc((void**)&dco, P * sizeof(ConfOut)));
+    for (int p = 0; p < P; p++) {
+        memset(&hjo[p], 0, sizeof(JointsOut)), memset(&hto[p], 0, sizeof(TrackOut)), memset(&hco[p], 0, sizeof(ConfOut));
+        memcpy(hjo[p].j2d, j2d + p * OVERLAY_NJ * 2, sizeof hjo[p].j2d);
+        for (int k = 0; k < 4; k++) hto[p].rect[k] = rects[4 * p + k];
+        hto[p].status = status[p];
+        if (conf) memcpy(hco[p].conf, conf + p * OVERLAY_NJ, sizeof hco[p].conf);
+        pin.jo[p] = djo + p, pin.to[p] = dto + p, pin.co[p] = in.has_conf ? dco + p : nullptr;
+    }
+    PP_HIP(hipMemcpyAsync(djo, hjo.data(), P * sizeof(JointsOut), hipMemcpyHostToDevice, D.st));
+    PP_HIP(hipMemcpyAsync(dto, hto.data(), P * sizeof(TrackOut), hipMemcpyHostToDevice, D.st));
+    PP_HIP(hipMemcpyAsync(dco, hco.data(), P * sizeof(ConfOut), hipMemcpyHostToDevice, D.st));
+    PP_HIP(launch_preview_people(a, in, pin, D.st));
+    PP_HIP(hipMemcpyAsync(out, dout + GUARD, (size_t)out_size, hipMemcpyDeviceToHost, D.st));
+    PP_HIP(hipMemcpyAsync(guards, dout, GUARD, hipMemcpyDeviceToHost, D.st));
+    PP_HIP(hipMemcpyAsync(guards + GUARD, dout + GUARD + out_size, GUARD, hipMemcpyDeviceToHost, D.st));
+    PP_HIP(hipMemcpyAsync(src, ds, (size_t)src_size, hipMemcpyDeviceToHost, D.st));
+    PP_HIP(hipStreamSynchronize(D.st));
+    return PP_OK;
+}
+
 // The kernel's own duration (tools/preview_rate.py): n launches over an (H, W) frame the shim makes itself -- format 0: packed BGR,
 // 2: NV12 in one buffer -- under `orient` at `factor`, with a fan of limbs around the picture's centre and a rect a twentieth in from its
 // border, device events around each launch, ms_out[n].  out_hw: the output's size.

@@ -720,6 +720,7 @@ int vnect_set_stream_batch(vnect_handle* h, int n)
         if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: a pyramid-sharded handle serves one stream");
         if (n < 1 || n > 2) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: n must be 1 or 2");
         if (2 * h->Snet > VNECT_MAX_SCALES && n == 2) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: 2 x num_scales exceeds VNECT_MAX_SCALES");
+        if (h->people && n == 2) return fail(h, VNECT_E_ARG, "vnect_set_stream_batch: not together with vnect_set_people");
         h->stream_batch = n;
         return VNECT_OK;
     });
@@ -832,6 +833,92 @@ int vnect_track_policy(vnect_handle* h, int stream, double min_confidence, int m
         const TrackPolicy p{min_confidence, min_joints, action};
         HIPCK(h, hipMemcpy(h->d_policy + stream, &p, sizeof p, hipMemcpyHostToDevice));
         sm.policy = p;
+        return VNECT_OK;
+    });
+}
+
+// ---- people mode (ABI v7, additive; PEOPLE.md): several persons of one video, person p on stream p, one submit per frame -----------------
+int vnect_set_people(vnect_handle* h, int n, int pair)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (n < 1 || n > VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "vnect_set_people: n must be 1 .. VNECT_MAX_STREAMS");
+        if (pair != 0 && pair != 1) return fail(h, VNECT_E_ARG, "vnect_set_people: pair must be 0 or 1");
+        if (h->finalized || h->pre_only) return fail(h, VNECT_E_STATE, "vnect_set_people after vnect_finalize or on a preprocess_only handle");
+        if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_set_people: a pyramid-sharded handle serves one stream");
+        if (h->stream_batch == 2) return fail(h, VNECT_E_ARG, "vnect_set_people: not together with vnect_set_stream_batch(h, 2)");
+        h->people = n, h->people_pair = pair != 0;
+        return VNECT_OK;
+    });
+}
+
+// n within what vnect_set_people gave, on a finalized people handle
+static int people_ok(vnect_handle* h, const char* who, int n)
+{
+    if (!h->people) return fail(h, VNECT_E_STATE, std::string(who) + ": not a people handle (vnect_set_people before vnect_finalize)");
+    if (n < 1 || n > h->people) return fail(h, VNECT_E_ARG, std::string(who) + ": n must be 1 .. the n vnect_set_people was given");
+    if (!h->finalized) return fail(h, VNECT_E_STATE, std::string(who) + " before vnect_finalize");
+    return VNECT_OK;
+}
+
+int vnect_people_begin(vnect_handle* h, int n, int H, int W, const int32_t* rects)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = people_ok(h, "vnect_people_begin", n);
+        if (rc) return rc;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return people_begin_impl(h, n, H, W, rects);
+    });
+}
+
+int vnect_submit_people(vnect_handle* h, int n, int slot, double t2d, double t3d)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        int rc = people_ok(h, "vnect_submit_people", n);
+        if (rc) return rc;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        return enqueue_people(h, n, slot, t2d, t3d, FrameSrc());  // (a FrameSrc is born SRC_SLOT)
+    });
+}
+
+int vnect_submit_people_device(vnect_handle* h, int n, const vnect_device_frame* frame, void* producer_stream, double t2d, double t3d,
+                               const vnect_overlay_style* style, const vnect_preview_spec* preview_spec)
+{
+    return guarded(&h, [&]() -> int {
+        static const char* who = "vnect_submit_people_device";
+        if (!h) return VNECT_E_ARG;
+        int rc = people_ok(h, who, n);
+        if (rc) return rc;
+        for (int p = 0; p < n; p++)
+            if ((rc = tracked_ok(h, p))) return rc;
+        HIPCK(h, hipSetDevice(h->cfg.device));
+        const int orient = h->streams[0].orient;  // (enqueue_people refuses persons that began under another one)
+        FrameSrc s;
+        if (preview_spec) {  // the frame's one picture; the frame itself is drawn into only where a style is given too
+            vnect_preview_spec sp;
+            const bool sized = preview_spec->struct_size == (int32_t)sizeof(vnect_preview_spec);
+            if (sized) sp = *preview_spec, sp.draw_frame = style ? 1 : 0;
+            if ((rc = check_tracked_preview(h, who, frame, producer_stream, style, sized ? &sp : preview_spec, orient, &s))) return rc;
+        } else if (style) {
+            OverlayTarget t;
+            OverlayInput in;
+            if ((rc = check_draw(h, who, frame, producer_stream, style, orient, &t, &in, &s))) return rc;
+            s.draw = true, s.draw_target = t, s.draw_in = in;
+        } else if ((rc = check_device_frame(h, frame, producer_stream, who, false, orient, &s))) {
+            return rc;
+        }
+        return enqueue_people(h, n, -1, t2d, t3d, s);
+    });
+}
+
+int vnect_result_people(vnect_handle* h, int32_t* units_out, int32_t* paired_out)
+{
+    return guarded(&h, [&]() -> int {
+        if (!h) return VNECT_E_ARG;
+        if (!units_out || !paired_out) return fail(h, VNECT_E_ARG, "vnect_result_people: bad argument");
+        *units_out = h->last_people_units, *paired_out = h->last_people_paired;
         return VNECT_OK;
     });
 }

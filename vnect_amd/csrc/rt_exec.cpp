@@ -119,26 +119,34 @@ void deliver_confidence(vnect_handle* h, int ring, bool tracked)
     h->have_conf = true;
 }
 
+// a tracked frame outside the slots: the crop's rows (packed) into the stream's buffer, on `st` (which has waited for the frame's producer)
+static int copy_tracked_crop(vnect_handle* h, int stream, const FrameSrc& src, hipStream_t st)
+{
+    TrackState* ts = h->d_track + stream;
+    const Stream& sm = h->streams[stream];
+    if (src.orient && src.where != SRC_SLOT) {  // stored rotated / mirrored: the crop (oriented coordinates) through the oriented copy
+        HIPCK(h, launch_orient_copy_track(ts, orient_src_of(src), src.orient, src.H, src.W, sm.track_buf, st));
+        return VNECT_OK;
+    }
+    switch (src.where) {
+    case SRC_SLOT: break;
+    case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy_track(ts, src.bgr.data, sm.track_buf, sm.track_H, sm.track_W, src.bgr.stride, src.bgr.end, st)); break;
+    case SRC_NV12: HIPCK(h, launch_nv12_copy_track(ts, src.nv, sm.track_buf, sm.track_H, sm.track_W, st)); break;
+    case SRC_DEVICE: HIPCK(h, launch_ingest_copy_track(ts, src.ing, sm.track_buf, sm.track_H, sm.track_W, st)); break;
+    }
+    return VNECT_OK;
+}
+
 // gen_input_batch of a tracked frame on lane L: the crop the stream's state names (its rows first copied out of the frame when that
 // lies outside the slots), the pyramid from it, and on a stem_mode 2 lane the stem from the batch tensor (the host does not know whether
 // the crop's squarify step is a copy, which the stem's frame form needs; the results are the same bit for bit)
 static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn& dyn, const FrameSrc& src, bool timed)
 {
     TrackState* ts = h->d_track + stream;
-    const Stream& sm = h->streams[stream];
     // a frame outside the slots: this lane's stream waits for its producer, then copies the crop's rows (packed) into the stream's buffer
     int rc = wait_for_producer(h, src.producer, L->st);
     if (rc) return rc;
-    if (src.orient && src.where != SRC_SLOT) {  // stored rotated / mirrored: the crop (oriented coordinates) through the oriented copy
-        HIPCK(h, launch_orient_copy_track(ts, orient_src_of(src), src.orient, src.H, src.W, sm.track_buf, L->st));
-    } else {
-        switch (src.where) {
-        case SRC_SLOT: break;
-        case SRC_PINNED_BGR: HIPCK(h, launch_frame_copy_track(ts, src.bgr.data, sm.track_buf, sm.track_H, sm.track_W, src.bgr.stride, src.bgr.end, L->st)); break;
-        case SRC_NV12: HIPCK(h, launch_nv12_copy_track(ts, src.nv, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
-        case SRC_DEVICE: HIPCK(h, launch_ingest_copy_track(ts, src.ing, sm.track_buf, sm.track_H, sm.track_W, L->st)); break;
-        }
-    }
+    if ((rc = copy_tracked_crop(h, stream, src, L->st))) return rc;
     HIPCK(h, launch_pyramid_track(ts, dyn, src.where != SRC_SLOT, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
     if (L->stem_mode == 2) {
         StemArgs a = stamped(L, L->stem, L->l_conv1, timed);
@@ -295,7 +303,8 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     Stream& sm = h->streams[stream];
     if (tk && from_slot && (h->slots[slot].H != sm.track_H || h->slots[slot].W != sm.track_W))
         return fail(h, VNECT_E_ARG, "the slot's frame is not of the size vnect_track_begin gave for this stream");
-    if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
+    if (!(tk && tk->people_unit) && units_in_flight(h) >= max_in_flight(h))  // (a people frame's units were counted together: enqueue_people)
+        return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
     if (h->sharded && !comm_ready(h))  // refuse before any filter / timestamp state changes
         return fail(h, VNECT_E_STATE, "pyramid-sharded handle: call vnect_comm_init / vnect_comm_p2p_init before inference");
     FrameParams fp;
@@ -598,6 +607,9 @@ int prime(vnect_handle* h)
         }
         for (int d = 0; d < 2 * depth && !rc; d++) rc = collect_impl(h, nullptr, nullptr);
     }
+    // (People mode's pair plans -- pplans -- are NOT warmed here: a paired unit needs tracking streams and their crop buffers, which begin on
+    // a finalized handle.  Their graphs are built and their arenas allocated; the first paired frames of a handle pay the cold caches,
+    // PEOPLE.md says so.)
     // A fresh handle's state comes back UNCONDITIONALLY: whatever is still in flight is drained and dropped, the slot is emptied, the
     // filter banks are rebuilt.  What the failure means for vnect_finalize depends on its kind (advisor, round 4):
     //  * VNECT_E_HIP / VNECT_E_INTERNAL / VNECT_E_COMM -- a launch was refused or the device faulted on the launch plan this handle
@@ -713,22 +725,31 @@ int forward_batch(vnect_handle* h, const float* batch, float* out)
 
 // ---- tracking on the device (vnect_track_begin) --------------------------------------------------------------------------------------
 // The stream's first crop and its geometry, built here with crop.h (what the box kernel runs on the device for every later frame).
-int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4)
+// what vnect_track_begin refuses, before anything changes; r: the stream's first rect behind the loop's fallback
+static int track_begin_check(vnect_handle* h, int stream, int H, int W, const int32_t* rect4, int r[4])
 {
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
     if (h->sharded) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a pyramid-sharded handle is not supported");
     if (!h->bplans.empty()) return fail(h, VNECT_E_ARG, "vnect_track_begin: tracking on a handle with the two-stream batch is not supported");
     if (H < 1 || W < 1 || H > 65532 || (size_t)H * W * 3 > (size_t)h->cfg.max_frame_bytes)
         return fail(h, VNECT_E_ARG, "vnect_track_begin: frame size out of range (1 .. 65532 rows, at most max_frame_bytes)");
-    Stream& sm = h->streams[stream];
-    if (sm.seq >= (long long)h->seq_collect) return fail(h, VNECT_E_STATE, "vnect_track_begin: frames of this stream in flight");
-    int r[4] = {0, 0, W, H};
+    if (h->streams[stream].seq >= (long long)h->seq_collect) return fail(h, VNECT_E_STATE, "vnect_track_begin: frames of this stream in flight");
+    r[0] = 0, r[1] = 0, r[2] = W, r[3] = H;
     if (rect4) {
         for (int k = 0; k < 4; k++) r[k] = rect4[k];
         box_fallback(W, H, r);  // runner.track applies its fallback to the initial rect as well
         if (r[0] < 0 || r[1] < 0 || r[0] >= W || r[1] >= H)
             return fail(h, VNECT_E_ARG, "vnect_track_begin: the rect's origin must lie inside the frame");
     }
+    return VNECT_OK;
+}
+
+int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4)
+{
+    int r[4];
+    int rc0 = track_begin_check(h, stream, H, W, rect4, r);
+    if (rc0) return rc0;
+    Stream& sm = h->streams[stream];
     // a rect past the frame's far edges crops what numpy slicing crops (frame[y:y + h, x:x + w]) and is reported as given
     std::vector<TrackState> ts(1);
     memset(&ts[0], 0, sizeof(TrackState));
@@ -757,6 +778,158 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
     HIPCK(h, hipMemcpyAsync(h->d_track + stream, &t, sizeof(TrackState), hipMemcpyHostToDevice, h->st));
     HIPCK(h, hipStreamSynchronize(h->st));
     sm.track_on = true, sm.track_stopped = false, sm.track_H = H, sm.track_W = W, sm.track_seq = 1, sm.orient = h->orient;
+    return VNECT_OK;
+}
+
+// ---- people mode (vnect_set_people; PEOPLE.md): P persons of ONE video, person p on stream p, one submit per frame -------------------------
+// No reference counterpart: hog_box.py:26-31 keeps the biggest rectangle and run_estimator_ps.py:80-109 follows that one person.  Each person's
+// loop is that loop, on the device as for any tracked stream; what is new is that the persons of a frame go out together, two of them through
+// ONE conv stack where the handle has the pair plan, and that the frame is drawn into only after every person's pyramid has read it.
+int people_begin_impl(vnect_handle* h, int n, int H, int W, const int32_t* rects)
+{
+    int r[4], rc;
+    for (int p = 0; p < n; p++)  // all or nothing: every stream's refusals first
+        if ((rc = track_begin_check(h, p, H, W, rects ? rects + 4 * p : nullptr, r))) return rc;
+    for (int p = 0; p < n; p++)
+        if ((rc = track_begin_impl(h, p, H, W, rects ? rects + 4 * p : nullptr))) return rc;  // (only a HIP error can still stop it)
+    return VNECT_OK;
+}
+
+// A paired unit: persons s0 and s0 + 1 of one frame on one lane's pair plan -- both crops' pyramids in one launch, the conv stack once for
+// 2 S images, then each person's post-processing + box stage on its own half of the maps, with its own filter bank, state, rule and ring
+// slot.  The caller (enqueue_people) has checked everything that can refuse.
+// The pair plan is post_merged like every batched plan, and the box stage is always the tail of post_kernel (launch_post_track): the A/B
+// switches of a single tracked frame -- VNECT_TRACK_BOX_LAUNCH, VNECT_NO_POST_MERGE -- and the test build's vnect_test_maps_override do NOT
+// apply to paired units (single units of a people frame go through enqueue_frame and honour them).
+static int enqueue_pair(vnect_handle* h, int s0, int slot, double t2d, double t3d, const FrameSrc& src)
+{
+    const bool from_slot = src.where == SRC_SLOT;
+    const bool timed = h->profiling;
+    Plan* L = pick_lane(h, timed);
+    Plan* b = h->pplans[std::find(h->lanes.begin(), h->lanes.end(), L) - h->lanes.begin()];
+    FrameDyn dyn[2] = {};
+    int rc;
+    for (int k = 0; k < 2; k++) {
+        const Stream& sm = h->streams[s0 + k];
+        // a person's crop is its previous frame's box stage's output: everything of the unit waits for both persons' previous frames
+        if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
+        dyn[k].t2d = t2d, dyn[k].t3d = t3d;
+        if (from_slot) dyn[k].row_stride = h->slots[slot].stride, dyn[k].frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+        else dyn[k].frame = sm.track_buf;
+        dyn[k].xfail = &h->d_track[s0 + k].fail, dyn[k].xseq = sm.track_seq;
+    }
+    if ((rc = wait_for_producer(h, src.producer, L->st))) return rc;
+    for (int k = 0; k < 2; k++)
+        if ((rc = copy_tracked_crop(h, s0 + k, src, L->st))) return rc;
+    HIPCK(h, launch_pyramid_track_pair(h->d_track + s0, dyn[0], dyn[1], !from_slot, h->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
+    if (b->stem_mode == 2) {  // from the batch tensor: the host does not know whether a crop's squarify step is a copy
+        StemArgs a = stamped(b, b->stem, b->l_conv1, timed);
+        a.from_frame = 0;
+        HIPCK(h, launch_stem(a, b->st));
+    }
+    if (replays(h, b) && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
+    else if ((rc = run_frame_kernels(b, timed))) return rc;
+    const size_t half = (size_t)b->S * HM * HM * MAPC;
+    const float* maps = b->tensors[b->t_out].d;
+    for (int k = 0; k < 2; k++) {
+        const int s = s0 + k, ring = (int)((h->seq_submit + k) % RING);
+        const Stream& sm = h->streams[s];
+        const InFlight& e = h->ring[ring];
+        HIPCK(h, launch_post_track(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + s, h->d_track + s, dyn[k], h->cfg.numpy_promotion, e.out_dev,
+                                   h->h_tout_dev + ring, b->st, h->h_conf_dev + ring, h->d_policy + s, nullptr));
+        if (sm.v3_on) {
+            View3dArgs a = sm.v3;
+            a.out = h->v3_dev[ring], a.pitch = 3LL * a.cols;
+            HIPCK(h, launch_view3d(a, nullptr, nullptr, e.out_dev, a.has_conf ? h->h_conf_dev + ring : nullptr, b->st));
+            HIPCK(h, hipMemcpyAsync(h->v3_host[ring], h->v3_dev[ring], 3 * (size_t)a.cols * a.rows, hipMemcpyDeviceToHost, b->st));
+        }
+        HIPCK(h, hipEventRecord(e.done, b->st));
+    }
+    for (int k = 0; k < 2; k++) {  // every launch of the unit has been accepted: commit
+        Stream& sm = h->streams[s0 + k];
+        InFlight& e = h->ring[h->seq_submit % RING];
+        e.stream = s0 + k, e.unit = h->unit_submit, e.batch = true, e.prof = (timed && k == 1) ? b : nullptr, e.tracked = true;
+        e.pv_h = e.pv_w = 0;
+        e.v3_h = sm.v3_on ? sm.v3.rows : 0, e.v3_w = sm.v3_on ? sm.v3.cols : 0;
+        e.redetect = false;
+        e.before = sm.t;
+        commit_time(sm, t2d, t3d);
+        sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
+        sm.track_seq++;
+        if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
+        h->seq_submit++;
+    }
+    h->unit_submit++;
+    return VNECT_OK;
+}
+
+int enqueue_people(vnect_handle* h, int n, int slot, double t2d, double t3d, const FrameSrc& src)
+{
+    const bool from_slot = src.where == SRC_SLOT;
+    int rc;
+    if (from_slot && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0)) return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+    // atomic: every refusal of every person before anything changes
+    for (int p = 0; p < n; p++) {
+        const Stream& sm = h->streams[p];
+        if (!sm.track_on) return fail(h, VNECT_E_STATE, "person " + std::to_string(p) + " is not tracking: call vnect_people_begin first");
+        if (sm.track_stopped)
+            return fail(h, VNECT_E_STATE, "tracking of person " + std::to_string(p) + " stopped at a refused crop: call vnect_people_begin");
+        const int fH = from_slot ? h->slots[slot].H : (src.orient & 1) ? src.W : src.H, fW = from_slot ? h->slots[slot].W : (src.orient & 1) ? src.H : src.W;
+        if (fH != sm.track_H || fW != sm.track_W || (!from_slot && sm.orient != src.orient))
+            return fail(h, VNECT_E_ARG, "the frame is not of the size (and orientation) vnect_people_begin gave for person " + std::to_string(p));
+        if ((rc = check_time(h, sm, t2d, t3d))) return rc;
+    }
+    const bool pair = !h->pplans.empty();
+    const int units = pair ? (n + 1) / 2 : n;
+    // (one people frame is always accepted when nothing is in flight: four persons run singly are four units, on any handle)
+    if (units_in_flight(h) && units_in_flight(h) + (unsigned long long)units > max_in_flight(h))
+        return fail(h, VNECT_E_STATE, "too many frames in flight for this people frame's units: collect first");
+    if (h->seq_submit - h->seq_collect + (unsigned long long)n > (unsigned long long)RING)
+        return fail(h, VNECT_E_STATE, "too many results in flight for this people frame: collect first");
+    const unsigned long long seq0 = h->seq_submit;
+    FrameSrc one = src;  // a single unit is the tracked frame as it is today, but for drawing: that waits for every person's pyramid
+    one.draw = one.preview = false, one.people_unit = true;
+    int paired = 0;
+    for (int p = 0; p < n;) {
+        if (pair && p + 1 < n) {
+            if ((rc = enqueue_pair(h, p, slot, t2d, t3d, src))) return rc;
+            p += 2, paired++;
+        } else {
+            int ring;
+            if ((rc = enqueue_frame(h, slot, t2d, t3d, &ring, p, &one))) return rc;
+            p += 1;
+        }
+    }
+    h->last_people_units = pair ? units : n, h->last_people_paired = paired;
+    if (!src.draw && !src.preview) return VNECT_OK;
+    // run_estimator_ps.py:92-94 once per person, in person order, behind EVERY unit's joints: nothing writes the frame before every
+    // person's pyramid (or crop copy) has read it.  The last person's `done` is recorded again behind the drawing, so the frame is the
+    // caller's again when that person has been collected.
+    Plan* last = h->streams[n - 1].lane;
+    for (int p = 0; p + 1 < n; p++)
+        if (h->streams[p].lane != last) HIPCK(h, hipStreamWaitEvent(last->st, h->ring[(seq0 + p) % RING].done, 0));
+    // run_estimator_ps.py:94-96 for everybody at once: the ONE picture of the frame (preview.h: PreviewPeople), first, so that it reads the
+    // clean frame; it belongs to the LAST person's delivery (vnect_result_preview)
+    if (src.preview) {
+        const int ring = (int)((seq0 + n - 1) % RING);
+        PreviewArgs a = src.pv;
+        a.out = h->pv_dev[ring], a.pitch = 3LL * a.g.dw;
+        PreviewPeopleIn pin{};
+        pin.P = n;
+        for (int p = 0; p < n; p++) {
+            const int rp = (int)((seq0 + p) % RING);
+            pin.jo[p] = h->ring[rp].out_dev, pin.to[p] = h->h_tout_dev + rp, pin.co[p] = src.pv_in.has_conf ? h->h_conf_dev + rp : nullptr;
+        }
+        HIPCK(h, launch_preview_people(a, src.pv_in, pin, last->st));
+        HIPCK(h, hipMemcpyAsync(h->pv_host[ring], h->pv_dev[ring], 3 * (size_t)a.g.dw * a.g.dh, hipMemcpyDeviceToHost, last->st));
+        h->ring[ring].pv_h = a.g.dh, h->ring[ring].pv_w = a.g.dw;
+    }
+    for (int p = 0; src.draw && p < n; p++) {
+        const int ring = (int)((seq0 + p) % RING);
+        HIPCK(h, launch_overlay(src.draw_target, src.draw_in, h->ring[ring].out_dev, h->h_tout_dev + ring, src.draw_in.has_conf ? h->h_conf_dev + ring : nullptr,
+                                last->st));
+    }
+    HIPCK(h, hipEventRecord(h->ring[(seq0 + n - 1) % RING].done, last->st));
     return VNECT_OK;
 }
 

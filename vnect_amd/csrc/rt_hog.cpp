@@ -233,6 +233,9 @@ int track_redetect_impl(vnect_handle* h, int stream, const vnect_hog_spec* spec,
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return refuse(h, who, "stream out of range");
     if (h->sharded) return refuse(h, who, "tracking on a pyramid-sharded handle is not supported");
     if (h->stream_batch == 2 || !h->bplans.empty()) return refuse(h, who, "tracking on a handle with the two-stream batch is not supported");
+    // the pick takes the LARGEST detection, which would hand a lost person the other person (PEOPLE.md: a pick that excludes the others' boxes
+    // is not built)
+    if (h->people && enable) return refuse(h, who, "re-detection on a people handle (vnect_set_people) is not supported");
     if (!h->finalized) return fail(h, VNECT_E_STATE, std::string(who) + " before vnect_finalize");
     Stream& sm = h->streams[stream];
     HogSpec sp{};

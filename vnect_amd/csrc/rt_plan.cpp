@@ -814,10 +814,11 @@ int finalize_impl(vnect_handle* h)
 // build_plan makes either kind of further plan from lane 0's: a lane (lane 0's plan as it is, on a stream of its own) or, `batch`, the
 // batched plan that runs on `lane`'s stream.  Same layers and weights; its own activation arena, split-K workspace, arg-max scratch,
 // geometry block(s) and graph.
-static int build_plan(vnect_handle* h, bool batch, Plan* lane = nullptr)
+// (`pair`: a batched plan kept in pplans -- people mode's plan of two persons of one video)
+static int build_plan(vnect_handle* h, bool batch, Plan* lane = nullptr, bool pair = false)
 {
     Plan* p = new Plan();
-    (batch ? h->bplans : h->lanes).push_back(p);
+    (pair ? h->pplans : batch ? h->bplans : h->lanes).push_back(p);
     p->owner = h, p->S = h->S, p->Snet = batch ? 2 * h->Snet : h->Snet, p->bf16 = h->bf16, p->f16 = h->f16, p->two_frames = batch;
     p->owns_stream = !batch;
     if (batch) p->st = lane->st;
@@ -864,9 +865,12 @@ int build_plans(vnect_handle* h)
     int rc = VNECT_OK;
     if (h->cfg.lanes >= 2 && !h->sharded && !h->keep_activations)
         for (int i = 1; i < h->cfg.lanes && !rc; i++) rc = build_plan(h, false);
-    if (rc || h->stream_batch < 2) return rc;
+    // people mode with pairing (vnect_set_people): the same batched plan per lane, for two persons' crops of one frame; a pyramid
+    // of more than VNECT_MAX_SCALES / 2 scales has none, and its people run singly
+    const bool pairs = h->people >= 2 && h->people_pair && 2 * h->Snet <= VNECT_MAX_SCALES;
+    if (rc || (h->stream_batch < 2 && !pairs)) return rc;
     if (h->layers.size() > 128) return fail(h, VNECT_E_STATE, "internal: more layers than the profiling buffers hold");
-    for (size_t i = 0; i < h->lanes.size() && !rc; i++) rc = build_plan(h, true, h->lanes[i]);
+    for (size_t i = 0; i < h->lanes.size() && !rc; i++) rc = build_plan(h, true, h->lanes[i], pairs);
     return rc;
 }
 
@@ -891,6 +895,8 @@ void destroy_plans(vnect_handle* h)
 {
     for (Plan* b : h->bplans) destroy_plan(b);
     h->bplans.clear();
+    for (Plan* b : h->pplans) destroy_plan(b);
+    h->pplans.clear();
     for (size_t i = 1; i < h->lanes.size(); i++) destroy_plan(h->lanes[i]);
     h->lanes.resize(1);
 }

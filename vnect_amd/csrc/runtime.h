@@ -207,6 +207,12 @@ struct vnect_handle : Plan {
                                 // joints kernel (the filters are a chain)
     int stream_batch = 1;
     std::vector<Plan*> bplans;  // two video streams per launch: the batched plan once per lane, bplans[i] on lanes[i]'s stream
+    // people mode (vnect_set_people; PEOPLE.md): persons 0 .. people-1 of ONE video are streams 0 .. people-1, submitted together
+    int people = 0;             // 0: off
+    bool people_pair = false;   // finalize builds pplans when people >= 2 and 2 S images fit a batch
+    std::vector<Plan*> pplans;  // the (2 S)-image plan of a PAIR of persons once per lane, pplans[i] on lanes[i]'s stream (a batched plan
+                                // under another name: a handle with bplans refuses tracking, a people handle is made for it)
+    int last_people_units = 0, last_people_paired = 0;  // vnect_result_people: of the people frame submitted last
     // pre/post
     uint8_t* frames = nullptr;  // num_frame_slots * max_frame_bytes
     // A host frame's way to a slot: pinned (page-locked) buffers.  [0], [1] are the caller's capture buffers (vnect_frame_buffer; they
@@ -383,7 +389,7 @@ int build_up_table(vnect_handle* h);
 int squarify_params(vnect_handle* h, int H, int W, FrameParams* fp);
 int add_tensor(vnect_handle* h, const std::string& name, int S, int H, int W, int C, int Cs, bool force_f32 = false);
 int finalize_impl(vnect_handle* h);
-int build_plans(vnect_handle* h);   // lanes 1 .. cfg.lanes - 1 and the batched plans
+int build_plans(vnect_handle* h);   // lanes 1 .. cfg.lanes - 1, the batched plans and people mode's pair plans
 void destroy_plan(Plan* p);         // every plan's teardown, lane 0's (the handle's) included
 void destroy_plans(vnect_handle* h);  // all but lane 0
 bool plan_writes(const Plan* p, int tensor);  // does a launch of the plan (or the pre-processing) write this tensor?
@@ -425,6 +431,7 @@ struct FrameSrc {
     Nv12Src nv{};             // SRC_NV12,
     IngestSrc ing{};          // SRC_DEVICE
     void* producer = VNECT_STREAM_SYNCED;  // a device frame's producer stream as the caller gave it; every host source is synced
+    bool people_unit = false;  // a single unit of a people frame (enqueue_people has checked the in-flight limit for all of the frame's units)
     // a tracked device frame that is also drawn into (vnect_submit_tracked_device_draw): one overlay launch behind its box stage
     bool draw = false;
     OverlayTarget draw_target{};
@@ -439,6 +446,11 @@ struct FrameSrc {
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const FrameSrc* tk = nullptr);
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
 int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* rect4);
+// people mode: vnect_track_begin for streams 0 .. n-1 (rects: 4 n values or nullptr), all or nothing
+int people_begin_impl(vnect_handle* h, int n, int H, int W, const int32_t* rects);
+// the next frame of persons 0 .. n-1 -- in `slot`, or (slot -1) where src says -- as ceil(n / 2) lane units; atomic.  src.draw: the P overlay
+// launches behind every unit's joints, in person order
+int enqueue_people(vnect_handle* h, int n, int slot, double t2d, double t3d, const FrameSrc& src);
 int prime(vnect_handle* h);
 int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots, const double* t2d, const double* t3d);
 int forward_batch(vnect_handle* h, const float* batch, float* out);

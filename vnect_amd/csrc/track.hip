@@ -41,6 +41,39 @@ hipError_t launch_pyramid_track(const TrackState* ts, FrameDyn dyn, int packed, 
     return hipGetLastError();
 }
 
+// pyramid_track_kernel for TWO tracked streams whose states lie side by side (people mode: persons 2 u and 2 u + 1 of one video), into the
+// batched plan's (2 S)-image input tensor: image i is scale i % S of person i / S, cropped with ts[i / S] out of that person's frame
+// argument.  Per pixel it is pyramid_track_kernel's code, so each half holds the bytes a launch of that kernel for its person writes.
+template <typename T>
+__global__ void pyramid_track_pair_kernel(const TrackState* __restrict__ ts2, const FrameDyn dyn0, const FrameDyn dyn1, int packed,
+                                          const ScaleTabs* __restrict__ tabs, int S, T* __restrict__ batch4)
+{
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, i = blockIdx.z;
+    if (x >= BOX) return;
+    const int k = i >= S ? 1 : 0, s = i - k * S;  // (uniform over the workgroup)
+    const TrackState* ts = ts2 + k;
+    FrameDyn d = k ? dyn1 : dyn0;
+    if (packed) d.row_stride = 3LL * ts->w;
+    else d.frame = d.frame + (long long)ts->y * d.row_stride + 3LL * ts->x;
+    int v[3];
+    pyramid_pixel(&ts->fp, d, tabs, s, y, x, v);
+    f32x4t o = {tabs->lut[v[0]], tabs->lut[v[1]], tabs->lut[v[2]], 0.f};
+    store_wt((tx4*)(batch4 + (((long long)i * BOX + y) * BOX + x) * 4), __builtin_convertvector(o, tx4));
+}
+
+hipError_t launch_pyramid_track_pair(const TrackState* ts2, FrameDyn dyn0, FrameDyn dyn1, int packed, const ScaleTabs* tabs, void* batch4, int S, int el,
+                                     hipStream_t st)
+{
+    if (S < 1 || 2 * S > VNECT_MAX_IMAGES) return hipErrorInvalidValue;
+    dim3 g((BOX + 127) / 128, BOX, 2 * S);
+    with_el(el, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pyramid_track_pair_kernel<T>, g, dim3(128), 0, st, ts2, dyn0, dyn1, packed, tabs, S, (T*)batch4);
+    });
+    return hipGetLastError();
+}
+
 // The box stage as its own launch, behind post_kernel (or joints_kernel): the joints come back from the result ring slot.  One workgroup, one
 // thread per table entry.  A frame whose own crop was refused (its joints stage skipped, post_kernel's xfail test) keeps the stream
 // stopped: the next frame is refused too, until vnect_track_begin.

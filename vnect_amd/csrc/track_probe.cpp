@@ -313,4 +313,65 @@ int tp_pyramid(const uint8_t* frame, int H, int W, int64_t stride, int n, const 
     return 0;
 }
 
+// The pair pyramid (launch_pyramid_track_pair; tests/test_gpu_people_kernels.py) of n PAIRS of states over ONE (H, W, 3) frame: states holds
+// 2 n of them, pair i is states 2 i and 2 i + 1, side by side in device memory as the runtime's streams are.  packed[i] = 0: both persons
+// read their crop at (x, y) of the whole frame; 1: each from a buffer of its own packed rows.  2 S <= 8.  out: n x (2 S, 368, 368, 4)
+// elements, every byte pre-filled with `fill` (a pixel the kernel does not write, or writes at another image's offset, keeps or misplaces
+// it).  err (2 n): per state.
+int tp_pyramid_pair(const uint8_t* frame, int H, int W, int64_t stride, int n, const uint8_t* states, const int32_t* packed, const double* scales, int S,
+                    int el, int fill, void* out, int32_t* err)
+{
+    if (n < 1) return 0;
+    if (S < 1 || 2 * S > 8 || el < EL_F32 || el > EL_F16) return -1;
+    std::vector<ScaleTabs> tabs(1);
+    memset(&tabs[0], 0, sizeof(ScaleTabs));
+    tabs[0].S = S;
+    plan::fill_lut(tabs[0].lut);
+    for (int i = 0; i < S; i++)
+        if (plan::build_scale_tab(scales[i], &tabs[0], i)) return -1;
+    const long long used = H > 0 ? (long long)(H - 1) * stride + 3LL * W : 0;
+    const int fe = check_frame(H, W, stride, used);
+    int bad = 0;
+    std::vector<TrackState> hs(2 * n);
+    std::vector<size_t> off(2 * n + 1, 0);
+    for (int i = 0; i < 2 * n; i++) {
+        memcpy(&hs[i], states + (size_t)i * sizeof(TrackState), sizeof(TrackState));
+        err[i] = fe ? fe : check_frame_state(hs[i], H, W);
+        if (!err[i] && (hs[i].uw != hs[i].w || hs[i].uh != hs[i].h)) err[i] = TP_E_STATE;
+        bad += err[i] != TP_OK;
+        off[i + 1] = off[i] + (err[i] || !packed[i / 2] ? 0 : ((3 * (size_t)hs[i].w * hs[i].h + 255) & ~(size_t)255));
+    }
+    if (bad) return bad;
+    std::vector<uint8_t> pk(off[2 * n] ? off[2 * n] : 1, 0);
+    for (size_t k = 0; k < pk.size(); k++) pk[k] = (uint8_t)(k * 2654435761u >> 24);
+    for (int i = 0; i < 2 * n; i++)
+        if (packed[i / 2])
+            for (int r = 0; r < hs[i].h; r++)
+                memcpy(&pk[off[i] + (size_t)r * 3 * hs[i].w], frame + (size_t)(hs[i].y + r) * stride + (size_t)3 * hs[i].x, (size_t)3 * hs[i].w);
+    Dev D;
+    TP_HIP(hipStreamCreate(&D.st));
+    uint8_t *dframe = nullptr, *dpk = nullptr, *dout = nullptr;
+    TrackState* ds = nullptr;
+    ScaleTabs* dt = nullptr;
+    const size_t per = (size_t)2 * S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
+    TP_HIP(D.alloc((void**)&dframe, (size_t)used));
+    TP_HIP(D.alloc((void**)&dpk, pk.size()));
+    TP_HIP(D.alloc((void**)&ds, (size_t)2 * n * sizeof(TrackState)));
+    TP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    TP_HIP(D.alloc((void**)&dout, (size_t)n * per));
+    TP_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)2 * n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    TP_HIP(hipMemsetAsync(dout, fill & 0xFF, (size_t)n * per, D.st));
+    for (int i = 0; i < n; i++) {
+        FrameDyn dyn[2] = {};
+        for (int k = 0; k < 2; k++) dyn[k].frame = packed[i] ? dpk + off[2 * i + k] : dframe, dyn[k].row_stride = stride;
+        TP_HIP(launch_pyramid_track_pair(&ds[2 * i], dyn[0], dyn[1], packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
+    }
+    TP_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
+    TP_HIP(hipStreamSynchronize(D.st));
+    return 0;
+}
+
 }  // extern "C"

@@ -28,7 +28,8 @@ class VNectEstimator:
     joint_parents = [16, 15, 1, 2, 3, 1, 5, 6, 14, 8, 9, 14, 11, 12, 14, 14, 1, 4, 7, 10, 13]
 
     def __init__(self, scales=None, weights=None, seed=MASTER_SEED, device=0, precision="fp32", paper_res2c=False,
-                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1, orientation=0, hog_detector=None):
+                 use_graph="auto", numpy_promotion="legacy", verbose=True, lanes=1, orientation=0, hog_detector=None,
+                 people=0, pair_people=False):
         if verbose:
             print('Initializing VNect Estimator...')
         # src/estimator.py:32; "for faster loops, use less scales e.g. [1], [1, 0.7]"
@@ -43,6 +44,11 @@ class VNectEstimator:
         self._cfg = dict(device=device, precision=PRECISIONS[precision],
                          paper_res2c=paper_res2c, use_graph=use_graph,
                          numpy_promotion={"legacy": 0, "nep50": 1}[numpy_promotion], lanes=lanes)
+        # people mode (additive; PEOPLE.md): ``people=P`` (1 .. 4) -- runner.track_people_on_device follows P persons of one video,
+        # person p on stream p; ``pair_people``: two persons' crops share one conv stack where the scale list allows (2 S <= 8)
+        self.people = int(people)
+        if self.people:
+            self._cfg.update(people=self.people, pair=bool(pair_people))
         self._submitted = 0
         self._weights = weights
         self._orientation = self._check_orientation(orientation)

@@ -476,6 +476,178 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                         pass
 
 
+def people_boxes(estimator, frame, people, pixel_format="bgr", orientation=None, stream=None, **spec):
+    """The first boxes of ``people`` persons in one frame (PEOPLE.md; the reference keeps one: src/hog_box.py:26-31).  The detections of
+    ``estimator.detect_people`` ordered by area, largest first, equal areas by (y, x); the first ``people`` of them through ``cal_rect``;
+    missing ones are the whole frame.  Host-only and deterministic.  Returns ``people`` rects [x, y, w, h] in the oriented picture's
+    coordinates."""
+    from . import _native
+    rects, _ = estimator.detect_people(frame, pixel_format=pixel_format, orientation=orientation, stream=stream, **spec)
+    if _native.is_device_array(frame):
+        f = _native.device_frame(frame, pixel_format)
+        H, W = int(f.H), int(f.W)
+    else:
+        H, W = frame.shape[:2]
+        if pixel_format == "nv12":
+            H = H * 2 // 3
+    if (estimator.orientation if orientation is None else orientation) & 1:
+        H, W = W, H
+    found = sorted(([int(v) for v in r] for r in rects), key=lambda r: (-r[2] * r[3], r[1], r[0]))
+    boxes = [cal_rect(r, H, W) for r in found[:int(people)]]
+    return boxes + [[0, 0, W, H] for _ in range(int(people) - len(boxes))]
+
+
+def track_people_on_device(estimator, frames, rects, timestamps=None, ahead=1, source="device", pixel_format="bgr", confidence=False,
+                           lost=None, draw=False, orientation=None, preview=False, view3d=False):
+    """P persons of ONE video tracked on a people estimator (``VNectEstimator(people=P)``; PEOPLE.md): person p is stream p and starts at
+    ``rects[p]`` (``people_boxes`` chooses them; None: the whole frame).  Every frame is submitted ONCE for everybody
+    (vnect_submit_people*); two persons' crops share a conv stack where the estimator pairs.  Yields one tuple per frame: a list of P
+    ``(joints_2d, joints_3d, rect_used[, confidence, lost][, view])`` -- each person's sequence is what ``track`` yields for that person
+    alone on an estimator of its own, bit for bit.  ``source``: "device" (arrays in device memory, read where they lie and held until the
+    frame has been collected) or "resident" (host arrays, uploaded whole); pinned sources are not supported.
+    ``timestamps``, ``pixel_format``, ``confidence``, ``lost``, ``orientation``, ``view3d``: as in ``track_on_device``, for every person.
+    ``draw`` (``source="device"`` only): every person's skeleton and rect are drawn into the frame, in person order, only after every
+    person's crop has been read from the clean frame: the results are those of ``draw=False``.
+    ``preview`` (``source="device"`` only; True, a factor or an ``_native.preview_spec(...)``): every yielded tuple gets the frame's ONE
+    display picture appended -- the clean frame annotated with every person in person order (``render.draw_limbs_2d_exact`` P times), then
+    scaled (``render.resize_u8_exact``) -- computed on the device; the frame is written only if ``draw`` is given too.
+    ``ahead``: frames submitted before the oldest is collected, clipped to what the unit limit (``max(lanes, 2)`` units in flight, a frame
+    is ceil(P / 2) units paired, P unpaired) and the result ring (8) allow.  However the loop ends, nothing stays in flight."""
+    from collections import deque
+
+    from . import _native
+    h = estimator.handle
+    P = len(rects)
+    if not 1 <= P <= int(getattr(h, "people", 0)):
+        raise ValueError("rects must hold 1 .. people rects: make the estimator with VNectEstimator(people=P)")
+    if source not in ("device", "resident"):
+        raise ValueError("source must be 'device' or 'resident' (pinned sources are not supported in people mode)")
+    device = source == "device"
+    style = None
+    if draw is not False and draw is not None:
+        if not device:
+            raise ValueError("draw= annotates frames in device memory: it needs source='device'")
+        style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
+    spec = None
+    if preview is not False and preview is not None:
+        if not device:
+            raise ValueError("preview= scales frames in device memory: it needs source='device'")
+        if isinstance(preview, _native.PreviewSpec):
+            spec = _native.preview_spec(preview.factor, "rgb" if preview.out_format == _native.PIX_RGB else "bgr", style is not None)
+        else:
+            spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
+    vspec = None
+    if view3d is not False and view3d is not None:
+        vspec = view3d if isinstance(view3d, _native.View3dSpec) else _native.view3d_spec(parents=estimator.joint_parents)
+    nv12 = _nv12_checks(pixel_format, False, source)
+    code = _orientations(estimator, orientation, 1, False)[0]
+    rule = lost_rule(lost)
+    lanes = max(int(estimator._cfg.get("lanes", 1)), 1)
+    paired = bool(getattr(h, "pair_people", False)) and P >= 2 and 2 * len(estimator.scales) <= 8
+    units = (P + 1) // 2 if paired else P
+    window = max(0, min(int(ahead), max(lanes, 2) // units - 1, 8 // P - 1)) + 1
+    ts = iter(timestamps) if timestamps is not None else None
+    nslots = int(getattr(h, "num_frame_slots", 0) or 4)
+    inflight = deque()                         # submission numbers
+    held = {}                                  # submission number -> the device frame it reads, until its last person has been collected
+    count = 0
+    begun = False
+
+    def size_of(f):                            # (H, W) of the picture a frame array holds, as it is stored
+        if device:
+            return (f.H, f.W)
+        return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
+
+    def collect():
+        k = inflight.popleft()
+        people = []
+        try:
+            for p in range(P):
+                s, j2, j3, used = h.collect_tracked()
+                res = (j2, j3, used)
+                if confidence:
+                    res += h.result_confidence()
+                if vspec is not None:
+                    res += (h.result_view3d(),)
+                people.append(res)
+        except _native.VnectError as e:
+            for _ in range(P - 1 - len(people)):   # the frame's other persons: collected and dropped
+                try:
+                    h.collect_tracked()
+                except _native.VnectError:
+                    pass
+            estimator._raise_like_reference(e)
+        finally:
+            held.pop(k, None)
+        if spec is not None:                       # the frame's one picture came with its last person
+            return (people, h.result_preview())
+        return (people,)
+
+    try:
+        for f in frames:
+            if device:
+                frame = _native.device_frame(f, pixel_format)
+                frame._producer = _native.default_stream()
+            else:
+                frame = np.ascontiguousarray(f, dtype=np.uint8)
+            H, W = size_of(frame)
+            if not begun:
+                estimator._orient(code)        # every person keeps the code in force now; H, W below: the picture's
+                pH, pW = (W, H) if code & 1 else (H, W)
+                h.people_begin(P, pH, pW, [[0, 0, pW, pH] if r is None else r for r in rects])
+                begun = True
+                for p in range(P):
+                    if rule is not None:
+                        h.track_policy(p, *rule)
+                    if vspec is not None:
+                        h.track_view3d(p, vspec)
+                size = (H, W)
+            elif (H, W) != size:
+                raise ValueError("frames of one video must have one size")
+            t2d, t3d = estimator._stamps(next(ts) if ts is not None else None)
+            try:
+                if device:
+                    h.submit_people_device(P, frame, t2d, t3d, frame._producer, style, spec)
+                    held[count] = frame
+                else:
+                    slot = count % nslots
+                    estimator._orient(code)    # (the slot holds the oriented frame from its upload on)
+                    if nv12:
+                        h.upload_frame_nv12(slot, frame)
+                    else:
+                        h.upload_frame(slot, frame)
+                    h.submit_people(P, slot, t2d, t3d)
+            except _native.VnectError as e:    # as in track: every earlier frame's results first
+                while inflight:
+                    yield collect()
+                estimator._raise_like_reference(e)
+            inflight.append(count)
+            count += 1
+            while len(inflight) >= window:
+                yield collect()
+        while inflight:
+            yield collect()
+    finally:
+        while inflight:
+            inflight.popleft()
+            for _ in range(P):
+                try:
+                    h.collect_tracked()
+                except _native.VnectError:
+                    pass
+        held.clear()
+        estimator._orient(None)                 # the estimator's own orientation again
+        if begun:                               # nothing is in flight any more: no view, no rule
+            for p in range(P):
+                try:
+                    if vspec is not None:
+                        h.track_view3d(p, None)
+                    if rule is not None:
+                        h.track_policy(p, 0.0, 1, "off")
+                except _native.VnectError:
+                    pass
+
+
 def synthetic_stream(stream, n_frames, height=368, width=368, smooth=True):
     """Deterministic synthetic video: frame k of stream s has seed 1234 + 1000*s + k."""
     from .parallel import stream_seed
