@@ -139,6 +139,14 @@ def test_every_person_equals_its_own_loop(P, precision):
     _same(_run(P, precision=precision), _reference(precision, S3, SMALL, P), (P, precision))
 
 
+def test_box_launch_switch_inside_a_people_frame(monkeypatch):
+    """VNECT_TRACK_BOX_LAUNCH=1 with P = 3: the frame is a paired unit, which ignores the switch (PEOPLE.md, Limits), and a single unit,
+    which honours it -- 2 units, 1 pair (_run asserts it), and every person's results are still the references' bit for bit."""
+    want = _reference("bf16", S3, SMALL, 3)
+    monkeypatch.setenv("VNECT_TRACK_BOX_LAUNCH", "1")
+    _same(_run(3, precision="bf16"), want, (3, "bf16", "box launch"))
+
+
 @pytest.mark.parametrize("P,precision,scales", [(4, "fp32", S1), (3, "bf16", S1), (3, "bf16", S5), (2, "fp32", S5)])
 def test_one_scale_pairs_and_five_scales_run_singly(P, precision, scales):
     """[1.0]: a pair is two images.  Five scales: 2 S > 8, there is no pair plan, the people run singly, and that is not an error."""

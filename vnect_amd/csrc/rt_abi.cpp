@@ -14,10 +14,8 @@ static int preprocess_slot0(vnect_handle* h, float* batch_out, double* scaler, i
     FrameParams fp;
     int rc;
     if ((rc = squarify_params(h, h->slots[0].H, h->slots[0].W, &fp))) return rc;
-    FrameDyn dyn{};
-    dyn.row_stride = h->slots[0].stride, dyn.frame = h->frames;
     if ((rc = sync_geometry(h, fp))) return rc;
-    if ((rc = run_pre(h, dyn, false, true))) return rc;
+    if ((rc = run_pre(h, slot_dyn(h, 0, 0.0, 0.0), false, true))) return rc;
     if (batch_out) {
         const long long npix = (long long)h->Snet * BOX * BOX;
         HIPCK(h, launch_strip4to3(h->tensors[h->t_input4].d, h->in3, npix, h->el(), h->st));
@@ -286,10 +284,8 @@ void vnect_destroy(vnect_handle* h)
         if (h->xopened[r] && h->xpeer[r]) hipIpcCloseMemHandle(h->xpeer[r]);
     if (h->h_xstatus) hipHostFree(h->h_xstatus);
     if (h->h_tout) hipHostFree(h->h_tout);
-    for (int i = 0; i < RING; i++)
-        if (h->pv_host[i]) hipHostFree(h->pv_host[i]);  // (pv_dev: dev_allocs)
-    for (int i = 0; i < RING; i++)
-        if (h->v3_host[i]) hipHostFree(h->v3_host[i]);  // (v3_dev: dev_allocs)
+    ring_pictures_free_host(h->previews);
+    ring_pictures_free_host(h->views);
     if (h->h_conf) hipHostFree(h->h_conf);
     if (h->h_redet) hipHostFree(h->h_redet);
     for (int i = 0; i < 3; i++)
@@ -826,7 +822,7 @@ int vnect_track_policy(vnect_handle* h, int stream, double min_confidence, int m
         if (!h->finalized) return fail(h, VNECT_E_STATE, "vnect_track_policy before vnect_finalize");
         Stream& sm = h->streams[stream];
         // the box stage of a tracked frame in flight reads the rule whenever it runs: no change under it
-        if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+        if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].f.tracked)
             return fail(h, VNECT_E_STATE, "vnect_track_policy: the stream has a tracked frame in flight: collect it first");
         HIPCK(h, hipSetDevice(h->cfg.device));
         // (an untracked frame of the stream may still be in flight, and so may other streams' frames: none of them reads this rule)
@@ -1062,9 +1058,7 @@ int vnect_result_preview(vnect_handle* h, const uint8_t** data, int32_t hw[2], i
 {
     return guarded(&h, [&]() -> int {
         if (!h || !data || !hw || !pitch) return h ? fail(h, VNECT_E_ARG, "vnect_result_preview: bad argument") : VNECT_E_ARG;
-        hw[0] = h->last_pv_h, hw[1] = h->last_pv_w;
-        *data = h->last_pv_ring >= 0 ? h->pv_host[h->last_pv_ring] : nullptr;
-        *pitch = 3LL * h->last_pv_w;
+        h->previews.result(data, hw, pitch);
         return VNECT_OK;
     });
 }
@@ -1104,9 +1098,7 @@ int vnect_result_view3d(vnect_handle* h, const uint8_t** data, int32_t hw[2], in
 {
     return guarded(&h, [&]() -> int {
         if (!h || !data || !hw || !pitch) return h ? fail(h, VNECT_E_ARG, "vnect_result_view3d: bad argument") : VNECT_E_ARG;
-        hw[0] = h->last_v3_h, hw[1] = h->last_v3_w;
-        *data = h->last_v3_ring >= 0 ? h->v3_host[h->last_v3_ring] : nullptr;
-        *pitch = 3LL * h->last_v3_w;
+        h->views.result(data, hw, pitch);
         return VNECT_OK;
     });
 }

@@ -146,25 +146,9 @@ int check_tracked_preview(vnect_handle* h, const char* who, const vnect_device_f
     for (int k = 0; k < 3; k++) a.col[0][k] = t.col[0][k], a.col[1][k] = t.col[1][k];
     if ((rc = spec_in(h, who, spec, orient, s->H, s->W, &a.g))) return rc;
     const size_t need = 3 * (size_t)a.g.dw * a.g.dh;
-    if (need > h->pv_cap) {
-        if (h->seq_submit != h->seq_collect)
-            return fail(h, VNECT_E_STATE, std::string(who) + ": a larger preview needs larger buffers, which are re-sized only while nothing is in flight: collect first");
-        for (int i = 0; i < RING; i++) {
-            if (h->pv_host[i]) HIPCK(h, hipHostFree(h->pv_host[i]));
-            h->pv_host[i] = nullptr;
-            if (h->pv_dev[i]) {
-                HIPCK(h, hipFree(h->pv_dev[i]));
-                h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->pv_dev[i]));
-                h->pv_dev[i] = nullptr;
-            }
-        }
-        h->pv_cap = 0, h->last_pv_ring = -1, h->last_pv_h = h->last_pv_w = 0;
-        for (int i = 0; i < RING; i++) {
-            HIPCK(h, hipHostMalloc((void**)&h->pv_host[i], need, hipHostMallocDefault));
-            if ((rc = dev_alloc(h, &h->pv_dev[i], need))) return rc;
-        }
-        h->pv_cap = need;
-    }
+    if (need > h->previews.cap && h->seq_submit != h->seq_collect)
+        return fail(h, VNECT_E_STATE, std::string(who) + ": a larger preview needs larger buffers, which are re-sized only while nothing is in flight: collect first");
+    if ((rc = ring_pictures_size(h, h->previews, need))) return rc;
     a.src = orient_src_of(*s), a.o = orient, a.H = s->H, a.W = s->W, a.out_rgb = spec->out_format == VNECT_PIX_RGB, a.has_joints = 1;
     s->preview = true, s->pv = a, s->pv_in = in;
     return VNECT_OK;
@@ -243,13 +227,7 @@ int preview_device_impl(vnect_handle* h, const vnect_device_frame* f, void* stre
         const size_t need = row * (size_t)a.g.dh;
         if (need > h->preview_stage_cap) {
             if (h->upload_st) HIPCK(h, hipStreamSynchronize(h->upload_st));
-            if (h->preview_stage) {
-                HIPCK(h, hipFree(h->preview_stage));
-                h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->preview_stage));
-                h->preview_stage = nullptr, h->preview_stage_cap = 0;
-            }
-            if ((rc = dev_alloc(h, &h->preview_stage, need))) return rc;
-            h->preview_stage_cap = need;
+            if ((rc = dev_grow(h, &h->preview_stage, &h->preview_stage_cap, need))) return rc;
         }
         a.out = h->preview_stage, a.pitch = (long long)row;
     }

@@ -1,5 +1,6 @@
-// rt_exec.cpp -- running frames on a plan: launch sequences, the hipGraph and its profiling twin, lane choice, video streams, submit /
-// collect, the warm start.  One call of VNectEstimator.__call__ (the reference's src/estimator.py:97-142) is enqueue_frame +
+// rt_exec.cpp -- running frames on a plan: launch sequences, the hipGraph and its profiling twin, lane choice, video streams, the enqueue
+// stages and the submits built from them (a frame, a batch of two streams, a pair of persons; people mode on top), collect, the warm
+// start.  One call of VNectEstimator.__call__ (the reference's src/estimator.py:97-142) is enqueue_frame +
 // collect_impl.  (How a frame gets into a slot, or a tracked frame's description to enqueue_frame: rt_ingest.cpp.)
 #include "runtime.h"
 
@@ -20,17 +21,24 @@ static Args stamped(const Plan* p, const Args& args, int li, bool timed)
 // the maps the merge reads: the plan's own, or on a pyramid-sharded handle all ranks'
 static const float* maps_of(const Plan* p) { return p->owner->sharded ? p->owner->gather : p->tensors[p->t_out].d; }
 
+// the stem from the batch tensor, which a pyramid launch (or vnect_forward) has written
+static int stem_from_batch(Plan* p, bool timed)
+{
+    StemArgs a = stamped(p, p->stem, p->l_conv1, timed);
+    a.from_frame = 0;
+    HIPCK(p, launch_stem(a, p->st));
+    return VNECT_OK;
+}
+
 // `stem_done`: the caller has launched the stem from the frame already (enqueue_frame: it takes the frame's arguments by value)
 int run_network(Plan* h, bool timed, bool stem_done)
 {
+    int rc;
     for (Layer& L : h->layers) {
         const int li = (int)(&L - h->layers.data());
         if (h->stem_mode && (li == h->l_conv1 || li == h->l_pool1)) {
-            if (li == h->l_conv1 && !stem_done) {  // from the batch tensor (stem_mode 1, or vnect_forward on a stem_mode 2 handle)
-                StemArgs a = stamped(h, h->stem, li, timed);
-                a.from_frame = 0;
-                HIPCK(h, launch_stem(a, h->st));
-            }
+            // (stem_mode 1, or vnect_forward on a stem_mode 2 handle)
+            if (li == h->l_conv1 && !stem_done && (rc = stem_from_batch(h, timed))) return rc;
             continue;
         }
         if (h->stem_mode && h->stem_pair && li == h->l_pool1 + 1) continue;  // ran inside the stem launch
@@ -66,23 +74,18 @@ int run_pre(Plan* h, const FrameDyn& dyn, bool timed, bool want_batch)
 {
     const vnect_handle* o = h->owner;
     const int scale0 = o->sharded ? o->cfg.pyramid_rank : 0;
-    if (h->stem_mode == 2 && !want_batch) {
+    const bool stem = h->stem_mode == 2 && !want_batch;
+    // gen_input_batch + conv1 + pool1 in ONE launch, the batch tensor never written: for frames whose squarify step is a copy (long
+    // side == 368) at scales whose rectangles fit the kernel's scratch.  Any other frame: pyramid_kernel, then the stem from the
+    // batch tensor -- both in front of the graph, which starts at res2a either way.  Same results bit for bit.
+    if (stem && h->stem_frame_ok && h->fp_dev_valid && h->fp_dev.sq.copy) {
         StemArgs a = stamped(h, h->stem, h->l_conv1, timed);
-        // gen_input_batch + conv1 + pool1 in ONE launch, the batch tensor never written: for frames whose squarify step is a copy (long
-        // side == 368) at scales whose rectangles fit the kernel's scratch.  Any other frame: pyramid_kernel, then the stem from the
-        // batch tensor -- both in front of the graph, which starts at res2a either way.  Same results bit for bit.
-        if (h->stem_frame_ok && h->fp_dev_valid && h->fp_dev.sq.copy) {
-            a.from_frame = 1, a.dyn = dyn;
-            HIPCK(h, launch_stem(a, h->st));
-            return VNECT_OK;
-        }
-        HIPCK(h, launch_pyramid(h->d_fp, dyn, o->d_stabs, h->tensors[h->t_input4].d, h->Snet, scale0, h->el(), h->st));
-        a.from_frame = 0;
+        a.from_frame = 1, a.dyn = dyn;
         HIPCK(h, launch_stem(a, h->st));
         return VNECT_OK;
     }
     HIPCK(h, launch_pyramid(h->d_fp, dyn, o->d_stabs, h->tensors[h->t_input4].d, h->Snet, scale0, h->el(), h->st));
-    return VNECT_OK;
+    return stem ? stem_from_batch(h, timed) : VNECT_OK;
 }
 
 // multi-scale merge + arg-max (graph-capturable: no per-frame arguments)
@@ -148,12 +151,7 @@ static int run_pre_tracked(vnect_handle* h, Plan* L, int stream, const FrameDyn&
     if (rc) return rc;
     if ((rc = copy_tracked_crop(h, stream, src, L->st))) return rc;
     HIPCK(h, launch_pyramid_track(ts, dyn, src.where != SRC_SLOT, h->d_stabs, L->tensors[L->t_input4].d, L->Snet, L->el(), L->st));
-    if (L->stem_mode == 2) {
-        StemArgs a = stamped(L, L->stem, L->l_conv1, timed);
-        a.from_frame = 0;
-        HIPCK(h, launch_stem(a, L->st));
-    }
-    return VNECT_OK;
+    return L->stem_mode == 2 ? stem_from_batch(L, timed) : VNECT_OK;
 }
 
 // OneEuroFilter.py:65-66: `if self.__lasttime and timestamp: self.__freq = 1.0 / (timestamp - self.__lasttime)`.
@@ -273,7 +271,7 @@ int build_graph(Plan* h)
 // Frames (or batches of two streams' frames) in flight, and how many may be: one lane queues two on its stream, more lanes one each
 static unsigned long long units_in_flight(const vnect_handle* h)
 {
-    return h->seq_submit == h->seq_collect ? 0 : h->unit_submit - h->ring[h->seq_collect % RING].unit;
+    return h->seq_submit == h->seq_collect ? 0 : h->unit_submit - h->ring[h->seq_collect % RING].f.unit;
 }
 static unsigned long long max_in_flight(const vnect_handle* h) { return std::max<size_t>(h->lanes.size(), 2); }
 
@@ -291,6 +289,113 @@ static Plan* pick_lane(vnect_handle* h, bool timed)
 // meanwhile), a frame submitted behind others replays the graph (the host must stay ahead of two or three lanes)
 static bool replays(const vnect_handle* h, const Plan* p) { return p->gexec && (h->cfg.use_graph == 1 || h->seq_submit != h->seq_collect); }
 
+// ---- the ring's pictures (RingPictures: tracked previews, tracked 3-D views) ---------------------------------------------------------------
+int ring_pictures_size(vnect_handle* h, RingPictures& p, size_t need)
+{
+    if (need <= p.cap) return VNECT_OK;
+    int rc;
+    for (int i = 0; i < RING; i++) {
+        if (p.host[i]) HIPCK(h, hipHostFree(p.host[i]));
+        p.host[i] = nullptr;
+        if ((rc = dev_free(h, &p.dev[i]))) return rc;
+    }
+    p.cap = 0, p.deliver(-1, 0, 0);
+    for (int i = 0; i < RING; i++) {
+        HIPCK(h, hipHostMalloc((void**)&p.host[i], need, hipHostMallocDefault));
+        if ((rc = dev_alloc(h, &p.dev[i], need))) return rc;
+    }
+    p.cap = need;
+    return VNECT_OK;
+}
+
+int ring_pictures_copy(vnect_handle* h, const RingPictures& p, int ring, size_t bytes, hipStream_t st)
+{
+    HIPCK(h, hipMemcpyAsync(p.host[ring], p.dev[ring], bytes, hipMemcpyDeviceToHost, st));
+    return VNECT_OK;
+}
+
+void ring_pictures_free_host(RingPictures& p)
+{
+    for (uint8_t* q : p.host)
+        if (q) hipHostFree(q);
+}
+
+// ---- the stages of a submit: what enqueue_frame, enqueue_batch and enqueue_pair (and enqueue_people's drawing) are built from ------------------
+// The stream's previous frame ran on another lane and may still be in flight: `lane`'s stream waits for it.  (A batched plan and a pair plan
+// run on their lane's stream.)  WHERE a submit waits is its own decision: the filters are a chain within a video stream, so a frame's
+// post-processing waits; a tracked frame's crop is the previous frame's box stage's output, so everything of it waits.
+static int wait_prev(vnect_handle* h, const Stream& sm, Plan* lane)
+{
+    if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != lane) HIPCK(h, hipStreamWaitEvent(lane->st, h->ring[sm.seq % RING].done, 0));
+    return VNECT_OK;
+}
+
+// the conv stack (+ merge + arg-max) of plan p: its graph, its profiling twin where it has one, or the launches themselves
+static int launch_stack(const vnect_handle* h, Plan* p, bool timed)
+{
+    if (replays(h, p) && !timed) HIPCK(p, hipGraphLaunch(p->gexec, p->st));
+    else if (p->pgexec && timed) HIPCK(p, hipGraphLaunch(p->pgexec, p->st));
+    else return run_frame_kernels(p, timed);
+    return VNECT_OK;
+}
+
+// lane's plan among `plans` (bplans, pplans: plans[i] runs on lanes[i]'s stream)
+static Plan* sibling(const std::vector<Plan*>& plans, const vnect_handle* h, const Plan* lane)
+{
+    return plans[std::find(h->lanes.begin(), h->lanes.end(), lane) - h->lanes.begin()];
+}
+
+static bool slot_ok(const vnect_handle* h, int slot) { return slot >= 0 && slot < (int)h->slots.size() && h->slots[slot].H != 0; }
+
+// a tracked frame of `stream` as the kernels address it: the whole frame in `slot`, or the stream's crop buffer
+static FrameDyn tracked_dyn(const vnect_handle* h, int stream, bool from_slot, int slot, double t2d, double t3d)
+{
+    const Stream& sm = h->streams[stream];
+    FrameDyn dyn{};
+    if (from_slot) dyn = slot_dyn(h, slot, t2d, t3d);
+    else dyn.t2d = t2d, dyn.t3d = t3d, dyn.frame = sm.track_buf;  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
+    dyn.xfail = &h->d_track[stream].fail, dyn.xseq = sm.track_seq;  // a refused crop skips the joints stage
+    return dyn;
+}
+
+// a preview's arguments with ring slot `ring`'s device buffer as the output, and that picture's way on to the slot's pinned buffer
+static PreviewArgs preview_into(const vnect_handle* h, const PreviewArgs& pv, int ring)
+{
+    PreviewArgs a = pv;
+    a.out = h->previews.dev[ring], a.pitch = 3LL * a.g.dw;
+    return a;
+}
+static int preview_copy(vnect_handle* h, const PreviewArgs& a, int ring, hipStream_t st)
+{
+    return ring_pictures_copy(h, h->previews, ring, 3 * (size_t)a.g.dw * a.g.dh, st);
+}
+
+// run_estimator_ps.py:90 (q_joints.put(joints_3d): the 3-D plot's input): the 3-D view (vnect_track_view3d) of the frame in ring slot `ring` --
+// joints_3d, status and confidences read from the slot -- into the slot's device buffer and on to its pinned host buffer
+static int view3d_tail(vnect_handle* h, const Stream& sm, int ring, hipStream_t st)
+{
+    View3dArgs a = sm.v3;
+    a.out = h->views.dev[ring], a.pitch = 3LL * a.cols;
+    HIPCK(h, launch_view3d(a, nullptr, nullptr, h->ring[ring].out_dev, a.has_conf ? h->h_conf_dev + ring : nullptr, st));
+    return ring_pictures_copy(h, h->views, ring, 3 * (size_t)a.cols * a.rows, st);
+}
+
+// Every launch of a frame has been accepted: only now its description `f` goes into its ring entry, whole, and the stream, the lane and the slot
+// move on to it.  (unit_submit advances once per UNIT: the caller's.)  Returns the frame's ring slot.
+static int commit_result(vnect_handle* h, Plan* lane, int slot, double t2d, double t3d, FrameInfo f)
+{
+    Stream& sm = h->streams[f.stream];
+    const int ring = (int)(h->seq_submit % RING);
+    f.unit = h->unit_submit;
+    if (f.tracked) f.before = sm.t, sm.track_seq++;  // (a refused crop rolls the timestamps back)
+    h->ring[ring].f = f;
+    commit_time(sm, t2d, t3d);
+    sm.seq = lane->lane_seq = (long long)h->seq_submit, sm.lane = lane;
+    if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
+    h->seq_submit++;
+    return ring;
+}
+
 // enqueue one frame from a resident slot; results land in its ring entry's slot.  `tk`: a tracked frame (vnect_submit_tracked*) -- its crop and
 // geometry are the stream's state on the device, the frame is the whole one (in `slot`, or outside the slots where tk says: then slot is -1)
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream, const FrameSrc* tk)
@@ -298,9 +403,8 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     const bool from_slot = !tk || tk->where == SRC_SLOT;
     if (stream < 0 || stream >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
     if (stream != 0 && h->sharded) return fail(h, VNECT_E_ARG, "a pyramid-sharded handle serves one stream");
-    if (from_slot && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0))
-        return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
-    Stream& sm = h->streams[stream];
+    if (from_slot && !slot_ok(h, slot)) return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+    const Stream& sm = h->streams[stream];
     if (tk && from_slot && (h->slots[slot].H != sm.track_H || h->slots[slot].W != sm.track_W))
         return fail(h, VNECT_E_ARG, "the slot's frame is not of the size vnect_track_begin gave for this stream");
     if (!(tk && tk->people_unit) && units_in_flight(h) >= max_in_flight(h))  // (a people frame's units were counted together: enqueue_people)
@@ -313,16 +417,8 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     rc = check_time(h, sm, t2d, t3d);
     if (rc) return rc;
     const int ring = (int)(h->seq_submit % RING);
-    InFlight& e = h->ring[ring];
-    FrameDyn dyn{};
-    dyn.t2d = t2d, dyn.t3d = t3d;
-    if (!from_slot) {
-        dyn.frame = sm.track_buf;  // (the crop's rows, packed: pyramid_track_kernel takes their stride from the state)
-    } else {
-        dyn.row_stride = h->slots[slot].stride;
-        dyn.frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-    }
-    if (tk) dyn.xfail = &h->d_track[stream].fail, dyn.xseq = sm.track_seq;  // a refused crop skips the joints stage
+    const InFlight& e = h->ring[ring];
+    FrameDyn dyn = tk ? tracked_dyn(h, stream, from_slot, slot, t2d, t3d) : slot_dyn(h, slot, t2d, t3d);
     const bool timed = h->profiling;
     // Lane: the first whose last frame has been collected (lane 0 when nothing is in flight).  Frames on different lanes
     // overlap -- the idle CUs between one frame's launches are the other frames' -- and only the post-processing launch of a frame
@@ -330,24 +426,16 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // frame.  Measured (round 3, A/B in one call): 1 388-1 390 frames/s three deep with the merged launch, 1 388-1 389 with the two
     // launches -- ordering the 17-us merged launch instead of the 11-us joints kernel costs nothing measurable.
     Plan* L = pick_lane(h, timed);
-    // the stream's previous frame ran on another lane and may still be in flight: the filters are a chain (its post-processing waits
-    // for it), and a tracked frame's crop is that frame's box kernel's output (everything of it waits)
-    const bool after_prev = sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L;
     if (!tk && (rc = sync_geometry(L, fp))) return rc;
-    if (tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
+    // a tracked frame's crop is its previous frame's box kernel's output: everything of it waits
+    if (tk && (rc = wait_prev(h, sm, L))) return rc;
     if (timed) HIPCK(h, hipEventRecord(h->ev[0], L->st));
     {
         RoctxRange r("vnect:gen_input_batch");
         if ((rc = tk ? run_pre_tracked(h, L, stream, dyn, *tk, timed) : run_pre(L, dyn, timed))) return rc;
     }
     RoctxRange r_net("vnect:conv_stack+merge+argmax");
-    if (replays(h, L) && !timed) {
-        HIPCK(h, hipGraphLaunch(L->gexec, L->st));
-    } else if (L->pgexec && timed) {
-        HIPCK(h, hipGraphLaunch(L->pgexec, L->st));
-    } else if ((rc = run_frame_kernels(L, timed))) {
-        return rc;
-    }
+    if ((rc = launch_stack(h, L, timed))) return rc;
 #if defined(VNECT_TEST_HOOKS) && VNECT_TEST_HOOKS
     // test build only (vnect_test_maps_override): the conv stack's output replaced by the caller's maps, on the frame's own lane stream --
     // everything behind it (post-processing, box stage, ring slot, collect) is the product's path on chosen maps
@@ -364,7 +452,7 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     if (g_roctx.pop) g_roctx.pop(), g_roctx.push(L->post_merged ? "vnect:merge+argmax+filters+readoff" : "vnect:filters+readoff");  // r_net's pop now closes this range
     // the filters are a chain WITHIN a video stream: this frame's post-processing waits for the stream's previous frame if that one
     // ran on another lane and may still be in flight (frames of other streams are no concern of it)
-    if (!tk && after_prev) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
+    if (!tk && (rc = wait_prev(h, sm, L))) return rc;
     // writes the ring slot in pinned host memory
     // A tracked frame also turns its joints into frame coordinates and grows the next crop and its geometry (trackbox.h): as the tail of
     // post_kernel (the default: measured faster, TRACKING.md), or -- the two-launch post-processing, VNECT_TRACK_BOX_LAUNCH=1 (A/B, read per
@@ -393,38 +481,36 @@ int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_o
     // run_estimator_ps.py:94-96: the frame's preview -- annotated with its own joints and rect_used, read from its ring slot, and scaled --
     // into the slot's device buffer and on to its pinned host buffer; in front of the overlay launch, so that it reads the clean frame
     if (tk && tk->preview) {
-        PreviewArgs a = tk->pv;
-        a.out = h->pv_dev[ring], a.pitch = 3LL * a.g.dw;
+        const PreviewArgs a = preview_into(h, tk->pv, ring);
         HIPCK(h, launch_preview(a, tk->pv_in, e.out_dev, h->h_tout_dev + ring, tk->pv_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
-        HIPCK(h, hipMemcpyAsync(h->pv_host[ring], h->pv_dev[ring], 3 * (size_t)a.g.dw * a.g.dh, hipMemcpyDeviceToHost, L->st));
+        if ((rc = preview_copy(h, a, ring, L->st))) return rc;
     }
     // run_estimator_ps.py:92-94: the frame itself annotated with its own joints and the rect it was cropped with, read from its ring slot
     if (tk && tk->draw)
         HIPCK(h, launch_overlay(tk->draw_target, tk->draw_in, e.out_dev, h->h_tout_dev + ring, tk->draw_in.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
-    // run_estimator_ps.py:90 (q_joints.put(joints_3d): the 3-D plot's input): the frame's 3-D view (vnect_track_view3d) -- joints_3d, status and
-    // confidences read from its ring slot -- into the slot's device buffer and on to its pinned host buffer
     const bool v3 = tk && sm.v3_on;
-    if (v3) {
-        View3dArgs a = sm.v3;
-        a.out = h->v3_dev[ring], a.pitch = 3LL * a.cols;
-        HIPCK(h, launch_view3d(a, nullptr, nullptr, e.out_dev, a.has_conf ? h->h_conf_dev + ring : nullptr, L->st));
-        HIPCK(h, hipMemcpyAsync(h->v3_host[ring], h->v3_dev[ring], 3 * (size_t)a.cols * a.rows, hipMemcpyDeviceToHost, L->st));
-    }
+    if (v3 && (rc = view3d_tail(h, sm, ring, L->st))) return rc;
     if (timed) HIPCK(h, hipEventRecord(h->ev[3], L->st));
     HIPCK(h, hipEventRecord(e.done, L->st));
-    // only now: every launch of the frame has been accepted
-    e.stream = stream, e.unit = h->unit_submit++, e.batch = false, e.prof = nullptr, e.tracked = tk != nullptr;
-    e.pv_h = tk && tk->preview ? tk->pv.g.dh : 0, e.pv_w = tk && tk->preview ? tk->pv.g.dw : 0;
-    e.v3_h = v3 ? sm.v3.rows : 0, e.v3_w = v3 ? sm.v3.cols : 0;
-    e.redetect = redetect;
-    e.before = sm.t;  // (a tracked frame's refused crop rolls back)
-    commit_time(sm, t2d, t3d);
-    sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
-    if (tk) sm.track_seq++;
-    if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
-    h->seq_submit++;
-    *ring_out = ring;
+    FrameInfo f{};
+    f.stream = stream, f.tracked = tk != nullptr, f.redetect = redetect;
+    if (tk && tk->preview) f.pv_h = tk->pv.g.dh, f.pv_w = tk->pv.g.dw;
+    if (v3) f.v3_h = sm.v3.rows, f.v3_w = sm.v3.cols;
+    *ring_out = commit_result(h, L, slot, t2d, t3d, f);
+    h->unit_submit++;
     return VNECT_OK;
+}
+
+// A layer's span on the profiling stamps of plan p (100 MHz ticks): its first workgroup's start, and for a conv launch its latest workgroup
+// end (slots past the grid stay 0); any other layer has no end stamps, t1 is 0
+struct LayerSpan { unsigned long long t0, t1; };
+static LayerSpan layer_span(const Plan* p, size_t i)
+{
+    LayerSpan s{p->h_prof[PROF_SLOTS * i], 0};
+    const unsigned long long* e = p->h_prof_end + (size_t)PROF_WGS * i;
+    if (p->layers[i].op == OP_CONV)
+        for (int k = 0; k < PROF_WGS; k++) s.t1 = std::max(s.t1, e[k]);
+    return s;
 }
 
 // a profiled batch's per-layer times (vnect_get_batch_layer_info): first workgroup start to last workgroup end of every conv launch
@@ -432,12 +518,8 @@ static void read_layer_ms(Plan* b)
 {
     for (size_t i = 0; i < b->layers.size(); i++) {
         Layer& L = b->layers[i];
-        const unsigned long long t0 = b->h_prof[PROF_SLOTS * i];
-        unsigned long long t1 = 0;
-        const unsigned long long* e = b->h_prof_end + (size_t)PROF_WGS * i;
-        if (L.op == OP_CONV)
-            for (int k = 0; k < PROF_WGS; k++) t1 = std::max(t1, e[k]);
-        L.last_ms = (L.op == OP_CONV && t1 > t0) ? (float)((double)(t1 - t0) * 1e-5) : 0.f;
+        const LayerSpan s = layer_span(b, i);
+        L.last_ms = (L.op == OP_CONV && s.t1 > s.t0) ? (float)((double)(s.t1 - s.t0) * 1e-5) : 0.f;
     }
 }
 
@@ -448,9 +530,10 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
     // the caller is about to consume the joints: poll (a frame is ~1 ms) before falling back to a blocking wait, whose
     // wake-up alone costs tens of microseconds of idle GPU per frame
     hipError_t q = hipErrorNotReady;
-    InFlight& e = h->ring[ring];
-    for (int spin = 0; spin < 200000 && (q = hipEventQuery(e.done)) == hipErrorNotReady; spin++) {}
-    if (q == hipErrorNotReady) q = hipEventSynchronize(e.done);
+    FrameInfo& e = h->ring[ring].f;
+    const hipEvent_t done = h->ring[ring].done;
+    for (int spin = 0; spin < 200000 && (q = hipEventQuery(done)) == hipErrorNotReady; spin++) {}
+    if (q == hipErrorNotReady) q = hipEventSynchronize(done);
     HIPCK(h, q);
     h->seq_collect++;
     if (h->h_xstatus && h->h_xstatus[ring]) {  // one word per ring slot: the error lands on the frame it belongs to
@@ -460,9 +543,9 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         return fail(h, VNECT_E_COMM, "pyramid exchange: a peer's maps did not arrive within the bound (ranks out of step?); "
                                      "destroy the handles of every rank and reconnect");
     }
-    h->last_pv_ring = -1, h->last_pv_h = h->last_pv_w = 0;  // (a frame whose crop was refused has no preview)
-    h->last_v3_ring = -1, h->last_v3_h = h->last_v3_w = 0;  // (nor a 3-D view)
-    h->last_redet = RedetectOut{};                          // (nor a detection)
+    h->previews.deliver(-1, 0, 0);   // (a frame whose crop was refused has no preview)
+    h->views.deliver(-1, 0, 0);      // (nor a 3-D view)
+    h->last_redet = RedetectOut{};   // (nor a detection)
     if (stream_out) *stream_out = e.stream;
     if (rect_out)
         for (int k = 0; k < 4; k++) rect_out[k] = e.tracked ? h->h_tout[ring].rect[k] : -1;
@@ -476,8 +559,8 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         sm.t = e.before;
         return fail(h, VNECT_E_ARG, crop_refusal(h->h_tout[ring].status));
     }
-    if (j2) memcpy(j2, e.out->j2d, sizeof(double) * NJ * 2);
-    if (j3) memcpy(j3, e.out->j3d, sizeof(float) * NJ * 3);
+    if (j2) memcpy(j2, h->ring[ring].out->j2d, sizeof(double) * NJ * 2);
+    if (j3) memcpy(j3, h->ring[ring].out->j3d, sizeof(float) * NJ * 3);
     deliver_confidence(h, ring, e.tracked);
     if (e.tracked && e.redetect) {  // the frame's verdict, from its own ring slot like the confidences; what the kernel did not write reads as zero
         const RedetectOut& r = h->h_redet[ring];
@@ -485,8 +568,8 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         if (r.status != HOG_RD_NOT_RUN) h->last_redet.hits = r.hits;
         if (r.status == HOG_RD_FOUND) memcpy(h->last_redet.rect, r.rect, sizeof r.rect);
     }
-    if (e.tracked && e.pv_h) h->last_pv_ring = ring, h->last_pv_h = e.pv_h, h->last_pv_w = e.pv_w;
-    if (e.tracked && e.v3_h) h->last_v3_ring = ring, h->last_v3_h = e.v3_h, h->last_v3_w = e.v3_w;
+    if (e.tracked && e.pv_h) h->previews.deliver(ring, e.pv_h, e.pv_w);
+    if (e.tracked && e.v3_h) h->views.deliver(ring, e.v3_h, e.v3_w);
     if (e.prof) read_layer_ms(e.prof), e.prof = nullptr;
     if (h->profiling && !e.batch) {
         float frame_ms = 0;
@@ -496,13 +579,10 @@ int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out, in
         for (size_t i = 0; i < h->layers.size(); i++) {
             Layer& L = h->layers[i];
             unsigned long long* p = h->h_prof + PROF_SLOTS * i;
-            const unsigned long long t0 = p[0];
-            unsigned long long t1 = 0;
-            if (L.op == OP_CONV) {  // latest workgroup end of this launch (slots past the grid stay 0)
-                const unsigned long long* e = h->h_prof_end + (size_t)PROF_WGS * i;
-                for (int k = 0; k < PROF_WGS; k++) t1 = std::max(t1, e[k]);
+            const LayerSpan s = layer_span(h, i);
+            const unsigned long long t0 = s.t0, t1 = s.t1;
+            if (L.op == OP_CONV)
                 for (int k = 1; k <= 8; k++) p[k] = t1;  // vnect_get_layer_stamps keeps its layout
-            }
             L.last_ms = 0;
             if (L.op != OP_CONV || t1 <= t0) continue;
             L.last_ms = (float)((double)(t1 - t0) * 1e-5);  // 100 MHz ticks -> ms
@@ -654,8 +734,7 @@ int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots,
     FrameDyn dyn[2] = {};
     for (int k = 0; k < 2; k++) {
         if (streams[k] < 0 || streams[k] >= VNECT_MAX_STREAMS) return fail(h, VNECT_E_ARG, "stream out of range");
-        if (slots[k] < 0 || slots[k] >= (int)h->slots.size() || h->slots[slots[k]].H == 0)
-            return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+        if (!slot_ok(h, slots[k])) return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
     }
     if (streams[0] == streams[1]) return fail(h, VNECT_E_ARG, "a batch takes frames of two DIFFERENT streams (a stream's frames are a chain)");
     if (units_in_flight(h) >= max_in_flight(h)) return fail(h, VNECT_E_STATE, "too many frames in flight: collect one first");
@@ -664,45 +743,37 @@ int enqueue_batch(vnect_handle* h, const int32_t* streams, const int32_t* slots,
         const auto& si = h->slots[slots[k]];
         if ((rc = squarify_params(h, si.H, si.W, &fp[k]))) return rc;
         if ((rc = check_time(h, h->streams[streams[k]], t2d[k], t3d[k]))) return rc;
-        dyn[k].t2d = t2d[k], dyn[k].t3d = t3d[k];
-        dyn[k].row_stride = si.stride;
-        dyn[k].frame = h->frames + (size_t)slots[k] * h->cfg.max_frame_bytes;
+        dyn[k] = slot_dyn(h, slots[k], t2d[k], t3d[k]);
     }
     const bool timed = h->profiling;
     Plan* L = pick_lane(h, timed);
-    Plan* b = h->bplans[std::find(h->lanes.begin(), h->lanes.end(), L) - h->lanes.begin()];
+    Plan* b = sibling(h->bplans, h, L);
     if ((rc = sync_geometry(b, fp[0], 0)) || (rc = sync_geometry(b, fp[1], 1))) return rc;
     // gen_input_batch of both frames inside the stem launch (as run_pre does for one frame), or the batch tensor first
-    const bool frame_stem = b->stem_mode == 2 && b->stem_frame_ok && fp[0].sq.copy && fp[1].sq.copy;
-    if (!frame_stem)
-        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], h->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
-    if (b->stem_mode == 2) {
+    if (b->stem_mode == 2 && b->stem_frame_ok && fp[0].sq.copy && fp[1].sq.copy) {
         StemArgs a = stamped(b, b->stem, b->l_conv1, timed);
-        a.from_frame = frame_stem;
+        a.from_frame = 1;
         a.dyn = dyn[0], a.frame2 = dyn[1].frame, a.stride2 = dyn[1].row_stride;
         HIPCK(h, launch_stem(a, b->st));
+    } else {
+        HIPCK(h, launch_pyramid_streams(b->d_fp, b->d_fp2, dyn[0], dyn[1], h->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
+        if (b->stem_mode == 2 && (rc = stem_from_batch(b, timed))) return rc;
     }
-    if (replays(h, b) && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
-    else if ((rc = run_frame_kernels(b, timed))) return rc;
+    if ((rc = launch_stack(h, b, timed))) return rc;
     const size_t half = (size_t)b->S * HM * HM * MAPC;
     const float* maps = b->tensors[b->t_out].d;
     for (int k = 0; k < 2; k++) {
-        const Stream& sm = h->streams[streams[k]];
-        const InFlight& e = h->ring[(h->seq_submit + k) % RING];
-        // the filters are a chain within a stream: wait for its previous frame if that one ran on another lane and may be in flight
-        if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L) HIPCK(h, hipStreamWaitEvent(b->st, h->ring[sm.seq % RING].done, 0));
+        const int ring = (int)((h->seq_submit + k) % RING);
+        // the filters are a chain within a stream: each member's post-processing waits for its own stream's previous frame
+        if ((rc = wait_prev(h, h->streams[streams[k]], L))) return rc;
         HIPCK(h, launch_post(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + streams[k], k ? b->d_fp2 : b->d_fp, dyn[k], h->cfg.numpy_promotion,
-                             e.out_dev, b->st, h->h_conf_dev + (h->seq_submit + k) % RING));
-        HIPCK(h, hipEventRecord(e.done, b->st));
+                             h->ring[ring].out_dev, b->st, h->h_conf_dev + ring));
+        HIPCK(h, hipEventRecord(h->ring[ring].done, b->st));
     }
-    for (int k = 0; k < 2; k++) {  // every launch of the batch has been accepted: commit
-        Stream& sm = h->streams[streams[k]];
-        InFlight& e = h->ring[h->seq_submit % RING];
-        e.stream = streams[k], e.unit = h->unit_submit, e.batch = true, e.prof = (timed && k == 1) ? b : nullptr, e.tracked = false;
-        commit_time(sm, t2d[k], t3d[k]);
-        sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
-        h->slots[slots[k]].last_use = (long long)h->seq_submit;
-        h->seq_submit++;
+    for (int k = 0; k < 2; k++) {
+        FrameInfo f{};
+        f.stream = streams[k], f.batch = true, f.prof = (timed && k == 1) ? b : nullptr;
+        commit_result(h, L, slots[k], t2d[k], t3d[k], f);
     }
     h->unit_submit++;
     return VNECT_OK;
@@ -760,14 +831,8 @@ int track_begin_impl(vnect_handle* h, int stream, int H, int W, const int32_t* r
     const size_t need = (size_t)H * W * 3 + 16;
     if (sm.track_cap < need) {  // the crop buffer of pinned frames (the largest crop is the frame)
         for (Plan* l : h->lanes) HIPCK(h, hipStreamSynchronize(l->st));
-        if (sm.track_buf) {
-            HIPCK(h, hipFree(sm.track_buf));
-            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)sm.track_buf));
-            sm.track_buf = nullptr, sm.track_cap = 0;
-        }
-        int rc = dev_alloc(h, &sm.track_buf, need);
+        int rc = dev_grow(h, &sm.track_buf, &sm.track_cap, need);
         if (rc) return rc;
-        sm.track_cap = need;
     }
     // vnect_track_redetect is set on the stream: its level table and workspace for this size and orientation, now that they are known --
     // the last step that can refuse, so a refused vnect_track_begin leaves the stream's track and its detection plan as they were
@@ -806,58 +871,36 @@ static int enqueue_pair(vnect_handle* h, int s0, int slot, double t2d, double t3
     const bool from_slot = src.where == SRC_SLOT;
     const bool timed = h->profiling;
     Plan* L = pick_lane(h, timed);
-    Plan* b = h->pplans[std::find(h->lanes.begin(), h->lanes.end(), L) - h->lanes.begin()];
-    FrameDyn dyn[2] = {};
+    Plan* b = sibling(h->pplans, h, L);
+    FrameDyn dyn[2];
     int rc;
     for (int k = 0; k < 2; k++) {
-        const Stream& sm = h->streams[s0 + k];
         // a person's crop is its previous frame's box stage's output: everything of the unit waits for both persons' previous frames
-        if (sm.seq >= (long long)h->seq_collect && sm.lane && sm.lane != L) HIPCK(h, hipStreamWaitEvent(L->st, h->ring[sm.seq % RING].done, 0));
-        dyn[k].t2d = t2d, dyn[k].t3d = t3d;
-        if (from_slot) dyn[k].row_stride = h->slots[slot].stride, dyn[k].frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
-        else dyn[k].frame = sm.track_buf;
-        dyn[k].xfail = &h->d_track[s0 + k].fail, dyn[k].xseq = sm.track_seq;
+        if ((rc = wait_prev(h, h->streams[s0 + k], L))) return rc;
+        dyn[k] = tracked_dyn(h, s0 + k, from_slot, slot, t2d, t3d);
     }
     if ((rc = wait_for_producer(h, src.producer, L->st))) return rc;
     for (int k = 0; k < 2; k++)
         if ((rc = copy_tracked_crop(h, s0 + k, src, L->st))) return rc;
     HIPCK(h, launch_pyramid_track_pair(h->d_track + s0, dyn[0], dyn[1], !from_slot, h->d_stabs, b->tensors[b->t_input4].d, b->S, b->el(), b->st));
-    if (b->stem_mode == 2) {  // from the batch tensor: the host does not know whether a crop's squarify step is a copy
-        StemArgs a = stamped(b, b->stem, b->l_conv1, timed);
-        a.from_frame = 0;
-        HIPCK(h, launch_stem(a, b->st));
-    }
-    if (replays(h, b) && !timed) HIPCK(h, hipGraphLaunch(b->gexec, b->st));
-    else if ((rc = run_frame_kernels(b, timed))) return rc;
+    // (the stem from the batch tensor: the host does not know whether a crop's squarify step is a copy)
+    if (b->stem_mode == 2 && (rc = stem_from_batch(b, timed))) return rc;
+    if ((rc = launch_stack(h, b, timed))) return rc;
     const size_t half = (size_t)b->S * HM * HM * MAPC;
     const float* maps = b->tensors[b->t_out].d;
     for (int k = 0; k < 2; k++) {
         const int s = s0 + k, ring = (int)((h->seq_submit + k) % RING);
-        const Stream& sm = h->streams[s];
-        const InFlight& e = h->ring[ring];
-        HIPCK(h, launch_post_track(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + s, h->d_track + s, dyn[k], h->cfg.numpy_promotion, e.out_dev,
-                                   h->h_tout_dev + ring, b->st, h->h_conf_dev + ring, h->d_policy + s, nullptr));
-        if (sm.v3_on) {
-            View3dArgs a = sm.v3;
-            a.out = h->v3_dev[ring], a.pitch = 3LL * a.cols;
-            HIPCK(h, launch_view3d(a, nullptr, nullptr, e.out_dev, a.has_conf ? h->h_conf_dev + ring : nullptr, b->st));
-            HIPCK(h, hipMemcpyAsync(h->v3_host[ring], h->v3_dev[ring], 3 * (size_t)a.cols * a.rows, hipMemcpyDeviceToHost, b->st));
-        }
-        HIPCK(h, hipEventRecord(e.done, b->st));
+        HIPCK(h, launch_post_track(maps + k * half, h->mgeo, b->d_part, b->d_ticket, h->d_fb + s, h->d_track + s, dyn[k], h->cfg.numpy_promotion,
+                                   h->ring[ring].out_dev, h->h_tout_dev + ring, b->st, h->h_conf_dev + ring, h->d_policy + s, nullptr));
+        if (h->streams[s].v3_on && (rc = view3d_tail(h, h->streams[s], ring, b->st))) return rc;
+        HIPCK(h, hipEventRecord(h->ring[ring].done, b->st));
     }
-    for (int k = 0; k < 2; k++) {  // every launch of the unit has been accepted: commit
-        Stream& sm = h->streams[s0 + k];
-        InFlight& e = h->ring[h->seq_submit % RING];
-        e.stream = s0 + k, e.unit = h->unit_submit, e.batch = true, e.prof = (timed && k == 1) ? b : nullptr, e.tracked = true;
-        e.pv_h = e.pv_w = 0;
-        e.v3_h = sm.v3_on ? sm.v3.rows : 0, e.v3_w = sm.v3_on ? sm.v3.cols : 0;
-        e.redetect = false;
-        e.before = sm.t;
-        commit_time(sm, t2d, t3d);
-        sm.seq = L->lane_seq = (long long)h->seq_submit, sm.lane = L;
-        sm.track_seq++;
-        if (slot >= 0) h->slots[slot].last_use = (long long)h->seq_submit;
-        h->seq_submit++;
+    for (int k = 0; k < 2; k++) {
+        const Stream& sm = h->streams[s0 + k];
+        FrameInfo f{};
+        f.stream = s0 + k, f.batch = true, f.prof = (timed && k == 1) ? b : nullptr, f.tracked = true;
+        if (sm.v3_on) f.v3_h = sm.v3.rows, f.v3_w = sm.v3.cols;
+        commit_result(h, L, slot, t2d, t3d, f);
     }
     h->unit_submit++;
     return VNECT_OK;
@@ -867,7 +910,7 @@ int enqueue_people(vnect_handle* h, int n, int slot, double t2d, double t3d, con
 {
     const bool from_slot = src.where == SRC_SLOT;
     int rc;
-    if (from_slot && (slot < 0 || slot >= (int)h->slots.size() || h->slots[slot].H == 0)) return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
+    if (from_slot && !slot_ok(h, slot)) return fail(h, VNECT_E_ARG, "frame slot empty or out of range");
     // atomic: every refusal of every person before anything changes
     for (int p = 0; p < n; p++) {
         const Stream& sm = h->streams[p];
@@ -912,8 +955,7 @@ int enqueue_people(vnect_handle* h, int n, int slot, double t2d, double t3d, con
     // clean frame; it belongs to the LAST person's delivery (vnect_result_preview)
     if (src.preview) {
         const int ring = (int)((seq0 + n - 1) % RING);
-        PreviewArgs a = src.pv;
-        a.out = h->pv_dev[ring], a.pitch = 3LL * a.g.dw;
+        const PreviewArgs a = preview_into(h, src.pv, ring);
         PreviewPeopleIn pin{};
         pin.P = n;
         for (int p = 0; p < n; p++) {
@@ -921,8 +963,8 @@ int enqueue_people(vnect_handle* h, int n, int slot, double t2d, double t3d, con
             pin.jo[p] = h->ring[rp].out_dev, pin.to[p] = h->h_tout_dev + rp, pin.co[p] = src.pv_in.has_conf ? h->h_conf_dev + rp : nullptr;
         }
         HIPCK(h, launch_preview_people(a, src.pv_in, pin, last->st));
-        HIPCK(h, hipMemcpyAsync(h->pv_host[ring], h->pv_dev[ring], 3 * (size_t)a.g.dw * a.g.dh, hipMemcpyDeviceToHost, last->st));
-        h->ring[ring].pv_h = a.g.dh, h->ring[ring].pv_w = a.g.dw;
+        if ((rc = preview_copy(h, a, ring, last->st))) return rc;
+        h->ring[ring].f.pv_h = a.g.dh, h->ring[ring].f.pv_w = a.g.dw;  // (after the fact: the last person's unit was committed without it)
     }
     for (int p = 0; src.draw && p < n; p++) {
         const int ring = (int)((seq0 + p) % RING);

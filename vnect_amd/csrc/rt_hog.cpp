@@ -40,7 +40,7 @@ int hog_set_detector_impl(vnect_handle* h, const float* w, int n)
     std::vector<float> d;
     if (!hog_detector(w, n, &d)) return refuse(h, who, "the detector is 3781 finite floats, rho last (or 3780: rho 0)");
     for (const Stream& sm : h->streams)  // (a re-detecting stream's frame in flight reads the detector whenever its chain runs)
-        if (sm.rd_on && sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+        if (sm.rd_on && sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].f.tracked)
             return fail(h, VNECT_E_STATE, std::string(who) + ": a re-detecting stream has a tracked frame in flight: collect it first");
     if (!h->hog_det_dev) {
         int rc = dev_alloc(h, &h->hog_det_dev, d.size());
@@ -78,15 +78,7 @@ static int grow(vnect_handle* h, int i, size_t need)
 {
     if (need <= h->hog_cap[i]) return VNECT_OK;
     if (h->upload_st) HIPCK(h, hipStreamSynchronize(h->upload_st));
-    if (h->hog_buf[i]) {
-        HIPCK(h, hipFree(h->hog_buf[i]));
-        h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->hog_buf[i]));
-        h->hog_buf[i] = nullptr, h->hog_cap[i] = 0;
-    }
-    int rc = dev_alloc(h, &h->hog_buf[i], need);
-    if (rc) return rc;
-    h->hog_cap[i] = need;
-    return VNECT_OK;
+    return dev_grow(h, &h->hog_buf[i], &h->hog_cap[i], need);
 }
 
 // the host-built tables on the device (and the handle's level table), once
@@ -196,15 +188,9 @@ int hog_detect_host_impl(vnect_handle* h, const uint8_t* bgr, int H, int W, int6
 static int rd_grow(vnect_handle* h, Stream& sm, int i, size_t need)
 {
     if (need <= sm.rd_bytes[i]) return VNECT_OK;
-    if (sm.rd_buf[i]) {
-        HIPCK(h, hipFree(sm.rd_buf[i]));
-        h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)sm.rd_buf[i]));
-        sm.rd_buf[i] = nullptr, sm.rd_bytes[i] = 0;
-    }
-    int rc = dev_alloc(h, &sm.rd_buf[i], need);
+    int rc = dev_grow(h, &sm.rd_buf[i], &sm.rd_bytes[i], need);
     if (rc) return rc;
     HIPCK(h, hipMemset(sm.rd_buf[i], 0, need));  // (the gate, the counter and the class sums start at zero)
-    sm.rd_bytes[i] = need;
     return VNECT_OK;
 }
 
@@ -247,7 +233,7 @@ int track_redetect_impl(vnect_handle* h, int stream, const vnect_hog_spec* spec,
         if (sp.max_hits > HOG_TRACK_MAX_HITS) return refuse(h, who, "max_hits of a tracked stream is at most 4096");
     }
     // the chain of a tracked frame in flight reads the setting's workspace whenever it runs: no change under it
-    if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].tracked)
+    if (sm.seq >= (long long)h->seq_collect && h->ring[sm.seq % RING].f.tracked)
         return fail(h, VNECT_E_STATE, std::string(who) + ": the stream has a tracked frame in flight: collect it first");
     if (!enable) {
         sm.rd_on = false;

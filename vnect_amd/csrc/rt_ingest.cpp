@@ -288,14 +288,8 @@ static int claim_slot(vnect_handle* h, int slot, size_t bytes)
 {
     if (h->pre_only && bytes > h->pre_frame_cap) {  // the one slot of a pre-processing-only handle grows with its frames
         HIPCK(h, hipStreamSynchronize(h->st));
-        if (h->frames) {
-            HIPCK(h, hipFree(h->frames));
-            h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->frames));
-            h->frames = nullptr, h->pre_frame_cap = 0;
-        }
-        int rc = dev_alloc(h, &h->frames, bytes);
+        int rc = dev_grow(h, &h->frames, &h->pre_frame_cap, bytes);
         if (rc) return rc;
-        h->pre_frame_cap = bytes;
     }
     // a frame still being read by an in-flight inference must not be overwritten: wait for that inference only (frames in
     // other slots keep running, so a pipelined caller uploads frame k+1 while frames k and k-1 compute)

@@ -53,13 +53,7 @@ int view3d_device_impl(vnect_handle* h, const float* j3d, const double* conf, co
         const size_t need = row * (size_t)a.rows;
         if (need > h->view_stage_cap) {
             HIPCK(h, hipStreamSynchronize(h->upload_st));
-            if (h->view_stage) {
-                HIPCK(h, hipFree(h->view_stage));
-                h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->view_stage));
-                h->view_stage = nullptr, h->view_stage_cap = 0;
-            }
-            if ((rc = dev_alloc(h, &h->view_stage, need))) return rc;
-            h->view_stage_cap = need;
+            if ((rc = dev_grow(h, &h->view_stage, &h->view_stage_cap, need))) return rc;
         }
         a.out = h->view_stage, a.pitch = (long long)row;
     }
@@ -88,24 +82,7 @@ int track_view3d_impl(vnect_handle* h, int stream, const vnect_view3d_spec* spec
         sm.v3_on = false;
         return VNECT_OK;
     }
-    const size_t need = 3 * (size_t)a.cols * a.rows;
-    if (need > h->v3_cap) {
-        for (int i = 0; i < RING; i++) {
-            if (h->v3_host[i]) HIPCK(h, hipHostFree(h->v3_host[i]));
-            h->v3_host[i] = nullptr;
-            if (h->v3_dev[i]) {
-                HIPCK(h, hipFree(h->v3_dev[i]));
-                h->dev_allocs.erase(std::find(h->dev_allocs.begin(), h->dev_allocs.end(), (void*)h->v3_dev[i]));
-                h->v3_dev[i] = nullptr;
-            }
-        }
-        h->v3_cap = 0, h->last_v3_ring = -1, h->last_v3_h = h->last_v3_w = 0;
-        for (int i = 0; i < RING; i++) {
-            HIPCK(h, hipHostMalloc((void**)&h->v3_host[i], need, hipHostMallocDefault));
-            if ((rc = dev_alloc(h, &h->v3_dev[i], need))) return rc;
-        }
-        h->v3_cap = need;
-    }
+    if ((rc = ring_pictures_size(h, h->views, 3 * (size_t)a.cols * a.rows))) return rc;
     sm.v3 = a, sm.v3_on = true;
     return VNECT_OK;
 }

@@ -1,11 +1,15 @@
 // runtime.h -- internal header of the host runtime of libvnect_hip.so (not part of the ABI: include/vnect_abi.h is).
-// The runtime is six translation units along its seams:
+// The runtime is eight translation units along its seams:
 //   rt_plan.cpp    weights -> packed device layouts, the launch plan (layers, tiles, fused forms), the activation arena, the resize tables,
 //                  the further plans built from lane 0's (lanes, batched plans)
-//   rt_exec.cpp    running frames: launch sequences, hipGraph, lanes, streams, submit / collect, warm start, roctx ranges
+//   rt_exec.cpp    running frames: launch sequences, hipGraph, lanes, streams, the enqueue stages and the three submits built from them
+//                  (frame, batch, pair) with people mode on top, collect, device tracking's begin, warm start, roctx ranges
 //   rt_ingest.cpp  frames into slots: one resolver per source (host BGR, host NV12, device memory, a pinned buffer by index) that validates
 //                  the caller's frame into a FrameSrc, the pinned staging buffers, and ingest(), the one way from a FrameSrc into a slot
-//   rt_draw.cpp    frames out: the overlay drawn into a caller's device frame (overlay.h), on its own or as the tail of a tracked frame
+//   rt_draw.cpp    frames out: the overlay drawn into a caller's device frame (overlay.h), on its own or as the tail of a tracked frame;
+//                  the preview (preview.h)
+//   rt_hog.cpp     the person detector (hog.h): the synchronous detection calls and re-detection inside the tracked loop
+//   rt_view.cpp    the 3-D view (view3d.h): one picture of given joints, and a tracked stream's setting
 //   rt_comm.cpp    the pyramid exchange: RCCL (dlopen'ed) and peer writes, vnect_comm_*
 //   rt_abi.cpp     the extern "C" entry points of include/vnect_abi.h (argument checks, device selection, the no-exception guard)
 #pragma once
@@ -137,11 +141,8 @@ struct Plan {
 // a stream's filter timestamps as the host holds them (check_time / commit_time; the device has them in d_fb[stream])
 struct TimeState { bool have2 = false, have3 = false; double last2 = 0, last3 = 0; };
 
-// A frame in flight: one entry of the result ring.
-struct InFlight {
-    JointsOut* out = nullptr;      // pinned, device-mapped: joints_kernel writes a frame's results straight into its ring slot
-    JointsOut* out_dev = nullptr;  // the same slot as the device addresses it
-    hipEvent_t done = nullptr;
+// What a frame puts into its entry of the result ring: assigned whole when the frame is committed (rt_exec.cpp: commit_result)
+struct FrameInfo {
     int stream = 0;
     unsigned long long unit = 0;  // the in-flight limit counts UNITS (a frame, or a batch of two streams' frames): this entry's
     bool batch = false;           // the entry is a frame of a batch (the handle's own profiling figures skip it)
@@ -151,6 +152,31 @@ struct InFlight {
     int v3_h = 0, v3_w = 0;        // a tracked frame that carries a 3-D view (vnect_track_view3d): its size; 0: none
     bool redetect = false;         // a tracked frame of a re-detecting stream (vnect_track_redetect): its ring slot's RedetectOut is its verdict
     TimeState before{};  // a tracked frame's stream timestamps before it was committed (a refused crop rolls them back)
+};
+
+// One entry of the result ring: what the slot owns for the handle's life, and the frame in flight there
+struct InFlight {
+    JointsOut* out = nullptr;      // pinned, device-mapped: joints_kernel writes a frame's results straight into its ring slot
+    JointsOut* out_dev = nullptr;  // the same slot as the device addresses it
+    hipEvent_t done = nullptr;
+    FrameInfo f;
+};
+
+// A picture per result-ring slot (a tracked frame's preview, its 3-D view): a device buffer the kernel writes and a pinned host buffer its
+// copy lands in, all `cap` bytes, re-sized only while nothing is in flight (ring_pictures_size); and the picture of the frame
+// vnect_collect_tracked delivered last
+struct RingPictures {
+    uint8_t* dev[RING] = {};
+    uint8_t* host[RING] = {};
+    size_t cap = 0;
+    int last_ring = -1, last_h = 0, last_w = 0;
+    void deliver(int ring, int h, int w) { last_ring = ring, last_h = h, last_w = w; }  // (-1, 0, 0): the frame delivered last has none
+    void result(const uint8_t** data, int32_t hw[2], int64_t* pitch) const  // vnect_result_preview, vnect_result_view3d
+    {
+        hw[0] = last_h, hw[1] = last_w;
+        *data = last_ring >= 0 ? host[last_ring] : nullptr;
+        *pitch = 3LL * last_w;
+    }
 };
 
 // A video stream (vnect_submit_stream; stream 0 is what every other entry point uses): d_fb[stream] and d_track[stream] on the device, and here
@@ -224,22 +250,13 @@ struct vnect_handle : Plan {
     size_t pre_frame_cap = 0;   // preprocess_only: bytes of the one, growable frame slot
     uint8_t* preview_stage = nullptr;  // vnect_preview_device with a host `out`: the kernel's packed output, copied out from here (grown on demand)
     size_t preview_stage_cap = 0;
-    // tracked previews (vnect_submit_tracked_device_preview): per result-ring slot a device buffer the kernel writes and a pinned host buffer
-    // its copy lands in, all pv_cap bytes; sized at the first such submit and re-sized only while nothing is in flight
-    uint8_t* pv_dev[RING] = {};
-    uint8_t* pv_host[RING] = {};
-    size_t pv_cap = 0;
-    int last_pv_ring = -1, last_pv_h = 0, last_pv_w = 0;  // the preview of the frame vnect_collect_tracked delivered last (vnect_result_preview)
+    RingPictures previews;  // tracked previews (vnect_submit_tracked_device_preview): sized at the first such submit
     // the 3-D view (rt_view.cpp; view3d.h).  vnect_view3d_device: the confidences and joints on the device (21 doubles, then 63 floats) and, for
-    // a host `out`, the kernel's packed output (grown on demand).  Tracked views (vnect_track_view3d): per result-ring slot a device buffer
-    // the kernel writes and a pinned host buffer its copy lands in, all v3_cap bytes; re-sized only while nothing is in flight
+    // a host `out`, the kernel's packed output (grown on demand).  Tracked views (vnect_track_view3d): sized when the setting is made
     double* view_in = nullptr;
     uint8_t* view_stage = nullptr;
     size_t view_stage_cap = 0;
-    uint8_t* v3_dev[RING] = {};
-    uint8_t* v3_host[RING] = {};
-    size_t v3_cap = 0;
-    int last_v3_ring = -1, last_v3_h = 0, last_v3_w = 0;  // the view of the frame vnect_collect_tracked delivered last (vnect_result_view3d)
+    RingPictures views;
     // the person detector (rt_hog.cpp; hog.h): the detector as given (3781 floats, rho last) and on the device, the host-built tables and the
     // level table on the device, the workspace of the three launches and a host frame's device copy -- each grown on demand, never shrunk
     std::vector<float> hog_det;
@@ -259,7 +276,7 @@ struct vnect_handle : Plan {
     double* h_filt_dev = nullptr;
     InFlight ring[RING];
     unsigned long long seq_submit = 0, seq_collect = 0;
-    unsigned long long unit_submit = 0;  // units submitted so far (InFlight::unit)
+    unsigned long long unit_submit = 0;  // units submitted so far (FrameInfo::unit)
     Stream streams[VNECT_MAX_STREAMS];
     TrackState* d_track = nullptr;  // [VNECT_MAX_STREAMS]: per stream the next crop and its geometry on the device
     TrackOut* h_tout = nullptr;     // pinned, device-mapped, [RING]: rect_used + status of every tracked frame in flight
@@ -355,6 +372,30 @@ int dev_alloc(Plan* p, T** out, size_t count)
     return VNECT_OK;
 }
 
+// a buffer of dev_alloc's back: freed, off the plan's list, the pointer null.  The caller has synchronised whatever may still use it.
+template <typename T>
+int dev_free(Plan* p, T** buf)
+{
+    if (!*buf) return VNECT_OK;
+    HIPCK(p, hipFree(*buf));
+    p->dev_allocs.erase(std::find(p->dev_allocs.begin(), p->dev_allocs.end(), (void*)*buf));
+    *buf = nullptr;
+    return VNECT_OK;
+}
+
+// the grow-on-demand buffer: room for `need` elements, never shrunk; *cap moves only when the new buffer is there
+template <typename T>
+int dev_grow(Plan* p, T** buf, size_t* cap, size_t need)
+{
+    if (need <= *cap) return VNECT_OK;
+    int rc = dev_free(p, buf);
+    if (rc) return rc;
+    *cap = 0;
+    if ((rc = dev_alloc(p, buf, need))) return rc;
+    *cap = need;
+    return VNECT_OK;
+}
+
 // Parameters (packed weights, biases, BN vectors) are carved out of a few large blocks instead of ~150 separate
 // allocations: contiguous, 256-byte aligned, and mapped with large page fragments, so a layer's first touch of its
 // weights does not start with a page-table walk per 4 KiB.
@@ -442,6 +483,20 @@ struct FrameSrc {
     PreviewArgs pv{};        // everything but `out` and `pitch`, which are the ring slot's
     OverlayInput pv_in{};    // the style
 };
+// a frame in a resident slot as the kernels address it
+inline FrameDyn slot_dyn(const vnect_handle* h, int slot, double t2d, double t3d)
+{
+    FrameDyn dyn{};
+    dyn.t2d = t2d, dyn.t3d = t3d;
+    dyn.row_stride = h->slots[slot].stride;
+    dyn.frame = h->frames + (size_t)slot * h->cfg.max_frame_bytes;
+    return dyn;
+}
+// the ring's pictures: room for `need` bytes per slot (only with nothing in flight: the callers see to that); slot `ring`'s picture of `bytes`
+// bytes to its pinned buffer, on `st`; teardown of the pinned buffers (the device buffers are on the handle's list)
+int ring_pictures_size(vnect_handle* h, RingPictures& p, size_t need);
+int ring_pictures_copy(vnect_handle* h, const RingPictures& p, int ring, size_t bytes, hipStream_t st);
+void ring_pictures_free_host(RingPictures& p);
 // tk: a tracked frame (vnect_submit_tracked*) -- in `slot` (SRC_SLOT) or where tk says (slot is -1 then)
 int enqueue_frame(vnect_handle* h, int slot, double t2d, double t3d, int* ring_out, int stream = 0, const FrameSrc* tk = nullptr);
 int collect_impl(vnect_handle* h, double* j2, float* j3, int32_t* stream_out = nullptr, int32_t* rect_out = nullptr);
