@@ -117,27 +117,67 @@ def test_pyramid_cases_meet_their_conditions():
     assert {1, 2, 3} <= thin
 
 
+def _make(*args):
+    return subprocess.check_output(["make", "-C", tc.CSRC] + list(args), text=True)
+
+
+def _db_rule(db, target):
+    """(prerequisites, recipe lines as written) of `target` in the database `make -p` prints"""
+    block = re.search(r"^%s:(.*)\n((?:.+\n)*)" % re.escape(target), db, re.M)
+    return block.group(1).split(), [ln for ln in block.group(2).splitlines() if ln.startswith("\t")]
+
+
 def test_trackprobe_links_the_products_objects():
-    """`make trackprobe` links the object files the shipped library links: its prerequisites are $(OBJ)/track.o and $(OBJ)/post.o, and no
-    .hip is compiled for it (the only compile of its own is the shim, track_probe.cpp)."""
+    """`make trackprobe` links the object files the shipped library links: its prerequisites, as make resolves them, are the product's
+    track.o and post.o, and no .hip is compiled for it (the only compile of its own is the shim, track_probe.cpp)."""
+    db = _make("-pn", "trackprobe")
+    prereq, recipe = _db_rule(db, "../lib/libvnect_trackprobe.so")
+    shipped, _ = _db_rule(_make("-pn"), "../lib/libvnect_hip.so")
+    assert "../lib/obj/track.o" in shipped and "../lib/obj/post.o" in shipped
+    assert prereq == ["../lib/obj/track.o", "../lib/obj/post.o", "../lib/obj/track_probe.o"], prereq
+    assert len(recipe) == 1 and "$(filter %.o,$^)" in recipe[0] and ".hip" not in recipe[0] and " -c " not in recipe[0], recipe
+    # one compile rule each for track.o and post.o, the product's: one rule line in the Makefile, and in a build from nothing one
+    # command that writes the object, the same command the product's own build runs
     mk = open(os.path.join(tc.CSRC, "Makefile")).read()
-    rule = re.search(r"^\$\(OUT\)/libvnect_trackprobe\$\(VARIANT\)\.so:(.*)\n\t(.*)$", mk, re.M)
-    shipped = re.search(r"^\$\(OUT\)/libvnect_hip\$\(VARIANT\)\.so:(.*)$", mk, re.M).group(1).split()
-    prereq = rule.group(1).split()
-    assert "$(OBJ)/track.o" in prereq and "$(OBJ)/post.o" in prereq and "$(OBJ)/track.o" in shipped and "$(OBJ)/post.o" in shipped
-    assert [p for p in prereq if p.endswith(".o")] == ["$(OBJ)/track.o", "$(OBJ)/post.o", "$(OBJ)/track_probe.o"], prereq
-    assert "$(filter %.o,$^)" in rule.group(2) and ".hip" not in rule.group(2) and " -c " not in rule.group(2)
-    assert len(re.findall(r"^\$\(OBJ\)/(?:track|post)\.o:", mk, re.M)) == 2      # one rule each: the product's
-    # what make would run if only the shim had changed: the shim's compile and the link of the three objects, nothing else
-    out = subprocess.check_output(["make", "-C", tc.CSRC, "-n", "-W", "track_probe.cpp", "-o", "../lib/obj/track.o", "-o", "../lib/obj/post.o",
-                                   "trackprobe"], text=True)
-    cmds = [ln for ln in out.splitlines() if "hipcc" in ln]
-    assert len(cmds) == 2 and "-c track_probe.cpp" in cmds[0] and ".hip" not in out, out
-    assert "../lib/obj/track.o ../lib/obj/post.o ../lib/obj/track_probe.o" in cmds[1] and "libvnect_trackprobe.so" in cmds[1], cmds[1]
+    assert len(re.findall(r"^\$\(OBJ\)/(?:track|post)\.o:", mk, re.M)) == 2
+    product, probe = _make("-n", "-B").splitlines(), _make("-n", "-B", "trackprobe").splitlines()
+    for k in ("track", "post"):
+        writes = [ln for ln in probe if "-o ../lib/obj/%s.o" % k in ln]
+        assert len(writes) == 1 and "-c %s.hip" % k in writes[0] and product.count(writes[0]) == 1, writes
     # ... and the product does not know it: not in the exported-symbol map, not loaded by the binding
     assert "tp_" not in open(os.path.join(tc.CSRC, "vnect.map")).read()
     native = open(os.path.join(tc.ROOT, "vnect_amd", "_native.py")).read()
     assert "CDLL(LIB_PATH)" in native and "CDLL(TRACKPROBE" not in native
+
+
+PROBE_LINKS = {   # probe: its shim, and the product's objects it links, in link order
+    "track": ("track_probe.cpp", ["track", "post"]),
+    "nv12": ("nv12_probe.cpp", ["track", "post"]),
+    "ingest": ("ingest_probe.hip", ["track", "post"]),
+    "overlay": ("overlay_probe.hip", ["overlay"]),
+    "orient": ("orient_probe.hip", ["orient", "track", "post"]),
+    "preview": ("preview_probe.hip", ["preview"]),
+    "hog": ("hog_probe.hip", ["hog"]),
+    "redetect": ("redetect_probe.hip", ["hog"]),
+    "view3d": ("view3d_probe.hip", ["view3d"]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PROBE_LINKS))
+def test_probe_compiles_only_its_shim(name):
+    """What make would run if only a probe's shim had changed: the shim's compile and the link of the product's objects with it,
+    nothing else -- no probe recompiles a kernel."""
+    shim, kernels = PROBE_LINKS[name]
+    objs = ["../lib/obj/%s.o" % k for k in kernels]
+    out = _make("-n", "-W", shim, *[a for o in objs for a in ("-o", o)], name + "probe")
+    cmds = [ln for ln in out.splitlines() if "hipcc" in ln]
+    assert len(cmds) == 2 and "-c %s " % shim in cmds[0] and out.count(".hip") + out.count(".cpp") == 1, out
+    assert " ".join(objs + ["../lib/obj/%s_probe.o" % name]) in cmds[1] and "libvnect_%sprobe.so" % name in cmds[1], cmds[1]
+    assert "-Wl,--no-undefined" in cmds[1] and " -c " not in cmds[1]
+    # every object the probe links besides its shim is one the shipped library links
+    prereq, _ = _db_rule(_make("-pn", name + "probe"), "../lib/libvnect_%sprobe.so" % name)
+    shipped, _ = _db_rule(_make("-pn"), "../lib/libvnect_hip.so")
+    assert prereq == objs + ["../lib/obj/%s_probe.o" % name] and set(objs) <= set(shipped), prereq
 
 
 def test_refusal_scenario_reaches_a_refused_crop():

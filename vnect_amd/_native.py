@@ -310,29 +310,12 @@ VIEW3D_CPU_LIB = os.path.join(_HERE, "lib", "libvnect_view3d.so")         # g++'
 def build(force=False):
     """hipcc --offload-arch=gfx950 build of the library (works without a GPU), and of its test twins: the same kernel objects under a
     host runtime compiled with the test hooks (`make testhooks`; tests/test_gpu_surface.py, tests/test_gpu_track_maps.py), and the
-    tracking kernels' objects behind a probe shim (`make trackprobe`; tests/test_gpu_track_kernels.py).  The product loads neither."""
+    kernels' objects behind probe shims (`make trackprobe` ...; tests/test_gpu_*_kernels.py).  The product loads none of them."""
     src = os.path.join(_HERE, "csrc")
     cmd = ["make", "-C", src] + (["-B"] if force else [])
     subprocess.check_call(cmd, stdout=subprocess.DEVNULL)
-    subprocess.check_call(["make", "-C", src, "testhooks"], stdout=subprocess.DEVNULL)
-    # the tracking kernels' probe (tests/test_gpu_track_kernels.py): the same track.o / post.o behind a test shim
-    subprocess.check_call(["make", "-C", src, "trackprobe"], stdout=subprocess.DEVNULL)
-    # the NV12 copies' probe (tests/test_gpu_nv12_kernels.py) and g++'s build of the conversion itself (tests/test_nv12_cpu.py)
-    subprocess.check_call(["make", "-C", src, "nv12probe", "nv12"], stdout=subprocess.DEVNULL)
-    # the device-frame copies' probe (tests/test_gpu_device_ingest_kernels.py) and g++'s build of their lane windows (tests/test_device_frames_cpu.py)
-    subprocess.check_call(["make", "-C", src, "ingestprobe", "ingest"], stdout=subprocess.DEVNULL)
-    # the overlay's probe (tests/test_gpu_overlay_kernels.py) and g++'s build of the drawing rule (tests/test_overlay_cpu.py)
-    subprocess.check_call(["make", "-C", src, "overlayprobe", "overlay"], stdout=subprocess.DEVNULL)
-    # the oriented copies' probe (tests/test_gpu_orient_kernels.py) and g++'s build of their tile walk (tests/test_orient_cpu.py)
-    subprocess.check_call(["make", "-C", src, "orientprobe", "orient"], stdout=subprocess.DEVNULL)
-    # the preview's probe (tests/test_gpu_preview_kernels.py) and g++'s build of its tile walk (tests/test_preview_cpu.py)
-    subprocess.check_call(["make", "-C", src, "previewprobe", "preview"], stdout=subprocess.DEVNULL)
-    # the detector's probe (tests/test_gpu_hog_kernels.py) and g++'s build of its walk (tests/test_hog_cpu.py)
-    subprocess.check_call(["make", "-C", src, "hogprobe", "hog"], stdout=subprocess.DEVNULL)
-    # the re-detection's probe (tests/test_gpu_redetect_kernels.py): the same hog.o behind csrc/redetect_probe.hip
-    subprocess.check_call(["make", "-C", src, "redetectprobe"], stdout=subprocess.DEVNULL)
-    # the 3-D view's probe (tests/test_gpu_view3d_kernels.py) and g++'s build of its tile walk (tests/test_view3d_cpu.py)
-    subprocess.check_call(["make", "-C", src, "view3dprobe", "view3d"], stdout=subprocess.DEVNULL)
+    # the test-hooks twin, the nine kernel probes and g++'s builds of the kernels' headers: the tables of csrc/Makefile behind `make tests`
+    subprocess.check_call(["make", "-C", src, "tests"], stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 

@@ -13,6 +13,7 @@
 #include "hostplan.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -22,61 +23,17 @@ enum { IP_OK = 0, IP_E_FRAME = 1, IP_E_RECT = 2, IP_E_ROOM = 3, IP_E_GEOM = 4 };
 constexpr uint8_t DST_FILL = 0xC7;  // the canary a destination holds before its launch
 constexpr int DST_GUARD = 64;       // canary bytes in front of and behind every destination (which starts 64-byte aligned, plus its phase)
 
-#define IP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device allocations of one call, freed however it ends
-    std::vector<void*> dev;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-};
-
 int check_frame(int64_t cap, int64_t data_off, int H, int W, int64_t sy, int64_t sx, int64_t sc)
 {
-    if (cap < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20) || sy < 1 || sx < 1 || sc < 1 || sy > (1 << 24) || sx > (1 << 20) || sc > (1 << 28) || data_off < 0)
-        return IP_E_FRAME;
-    return data_off + ingest_span(H, W, sy, sx, sc) > cap ? IP_E_FRAME : IP_OK;
+    return packed_fits(cap, data_off, H, W, sy, sx, sc, 1 << 20) ? IP_OK : IP_E_FRAME;
 }
-int check_rect(const int32_t* r, int H, int W)
-{
-    return (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || (int64_t)r[0] + r[2] > W || (int64_t)r[1] + r[3] > H) ? IP_E_RECT : IP_OK;
-}
+int check_rect(const int32_t* r, int H, int W) { return rect_inside(r, H, W) ? IP_OK : IP_E_RECT; }
 TrackState state_of(const int32_t* r, int H, int W)
 {
     TrackState t;
     memset(&t, 0, sizeof t);
     t.x = r[0], t.y = r[1], t.w = t.uw = r[2], t.h = t.uh = r[3], t.H = H, t.W = W;
     return t;
-}
-
-// `buf` (cap bytes) into an allocation of its own of exactly cap bytes (rounded up only as hipMalloc rounds): flush against the start of
-// the allocation's address range, or (flush_end) against its end.  lo / end: the range as hipMemGetAddressRange reports it.
-int place(Dev& D, const uint8_t* buf, int64_t cap, int flush_end, uint8_t** frame, uint8_t** lo, uint8_t** end)
-{
-    uint8_t* a = nullptr;
-    IP_HIP(D.alloc((void**)&a, (size_t)cap));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    IP_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a));
-    if ((uint8_t*)base > a || size < (size_t)cap + (size_t)(a - (uint8_t*)base)) return -999;
-    *lo = (uint8_t*)base, *end = (uint8_t*)base + size;
-    *frame = flush_end ? *end - cap : *lo;
-    IP_HIP(hipMemsetAsync(base, 0x5A, size, D.st));
-    IP_HIP(hipMemcpyAsync(*frame, buf, (size_t)cap, hipMemcpyHostToDevice, D.st));
-    return 0;
 }
 
 // a bounded wait on the 100 MHz clock: at most `ticks` ticks, and at most 2^24 passes whatever the clock does
@@ -119,27 +76,26 @@ int ip_copy(const uint8_t* buf, int64_t cap, int flush_end, int64_t data_off, in
     }
     if (bad) return bad;
     Dev D;
-    IP_HIP(hipStreamCreate(&D.st));
-    const size_t region = (size_t)dst_cap + 2 * DST_GUARD;
-    uint8_t *frame = nullptr, *lo = nullptr, *end = nullptr, *dst = nullptr;
+    PROBE_HIP(hipStreamCreate(&D.st));
+    uint8_t *frame = nullptr, *lo = nullptr, *end = nullptr;
     TrackState* ds = nullptr;
+    Guarded dst;
     int rc = place(D, buf, cap, flush_end, &frame, &lo, &end);
     if (rc) return rc;
     std::vector<TrackState> hs(n);
     for (int i = 0; i < n; i++) hs[i] = state_of(rects + 4 * i, H, W);
-    IP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    IP_HIP(D.alloc((void**)&dst, (size_t)n * region));
-    IP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    IP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dst, (size_t)dst_cap, DST_GUARD, DST_FILL, nullptr, n));
     const IngestSrc s = {frame + data_off, (long long)sy, (long long)sx, (long long)sc, lo, end, order};
     for (int i = 0; i < n; i++) {
-        uint8_t* d = dst + (size_t)i * region + DST_GUARD + phase;
+        uint8_t* d = dst.data(i) + phase;
         const int32_t* r = rects + 4 * i;
-        if (mode[i] & 1) IP_HIP(launch_ingest_copy_track(&ds[i], s, d, H, W, D.st, (mode[i] >> 1) & 1));
-        else IP_HIP(launch_ingest_copy(s, H, W, r[0], r[1], r[2], r[3], d, D.st, (mode[i] >> 1) & 1));
+        if (mode[i] & 1) PROBE_HIP(launch_ingest_copy_track(&ds[i], s, d, H, W, D.st, (mode[i] >> 1) & 1));
+        else PROBE_HIP(launch_ingest_copy(s, H, W, r[0], r[1], r[2], r[3], d, D.st, (mode[i] >> 1) & 1));
     }
-    IP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
-    IP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(read_regions(D, dst, dst_out));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -163,29 +119,27 @@ int ip_copy_nv12(const uint8_t* ybuf, int64_t ycap, int64_t y_off, int64_t ys, c
     }
     if (bad) return bad;
     Dev D;
-    IP_HIP(hipStreamCreate(&D.st));
-    const size_t region = (size_t)dst_cap + 2 * DST_GUARD;
-    uint8_t *yf = nullptr, *ylo = nullptr, *yend = nullptr, *uf = nullptr, *ulo = nullptr, *uend = nullptr, *dst = nullptr;
+    PROBE_HIP(hipStreamCreate(&D.st));
+    uint8_t *yf = nullptr, *ylo = nullptr, *yend = nullptr, *uf = nullptr, *ulo = nullptr, *uend = nullptr;
     TrackState* ds = nullptr;
+    Guarded dst;
     int rc = place(D, ybuf, ycap, 1, &yf, &ylo, &yend);
     if (rc) return rc;
     if ((rc = place(D, uvbuf, uvcap, 0, &uf, &ulo, &uend))) return rc;
     std::vector<TrackState> hs(n);
     for (int i = 0; i < n; i++) hs[i] = state_of(rects + 4 * i, H, W);
-    IP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    IP_HIP(D.alloc((void**)&dst, (size_t)n * region));
-    IP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    IP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dst, (size_t)dst_cap, DST_GUARD, DST_FILL, nullptr, n));
     Nv12Src s = {yf + y_off, (long long)ys, uf + uv_off, (long long)uvs, ylo, yend};
     s.uv_lo = ulo, s.uv_end = uend, s.any_bounds = 1;
     for (int i = 0; i < n; i++) {
-        uint8_t* d = dst + (size_t)i * region + DST_GUARD;
         const int32_t* r = rects + 4 * i;
-        if (mode[i] & 1) IP_HIP(launch_nv12_copy_track(&ds[i], s, d, H, W, D.st));
-        else IP_HIP(launch_nv12_copy(s, r[0], r[1], r[2], r[3], d, D.st));
+        if (mode[i] & 1) PROBE_HIP(launch_nv12_copy_track(&ds[i], s, dst.data(i), H, W, D.st));
+        else PROBE_HIP(launch_nv12_copy(s, r[0], r[1], r[2], r[3], dst.data(i), D.st));
     }
-    IP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
-    IP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(read_regions(D, dst, dst_out));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -207,28 +161,28 @@ int ip_pyramid(const uint8_t* buf, int64_t cap, int H, int W, int64_t sy, int64_
     hs[0].status = crop_squarify(hs[0].h, hs[0].w, &hs[0].fp);
     if (hs[0].status != SQ_OK) return IP_E_GEOM;
     Dev D;
-    IP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     const size_t per = (size_t)S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
     uint8_t *frame = nullptr, *lo = nullptr, *end = nullptr, *crop = nullptr, *dout = nullptr;
     TrackState* ds = nullptr;
     ScaleTabs* dt = nullptr;
     int rc = place(D, buf, cap, 0, &frame, &lo, &end);
     if (rc) return rc;
-    IP_HIP(D.alloc((void**)&crop, (size_t)3 * rect[2] * rect[3] + 16));
-    IP_HIP(D.alloc((void**)&ds, sizeof(TrackState)));
-    IP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
-    IP_HIP(D.alloc((void**)&dout, per));
-    IP_HIP(hipMemcpyAsync(ds, hs.data(), sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    IP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
-    IP_HIP(hipMemsetAsync(crop, DST_FILL, (size_t)3 * rect[2] * rect[3] + 16, D.st));
-    IP_HIP(hipMemsetAsync(dout, 0xFF, per, D.st));
+    PROBE_HIP(D.alloc((void**)&crop, (size_t)3 * rect[2] * rect[3] + 16));
+    PROBE_HIP(D.alloc((void**)&ds, sizeof(TrackState)));
+    PROBE_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    PROBE_HIP(D.alloc((void**)&dout, per));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemsetAsync(crop, DST_FILL, (size_t)3 * rect[2] * rect[3] + 16, D.st));
+    PROBE_HIP(hipMemsetAsync(dout, 0xFF, per, D.st));
     const IngestSrc s = {frame, (long long)sy, (long long)sx, (long long)sc, lo, end, order};
-    IP_HIP(launch_ingest_copy_track(ds, s, crop, H, W, D.st));
+    PROBE_HIP(launch_ingest_copy_track(ds, s, crop, H, W, D.st));
     FrameDyn dyn = {};
     dyn.frame = crop;
-    IP_HIP(launch_pyramid_track(ds, dyn, 1, dt, dout, S, el, D.st));
-    IP_HIP(hipMemcpyAsync(out, dout, per, hipMemcpyDeviceToHost, D.st));
-    IP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(launch_pyramid_track(ds, dyn, 1, dt, dout, S, el, D.st));
+    PROBE_HIP(hipMemcpyAsync(out, dout, per, hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -241,51 +195,38 @@ int ip_time_copy(const void* frame_dev, const void* uv_dev, int format, int H, i
     if (!frame_dev || reps < 1 || reps > 10000 || check_rect(rect, H, W)) return IP_E_RECT;
     hipDeviceptr_t base = nullptr, ubase = nullptr;
     size_t size = 0, usize = 0;
-    IP_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)frame_dev));
+    PROBE_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)frame_dev));
     const uint8_t *lo = (const uint8_t*)base, *end = lo + size, *f = (const uint8_t*)frame_dev;
     if (format == 2) {
         if (!uv_dev || H < 2 || W < 2 || ((H | W) & 1) || sy < W || uvs < W) return IP_E_FRAME;
-        IP_HIP(hipMemGetAddressRange(&ubase, &usize, (hipDeviceptr_t)uv_dev));
+        PROBE_HIP(hipMemGetAddressRange(&ubase, &usize, (hipDeviceptr_t)uv_dev));
         if ((int64_t)(end - f) < (int64_t)(H - 1) * sy + W || (int64_t)((const uint8_t*)ubase + usize - (const uint8_t*)uv_dev) < (int64_t)(H / 2 - 1) * uvs + W) return IP_E_FRAME;
     } else if (sy < 1 || sx < 1 || sc < 1 || (int64_t)(end - f) < ingest_span(H, W, sy, sx, sc)) {
         return IP_E_FRAME;
     }
     Dev D;
-    IP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     uint8_t* dst = nullptr;
-    IP_HIP(D.alloc((void**)&dst, (size_t)3 * rect[2] * rect[3] + 64));
-    hipEvent_t e0, e1;
-    IP_HIP(hipEventCreate(&e0));
-    IP_HIP(hipEventCreate(&e1));
+    PROBE_HIP(D.alloc((void**)&dst, (size_t)3 * rect[2] * rect[3] + 64));
     const IngestSrc s = {f, (long long)sy, (long long)sx, (long long)sc, lo, end, format == 1 ? INGEST_RGB : INGEST_BGR};
     Nv12Src n = {f, (long long)sy, (const uint8_t*)uv_dev, (long long)uvs, lo, end};
     n.uv_lo = (const uint8_t*)ubase, n.uv_end = (const uint8_t*)ubase + usize, n.any_bounds = 1;
-    int rc = 0;
-    for (int i = -3; i < reps && !rc; i++) {  // (three warm launches)
-        hipError_t e = hipEventRecord(e0, D.st);
-        if (e == hipSuccess) e = format == 2 ? launch_nv12_copy(n, rect[0], rect[1], rect[2], rect[3], dst, D.st)
-                                             : launch_ingest_copy(s, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st, force_generic);
-        if (e == hipSuccess) e = hipEventRecord(e1, D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) rc = -(int)e - 1000;
-        else if (i >= 0) ms_out[i] = ms;
-    }
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-    return rc;
+    return timed_launches(D.st, reps, ms_out, [&](int) {
+        return format == 2 ? launch_nv12_copy(n, rect[0], rect[1], rect[2], rect[3], dst, D.st)
+                           : launch_ingest_copy(s, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st, force_generic);
+    });
 }
 
 // ---- device memory and streams for tests/test_gpu_device_frames.py -----------------------------------------------------------------------
 int ip_alloc(int64_t bytes, void** p)
 {
     if (bytes < 1 || !p) return IP_E_ROOM;
-    IP_HIP(hipMalloc(p, (size_t)bytes));
+    PROBE_HIP(hipMalloc(p, (size_t)bytes));
     return 0;
 }
 int ip_free(void* p)
 {
-    IP_HIP(hipFree(p));
+    PROBE_HIP(hipFree(p));
     return 0;
 }
 // the allocation `p` lies in: out[0] its base, out[1] its size (hipMemGetAddressRange)
@@ -293,38 +234,38 @@ int ip_range(const void* p, int64_t* out)
 {
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    IP_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p));
+    PROBE_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p));
     out[0] = (int64_t)(uintptr_t)base, out[1] = (int64_t)size;
     return 0;
 }
 int ip_h2d(void* dst, const void* src, int64_t n)
 {
-    IP_HIP(hipMemcpy(dst, src, (size_t)n, hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemcpy(dst, src, (size_t)n, hipMemcpyHostToDevice));
     return 0;
 }
 int ip_d2h(void* dst, const void* src, int64_t n)
 {
-    IP_HIP(hipMemcpy(dst, src, (size_t)n, hipMemcpyDeviceToHost));
+    PROBE_HIP(hipMemcpy(dst, src, (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 int ip_fill(void* dst, int value, int64_t n)
 {
-    IP_HIP(hipMemset(dst, value, (size_t)n));
+    PROBE_HIP(hipMemset(dst, value, (size_t)n));
     return 0;
 }
 int ip_stream_create(void** st)
 {
-    IP_HIP(hipStreamCreateWithFlags((hipStream_t*)st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags((hipStream_t*)st, hipStreamNonBlocking));
     return 0;
 }
 int ip_stream_sync(void* st)
 {
-    IP_HIP(hipStreamSynchronize((hipStream_t)st));
+    PROBE_HIP(hipStreamSynchronize((hipStream_t)st));
     return 0;
 }
 int ip_stream_destroy(void* st)
 {
-    IP_HIP(hipStreamDestroy((hipStream_t)st));
+    PROBE_HIP(hipStreamDestroy((hipStream_t)st));
     return 0;
 }
 // On `st`, without waiting: a kernel that spins `ms` milliseconds (at most 50) on the 100 MHz clock, then the copy of n bytes from
@@ -333,8 +274,8 @@ int ip_delayed_copy(void* st, void* dst_dev, const void* src_dev, int64_t n, dou
 {
     if (!(ms >= 0) || ms > 50 || n < 1) return IP_E_GEOM;
     hipLaunchKernelGGL(ip_spin_kernel, dim3(1), dim3(1), 0, (hipStream_t)st, (long long)(ms * 1e5), (unsigned*)nullptr);
-    IP_HIP(hipGetLastError());
-    IP_HIP(hipMemcpyAsync(dst_dev, src_dev, (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)st));
+    PROBE_HIP(hipGetLastError());
+    PROBE_HIP(hipMemcpyAsync(dst_dev, src_dev, (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)st));
     return 0;
 }
 

@@ -13,6 +13,7 @@
 #include "hostplan.h"
 #include "kernels.h"
 #include "nv12.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -21,35 +22,6 @@ namespace {
 enum { NP_OK = 0, NP_E_FRAME = 1, NP_E_RECT = 2, NP_E_ROOM = 3, NP_E_GEOM = 4 };
 constexpr uint8_t DST_FILL = 0xC7;  // the canary a destination holds before its launch
 constexpr int DST_GUARD = 64;       // canary bytes in front of and behind every destination (which starts 64-byte aligned)
-
-#define NP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device / pinned allocations of one call, freed however it ends
-    std::vector<void*> dev, host;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-        for (void* p : host) (void)hipHostFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-    hipError_t pinned(void** p, size_t n)
-    {
-        const hipError_t e = hipHostMalloc(p, n ? n : 4, hipHostMallocMapped);
-        if (e == hipSuccess) host.push_back(*p);
-        return e;
-    }
-};
 
 // an (H, W) NV12 image inside `cap` bytes: Y plane at y_off, rows ys apart; UV plane at uv_off, rows uvs apart; planes disjoint
 int check_image(int64_t cap, int64_t y_off, int64_t ys, int64_t uv_off, int64_t uvs, int H, int W)
@@ -60,10 +32,7 @@ int check_image(int64_t cap, int64_t y_off, int64_t ys, int64_t uv_off, int64_t 
     if (y_off < uv_end && uv_off < y_end) return NP_E_FRAME;
     return NP_OK;
 }
-int check_rect(const int32_t* r, int H, int W)
-{
-    return (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || (int64_t)r[0] + r[2] > W || (int64_t)r[1] + r[3] > H) ? NP_E_RECT : NP_OK;
-}
+int check_rect(const int32_t* r, int H, int W) { return rect_inside(r, H, W) ? NP_OK : NP_E_RECT; }
 TrackState state_of(const int32_t* r, int H, int W)
 {
     TrackState t;
@@ -98,29 +67,28 @@ int np_copy(const uint8_t* buf, int64_t cap, int64_t y_off, int64_t ys, int64_t 
     }
     if (bad) return bad;
     Dev D;
-    NP_HIP(hipStreamCreate(&D.st));
-    const size_t pcap = ((size_t)cap + 3) & ~(size_t)3, region = (size_t)dst_cap + 2 * DST_GUARD;
-    uint8_t *pin = nullptr, *pin_dev = nullptr, *dst = nullptr;
+    PROBE_HIP(hipStreamCreate(&D.st));
+    const size_t pcap = ((size_t)cap + 3) & ~(size_t)3;
+    uint8_t *pin = nullptr, *pin_dev = nullptr;
     TrackState* ds = nullptr;
-    NP_HIP(D.pinned((void**)&pin, pcap));
-    NP_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
+    Guarded dst;
+    PROBE_HIP(D.pinned((void**)&pin, pcap));
+    PROBE_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
     memset(pin, 0, pcap);
     memcpy(pin, buf, (size_t)cap);
     std::vector<TrackState> hs(n);
     for (int i = 0; i < n; i++) hs[i] = state_of(rects + 4 * i, H, W);
-    NP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    NP_HIP(D.alloc((void**)&dst, (size_t)n * region));
-    NP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    NP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dst, (size_t)dst_cap, DST_GUARD, DST_FILL, nullptr, n));
     const Nv12Src s = {pin_dev + y_off, (long long)ys, pin_dev + uv_off, (long long)uvs, pin_dev, pin_dev + pcap};
     for (int i = 0; i < n; i++) {
-        uint8_t* d = dst + (size_t)i * region + DST_GUARD;
         const int32_t* r = rects + 4 * i;
-        if (tracked[i]) NP_HIP(launch_nv12_copy_track(&ds[i], s, d, H, W, D.st));
-        else NP_HIP(launch_nv12_copy(s, r[0], r[1], r[2], r[3], d, D.st));
+        if (tracked[i]) PROBE_HIP(launch_nv12_copy_track(&ds[i], s, dst.data(i), H, W, D.st));
+        else PROBE_HIP(launch_nv12_copy(s, r[0], r[1], r[2], r[3], dst.data(i), D.st));
     }
-    NP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
-    NP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(read_regions(D, dst, dst_out));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -142,30 +110,30 @@ int np_pyramid(const uint8_t* nv12, int H, int W, const int32_t* rect, const dou
     hs[0].status = crop_squarify(hs[0].h, hs[0].w, &hs[0].fp);
     if (hs[0].status != SQ_OK) return NP_E_GEOM;
     Dev D;
-    NP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     const size_t pcap = ((size_t)cap + 3) & ~(size_t)3, per = (size_t)S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
     uint8_t *pin = nullptr, *pin_dev = nullptr, *crop = nullptr, *dout = nullptr;
     TrackState* ds = nullptr;
     ScaleTabs* dt = nullptr;
-    NP_HIP(D.pinned((void**)&pin, pcap));
-    NP_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
+    PROBE_HIP(D.pinned((void**)&pin, pcap));
+    PROBE_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
     memset(pin, 0, pcap);
     memcpy(pin, nv12, (size_t)cap);
-    NP_HIP(D.alloc((void**)&crop, (size_t)3 * rect[2] * rect[3] + 16));
-    NP_HIP(D.alloc((void**)&ds, sizeof(TrackState)));
-    NP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
-    NP_HIP(D.alloc((void**)&dout, per));
-    NP_HIP(hipMemcpyAsync(ds, hs.data(), sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    NP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
-    NP_HIP(hipMemsetAsync(crop, DST_FILL, (size_t)3 * rect[2] * rect[3] + 16, D.st));
-    NP_HIP(hipMemsetAsync(dout, 0xFF, per, D.st));
+    PROBE_HIP(D.alloc((void**)&crop, (size_t)3 * rect[2] * rect[3] + 16));
+    PROBE_HIP(D.alloc((void**)&ds, sizeof(TrackState)));
+    PROBE_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    PROBE_HIP(D.alloc((void**)&dout, per));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemsetAsync(crop, DST_FILL, (size_t)3 * rect[2] * rect[3] + 16, D.st));
+    PROBE_HIP(hipMemsetAsync(dout, 0xFF, per, D.st));
     const Nv12Src s = {pin_dev, (long long)W, pin_dev + (size_t)H * W, (long long)W, pin_dev, pin_dev + pcap};
-    NP_HIP(launch_nv12_copy_track(ds, s, crop, H, W, D.st));
+    PROBE_HIP(launch_nv12_copy_track(ds, s, crop, H, W, D.st));
     FrameDyn dyn = {};
     dyn.frame = crop;
-    NP_HIP(launch_pyramid_track(ds, dyn, 1, dt, dout, S, el, D.st));
-    NP_HIP(hipMemcpyAsync(out, dout, per, hipMemcpyDeviceToHost, D.st));
-    NP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(launch_pyramid_track(ds, dyn, 1, dt, dout, S, el, D.st));
+    PROBE_HIP(hipMemcpyAsync(out, dout, per, hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 

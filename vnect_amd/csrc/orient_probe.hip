@@ -11,6 +11,7 @@
 
 #include "kernels.h"
 #include "orient.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -19,45 +20,6 @@ namespace {
 enum { OP_OK = 0, OP_E_FRAME = 1, OP_E_RECT = 2, OP_E_ROOM = 3 };
 constexpr uint8_t DST_FILL = 0xC7;  // the canary a destination holds before its launch
 constexpr int DST_GUARD = 64;       // canary bytes in front of and behind every destination (which starts 64-byte aligned, plus its phase)
-
-#define OP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device allocations of one call, freed however it ends
-    std::vector<void*> dev;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-};
-
-// `buf` (cap bytes) into an allocation of its own of exactly cap bytes (rounded up only as hipMalloc rounds): flush against the start of
-// the allocation's address range, or (flush_end) against its end.  lo / end: the range as hipMemGetAddressRange reports it.
-int place(Dev& D, const uint8_t* buf, int64_t cap, int flush_end, uint8_t** frame, uint8_t** lo, uint8_t** end)
-{
-    uint8_t* a = nullptr;
-    OP_HIP(D.alloc((void**)&a, (size_t)cap));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    OP_HIP(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a));
-    if ((uint8_t*)base > a || size < (size_t)cap + (size_t)(a - (uint8_t*)base)) return -999;
-    *lo = (uint8_t*)base, *end = (uint8_t*)base + size;
-    *frame = flush_end ? *end - cap : *lo;
-    OP_HIP(hipMemsetAsync(base, 0x5A, size, D.st));
-    OP_HIP(hipMemcpyAsync(*frame, buf, (size_t)cap, hipMemcpyHostToDevice, D.st));
-    return 0;
-}
 
 }  // namespace
 
@@ -92,16 +54,16 @@ int op_copy(const uint8_t* buf0, int64_t cap0, int64_t off0, const uint8_t* buf1
     for (int i = 0; i < n; i++) {
         const int32_t* r = rects + 4 * i;
         err[i] = fe;
-        if (!err[i] && (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || (int64_t)r[0] + r[2] > Wo || (int64_t)r[1] + r[3] > Ho)) err[i] = OP_E_RECT;
+        if (!err[i] && !rect_inside(r, Ho, Wo)) err[i] = OP_E_RECT;
         if (!err[i] && (dst_cap < 64 || dst_cap % 64 != 0 || 3LL * r[2] * r[3] + phase > dst_cap)) err[i] = OP_E_ROOM;
         bad += err[i] != OP_OK;
     }
     if (bad) return bad;
     Dev D;
-    OP_HIP(hipStreamCreate(&D.st));
-    const size_t region = (size_t)dst_cap + 2 * DST_GUARD;
-    uint8_t *f0 = nullptr, *lo0 = nullptr, *end0 = nullptr, *f1 = nullptr, *lo1 = nullptr, *end1 = nullptr, *dst = nullptr;
+    PROBE_HIP(hipStreamCreate(&D.st));
+    uint8_t *f0 = nullptr, *lo0 = nullptr, *end0 = nullptr, *f1 = nullptr, *lo1 = nullptr, *end1 = nullptr;
     TrackState* ds = nullptr;
+    Guarded dst;
     int rc = place(D, buf0, cap0, flush_end, &f0, &lo0, &end0);
     if (rc) return rc;
     if (form == ORIENT_NV12 && buf1) {
@@ -115,19 +77,18 @@ int op_copy(const uint8_t* buf0, int64_t cap0, int64_t off0, const uint8_t* buf1
         memset(&hs[i], 0, sizeof(TrackState));
         hs[i].x = r[0], hs[i].y = r[1], hs[i].w = hs[i].uw = r[2], hs[i].h = hs[i].uh = r[3], hs[i].H = Ho, hs[i].W = Wo;
     }
-    OP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    OP_HIP(D.alloc((void**)&dst, (size_t)n * region));
-    OP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    OP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dst, (size_t)dst_cap, DST_GUARD, DST_FILL, nullptr, n));
     const OrientSrc s = {f0 + off0, form == ORIENT_NV12 ? f1 + off1 : nullptr, (long long)sy, (long long)sx, (long long)sc, lo0, end0, lo1, end1, form, order};
     for (int i = 0; i < n; i++) {
-        uint8_t* d = dst + (size_t)i * region + DST_GUARD + phase;
+        uint8_t* d = dst.data(i) + phase;
         const int32_t* r = rects + 4 * i;
-        if (tracked[i]) OP_HIP(launch_orient_copy_track(&ds[i], s, o, H, W, d, D.st));
-        else OP_HIP(launch_orient_copy(s, o, H, W, r[0], r[1], r[2], r[3], d, D.st));
+        if (tracked[i]) PROBE_HIP(launch_orient_copy_track(&ds[i], s, o, H, W, d, D.st));
+        else PROBE_HIP(launch_orient_copy(s, o, H, W, r[0], r[1], r[2], r[3], d, D.st));
     }
-    OP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
-    OP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(read_regions(D, dst, dst_out));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -141,56 +102,34 @@ int op_time_copy(int nv12, int pinned, int o, int H, int W, const int32_t* rect,
     int Ho, Wo;
     if (o < 0 || o > 7 || H < 2 || W < 2 || H > 8192 || W > 8192 || ((H | W) & 1) || reps < 1 || reps > 10000) return OP_E_FRAME;
     orient_size(o, H, W, &Ho, &Wo);
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] < 1 || rect[3] < 1 || rect[0] + rect[2] > Wo || rect[1] + rect[3] > Ho) return OP_E_RECT;
+    if (!rect_inside(rect, Ho, Wo)) return OP_E_RECT;
     const size_t bytes = nv12 ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
     Dev D;
-    OP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     uint8_t *f = nullptr, *hostp = nullptr, *dst = nullptr;
     std::vector<uint8_t> noise(bytes);
     for (size_t i = 0; i < bytes; i++) noise[i] = (uint8_t)((i * 2654435761u) >> 13);
     if (pinned) {
-        OP_HIP(hipHostMalloc((void**)&hostp, bytes, hipHostMallocMapped));
+        PROBE_HIP(D.pinned((void**)&hostp, bytes));
         memcpy(hostp, noise.data(), bytes);
-        const hipError_t e = hipHostGetDevicePointer((void**)&f, hostp, 0);
-        if (e != hipSuccess) {
-            (void)hipHostFree(hostp);
-            return -(int)e - 1000;
-        }
+        PROBE_HIP(hipHostGetDevicePointer((void**)&f, hostp, 0));
     } else {
-        OP_HIP(D.alloc((void**)&f, bytes));
-        OP_HIP(hipMemcpy(f, noise.data(), bytes, hipMemcpyHostToDevice));
+        PROBE_HIP(D.alloc((void**)&f, bytes));
+        PROBE_HIP(hipMemcpy(f, noise.data(), bytes, hipMemcpyHostToDevice));
     }
-    int rc = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = D.alloc((void**)&dst, (size_t)3 * rect[2] * rect[3] + 64);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
+    PROBE_HIP(D.alloc((void**)&dst, (size_t)3 * rect[2] * rect[3] + 64));
     const OrientSrc s = {f, nv12 ? f + (size_t)H * W : nullptr, nv12 ? (long long)W : 3LL * W, nv12 ? 1LL : 3LL, nv12 ? (long long)W : 1LL, f, f + bytes, f, f + bytes,
                          nv12 ? (int)ORIENT_NV12 : (int)INGEST_PACKED3, INGEST_BGR};
-    for (int i = -3; i < reps && e == hipSuccess; i++) {  // (three warm launches)
-        e = hipEventRecord(e0, D.st);
-        if (e == hipSuccess && o) e = launch_orient_copy(s, o, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st);
-        else if (e == hipSuccess && nv12) {
+    return timed_launches(D.st, reps, ms_out, [&](int) {
+        if (o) return launch_orient_copy(s, o, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st);
+        if (nv12) {
             const Nv12Src n = {f, (long long)W, f + (size_t)H * W, (long long)W, f, f + bytes};
-            e = launch_nv12_copy(n, rect[0], rect[1], rect[2], rect[3], dst, D.st);
-        } else if (e == hipSuccess && pinned) {
-            e = launch_frame_copy(f + (size_t)rect[1] * 3 * W + 3 * (size_t)rect[0], dst, rect[3], 3 * rect[2], 3LL * W, f + bytes, D.st);
-        } else if (e == hipSuccess) {
-            const IngestSrc g = {f, 3LL * W, 3LL, 1LL, f, f + bytes, INGEST_BGR};
-            e = launch_ingest_copy(g, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st);
+            return launch_nv12_copy(n, rect[0], rect[1], rect[2], rect[3], dst, D.st);
         }
-        if (e == hipSuccess) e = hipEventRecord(e1, D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (i >= 0) ms_out[i] = ms;
-    }
-    if (e != hipSuccess) rc = -(int)e - 1000;
-    (void)hipStreamSynchronize(D.st);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (hostp) (void)hipHostFree(hostp);
-    return rc;
+        if (pinned) return launch_frame_copy(f + (size_t)rect[1] * 3 * W + 3 * (size_t)rect[0], dst, rect[3], 3 * rect[2], 3LL * W, f + bytes, D.st);
+        const IngestSrc g = {f, 3LL * W, 3LL, 1LL, f, f + bytes, INGEST_BGR};
+        return launch_ingest_copy(g, H, W, rect[0], rect[1], rect[2], rect[3], dst, D.st);
+    });
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "crop.h"
 #include "kernels.h"
 #include "overlay.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -20,29 +21,6 @@ namespace {
 enum { OP_OK = 0, OP_E_ARG = 1 };
 constexpr uint8_t GUARD_FILL = 0xC7;
 constexpr int GUARD = 256;  // canary bytes in front of and behind the caller's bytes
-
-#define OP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device allocations of one call, freed however it ends
-    std::vector<void*> dev, pinned;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-        for (void* p : pinned) (void)hipHostFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-};
 
 }  // namespace
 
@@ -61,23 +39,15 @@ int op_draw(uint8_t* buf, int64_t cap, int64_t data_off, int64_t uv_off, int for
             const double* j2d, const double* conf, double min_conf, const int32_t* parents, const int32_t* rect4, const int32_t* limb_bgr,
             const int32_t* rect_bgr, int tracked, int status, uint8_t* guards)
 {
-    if (!buf || !j2d || !limb_bgr || !rect_bgr || !guards || cap < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20) || data_off < 0 || format < 0 || format > 2)
-        return OP_E_ARG;
+    if (!buf || !j2d || !limb_bgr || !rect_bgr || !guards || !frame_fits(cap, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, 1 << 20)) return OP_E_ARG;
     if (tracked && !rect4) return OP_E_ARG;
     OverlayTarget t;
     OverlayInput in;
     memset(&t, 0, sizeof t);
     memset(&in, 0, sizeof in);
     t.H = H, t.W = W;
-    if (format == 2) {
-        if (((H | W) & 1) || sy < W || uv_stride < W || uv_off < 0 || sy > (1 << 24) || uv_stride > (1 << 24)) return OP_E_ARG;
-        if (data_off + (int64_t)(H - 1) * sy + W > cap || uv_off + (int64_t)(H / 2 - 1) * uv_stride + W > cap) return OP_E_ARG;
-        t.nv12 = 1, t.sy = sy, t.sx = 1, t.uv_stride = uv_stride;
-    } else {
-        if (sy < 1 || sx < 1 || sc < 1 || sy > (1 << 24) || sx > (1 << 20) || sc > (1 << 28)) return OP_E_ARG;
-        if (data_off + (int64_t)(H - 1) * sy + (int64_t)(W - 1) * sx + 2 * sc + 1 > cap) return OP_E_ARG;
-        t.sy = sy, t.sx = sx, t.sc = sc;
-    }
+    if (format == 2) t.nv12 = 1, t.sy = sy, t.sx = 1, t.uv_stride = uv_stride;
+    else t.sy = sy, t.sx = sx, t.sc = sc;
     int lc[3], rc[3];
     for (int k = 0; k < 3; k++) {
         lc[k] = limb_bgr[k], rc[k] = rect_bgr[k];
@@ -92,13 +62,11 @@ int op_draw(uint8_t* buf, int64_t cap, int64_t data_off, int64_t uv_off, int for
     if (rect4 && (rect4[2] < 1 || rect4[3] < 1)) return OP_E_ARG;
 
     Dev D;
-    OP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    uint8_t* d = nullptr;
-    OP_HIP(D.alloc((void**)&d, (size_t)cap + 2 * GUARD));
-    OP_HIP(hipMemsetAsync(d, GUARD_FILL, (size_t)cap + 2 * GUARD, D.st));
-    OP_HIP(hipMemcpyAsync(d + GUARD, buf, (size_t)cap, hipMemcpyHostToDevice, D.st));
-    t.data = d + GUARD + data_off;
-    if (t.nv12) t.uv = d + GUARD + uv_off;
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    Guarded d;
+    PROBE_HIP(guarded(D, &d, (size_t)cap, GUARD, GUARD_FILL, buf));
+    t.data = d.data() + data_off;
+    if (t.nv12) t.uv = d.data() + uv_off;
     JointsOut* jo = nullptr;
     TrackOut* to = nullptr;
     ConfOut* co = nullptr;
@@ -111,13 +79,13 @@ int op_draw(uint8_t* buf, int64_t cap, int64_t data_off, int64_t uv_off, int for
         for (int k = 0; k < 4; k++) hto.rect[k] = rect4[k];
         hto.status = status;
         if (conf) memcpy(hco.conf, conf, sizeof hco.conf);
-        OP_HIP(D.alloc((void**)&jo, sizeof hjo));
-        OP_HIP(D.alloc((void**)&to, sizeof hto));
-        OP_HIP(hipMemcpyAsync(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice, D.st));
-        OP_HIP(hipMemcpyAsync(to, &hto, sizeof hto, hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(D.alloc((void**)&jo, sizeof hjo));
+        PROBE_HIP(D.alloc((void**)&to, sizeof hto));
+        PROBE_HIP(hipMemcpyAsync(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(hipMemcpyAsync(to, &hto, sizeof hto, hipMemcpyHostToDevice, D.st));
         if (in.has_conf) {
-            OP_HIP(D.alloc((void**)&co, sizeof hco));
-            OP_HIP(hipMemcpyAsync(co, &hco, sizeof hco, hipMemcpyHostToDevice, D.st));
+            PROBE_HIP(D.alloc((void**)&co, sizeof hco));
+            PROBE_HIP(hipMemcpyAsync(co, &hco, sizeof hco, hipMemcpyHostToDevice, D.st));
         }
     } else {
         memcpy(in.j2d, j2d, sizeof in.j2d);
@@ -127,11 +95,9 @@ int op_draw(uint8_t* buf, int64_t cap, int64_t data_off, int64_t uv_off, int for
             in.has_rect = 1;
         }
     }
-    OP_HIP(launch_overlay(t, in, jo, to, co, D.st));
-    OP_HIP(hipMemcpyAsync(buf, d + GUARD, (size_t)cap, hipMemcpyDeviceToHost, D.st));
-    OP_HIP(hipMemcpyAsync(guards, d, GUARD, hipMemcpyDeviceToHost, D.st));
-    OP_HIP(hipMemcpyAsync(guards + GUARD, d + GUARD + cap, GUARD, hipMemcpyDeviceToHost, D.st));
-    OP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(launch_overlay(t, in, jo, to, co, D.st));
+    PROBE_HIP(read_guarded(D, d, buf, guards));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return OP_OK;
 }
 
@@ -152,7 +118,7 @@ int op_time_draw(void* data_dev, void* uv_dev, int format, int H, int W, int64_t
     overlay_colours(&t, format == 1, OVERLAY_LIMB_BGR, OVERLAY_RECT_BGR);
     for (int i = 0; i < OVERLAY_NJ; i++) in.parents[i] = OVERLAY_PARENTS[i];
     Dev D;
-    OP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     JointsOut* jo = nullptr;
     TrackOut* to = nullptr;
     if (tracked) {
@@ -163,39 +129,23 @@ int op_time_draw(void* data_dev, void* uv_dev, int format, int H, int W, int64_t
         for (int k = 0; k < 4; k++) hto.rect[k] = rect4[k];
         if (tracked == 2) {  // in device-mapped pinned host memory, where the result ring's slots lie
             char* hp = nullptr;
-            OP_HIP(hipHostMalloc((void**)&hp, 4096, hipHostMallocMapped));
-            D.pinned.push_back(hp);
+            PROBE_HIP(D.pinned((void**)&hp, 4096));
             memcpy(hp, &hjo, sizeof hjo), memcpy(hp + 2048, &hto, sizeof hto);
             char* dp = nullptr;
-            OP_HIP(hipHostGetDevicePointer((void**)&dp, hp, 0));
+            PROBE_HIP(hipHostGetDevicePointer((void**)&dp, hp, 0));
             jo = (JointsOut*)dp, to = (TrackOut*)(dp + 2048);
         } else {
-            OP_HIP(D.alloc((void**)&jo, sizeof hjo));
-            OP_HIP(D.alloc((void**)&to, sizeof hto));
-            OP_HIP(hipMemcpy(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice));
-            OP_HIP(hipMemcpy(to, &hto, sizeof hto, hipMemcpyHostToDevice));
+            PROBE_HIP(D.alloc((void**)&jo, sizeof hjo));
+            PROBE_HIP(D.alloc((void**)&to, sizeof hto));
+            PROBE_HIP(hipMemcpy(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice));
+            PROBE_HIP(hipMemcpy(to, &hto, sizeof hto, hipMemcpyHostToDevice));
         }
     } else {
         memcpy(in.j2d, j2d, sizeof in.j2d);
         for (int k = 0; k < 4; k++) in.rect[k] = rect4[k];
         in.has_rect = 1;
     }
-    hipEvent_t e0, e1;
-    OP_HIP(hipEventCreate(&e0));
-    OP_HIP(hipEventCreate(&e1));
-    int rc = OP_OK;
-    for (int i = -3; i < n && rc == OP_OK; i++) {  // (three warm-up launches)
-        hipError_t e = hipEventRecord(e0, D.st);
-        if (e == hipSuccess) e = launch_overlay(t, in, jo, to, nullptr, D.st);
-        if (e == hipSuccess) e = hipEventRecord(e1, D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) rc = -(int)e - 1000;
-        else if (i >= 0) ms_out[i] = ms;
-    }
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-    return rc;
+    return timed_launches(D.st, n, ms_out, [&](int) { return launch_overlay(t, in, jo, to, nullptr, D.st); });
 }
 
 }  // extern "C"

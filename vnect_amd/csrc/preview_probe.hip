@@ -14,6 +14,7 @@
 #include "crop.h"
 #include "kernels.h"
 #include "preview.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -23,39 +24,7 @@ enum { PP_OK = 0, PP_E_ARG = 1 };
 constexpr uint8_t GUARD_FILL = 0xC7;
 constexpr int GUARD = 256;  // canary bytes in front of and behind the output's bytes
 
-#define PP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device allocations of one call, freed however it ends
-    std::vector<void*> dev;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-};
-
-// the frame's description, validated against the src_size bytes it must lie in
-bool frame_ok(int64_t src_size, int64_t data_off, int64_t uv_off, int format, int H, int W, int64_t sy, int64_t sx, int64_t sc, int64_t uv_stride, int orient)
-{
-    if (src_size < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20) || data_off < 0 || format < 0 || format > 2 || !orient_ok(orient)) return false;
-    if (format == 2) {
-        if (((H | W) & 1) || sy < W || uv_stride < W || uv_off < 0 || sy > (1 << 24) || uv_stride > (1 << 24)) return false;
-        return data_off + (int64_t)(H - 1) * sy + W <= src_size && uv_off + (int64_t)(H / 2 - 1) * uv_stride + W <= src_size;
-    }
-    if (sy < 1 || sx < 1 || sc < 1 || sy > (1 << 24) || sx > (1 << 20) || sc > (1 << 28)) return false;
-    return data_off + ingest_span(H, W, sy, sx, sc) <= src_size;
-}
+constexpr int MAX_SIDE = 1 << 20;  // the largest frame side the shim takes
 
 }  // namespace
 
@@ -78,7 +47,8 @@ int pp_preview(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off,
                const int32_t* rect4, const int32_t* limb_bgr, const int32_t* rect_bgr, double factor, int out_format, uint8_t* out, int64_t out_size,
                int64_t out_off, int64_t out_pitch, int uv_separate, int tracked, int status, uint8_t* guards)
 {
-    if (!src || !out || !guards || src_has_rect || !frame_ok(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, orient)) return PP_E_ARG;
+    if (!src || !out || !guards || src_has_rect || !orient_ok(orient)) return PP_E_ARG;
+    if (!frame_fits(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, MAX_SIDE)) return PP_E_ARG;
     if (uv_separate && (format != 2 || uv_off < data_off + (int64_t)(H - 1) * sy + W)) return PP_E_ARG;
     if (tracked && (!j2d || !rect4)) return PP_E_ARG;
     PreviewArgs a;
@@ -102,21 +72,20 @@ int pp_preview(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off,
     if (rect4 && (rect4[2] < 1 || rect4[3] < 1)) return PP_E_ARG;
 
     Dev D;
-    PP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    uint8_t *ds = nullptr, *duv = nullptr, *dout = nullptr;
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    uint8_t *ds = nullptr, *duv = nullptr;
+    Guarded dout;
     const int64_t main_size = uv_separate ? uv_off : src_size;  // the bytes of the first allocation
-    PP_HIP(D.alloc((void**)&ds, (size_t)main_size));
-    PP_HIP(hipMemcpyAsync(ds, src, (size_t)main_size, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)main_size));
+    PROBE_HIP(hipMemcpyAsync(ds, src, (size_t)main_size, hipMemcpyHostToDevice, D.st));
     if (uv_separate) {
-        PP_HIP(D.alloc((void**)&duv, (size_t)(src_size - uv_off)));
-        PP_HIP(hipMemcpyAsync(duv, src + uv_off, (size_t)(src_size - uv_off), hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(D.alloc((void**)&duv, (size_t)(src_size - uv_off)));
+        PROBE_HIP(hipMemcpyAsync(duv, src + uv_off, (size_t)(src_size - uv_off), hipMemcpyHostToDevice, D.st));
     }
-    PP_HIP(D.alloc((void**)&dout, (size_t)out_size + 2 * GUARD));
-    PP_HIP(hipMemsetAsync(dout, GUARD_FILL, (size_t)out_size + 2 * GUARD, D.st));
-    PP_HIP(hipMemcpyAsync(dout + GUARD, out, (size_t)out_size, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dout, (size_t)out_size, GUARD, GUARD_FILL, out));
     a.src = preview_source(format == 2, format == 1, ds + data_off, uv_separate ? duv : ds + uv_off, sy, sx, sc, uv_stride);
     a.H = H, a.W = W, a.o = orient;
-    a.out = dout + GUARD + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
+    a.out = dout.data() + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
     JointsOut* jo = nullptr;
     TrackOut* to = nullptr;
     ConfOut* co = nullptr;
@@ -129,13 +98,13 @@ int pp_preview(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off,
         for (int k = 0; k < 4; k++) hto.rect[k] = rect4[k];
         hto.status = status;
         if (conf) memcpy(hco.conf, conf, sizeof hco.conf);
-        PP_HIP(D.alloc((void**)&jo, sizeof hjo));
-        PP_HIP(D.alloc((void**)&to, sizeof hto));
-        PP_HIP(hipMemcpyAsync(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice, D.st));
-        PP_HIP(hipMemcpyAsync(to, &hto, sizeof hto, hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(D.alloc((void**)&jo, sizeof hjo));
+        PROBE_HIP(D.alloc((void**)&to, sizeof hto));
+        PROBE_HIP(hipMemcpyAsync(jo, &hjo, sizeof hjo, hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(hipMemcpyAsync(to, &hto, sizeof hto, hipMemcpyHostToDevice, D.st));
         if (in.has_conf) {
-            PP_HIP(D.alloc((void**)&co, sizeof hco));
-            PP_HIP(hipMemcpyAsync(co, &hco, sizeof hco, hipMemcpyHostToDevice, D.st));
+            PROBE_HIP(D.alloc((void**)&co, sizeof hco));
+            PROBE_HIP(hipMemcpyAsync(co, &hco, sizeof hco, hipMemcpyHostToDevice, D.st));
         }
         a.has_joints = 1;
     } else {
@@ -146,13 +115,11 @@ int pp_preview(uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_off,
             in.has_rect = 1;
         }
     }
-    PP_HIP(launch_preview(a, in, jo, to, co, D.st));
-    PP_HIP(hipMemcpyAsync(out, dout + GUARD, (size_t)out_size, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(guards, dout, GUARD, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(guards + GUARD, dout + GUARD + out_size, GUARD, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(src, ds, (size_t)main_size, hipMemcpyDeviceToHost, D.st));
-    if (uv_separate) PP_HIP(hipMemcpyAsync(src + uv_off, duv, (size_t)(src_size - uv_off), hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(launch_preview(a, in, jo, to, co, D.st));
+    PROBE_HIP(read_guarded(D, dout, out, guards));
+    PROBE_HIP(hipMemcpyAsync(src, ds, (size_t)main_size, hipMemcpyDeviceToHost, D.st));
+    if (uv_separate) PROBE_HIP(hipMemcpyAsync(src + uv_off, duv, (size_t)(src_size - uv_off), hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return PP_OK;
 }
 
@@ -165,7 +132,7 @@ int pp_preview_people(uint8_t* src, int64_t src_size, int64_t data_off, int64_t 
                       uint8_t* out, int64_t out_size, int64_t out_off, int64_t out_pitch, uint8_t* guards)
 {
     if (!src || !out || !guards || !j2d || !rects || !status || P < 1 || P > PREVIEW_MAX_PEOPLE) return PP_E_ARG;
-    if (!frame_ok(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, orient)) return PP_E_ARG;
+    if (!orient_ok(orient) || !frame_fits(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, MAX_SIDE)) return PP_E_ARG;
     PreviewArgs a;
     OverlayInput in;
     memset(&a, 0, sizeof a);
@@ -187,16 +154,15 @@ int pp_preview_people(uint8_t* src, int64_t src_size, int64_t data_off, int64_t 
     for (int p = 0; p < P; p++)
         if (rects[4 * p + 2] < 1 || rects[4 * p + 3] < 1) return PP_E_ARG;
     Dev D;
-    PP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    uint8_t *ds = nullptr, *dout = nullptr;
-    PP_HIP(D.alloc((void**)&ds, (size_t)src_size));
-    PP_HIP(hipMemcpyAsync(ds, src, (size_t)src_size, hipMemcpyHostToDevice, D.st));
-    PP_HIP(D.alloc((void**)&dout, (size_t)out_size + 2 * GUARD));
-    PP_HIP(hipMemsetAsync(dout, GUARD_FILL, (size_t)out_size + 2 * GUARD, D.st));
-    PP_HIP(hipMemcpyAsync(dout + GUARD, out, (size_t)out_size, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    uint8_t* ds = nullptr;
+    Guarded dout;
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)src_size));
+    PROBE_HIP(hipMemcpyAsync(ds, src, (size_t)src_size, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dout, (size_t)out_size, GUARD, GUARD_FILL, out));
     a.src = preview_source(format == 2, format == 1, ds + data_off, ds + uv_off, sy, sx, sc, uv_stride);
     a.H = H, a.W = W, a.o = orient, a.has_joints = 1;
-    a.out = dout + GUARD + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
+    a.out = dout.data() + out_off, a.pitch = out_pitch, a.out_rgb = out_format;
     std::vector<JointsOut> hjo(P);
     std::vector<TrackOut> hto(P);
     std::vector<ConfOut> hco(P);
@@ -206,9 +172,9 @@ int pp_preview_people(uint8_t* src, int64_t src_size, int64_t data_off, int64_t 
     JointsOut* djo = nullptr;
     TrackOut* dto = nullptr;
     ConfOut* dco = nullptr;
-    PP_HIP(D.alloc((void**)&djo, P * sizeof(JointsOut)));
-    PP_HIP(D.alloc((void**)&dto, P * sizeof(TrackOut)));
-    PP_HIP(D.alloc((void**)&dco, P * sizeof(ConfOut)));
+    PROBE_HIP(D.alloc((void**)&djo, P * sizeof(JointsOut)));
+    PROBE_HIP(D.alloc((void**)&dto, P * sizeof(TrackOut)));
+    PROBE_HIP(D.alloc((void**)&dco, P * sizeof(ConfOut)));
     for (int p = 0; p < P; p++) {
         memset(&hjo[p], 0, sizeof(JointsOut)), memset(&hto[p], 0, sizeof(TrackOut)), memset(&hco[p], 0, sizeof(ConfOut));
         memcpy(hjo[p].j2d, j2d + p * OVERLAY_NJ * 2, sizeof hjo[p].j2d);
@@ -217,15 +183,13 @@ int pp_preview_people(uint8_t* src, int64_t src_size, int64_t data_off, int64_t 
         if (conf) memcpy(hco[p].conf, conf + p * OVERLAY_NJ, sizeof hco[p].conf);
         pin.jo[p] = djo + p, pin.to[p] = dto + p, pin.co[p] = in.has_conf ? dco + p : nullptr;
     }
-    PP_HIP(hipMemcpyAsync(djo, hjo.data(), P * sizeof(JointsOut), hipMemcpyHostToDevice, D.st));
-    PP_HIP(hipMemcpyAsync(dto, hto.data(), P * sizeof(TrackOut), hipMemcpyHostToDevice, D.st));
-    PP_HIP(hipMemcpyAsync(dco, hco.data(), P * sizeof(ConfOut), hipMemcpyHostToDevice, D.st));
-    PP_HIP(launch_preview_people(a, in, pin, D.st));
-    PP_HIP(hipMemcpyAsync(out, dout + GUARD, (size_t)out_size, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(guards, dout, GUARD, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(guards + GUARD, dout + GUARD + out_size, GUARD, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipMemcpyAsync(src, ds, (size_t)src_size, hipMemcpyDeviceToHost, D.st));
-    PP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(hipMemcpyAsync(djo, hjo.data(), P * sizeof(JointsOut), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dto, hto.data(), P * sizeof(TrackOut), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dco, hco.data(), P * sizeof(ConfOut), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(launch_preview_people(a, in, pin, D.st));
+    PROBE_HIP(read_guarded(D, dout, out, guards));
+    PROBE_HIP(hipMemcpyAsync(src, ds, (size_t)src_size, hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return PP_OK;
 }
 
@@ -243,11 +207,11 @@ int pp_time(int format, int H, int W, int orient, double factor, int n, float* m
     out_hw[0] = a.g.dh, out_hw[1] = a.g.dw;
     const size_t bytes = format == 2 ? (size_t)H * W * 3 / 2 : (size_t)H * W * 3;
     Dev D;
-    PP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     uint8_t *ds = nullptr, *dout = nullptr;
-    PP_HIP(D.alloc((void**)&ds, bytes));
-    PP_HIP(hipMemsetAsync(ds, 0x5A, bytes, D.st));
-    PP_HIP(D.alloc((void**)&dout, (size_t)a.g.dh * a.g.dw * 3));
+    PROBE_HIP(D.alloc((void**)&ds, bytes));
+    PROBE_HIP(hipMemsetAsync(ds, 0x5A, bytes, D.st));
+    PROBE_HIP(D.alloc((void**)&dout, (size_t)a.g.dh * a.g.dw * 3));
     a.src = preview_source(format == 2, false, ds, ds + (size_t)H * W, format == 2 ? W : 3LL * W, 3, 1, W);
     a.H = H, a.W = W, a.o = orient, a.out = dout, a.pitch = 3LL * a.g.dw, a.has_joints = 1;
     preview_colours(&a, nullptr, nullptr);
@@ -256,22 +220,7 @@ int pp_time(int format, int H, int W, int orient, double factor, int n, float* m
         in.j2d[2 * i] = a.g.Hp * (0.5 + 0.35 * ((i * 7) % 11 - 5) / 5.0), in.j2d[2 * i + 1] = a.g.Wp * (0.5 + 0.12 * ((i * 5) % 9 - 4) / 4.0);
     }
     in.has_rect = 1, in.rect[0] = a.g.Wp / 20, in.rect[1] = a.g.Hp / 20, in.rect[2] = a.g.Wp - a.g.Wp / 10, in.rect[3] = a.g.Hp - a.g.Hp / 10;
-    hipEvent_t e0, e1;
-    PP_HIP(hipEventCreate(&e0));
-    PP_HIP(hipEventCreate(&e1));
-    int rc = PP_OK;
-    for (int i = -3; i < n && rc == PP_OK; i++) {  // (three warm-up launches)
-        hipError_t e = hipEventRecord(e0, D.st);
-        if (e == hipSuccess) e = launch_preview(a, in, nullptr, nullptr, nullptr, D.st);
-        if (e == hipSuccess) e = hipEventRecord(e1, D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) rc = -(int)e - 1000;
-        else if (i >= 0) ms_out[i] = ms;
-    }
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-    return rc;
+    return timed_launches(D.st, n, ms_out, [&](int) { return launch_preview(a, in, nullptr, nullptr, nullptr, D.st); });
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 
 #include "kernels.h"
 #include "hog.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -21,60 +22,15 @@ enum { RP_OK = 0, RP_E_ARG = 1 };
 constexpr uint8_t GUARD_FILL = 0xC7;
 constexpr int GUARD = 256;
 
-#define RP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {
-    std::vector<void*> dev;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-};
-struct Guarded {
-    uint8_t* base = nullptr;
-    size_t bytes = 0;
-    uint8_t* data() const { return base + GUARD; }
-};
-int guarded(Dev& D, Guarded* g, size_t bytes)
-{
-    g->bytes = bytes;
-    RP_HIP(D.alloc((void**)&g->base, bytes + 2 * GUARD));
-    RP_HIP(hipMemsetAsync(g->base, GUARD_FILL, bytes + 2 * GUARD, D.st));
-    return 0;
-}
 // the buffer read back; *guard_bad grows by the guard bytes that are no longer the canary, *changed by the data bytes that differ from `was`
-int read_back(Dev& D, const Guarded& g, const uint8_t* was, std::vector<uint8_t>* out, long long* guard_bad, long long* changed)
+hipError_t read_back(Dev& D, const Guarded& g, const uint8_t* was, std::vector<uint8_t>* out, long long* guard_bad, long long* changed)
 {
-    std::vector<uint8_t> z(g.bytes + 2 * GUARD);
-    RP_HIP(hipMemcpyAsync(z.data(), g.base, z.size(), hipMemcpyDeviceToHost, D.st));
-    RP_HIP(hipStreamSynchronize(D.st));
-    for (int i = 0; i < GUARD; i++) *guard_bad += (z[i] != GUARD_FILL) + (z[GUARD + g.bytes + i] != GUARD_FILL);
-    for (size_t i = 0; i < g.bytes; i++) *changed += z[GUARD + i] != (was ? was[i] : GUARD_FILL);
-    if (out) out->assign(z.begin() + GUARD, z.begin() + GUARD + g.bytes);
-    return 0;
-}
-
-bool frame_ok(int64_t src_size, int64_t data_off, int64_t uv_off, int format, int H, int W, int64_t sy, int64_t sx, int64_t sc, int64_t uv_stride, int orient)
-{
-    if (src_size < 1 || H < 1 || W < 1 || H > HOG_MAX_SIDE || W > HOG_MAX_SIDE || data_off < 0 || format < 0 || format > 2 || !orient_ok(orient)) return false;
-    if (format == 2) {
-        if (((H | W) & 1) || sy < W || uv_stride < W || uv_off < 0 || sy > (1 << 24) || uv_stride > (1 << 24)) return false;
-        return data_off + (int64_t)(H - 1) * sy + W <= src_size && uv_off + (int64_t)(H / 2 - 1) * uv_stride + W <= src_size;
-    }
-    if (sy < 1 || sx < 1 || sc < 1 || sy > (1 << 24) || sx > (1 << 20) || sc > (1 << 28)) return false;
-    return data_off + ingest_span(H, W, sy, sx, sc) <= src_size;
+    std::vector<uint8_t> z(g.bytes);
+    const hipError_t e = guard_damage(D, g, z.data(), guard_bad);
+    if (e != hipSuccess) return e;
+    for (size_t i = 0; i < g.bytes; i++) *changed += z[i] != (was ? was[i] : GUARD_FILL);
+    if (out) out->swap(z);
+    return hipSuccess;
 }
 
 // the workspace of one (H, W) detection on the device, every buffer guarded
@@ -90,19 +46,19 @@ int make_work(Dev& D, const HogPlan& p, const std::vector<float>& d, int max_hit
 {
     HogTables tab;
     hog_tables(&tab);
-    RP_HIP(D.alloc((void**)&w->lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
-    RP_HIP(D.alloc((void**)&w->tab, sizeof tab));
-    RP_HIP(D.alloc((void**)&w->det, sizeof(float) * d.size()));
-    RP_HIP(D.alloc((void**)&w->gate, 64));
-    RP_HIP(hipMemcpyAsync(w->lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemcpyAsync(w->tab, &tab, sizeof tab, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemcpyAsync(w->det, d.data(), sizeof(float) * d.size(), hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipStreamSynchronize(D.st));  // (tab and p.lv are the caller's: copied before they go)
-    int rc;
-    if ((rc = guarded(D, &w->votes, sizeof(float2) * (size_t)p.npix)) || (rc = guarded(D, &w->bins, (size_t)p.npix)) ||
-        (rc = guarded(D, &w->blocks, sizeof(float) * HOG_BLOCK_LEN * (size_t)p.nblk)) || (rc = guarded(D, &w->hits, sizeof(HogHit) * (size_t)max_hits)) ||
-        (rc = guarded(D, &w->cnt, 4)))
-        return rc;
+    PROBE_HIP(D.alloc((void**)&w->lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
+    PROBE_HIP(D.alloc((void**)&w->tab, sizeof tab));
+    PROBE_HIP(D.alloc((void**)&w->det, sizeof(float) * d.size()));
+    PROBE_HIP(D.alloc((void**)&w->gate, 64));
+    PROBE_HIP(hipMemcpyAsync(w->lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(w->tab, &tab, sizeof tab, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(w->det, d.data(), sizeof(float) * d.size(), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));  // (tab and p.lv are the caller's: copied before they go)
+    PROBE_HIP(guarded(D, &w->votes, sizeof(float2) * (size_t)p.npix, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &w->bins, (size_t)p.npix, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &w->blocks, sizeof(float) * HOG_BLOCK_LEN * (size_t)p.nblk, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &w->hits, sizeof(HogHit) * (size_t)max_hits, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &w->cnt, 4, GUARD, GUARD_FILL));
     return 0;
 }
 std::vector<float> seeded_detector()
@@ -131,7 +87,8 @@ int rp_gated(const uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_
              int orient, double hit_threshold, int stride_x, int stride_y, double scale0, double final_threshold, int nlevels, int max_hits, const float* det, int ndet,
              int gate, int cap, int count0, float* votes, uint8_t* bins, float* blocks, int32_t* hits3, float* hit_s, int64_t* info)
 {
-    if (!src || !info || cap < 0 || count0 < 0 || !frame_ok(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, orient)) return RP_E_ARG;
+    if (!src || !info || cap < 0 || count0 < 0 || !orient_ok(orient)) return RP_E_ARG;
+    if (!frame_fits(src_size, data_off, uv_off, format, H, W, sy, sx, sc, uv_stride, HOG_MAX_SIDE)) return RP_E_ARG;
     std::vector<float> d;
     HogSpec sp;
     if (!hog_detector(det, ndet, &d) || hog_spec(hit_threshold, stride_x, stride_y, scale0, final_threshold, nlevels, max_hits, &sp)) return RP_E_ARG;
@@ -139,28 +96,29 @@ int rp_gated(const uint8_t* src, int64_t src_size, int64_t data_off, int64_t uv_
     HogPlan& p = pv[0];
     if (hog_plan(orient, H, W, sp, &p) || !p.n) return RP_E_ARG;
     Dev D;
-    RP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     uint8_t* ds = nullptr;
-    RP_HIP(D.alloc((void**)&ds, (size_t)src_size));
-    RP_HIP(hipMemcpyAsync(ds, src, (size_t)src_size, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)src_size));
+    PROBE_HIP(hipMemcpyAsync(ds, src, (size_t)src_size, hipMemcpyHostToDevice, D.st));
     Work w;
     int rc = make_work(D, p, d, sp.max_hits, &w);
     if (rc) return rc;
     const unsigned c0 = (unsigned)count0;
-    RP_HIP(hipMemcpyAsync(w.cnt.data(), &c0, 4, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemcpyAsync(w.gate, &gate, 4, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(w.cnt.data(), &c0, 4, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(w.gate, &gate, 4, hipMemcpyHostToDevice, D.st));
     HogSrc a;
     memset(&a, 0, sizeof a);
     a.src = preview_source(format == 2, format == 1, ds + data_off, ds + uv_off, sy, sx, sc, uv_stride);
     a.H = H, a.W = W, a.o = orient;
-    RP_HIP(launch_hog_gated(a, p, w.dev(), sp.hit_threshold, sp.max_hits, 7, w.gate, cap, D.st));
+    PROBE_HIP(launch_hog_gated(a, p, w.dev(), sp.hit_threshold, sp.max_hits, 7, w.gate, cap, D.st));
     long long bad = 0, changed = 0, cchanged = 0;
     std::vector<uint8_t> v, b, k, hb, c, back((size_t)src_size);
-    if ((rc = read_back(D, w.votes, nullptr, &v, &bad, &changed)) || (rc = read_back(D, w.bins, nullptr, &b, &bad, &changed)) ||
-        (rc = read_back(D, w.blocks, nullptr, &k, &bad, &changed)) || (rc = read_back(D, w.hits, nullptr, &hb, &bad, &changed)) ||
-        (rc = read_back(D, w.cnt, nullptr, &c, &bad, &cchanged)))
-        return rc;
-    RP_HIP(hipMemcpy(back.data(), ds, (size_t)src_size, hipMemcpyDeviceToHost));
+    PROBE_HIP(read_back(D, w.votes, nullptr, &v, &bad, &changed));
+    PROBE_HIP(read_back(D, w.bins, nullptr, &b, &bad, &changed));
+    PROBE_HIP(read_back(D, w.blocks, nullptr, &k, &bad, &changed));
+    PROBE_HIP(read_back(D, w.hits, nullptr, &hb, &bad, &changed));
+    PROBE_HIP(read_back(D, w.cnt, nullptr, &c, &bad, &cchanged));
+    PROBE_HIP(hipMemcpy(back.data(), ds, (size_t)src_size, hipMemcpyDeviceToHost));
     bad += memcmp(back.data(), src, (size_t)src_size) != 0;
     unsigned count;
     memcpy(&count, c.data(), 4);
@@ -209,31 +167,33 @@ int rp_pick(int orient, int H, int W, double scale0, int nlevels, const int32_t*
     t.status = crop_squarify(t.h, t.w, &t.fp);
     t.fail = t.status != SQ_OK ? 1u : 0u;
     Dev D;
-    RP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     HogLevel* lv = nullptr;
     int* dgate = nullptr;
-    RP_HIP(D.alloc((void**)&lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
-    RP_HIP(D.alloc((void**)&dgate, 64));
-    if (p.n) RP_HIP(hipMemcpyAsync(lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemcpyAsync(dgate, &gate, 4, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(D.alloc((void**)&lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
+    PROBE_HIP(D.alloc((void**)&dgate, 64));
+    if (p.n) PROBE_HIP(hipMemcpyAsync(lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dgate, &gate, 4, hipMemcpyHostToDevice, D.st));
     Guarded gh, gc, gs, gt, go;
-    int rc;
-    if ((rc = guarded(D, &gh, sizeof(HogHit) * (size_t)n)) || (rc = guarded(D, &gc, 4)) || (rc = guarded(D, &gs, sizeof(int) * 5 * HOG_TRACK_MAX_HITS)) ||
-        (rc = guarded(D, &gt, sizeof(TrackState))) || (rc = guarded(D, &go, sizeof(RedetectOut))))
-        return rc;
+    PROBE_HIP(guarded(D, &gh, sizeof(HogHit) * (size_t)n, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &gc, 4, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &gs, sizeof(int) * 5 * HOG_TRACK_MAX_HITS, GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &gt, sizeof(TrackState), GUARD, GUARD_FILL));
+    PROBE_HIP(guarded(D, &go, sizeof(RedetectOut), GUARD, GUARD_FILL));
     const unsigned cnt = (unsigned)count;
-    if (n) RP_HIP(hipMemcpyAsync(gh.data(), hits.data(), sizeof(HogHit) * n, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemcpyAsync(gc.data(), &cnt, 4, hipMemcpyHostToDevice, D.st));
-    RP_HIP(hipMemsetAsync(gs.data(), 0, gs.bytes, D.st));
-    RP_HIP(hipMemcpyAsync(gt.data(), &t, sizeof t, hipMemcpyHostToDevice, D.st));
+    if (n) PROBE_HIP(hipMemcpyAsync(gh.data(), hits.data(), sizeof(HogHit) * n, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(gc.data(), &cnt, 4, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemsetAsync(gs.data(), 0, gs.bytes, D.st));
+    PROBE_HIP(hipMemcpyAsync(gt.data(), &t, sizeof t, hipMemcpyHostToDevice, D.st));
     const HogDev dv{lv, nullptr, nullptr, nullptr, nullptr, nullptr, (HogHit*)gh.data(), (unsigned*)gc.data(), nullptr};
-    RP_HIP(launch_hog_pick(dv, p.n, max_hits, threshold, dgate, (int*)gs.data(), (TrackState*)gt.data(), xseq, (RedetectOut*)go.data(), D.st));
+    PROBE_HIP(launch_hog_pick(dv, p.n, max_hits, threshold, dgate, (int*)gs.data(), (TrackState*)gt.data(), xseq, (RedetectOut*)go.data(), D.st));
     long long bad = 0, hchg = 0, cchg = 0, schg = 0, tchg = 0, ochg = 0;
     std::vector<uint8_t> zeros(gs.bytes, 0), st, ov;
-    if ((rc = read_back(D, gh, (const uint8_t*)hits.data(), nullptr, &bad, &hchg)) || (rc = read_back(D, gc, (const uint8_t*)&cnt, nullptr, &bad, &cchg)) ||
-        (rc = read_back(D, gs, zeros.data(), nullptr, &bad, &schg)) || (rc = read_back(D, gt, (const uint8_t*)&t, &st, &bad, &tchg)) ||
-        (rc = read_back(D, go, nullptr, &ov, &bad, &ochg)))
-        return rc;
+    PROBE_HIP(read_back(D, gh, (const uint8_t*)hits.data(), nullptr, &bad, &hchg));
+    PROBE_HIP(read_back(D, gc, (const uint8_t*)&cnt, nullptr, &bad, &cchg));
+    PROBE_HIP(read_back(D, gs, zeros.data(), nullptr, &bad, &schg));
+    PROBE_HIP(read_back(D, gt, (const uint8_t*)&t, &st, &bad, &tchg));
+    PROBE_HIP(read_back(D, go, nullptr, &ov, &bad, &ochg));
     memcpy(state_out, st.data(), sizeof t);
     memcpy(out6, ov.data(), sizeof(RedetectOut));
     if (state_want && want_next4) {
@@ -263,39 +223,23 @@ int rp_time(int H, int W, int gate, int cap, int n, float* ms_out)
     std::vector<uint8_t> host(bytes);
     for (size_t i = 0; i < bytes; i++) host[i] = (uint8_t)((i * 2654435761u >> 11) % 251);
     Dev D;
-    RP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     uint8_t* ds = nullptr;
-    RP_HIP(D.alloc((void**)&ds, bytes));
-    RP_HIP(hipMemcpy(ds, host.data(), bytes, hipMemcpyHostToDevice));
+    PROBE_HIP(D.alloc((void**)&ds, bytes));
+    PROBE_HIP(hipMemcpy(ds, host.data(), bytes, hipMemcpyHostToDevice));
     Work w;
     int rc = make_work(D, p, seeded_detector(), sp.max_hits, &w);
     if (rc) return rc;
     const int g = gate > 0;
-    RP_HIP(hipMemcpy(w.gate, &g, 4, hipMemcpyHostToDevice));
-    RP_HIP(hipMemset(w.cnt.data(), 0, 4));
+    PROBE_HIP(hipMemcpy(w.gate, &g, 4, hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemset(w.cnt.data(), 0, 4));
     HogSrc a;
     memset(&a, 0, sizeof a);
     a.src = preview_source(false, false, ds, ds, 3LL * W, 3, 1, W);
     a.H = H, a.W = W, a.o = 0;
-    hipEvent_t ev[4];
-    for (hipEvent_t& e : ev) RP_HIP(hipEventCreate(&e));
-    rc = RP_OK;
-    for (int i = -2; i < n && rc == RP_OK; i++) {  // (two warm-up rounds)
-        hipError_t e = hipEventRecord(ev[0], D.st);
-        for (int s = 0; s < 3 && e == hipSuccess; s++) {
-            e = gate < 0 ? launch_hog(a, p, w.dev(), 3.0e38, sp.max_hits, 1 << s, D.st) : launch_hog_gated(a, p, w.dev(), 3.0e38, sp.max_hits, 1 << s, w.gate, cap, D.st);
-            if (e == hipSuccess) e = hipEventRecord(ev[s + 1], D.st);
-        }
-        if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
-        for (int s = 0; s < 3 && e == hipSuccess; s++) {
-            float ms = 0.f;
-            e = hipEventElapsedTime(&ms, ev[s], ev[s + 1]);
-            if (i >= 0) ms_out[3 * i + s] = ms;
-        }
-        if (e != hipSuccess) rc = -(int)e - 1000;
-    }
-    for (hipEvent_t& e : ev) (void)hipEventDestroy(e);
-    return rc;
+    return timed_launches(D.st, n, ms_out, [&](int s) {
+        return gate < 0 ? launch_hog(a, p, w.dev(), 3.0e38, sp.max_hits, 1 << s, D.st) : launch_hog_gated(a, p, w.dev(), 3.0e38, sp.max_hits, 1 << s, w.gate, cap, D.st);
+    }, 3);
 }
 
 // the pick kernel's duration on `nhits` hits of a 1920 x 1080 frame (clusters of up to nine neighbouring windows), n rounds: ms_out[n]
@@ -327,44 +271,30 @@ int rp_time_pick(int nhits, int n, float* ms_out)
     tv[0].w = tv[0].uw = tv[0].W = 1920, tv[0].h = tv[0].uh = tv[0].H = 1080;
     tv[0].status = crop_squarify(1080, 1920, &tv[0].fp);
     Dev D;
-    RP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     HogLevel* lv = nullptr;
     HogHit* dh = nullptr;
     unsigned* dc = nullptr;
     int *gate = nullptr, *cls = nullptr;
     TrackState* ts = nullptr;
     RedetectOut* out = nullptr;
-    RP_HIP(D.alloc((void**)&lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
-    RP_HIP(D.alloc((void**)&dh, sizeof(HogHit) * (size_t)nhits));
-    RP_HIP(D.alloc((void**)&dc, 64));
-    RP_HIP(D.alloc((void**)&gate, 64));
-    RP_HIP(D.alloc((void**)&cls, sizeof(int) * 5 * HOG_TRACK_MAX_HITS));
-    RP_HIP(D.alloc((void**)&ts, sizeof(TrackState)));
-    RP_HIP(D.alloc((void**)&out, sizeof(RedetectOut)));
+    PROBE_HIP(D.alloc((void**)&lv, sizeof(HogLevel) * HOG_MAX_LEVELS));
+    PROBE_HIP(D.alloc((void**)&dh, sizeof(HogHit) * (size_t)nhits));
+    PROBE_HIP(D.alloc((void**)&dc, 64));
+    PROBE_HIP(D.alloc((void**)&gate, 64));
+    PROBE_HIP(D.alloc((void**)&cls, sizeof(int) * 5 * HOG_TRACK_MAX_HITS));
+    PROBE_HIP(D.alloc((void**)&ts, sizeof(TrackState)));
+    PROBE_HIP(D.alloc((void**)&out, sizeof(RedetectOut)));
     const unsigned cnt = (unsigned)nhits;
     const int one = 1;
-    RP_HIP(hipMemcpy(lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice));
-    if (nhits) RP_HIP(hipMemcpy(dh, hits.data(), sizeof(HogHit) * nhits, hipMemcpyHostToDevice));
-    RP_HIP(hipMemcpy(dc, &cnt, 4, hipMemcpyHostToDevice));
-    RP_HIP(hipMemcpy(gate, &one, 4, hipMemcpyHostToDevice));
-    RP_HIP(hipMemset(cls, 0, sizeof(int) * 5 * HOG_TRACK_MAX_HITS));
-    RP_HIP(hipMemcpy(ts, &tv[0], sizeof(TrackState), hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemcpy(lv, p.lv, sizeof(HogLevel) * p.n, hipMemcpyHostToDevice));
+    if (nhits) PROBE_HIP(hipMemcpy(dh, hits.data(), sizeof(HogHit) * nhits, hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemcpy(dc, &cnt, 4, hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemcpy(gate, &one, 4, hipMemcpyHostToDevice));
+    PROBE_HIP(hipMemset(cls, 0, sizeof(int) * 5 * HOG_TRACK_MAX_HITS));
+    PROBE_HIP(hipMemcpy(ts, &tv[0], sizeof(TrackState), hipMemcpyHostToDevice));
     const HogDev dv{lv, nullptr, nullptr, nullptr, nullptr, nullptr, dh, dc, nullptr};
-    hipEvent_t ev[2];
-    for (hipEvent_t& e : ev) RP_HIP(hipEventCreate(&e));
-    int rc = RP_OK;
-    for (int i = -2; i < n && rc == RP_OK; i++) {
-        hipError_t e = hipEventRecord(ev[0], D.st);
-        if (e == hipSuccess) e = launch_hog_pick(dv, p.n, HOG_TRACK_MAX_HITS, 2, gate, cls, ts, 1u, out, D.st);
-        if (e == hipSuccess) e = hipEventRecord(ev[1], D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        if (i >= 0) ms_out[i] = ms;
-        if (e != hipSuccess) rc = -(int)e - 1000;
-    }
-    for (hipEvent_t& e : ev) (void)hipEventDestroy(e);
-    return rc;
+    return timed_launches(D.st, n, ms_out, [&](int) { return launch_hog_pick(dv, p.n, HOG_TRACK_MAX_HITS, 2, gate, cls, ts, 1u, out, D.st); });
 }
 
 }  // extern "C"

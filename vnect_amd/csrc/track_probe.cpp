@@ -15,6 +15,7 @@
 #include "crop.h"
 #include "hostplan.h"
 #include "kernels.h"
+#include "probe_util.h"
 
 using namespace vnect;
 
@@ -29,35 +30,6 @@ struct BoxCase {  // one case of tp_box on the device
     TrackState ts;
     JointsOut jo;
     TrackOut to;
-};
-
-#define TP_HIP(x)                           \
-    do {                                    \
-        const hipError_t e_ = (x);          \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // device / pinned allocations of one call, freed however it ends
-    std::vector<void*> dev, host;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-        for (void* p : host) (void)hipHostFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-    hipError_t pinned(void** p, size_t n)
-    {
-        const hipError_t e = hipHostMalloc(p, n ? n : 4, hipHostMallocMapped);
-        if (e == hipSuccess) host.push_back(*p);
-        return e;
-    }
 };
 
 // A state that a frame-reading kernel (crop copy, tracked pyramid) may be launched with, over an (H, W) frame `stride` bytes a row:
@@ -116,11 +88,11 @@ int tp_box(int n, const uint8_t* states, const double* joints, const uint32_t* x
     }
     if (bad) return bad;
     Dev D;
-    TP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     const int CH = 4096;
     std::vector<BoxCase> hb(n < CH ? n : CH);
     BoxCase* db = nullptr;
-    TP_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
+    PROBE_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
     for (int c0 = 0; c0 < n; c0 += CH) {
         const int m = n - c0 < CH ? n - c0 : CH;
         memset(hb.data(), 0, (size_t)m * sizeof(BoxCase));
@@ -130,10 +102,10 @@ int tp_box(int n, const uint8_t* states, const double* joints, const uint32_t* x
             memcpy(hb[i].jo.j2d, joints + (size_t)(c0 + i) * NJ * 2, sizeof hb[i].jo.j2d);
             memset(&hb[i].to, GARBAGE, sizeof(TrackOut));
         }
-        TP_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
-        for (int i = 0; i < m; i++) TP_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st));
-        TP_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
-        TP_HIP(hipStreamSynchronize(D.st));
+        PROBE_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
+        for (int i = 0; i < m; i++) PROBE_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st));
+        PROBE_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
+        PROBE_HIP(hipStreamSynchronize(D.st));
         for (int i = 0; i < m; i++) {
             memcpy(states_out + (size_t)(c0 + i) * sizeof(TrackState), &hb[i].ts, sizeof(TrackState));
             memcpy(tout + (size_t)(c0 + i) * 6, &hb[i].to, sizeof(TrackOut));
@@ -172,15 +144,15 @@ int tp_box_policy(int n, const uint8_t* states, const double* joints, const uint
     }
     if (bad) return bad;
     Dev D;
-    TP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     const int CH = 4096;
     const int m_max = n < CH ? n : CH;
     std::vector<BoxCase> hb(m_max);
     std::vector<PolicyCase> hp(m_max);
     BoxCase* db = nullptr;
     PolicyCase* dp = nullptr;
-    TP_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
-    TP_HIP(D.alloc((void**)&dp, hp.size() * sizeof(PolicyCase)));
+    PROBE_HIP(D.alloc((void**)&db, hb.size() * sizeof(BoxCase)));
+    PROBE_HIP(D.alloc((void**)&dp, hp.size() * sizeof(PolicyCase)));
     for (int c0 = 0; c0 < n; c0 += CH) {
         const int m = n - c0 < CH ? n - c0 : CH;
         memset(hb.data(), 0, (size_t)m * sizeof(BoxCase));
@@ -193,13 +165,13 @@ int tp_box_policy(int n, const uint8_t* states, const double* joints, const uint
             hp[i].pol = TrackPolicy{min_conf[c0 + i], min_joints[c0 + i], action[c0 + i]};
             memset(&hp[i].co, GARBAGE, sizeof(ConfOut));
         }
-        TP_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
-        TP_HIP(hipMemcpyAsync(dp, hp.data(), (size_t)m * sizeof(PolicyCase), hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(hipMemcpyAsync(db, hb.data(), (size_t)m * sizeof(BoxCase), hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(hipMemcpyAsync(dp, hp.data(), (size_t)m * sizeof(PolicyCase), hipMemcpyHostToDevice, D.st));
         for (int i = 0; i < m; i++)
-            TP_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st, dp[i].conf, &dp[i].pol, &dp[i].co));
-        TP_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
-        TP_HIP(hipMemcpyAsync(hp.data(), dp, (size_t)m * sizeof(PolicyCase), hipMemcpyDeviceToHost, D.st));
-        TP_HIP(hipStreamSynchronize(D.st));
+            PROBE_HIP(launch_track_box(&db[i].ts, &db[i].jo, &db[i].to, xseq[c0 + i], D.st, dp[i].conf, &dp[i].pol, &dp[i].co));
+        PROBE_HIP(hipMemcpyAsync(hb.data(), db, (size_t)m * sizeof(BoxCase), hipMemcpyDeviceToHost, D.st));
+        PROBE_HIP(hipMemcpyAsync(hp.data(), dp, (size_t)m * sizeof(PolicyCase), hipMemcpyDeviceToHost, D.st));
+        PROBE_HIP(hipStreamSynchronize(D.st));
         for (int i = 0; i < m; i++) {
             memcpy(states_out + (size_t)(c0 + i) * sizeof(TrackState), &hb[i].ts, sizeof(TrackState));
             memcpy(tout + (size_t)(c0 + i) * 6, &hb[i].to, sizeof(TrackOut));
@@ -230,22 +202,20 @@ int tp_copy(const uint8_t* frame, int H, int W, int64_t stride, int n, const uin
     }
     if (bad) return bad;
     Dev D;
-    TP_HIP(hipStreamCreate(&D.st));
-    uint8_t *pin = nullptr, *pin_dev = nullptr, *dst = nullptr;
+    PROBE_HIP(hipStreamCreate(&D.st));
+    uint8_t *pin = nullptr, *pin_dev = nullptr;
     TrackState* ds = nullptr;
-    const size_t region = (size_t)dst_cap + 2 * DST_GUARD;
-    TP_HIP(D.pinned((void**)&pin, (size_t)cap));
-    TP_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
+    Guarded dst;
+    PROBE_HIP(D.pinned((void**)&pin, (size_t)cap));
+    PROBE_HIP(hipHostGetDevicePointer((void**)&pin_dev, pin, 0));
     memset(pin, 0, (size_t)cap);
     memcpy(pin, frame, (size_t)used);
-    TP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    TP_HIP(D.alloc((void**)&dst, (size_t)n * region));
-    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemsetAsync(dst, DST_FILL, (size_t)n * region, D.st));
-    for (int i = 0; i < n; i++)
-        TP_HIP(launch_frame_copy_track(&ds[i], pin_dev, dst + (size_t)i * region + DST_GUARD, H, W, stride, pin_dev + cap, D.st));
-    TP_HIP(hipMemcpyAsync(dst_out, dst, (size_t)n * region, hipMemcpyDeviceToHost, D.st));
-    TP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(guarded(D, &dst, (size_t)dst_cap, DST_GUARD, DST_FILL, nullptr, n));
+    for (int i = 0; i < n; i++) PROBE_HIP(launch_frame_copy_track(&ds[i], pin_dev, dst.data(i), H, W, stride, pin_dev + cap, D.st));
+    PROBE_HIP(read_regions(D, dst, dst_out));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -287,29 +257,29 @@ int tp_pyramid(const uint8_t* frame, int H, int W, int64_t stride, int n, const 
             for (int r = 0; r < hs[i].h; r++)
                 memcpy(&pk[off[i] + (size_t)r * 3 * hs[i].w], frame + (size_t)(hs[i].y + r) * stride + (size_t)3 * hs[i].x, (size_t)3 * hs[i].w);
     Dev D;
-    TP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     uint8_t *dframe = nullptr, *dpk = nullptr, *dout = nullptr;
     TrackState* ds = nullptr;
     ScaleTabs* dt = nullptr;
     const size_t per = (size_t)S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
-    TP_HIP(D.alloc((void**)&dframe, (size_t)used));
-    TP_HIP(D.alloc((void**)&dpk, pk.size()));
-    TP_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
-    TP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
-    TP_HIP(D.alloc((void**)&dout, (size_t)n * per));
-    TP_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemsetAsync(dout, 0xFF, (size_t)n * per, D.st));
+    PROBE_HIP(D.alloc((void**)&dframe, (size_t)used));
+    PROBE_HIP(D.alloc((void**)&dpk, pk.size()));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)n * sizeof(TrackState)));
+    PROBE_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    PROBE_HIP(D.alloc((void**)&dout, (size_t)n * per));
+    PROBE_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemsetAsync(dout, 0xFF, (size_t)n * per, D.st));
     for (int i = 0; i < n; i++) {
         FrameDyn dyn = {};
         dyn.frame = packed[i] ? dpk + off[i] : dframe;
         dyn.row_stride = stride;
-        TP_HIP(launch_pyramid_track(&ds[i], dyn, packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
+        PROBE_HIP(launch_pyramid_track(&ds[i], dyn, packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
     }
-    TP_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
-    TP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 
@@ -349,28 +319,28 @@ int tp_pyramid_pair(const uint8_t* frame, int H, int W, int64_t stride, int n, c
             for (int r = 0; r < hs[i].h; r++)
                 memcpy(&pk[off[i] + (size_t)r * 3 * hs[i].w], frame + (size_t)(hs[i].y + r) * stride + (size_t)3 * hs[i].x, (size_t)3 * hs[i].w);
     Dev D;
-    TP_HIP(hipStreamCreate(&D.st));
+    PROBE_HIP(hipStreamCreate(&D.st));
     uint8_t *dframe = nullptr, *dpk = nullptr, *dout = nullptr;
     TrackState* ds = nullptr;
     ScaleTabs* dt = nullptr;
     const size_t per = (size_t)2 * S * BOX * BOX * 4 * (el == EL_F32 ? 4 : 2);
-    TP_HIP(D.alloc((void**)&dframe, (size_t)used));
-    TP_HIP(D.alloc((void**)&dpk, pk.size()));
-    TP_HIP(D.alloc((void**)&ds, (size_t)2 * n * sizeof(TrackState)));
-    TP_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
-    TP_HIP(D.alloc((void**)&dout, (size_t)n * per));
-    TP_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)2 * n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
-    TP_HIP(hipMemsetAsync(dout, fill & 0xFF, (size_t)n * per, D.st));
+    PROBE_HIP(D.alloc((void**)&dframe, (size_t)used));
+    PROBE_HIP(D.alloc((void**)&dpk, pk.size()));
+    PROBE_HIP(D.alloc((void**)&ds, (size_t)2 * n * sizeof(TrackState)));
+    PROBE_HIP(D.alloc((void**)&dt, sizeof(ScaleTabs)));
+    PROBE_HIP(D.alloc((void**)&dout, (size_t)n * per));
+    PROBE_HIP(hipMemcpyAsync(dframe, frame, (size_t)used, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dpk, pk.data(), pk.size(), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(ds, hs.data(), (size_t)2 * n * sizeof(TrackState), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemcpyAsync(dt, &tabs[0], sizeof(ScaleTabs), hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(hipMemsetAsync(dout, fill & 0xFF, (size_t)n * per, D.st));
     for (int i = 0; i < n; i++) {
         FrameDyn dyn[2] = {};
         for (int k = 0; k < 2; k++) dyn[k].frame = packed[i] ? dpk + off[2 * i + k] : dframe, dyn[k].row_stride = stride;
-        TP_HIP(launch_pyramid_track_pair(&ds[2 * i], dyn[0], dyn[1], packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
+        PROBE_HIP(launch_pyramid_track_pair(&ds[2 * i], dyn[0], dyn[1], packed[i] ? 1 : 0, dt, dout + (size_t)i * per, S, el, D.st));
     }
-    TP_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
-    TP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(hipMemcpyAsync(out, dout, (size_t)n * per, hipMemcpyDeviceToHost, D.st));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "probe_util.h"
 #include "view3d.h"
 
 using namespace vnect;
@@ -20,35 +21,6 @@ enum { VP_OK = 0, VP_E_ARG = 1 };
 constexpr uint8_t GUARD_FILL = 0xC7;
 constexpr int GUARD = 256;  // canary bytes in front of and behind the output's bytes (a multiple of 4: out_off alone sets the alignment)
 
-#define VP_HIP(x)                                     \
-    do {                                              \
-        const hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return -(int)e_ - 1000; \
-    } while (0)
-
-struct Dev {  // allocations of one call, freed however it ends
-    std::vector<void*> dev, host;
-    hipStream_t st = nullptr;
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-        for (void* p : dev) (void)hipFree(p);
-        for (void* p : host) (void)hipHostFree(p);
-    }
-    hipError_t alloc(void** p, size_t n)
-    {
-        const hipError_t e = hipMalloc(p, n ? n : 1);
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-    hipError_t pinned(void** p, size_t n)
-    {
-        const hipError_t e = hipHostMalloc(p, n, hipHostMallocMapped);
-        if (e == hipSuccess) host.push_back(*p);
-        return e;
-    }
-};
-
 // the inputs of a launch in either form: form 0 -- joints and confidences in device memory; form 1 -- a JointsOut and a ConfOut in pinned,
 // device-mapped host memory, as a result-ring slot holds them
 int place_inputs(Dev& D, int form, int status, const float* j3d, const double* conf, bool has_conf, const float** dj, const double** dc, const JointsOut** jo,
@@ -58,30 +30,30 @@ int place_inputs(Dev& D, int form, int status, const float* j3d, const double* c
     if (form == 1) {
         JointsOut* hjo = nullptr;
         ConfOut* hco = nullptr;
-        VP_HIP(D.pinned((void**)&hjo, sizeof *hjo));
+        PROBE_HIP(D.pinned((void**)&hjo, sizeof *hjo));
         memset(hjo, 0, sizeof *hjo);
         memcpy(hjo->j3d, j3d, sizeof hjo->j3d);
         hjo->status = status;
         void* d = nullptr;
-        VP_HIP(hipHostGetDevicePointer(&d, hjo, 0));
+        PROBE_HIP(hipHostGetDevicePointer(&d, hjo, 0));
         *jo = (const JointsOut*)d;
         if (has_conf) {
-            VP_HIP(D.pinned((void**)&hco, sizeof *hco));
+            PROBE_HIP(D.pinned((void**)&hco, sizeof *hco));
             memset(hco, 0, sizeof *hco);
             memcpy(hco->conf, conf, sizeof hco->conf);
-            VP_HIP(hipHostGetDevicePointer(&d, hco, 0));
+            PROBE_HIP(hipHostGetDevicePointer(&d, hco, 0));
             *co = (const ConfOut*)d;
         }
         return VP_OK;
     }
     float* pj = nullptr;
-    VP_HIP(D.alloc((void**)&pj, sizeof(float) * VIEW3D_NJ * 3));
-    VP_HIP(hipMemcpyAsync(pj, j3d, sizeof(float) * VIEW3D_NJ * 3, hipMemcpyHostToDevice, D.st));
+    PROBE_HIP(D.alloc((void**)&pj, sizeof(float) * VIEW3D_NJ * 3));
+    PROBE_HIP(hipMemcpyAsync(pj, j3d, sizeof(float) * VIEW3D_NJ * 3, hipMemcpyHostToDevice, D.st));
     *dj = pj;
     if (has_conf) {
         double* pc = nullptr;
-        VP_HIP(D.alloc((void**)&pc, sizeof(double) * VIEW3D_NJ));
-        VP_HIP(hipMemcpyAsync(pc, conf, sizeof(double) * VIEW3D_NJ, hipMemcpyHostToDevice, D.st));
+        PROBE_HIP(D.alloc((void**)&pc, sizeof(double) * VIEW3D_NJ));
+        PROBE_HIP(hipMemcpyAsync(pc, conf, sizeof(double) * VIEW3D_NJ, hipMemcpyHostToDevice, D.st));
         *dc = pc;
     }
     return VP_OK;
@@ -111,23 +83,19 @@ int vp_view3d(const float* j3d, const double* conf, int rows, int cols, double e
     if (out_off + (int64_t)(a.rows - 1) * out_pitch + 3LL * a.cols > out_size) return VP_E_ARG;
     if (!conf) a.has_conf = 0;
     Dev D;
-    VP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    uint8_t* dout = nullptr;
-    VP_HIP(D.alloc((void**)&dout, (size_t)out_size + 2 * GUARD));
-    VP_HIP(hipMemsetAsync(dout, GUARD_FILL, (size_t)out_size + 2 * GUARD, D.st));
-    VP_HIP(hipMemcpyAsync(dout + GUARD, out, (size_t)out_size, hipMemcpyHostToDevice, D.st));
-    a.out = dout + GUARD + out_off, a.pitch = out_pitch;
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    Guarded dout;
+    PROBE_HIP(guarded(D, &dout, (size_t)out_size, GUARD, GUARD_FILL, out));
+    a.out = dout.data() + out_off, a.pitch = out_pitch;
     const float* dj;
     const double* dc;
     const JointsOut* jo;
     const ConfOut* co;
     const int rc = place_inputs(D, form, status, j3d, conf, a.has_conf != 0, &dj, &dc, &jo, &co);
     if (rc) return rc;
-    VP_HIP(launch_view3d(a, dj, dc, jo, co, D.st));
-    VP_HIP(hipMemcpyAsync(out, dout + GUARD, (size_t)out_size, hipMemcpyDeviceToHost, D.st));
-    VP_HIP(hipMemcpyAsync(guards, dout, GUARD, hipMemcpyDeviceToHost, D.st));
-    VP_HIP(hipMemcpyAsync(guards + GUARD, dout + GUARD + out_size, GUARD, hipMemcpyDeviceToHost, D.st));
-    VP_HIP(hipStreamSynchronize(D.st));
+    PROBE_HIP(launch_view3d(a, dj, dc, jo, co, D.st));
+    PROBE_HIP(read_guarded(D, dout, out, guards));
+    PROBE_HIP(hipStreamSynchronize(D.st));
     return VP_OK;
 }
 
@@ -139,31 +107,17 @@ int vp_time(const float* j3d, int rows, int cols, int order, int form, int n, fl
     const View3dSpecIn s = {rows, cols, 0.0, nullptr, 0.0, nullptr, nullptr, nullptr, NAN, 0, order};
     if (!j3d || !ms_out || n < 1 || (form != 0 && form != 1) || view3d_setup(s, OVERLAY_PARENTS, &a)) return VP_E_ARG;
     Dev D;
-    VP_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
+    PROBE_HIP(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
     uint8_t* dout = nullptr;
-    VP_HIP(D.alloc((void**)&dout, (size_t)3 * a.rows * a.cols));
+    PROBE_HIP(D.alloc((void**)&dout, (size_t)3 * a.rows * a.cols));
     a.out = dout, a.pitch = 3LL * a.cols, a.has_conf = 0;
     const float* dj;
     const double* dc;
     const JointsOut* jo;
     const ConfOut* co;
-    int rc = place_inputs(D, form, 0, j3d, nullptr, false, &dj, &dc, &jo, &co);
+    const int rc = place_inputs(D, form, 0, j3d, nullptr, false, &dj, &dc, &jo, &co);
     if (rc) return rc;
-    hipEvent_t e0, e1;
-    VP_HIP(hipEventCreate(&e0));
-    VP_HIP(hipEventCreate(&e1));
-    for (int i = -3; i < n && rc == VP_OK; i++) {  // (three warm-up launches)
-        hipError_t e = hipEventRecord(e0, D.st);
-        if (e == hipSuccess) e = launch_view3d(a, dj, dc, jo, co, D.st);
-        if (e == hipSuccess) e = hipEventRecord(e1, D.st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) rc = -(int)e - 1000;
-        else if (i >= 0) ms_out[i] = ms;
-    }
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-    return rc;
+    return timed_launches(D.st, n, ms_out, [&](int) { return launch_view3d(a, dj, dc, jo, co, D.st); });
 }
 
 }  // extern "C"
