@@ -293,3 +293,24 @@ def test_python_loop_leaves_nothing_in_flight():
     j2, j3 = est(frames[9], timestamp=times[9])
     assert j2.shape == (21, 2) and np.all(np.isfinite(j2))
     est.close()
+
+
+def test_refused_second_video_leaves_no_rule_or_view_on_the_first():
+    """runner.track_many_on_device whose second video's rect starts outside the frame: vnect_track_begin refuses it after the first
+    video's stream has been given a loss rule under which every frame is lost, and a 3-D view.  The loop raises and switches both off
+    again (vnect_track_begin itself resets neither): a plain loop on stream 0 afterwards is runner.track, bit for bit, with no frame
+    lost and no view rendered."""
+    from vnect_amd import _native, runner
+    w = _planted()
+    frames, times = _video(6, seed=1600), _times(6, 11)
+    est = _est(w)
+    with pytest.raises(_native.VnectError) as e:
+        list(runner.track_many_on_device(est, [frames, frames], rects=[None, [700, 0, 100, 100]], timestamps=[times, times],
+                                         lost=(1e30, 1, "hold"), view3d=True))
+    assert e.value.code == _native.E_ARG
+    got = list(runner.track_on_device(est, frames, timestamps=times, confidence=True))
+    view = est.handle.result_view3d()
+    est.close()
+    assert [lost for _, _, _, _, lost in got] == [0] * 6
+    assert view is None
+    _assert_same([(j2, j3, list(u)) for j2, j3, u, _, _ in got], _host(w, frames, times), "after a refused setup")

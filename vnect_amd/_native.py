@@ -69,6 +69,24 @@ class OverlayStyle(C.Structure):
                 ("parents", C.c_int32 * 21), ("has_parents", C.c_int32)]
 
 
+def _set_parents(s, parents):
+    """parents (None: the reference's joint_parents stay) into the parents / has_parents fields of an OverlayStyle or a View3dSpec"""
+    if parents is not None:
+        parents = [int(v) for v in parents]
+        if len(parents) != 21:
+            raise ValueError("parents must name one joint for each of the 21 joints")
+        s.has_parents = 1
+        for k, v in enumerate(parents):
+            s.parents[k] = v
+
+
+def _out_pix(out_format):
+    """the PIX_* code of a preview's or a view's out_format"""
+    if out_format not in ("bgr", "rgb"):
+        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    return PIX_RGB if out_format == "rgb" else PIX_BGR
+
+
 def overlay_style(min_confidence=None, colors=None, parents=None):
     """The OverlayStyle of a draw.  min_confidence None: no threshold; colors: None, or (limb_bgr, rect_bgr) -- either may be None for the
     reference's; parents: None for the reference's joint_parents, or 21 joint indices."""
@@ -79,13 +97,7 @@ def overlay_style(min_confidence=None, colors=None, parents=None):
         s.limb_bgr[k] = int((LIMB_BGR if limb is None else limb)[k])
         s.rect_bgr[k] = int((RECT_BGR if rect is None else rect)[k])
     s.min_confidence = float("nan") if min_confidence is None else float(min_confidence)
-    if parents is not None:
-        parents = [int(v) for v in parents]
-        if len(parents) != 21:
-            raise ValueError("parents must name one joint for each of the 21 joints")
-        s.has_parents = 1
-        for k, v in enumerate(parents):
-            s.parents[k] = v
+    _set_parents(s, parents)
     return s
 
 
@@ -99,12 +111,11 @@ class PreviewSpec(C.Structure):
 
 def preview_spec(factor=None, out_format="bgr", draw_frame=False):
     """The PreviewSpec of a preview.  factor None (or 0): the reference's 1024 / the picture's longer side; out_format "bgr" or "rgb"."""
-    if out_format not in ("bgr", "rgb"):
-        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    out_format = _out_pix(out_format)
     s = PreviewSpec()
     s.struct_size = C.sizeof(PreviewSpec)
     s.factor = 0.0 if factor is None else float(factor)
-    s.out_format = PIX_RGB if out_format == "rgb" else PIX_BGR
+    s.out_format = out_format
     s.draw_frame = int(bool(draw_frame))
     return s
 
@@ -127,8 +138,7 @@ def view3d_spec(size=400, view=None, extent=500.0, line_width=3.0, background=No
     3 x 3 matrix (render.view_matrix); background: None (white) or BGR; colors: None (matplotlib's cycle) or 21 BGR triples; parents: None
     for the reference's joint_parents; min_confidence None: no threshold; out_format "bgr" or "rgb"; order 0 (a higher limb index lies on
     top) or 1 (the nearer limb does)."""
-    if out_format not in ("bgr", "rgb"):
-        raise ValueError("out_format must be 'bgr' or 'rgb'")
+    out_format = _out_pix(out_format)
     s = View3dSpec()
     s.struct_size = C.sizeof(View3dSpec)
     rows, cols = (size, size) if np.isscalar(size) else size
@@ -155,15 +165,9 @@ def view3d_spec(size=400, view=None, extent=500.0, line_width=3.0, background=No
         for i in range(21):
             for k in range(3):
                 s.colors_bgr[i][k] = int(c[i, k])
-    if parents is not None:
-        parents = [int(v) for v in parents]
-        if len(parents) != 21:
-            raise ValueError("parents must name one joint for each of the 21 joints")
-        s.has_parents = 1
-        for k, v in enumerate(parents):
-            s.parents[k] = v
+    _set_parents(s, parents)
     s.min_confidence = float("nan") if min_confidence is None else float(min_confidence)
-    s.out_format = PIX_RGB if out_format == "rgb" else PIX_BGR
+    s.out_format = out_format
     s.order = int(order)
     return s
 
@@ -351,7 +355,22 @@ def lib():
 
 
 def _ptr(a, t):
-    return a.ctypes.data_as(t)
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def _joints_out():
+    """fresh (joints_2d (21, 2) float64, joints_3d (21, 3) float32) for the library to fill"""
+    return np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+
+
+def _fixed(a, dtype, shape, name, optional=False):
+    """a per-joint argument as a contiguous `dtype` array, which must have `shape`; an optional one may be None and stays None"""
+    if a is None and optional:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != shape:
+        raise ValueError("%s must be %s" % (name, str(shape)))
+    return a
 
 
 def _rect4(rect):
@@ -484,7 +503,7 @@ class Handle:
         maps = np.ascontiguousarray(maps, dtype=np.float32)
         if maps.shape != (self.num_scales, 46, 46, 84):
             raise ValueError("maps must be (%d,46,46,84)" % self.num_scales)
-        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        j2, j3 = _joints_out()
         self._ck(lib().vnect_postprocess(self._h, _ptr(maps, _f32p), t2d, t3d, scaler, offset_x, offset_y,
                                          _ptr(j2, _f64p), _ptr(j3, _f32p)))
         return j2, j3
@@ -492,7 +511,7 @@ class Handle:
     def infer(self, img, t2d, t3d):
         img = _as_frame(img)
         H, W = img.shape[:2]
-        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        j2, j3 = _joints_out()
         self._ck(lib().vnect_infer(self._h, _ptr(img, _u8p), H, W, img.strides[0], t2d, t3d, _ptr(j2, _f64p),
                                    _ptr(j3, _f32p)))
         return j2, j3
@@ -517,7 +536,7 @@ class Handle:
     # one pair of result buffers whose ctypes pointers are made once, and return fresh copies as the reference does.
     def _results(self):
         if getattr(self, "_res", None) is None:
-            j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+            j2, j3 = _joints_out()
             self._res = (j2, j3, _ptr(j2, _f64p), _ptr(j3, _f32p), lib().vnect_infer_resident, lib().vnect_collect)
         return self._res
 
@@ -635,7 +654,7 @@ class Handle:
 
     def infer_nv12(self, nv12, t2d, t3d, rect=None):
         y, ys, uv, uvs, H, W = _as_nv12(nv12)
-        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        j2, j3 = _joints_out()
         self._ck(lib().vnect_infer_nv12(self._h, y, ys, uv, uvs, H, W, _rect4(rect), t2d, t3d, _ptr(j2, _f64p), _ptr(j3, _f32p)))
         return j2, j3
 
@@ -658,7 +677,7 @@ class Handle:
         self._ck_device(lib().vnect_upload_frame_device(self._h, slot, C.byref(frame), _stream_arg(stream)))
 
     def infer_device(self, frame, t2d, t3d, stream=None):
-        j2, j3 = np.empty((21, 2), np.float64), np.empty((21, 3), np.float32)
+        j2, j3 = _joints_out()
         self._ck_device(lib().vnect_infer_device(self._h, C.byref(frame), _stream_arg(stream), t2d, t3d, _ptr(j2, _f64p), _ptr(j3, _f32p)))
         return j2, j3
 
@@ -673,16 +692,9 @@ class Handle:
     # -- the overlay: skeleton and crop rectangle drawn into a frame in device memory (include/vnect_abi.h; OVERLAY.md) -------------------
     def draw_device(self, frame, joints_2d, rect=None, confidence=None, style=None, stream=None):
         """vnect_draw_device: draws into `frame` (a DeviceFrame without a rect); done on return."""
-        j2 = np.ascontiguousarray(joints_2d, dtype=np.float64)
-        if j2.shape != (21, 2):
-            raise ValueError("joints_2d must be (21, 2)")
-        cf = None
-        if confidence is not None:
-            cf = np.ascontiguousarray(confidence, dtype=np.float64)
-            if cf.shape != (21,):
-                raise ValueError("confidence must be (21,)")
-        self._ck_device(lib().vnect_draw_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(j2, _f64p),
-                                                None if cf is None else _ptr(cf, _f64p), _rect4(rect),
+        j2 = _fixed(joints_2d, np.float64, (21, 2), "joints_2d")
+        cf = _fixed(confidence, np.float64, (21,), "confidence", optional=True)
+        self._ck_device(lib().vnect_draw_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(j2, _f64p), _ptr(cf, _f64p), _rect4(rect),
                                                 None if style is None else C.byref(style)))
 
     def submit_tracked_device_draw(self, stream, frame, t2d, t3d, producer=None, style=None):
@@ -701,17 +713,9 @@ class Handle:
     def preview_device(self, frame, spec, out, out_pitch, joints_2d=None, rect=None, confidence=None, style=None, stream=None):
         """vnect_preview_device: the preview of `frame` (a DeviceFrame without a rect) into the memory at address `out` (device or host),
         rows out_pitch bytes apart; done on return.  The frame is not written."""
-        j2 = cf = None
-        if joints_2d is not None:
-            j2 = np.ascontiguousarray(joints_2d, dtype=np.float64)
-            if j2.shape != (21, 2):
-                raise ValueError("joints_2d must be (21, 2)")
-        if confidence is not None:
-            cf = np.ascontiguousarray(confidence, dtype=np.float64)
-            if cf.shape != (21,):
-                raise ValueError("confidence must be (21,)")
-        self._ck_device(lib().vnect_preview_device(self._h, C.byref(frame), _stream_arg(stream), None if j2 is None else _ptr(j2, _f64p),
-                                                   None if cf is None else _ptr(cf, _f64p), _rect4(rect),
+        j2 = _fixed(joints_2d, np.float64, (21, 2), "joints_2d", optional=True)
+        cf = _fixed(confidence, np.float64, (21,), "confidence", optional=True)
+        self._ck_device(lib().vnect_preview_device(self._h, C.byref(frame), _stream_arg(stream), _ptr(j2, _f64p), _ptr(cf, _f64p), _rect4(rect),
                                                    None if style is None else C.byref(style), C.byref(spec), C.c_void_p(int(out)), int(out_pitch)))
 
     def submit_tracked_device_preview(self, stream, frame, t2d, t3d, producer=None, style=None, spec=None):
@@ -721,27 +725,25 @@ class Handle:
         self._ck_device(lib().vnect_submit_tracked_device_preview(self._h, stream, C.byref(frame), _stream_arg(producer), t2d, t3d,
                                                                   None if style is None else C.byref(style), C.byref(spec)))
 
-    def result_preview(self):
-        """vnect_result_preview: the (dh, dw, 3) preview of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
+    def _result_picture(self, fn):
+        """fn(handle, data, rows and columns, pitch): the (rows, columns, 3) picture of the frame delivered last as a fresh array, or None"""
         data, hw, pitch = _u8p(), (C.c_int32 * 2)(), C.c_int64()
-        self._ck(lib().vnect_result_preview(self._h, C.byref(data), hw, C.byref(pitch)))
+        self._ck(fn(self._h, C.byref(data), hw, C.byref(pitch)))
         if hw[0] < 1 or hw[1] < 1:
             return None
         return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
+
+    def result_preview(self):
+        """vnect_result_preview: the (dh, dw, 3) preview of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
+        return self._result_picture(lib().vnect_result_preview)
 
     # -- the 3-D view: the skeleton plot of joints_3d, rendered on the device (include/vnect_abi.h; VIEW3D.md) ---------------------------
     def view3d_device(self, joints_3d, spec, out, out_pitch, confidence=None):
         """vnect_view3d_device: the view of joints_3d (21, 3) into the memory at address `out` (device or host), rows out_pitch bytes apart;
         done on return."""
-        j3 = np.ascontiguousarray(joints_3d, dtype=np.float32)
-        if j3.shape != (21, 3):
-            raise ValueError("joints_3d must be (21, 3)")
-        cf = None
-        if confidence is not None:
-            cf = np.ascontiguousarray(confidence, dtype=np.float64)
-            if cf.shape != (21,):
-                raise ValueError("confidence must be (21,)")
-        self._ck_device(lib().vnect_view3d_device(self._h, _ptr(j3, _f32p), None if cf is None else _ptr(cf, _f64p),
+        j3 = _fixed(joints_3d, np.float32, (21, 3), "joints_3d")
+        cf = _fixed(confidence, np.float64, (21,), "confidence", optional=True)
+        self._ck_device(lib().vnect_view3d_device(self._h, _ptr(j3, _f32p), _ptr(cf, _f64p),
                                                   None if spec is None else C.byref(spec), C.c_void_p(int(out)), int(out_pitch)))
 
     def track_view3d(self, stream, spec):
@@ -751,11 +753,7 @@ class Handle:
 
     def result_view3d(self):
         """vnect_result_view3d: the (rows, cols, 3) view of the frame collect_tracked delivered last (a fresh array), or None if it has none."""
-        data, hw, pitch = _u8p(), (C.c_int32 * 2)(), C.c_int64()
-        self._ck(lib().vnect_result_view3d(self._h, C.byref(data), hw, C.byref(pitch)))
-        if hw[0] < 1 or hw[1] < 1:
-            return None
-        return np.ctypeslib.as_array(data, shape=(hw[0], hw[1] * 3)).reshape(hw[0], hw[1], 3).copy()
+        return self._result_picture(lib().vnect_result_view3d)
 
     # -- the person detector: HOG + linear SVM over a pyramid, on the device (include/vnect_abi.h; HOG.md) ------------------------------
     def track_redetect(self, stream, spec=None, enable=True):

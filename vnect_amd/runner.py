@@ -11,7 +11,12 @@
   largest detection through ``cal_rect``; ``track(lost=(c, n, "detect"))`` calls it for the frame behind a lost one.
 The capture, drawing and 3-D plotting of the reference stay out of scope.
 """
+from collections import deque
+from operator import itemgetter
+
 import numpy as np
+
+from . import _native
 
 
 def load_bgr(path):
@@ -115,7 +120,6 @@ def hog_box(estimator, frame, pixel_format="bgr", orientation=None, stream=None,
     """``HOGBox.__call__`` without its window (src/hog_box.py:26-31): the person detector over the frame
     (``estimator.detect_people``; HOG.md), the detection of the largest area -- the first of equals, as ``np.argmax`` picks it --
     through ``cal_rect``; the whole frame when nobody is found.  Returns [x, y, w, h] in the oriented picture's coordinates."""
-    from . import _native
     rects, _ = estimator.detect_people(frame, pixel_format=pixel_format, orientation=orientation, stream=stream, **spec)
     if _native.is_device_array(frame):
         f = _native.device_frame(frame, pixel_format)
@@ -228,6 +232,178 @@ def track(estimator, frames, rect=None, transpose=False, timestamps=None, pixel_
             yield joints_2d, joints_3d, used
 
 
+# ---- the device loops: track_many_on_device and track_people_on_device are one scheme -- a submission is one library submit that delivers
+# k results (a video's frame: 1; a people frame: one per person) -- built from the pieces below ----------------------------------------
+def _given(option):
+    return option is not False and option is not None
+
+
+def _loop_options(estimator, device, draw, preview, view3d, lost, redetect=False, preview_style=False):
+    """``draw=``, ``preview=``, ``view3d=``, ``lost=`` and ``redetect=`` of a device loop as (overlay style, preview spec, view spec, loss
+    rule, re-detect spec), each None where not asked for.  ``device``: the frames are in device memory."""
+    style = spec = vspec = rspec = None
+    if _given(draw):
+        if not device:
+            raise ValueError("draw= annotates frames in device memory: it needs source='device'")
+        style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
+    if _given(preview):
+        if not device:
+            raise ValueError("preview= scales frames in device memory: it needs source='device'")
+        if isinstance(preview, _native.PreviewSpec):
+            spec = _native.preview_spec(preview.factor, "rgb" if preview.out_format == _native.PIX_RGB else "bgr", style is not None)
+        else:
+            spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
+        # The one asymmetry between the loops: a multi-video preview without draw= is submitted with a default style, made only now that
+        # draw_frame has been decided without it; a people preview without draw= passes no style
+        if style is None and preview_style:
+            style = _native.overlay_style(parents=estimator.joint_parents)
+    if _given(view3d):
+        vspec = view3d if isinstance(view3d, _native.View3dSpec) else _native.view3d_spec(parents=estimator.joint_parents)
+    rule = lost_rule(lost)
+    if _given(redetect):
+        if not device:
+            raise ValueError("redetect= runs the detector over frames in device memory: it needs source='device'")
+        if rule is None:
+            raise ValueError("redetect= needs a lost=(min_confidence, min_joints, 'hold' | 'reset') rule: without one no frame is ever lost")
+        kw = dict(redetect) if isinstance(redetect, dict) else {}
+        kw.setdefault("max_hits", _native.HOG_TRACK_MAX_HITS)
+        rspec = _native.hog_spec(**kw)
+    return style, spec, vspec, rule, rspec
+
+
+def _stored_size(f, device, nv12):
+    """(H, W) of the picture a frame holds, as it is stored: a DeviceFrame's own, else from the array's shape"""
+    if device:
+        return (f.H, f.W)
+    return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
+
+
+def _device_frame(f, pixel_format):
+    """a device array's descriptor (which keeps the array alive); its producer is the stream current now"""
+    d = _native.device_frame(f, pixel_format)
+    d._producer = _native.default_stream()
+    return d
+
+
+def _upload(estimator, slot, frame, code, nv12):
+    """a host frame into resident slot `slot` under orientation `code` (the slot holds the oriented frame from its upload on)"""
+    estimator._orient(code)
+    if nv12:
+        estimator.handle.upload_frame_nv12(slot, frame)
+    else:
+        estimator.handle.upload_frame(slot, frame)
+
+
+def _extras(h, confidence, spec, vspec, rspec):
+    """what one delivery appends to its tuple, read from the result slot of the frame just delivered -- (confidence, lost flag), the
+    preview (the pinned buffer of its ring slot, copied before the next submit), the view, the re-detection status"""
+    if not (confidence or spec is not None or vspec is not None):
+        return tuple                           # (nothing to append: tuple() is ())
+
+    def extras():
+        res = ()
+        if confidence:
+            res += h.result_confidence()
+        if spec is not None:
+            res += (h.result_preview(),)
+        if vspec is not None:
+            res += (h.result_view3d(),)
+        if rspec is not None and confidence:
+            res += (h.result_redetect()[0],)
+        return res
+    return extras
+
+
+class _InFlight:
+    """A device loop: the submissions it has in flight, oldest first, and what it switched on for them.
+
+    ``k``: deliveries per submission; ``window``: submissions in flight at most; ``deliver(stream, joints_2d, joints_3d, rect_used)``:
+    one delivery's tuple; ``result(tuples)``: what the loop yields for a submission's k tuples.  ``run`` is the loop; a caller describes
+    its set-up and its submissions as a generator and yields from ``run`` of it."""
+
+    def __init__(self, estimator, k, window, deliver, result):
+        self.estimator, self.h = estimator, estimator.handle
+        self.k, self.each, self.window, self.deliver, self.result = k, range(k), window, deliver, result
+        self.queue = deque()                   # submission numbers
+        self.held = {}                         # submission number -> the device frame it reads, until its last delivery has been collected
+        self.count = 0                         # the next submission's number
+        self.on = []                           # (the call that switches a thing off again, its arguments)
+
+    def switch_on(self, stream, rspec, rule, vspec):
+        """re-detection, loss rule and view of one stream, as far as asked for (re-detection first: what it refuses leaves no rule behind)"""
+        h = self.h
+        if rspec is not None:
+            h.track_redetect(stream, rspec, True)
+            self.on.append((h.track_redetect, (stream, None, False)))
+        if rule is not None:
+            h.track_policy(stream, *rule)
+            self.on.append((h.track_policy, (stream, 0.0, 1, "off")))
+        if vspec is not None:
+            h.track_view3d(stream, vspec)
+            self.on.append((h.track_view3d, (stream, None)))
+
+    def collect(self):
+        n = self.queue.popleft()
+        got, deliver, collect_tracked = [], self.deliver, self.h.collect_tracked
+        try:
+            for _ in self.each:
+                got.append(deliver(*collect_tracked()))
+        except _native.VnectError as e:
+            for _ in range(self.k - 1 - len(got)):     # the submission's other deliveries: collected and dropped
+                try:
+                    self.h.collect_tracked()
+                except _native.VnectError:
+                    pass
+            self.estimator._raise_like_reference(e)
+        finally:
+            self.held.pop(n, None)
+        return self.result(got)
+
+    def run(self, submissions):
+        """The loop.  ``submissions`` yields (call, args, hold, after), its set-up done by the time it yields the first: ``call(*args)``
+        makes one library submit (and what belongs to it); ``hold``: the device frame it reads, or None; ``after``: the number of a
+        submission that must have been collected before ``call`` runs, or None.  A refused submit raises as in ``track``: behind every
+        earlier frame's results.  An accepted one is followed by results until the window has room again.  Whatever ends the loop -- a
+        refused crop or timestamp, the caller's ``break``, any exception, in the set-up too -- what is still in flight is collected and
+        dropped, the estimator's own orientation is back in force and exactly what ``switch_on`` switched on is off again, each call on
+        its own: the estimator is usable at once afterwards (``track`` leaves nothing in flight either)."""
+        queue, window, held, collect = self.queue, self.window, self.held, self.collect
+        try:
+            for call, args, hold, after in submissions:
+                try:
+                    if after is not None:
+                        while any(n == after for n in queue):
+                            yield collect()
+                    call(*args)
+                except _native.VnectError as e:
+                    while queue:
+                        yield collect()
+                    self.estimator._raise_like_reference(e)
+                if hold is not None:
+                    held[self.count] = hold
+                queue.append(self.count)
+                self.count += 1                # (the submission has been made: `submissions` reads the count for its next one)
+                while len(queue) >= window:
+                    yield collect()
+            while queue:
+                yield collect()
+        finally:
+            while queue:
+                queue.popleft()
+                for _ in self.each:
+                    try:
+                        self.h.collect_tracked()
+                    except _native.VnectError:
+                        pass
+            held.clear()
+            self.estimator._orient(None)
+            for off, args in self.on:          # (nothing is in flight any more)
+                try:
+                    off(*args)
+                except _native.VnectError:
+                    pass
+
+
 def track_on_device(estimator, frames, rect=None, transpose=False, timestamps=None, ahead=1, source="pinned", stream=0, pixel_format="bgr",
                     confidence=False, lost=None, draw=False, orientation=None, preview=False, view3d=False, redetect=False):
     """``track`` with the crop box kept on the GPU (vnect_track_begin / vnect_submit_tracked*): yields what ``track`` yields, bit for bit.
@@ -279,42 +455,12 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     elements of every tuple).
     ``orientation``: one code for all videos or one per video (ORIENTATION.md; None: the estimator's own): every stream keeps the code its track began with, so
     videos with different orientations share the handle; the estimator's own orientation is back in force afterwards."""
-    from collections import deque
-
-    from . import _native
-    if draw is not False and draw is not None and source != "device":
-        raise ValueError("draw= annotates frames in device memory: it needs source='device'")
-    style = None
-    if draw is not False and draw is not None:
-        style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
-    spec = None
-    if preview is not False and preview is not None:
-        if source != "device":
-            raise ValueError("preview= scales frames in device memory: it needs source='device'")
-        if isinstance(preview, _native.PreviewSpec):
-            spec = _native.preview_spec(preview.factor, "rgb" if preview.out_format == _native.PIX_RGB else "bgr", style is not None)
-        else:
-            spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
-        if style is None:
-            style = _native.overlay_style(parents=estimator.joint_parents)
-    vspec = None
-    if view3d is not False and view3d is not None:
-        vspec = view3d if isinstance(view3d, _native.View3dSpec) else _native.view3d_spec(parents=estimator.joint_parents)
+    device = source == "device"
+    style, spec, vspec, rule, rspec = _loop_options(estimator, device, draw, preview, view3d, lost, redetect, preview_style=True)
     nv12 = _nv12_checks(pixel_format, transpose, source)
     codes = _orientations(estimator, orientation, len(videos), transpose)
-    rule = lost_rule(lost)
-    rspec = None
-    if redetect is not False and redetect is not None:
-        if source != "device":
-            raise ValueError("redetect= runs the detector over frames in device memory: it needs source='device'")
-        if rule is None:
-            raise ValueError("redetect= needs a lost=(min_confidence, min_joints, 'hold' | 'reset') rule: without one no frame is ever lost")
-        kw = dict(redetect) if isinstance(redetect, dict) else {}
-        kw.setdefault("max_hits", _native.HOG_TRACK_MAX_HITS)
-        rspec = _native.hog_spec(**kw)
     if source not in ("pinned", "resident", "device"):
         raise ValueError("source must be 'pinned', 'resident' or 'device'")
-    device = source == "device"
     h = estimator.handle
     n = len(videos)
     streams = list(range(n)) if streams is None else [int(s) for s in streams]
@@ -322,75 +468,50 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
     tss = [iter(t) if t is not None else None for t in (timestamps if timestamps is not None else [None] * n)]
     rects = rects if rects is not None else [None] * n
     limit = max(int(estimator._cfg.get("lanes", 1)), 2)
-    window = max(0, min(int(ahead), limit - 1)) + 1
-
-    def size_of(f):                            # (H, W) of the picture a frame array holds
-        if device:
-            return (f.H, f.W)
-        return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
+    nslots = int(getattr(h, "num_frame_slots", 0) or 4)
+    video_of = {s: i for i, s in enumerate(streams)}
+    extras = _extras(h, confidence, spec, vspec, rspec)
+    loop = _InFlight(estimator, 1, max(0, min(int(ahead), limit - 1)) + 1,
+                     lambda s, j2, j3, used: (video_of[s], j2, j3, used) + extras(), itemgetter(0))
 
     def prep(f):
-        if device:                             # its descriptor (which keeps the array alive); the producer is the stream current now
-            d = _native.device_frame(f, pixel_format)
-            d._producer = _native.default_stream()
-            return d
+        if device:
+            return _device_frame(f, pixel_format)
         f = np.rot90(f, 3) if transpose else f
         return np.ascontiguousarray(f, dtype=np.uint8)
 
-    pending = [None] * n
-    for i in range(n):                         # the first frame of every video: its size starts the stream's track
-        f = next(its[i], None)
-        if f is not None:
-            pending[i] = prep(f)
-            H, W = size_of(pending[i])
-            estimator._orient(codes[i])        # the stream keeps the code in force now; H, W: the picture's
-            h.track_begin(streams[i], W if codes[i] & 1 else H, H if codes[i] & 1 else W, rects[i])
-            if rspec is not None:              # (nothing is in flight yet; first: what it refuses leaves no rule behind)
-                try:
-                    h.track_redetect(streams[i], rspec, True)
-                except _native.VnectError:
-                    for k in range(i):
-                        if pending[k] is not None:
-                            h.track_redetect(streams[k], None, False)
-                            if rule is not None:
-                                h.track_policy(streams[k], 0.0, 1, "off")
-                    raise
-            if rule is not None:
-                h.track_policy(streams[i], *rule)
-            if vspec is not None:
-                h.track_view3d(streams[i], vspec)
-    flat = []
-    if source == "pinned":                     # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
-        nbytes = max([p.size for p in pending if p is not None] + [3])
-        flat = [h.frame_buffer(b, 1, (nbytes + 2) // 3).reshape(-1) for b in range(2)]
-    nslots = int(getattr(h, "num_frame_slots", 0) or 4)
-    inflight = deque()                         # (video, submission number)
-    held = {}                                  # submission number -> the device frame it reads, until it has been collected
-    video_of = {s: i for i, s in enumerate(streams)}
-    count = 0
+    if spec is not None:                       # the device submit of this loop, and what it takes behind the producer stream
+        submit_device, tail = h.submit_tracked_device_preview, (style, spec)
+    elif style is not None:
+        submit_device, tail = h.submit_tracked_device_draw, (style,)
+    else:
+        submit_device, tail = h.submit_tracked_device, ()
 
-    def collect():
-        _, k = inflight.popleft()
-        try:
-            s, j2, j3, used = h.collect_tracked()
-        except _native.VnectError as e:
-            estimator._raise_like_reference(e)
-        finally:
-            held.pop(k, None)
-        res = (video_of[s], j2, j3, used)
-        if confidence:                          # (of the frame just delivered: taken from its own result slot)
-            res += h.result_confidence()
-        if spec is not None:                    # (likewise: the pinned buffer of its ring slot, copied before the next submit)
-            res += (h.result_preview(),)
-        if vspec is not None:
-            res += (h.result_view3d(),)
-        if rspec is not None and confidence:
-            res += (h.result_redetect()[0],)
-        return res
+    submit_pinned = h.submit_tracked_pinned_nv12 if nv12 else h.submit_tracked_pinned
 
-    # Whatever ends the loop early -- a refused crop or timestamp, the caller's `break`, any exception -- the frames still in flight are
-    # collected and dropped, so the estimator is usable at once afterwards (runner.track leaves nothing in flight either)
-    try:
+    def copy_submit_pinned(view, frame, *args):
+        view[...] = frame
+        submit_pinned(*args)
+
+    def submit_resident(s, frame, t2d, t3d, code):
+        slot = loop.count % nslots
+        _upload(estimator, slot, frame, code, nv12)
+        h.submit_tracked(s, slot, t2d, t3d)
+
+    def submissions():
+        pending, sizes = [None] * n, [None] * n
+        for i in range(n):                     # the first frame of every video: its size starts the stream's track
+            f = next(its[i], None)
+            if f is not None:
+                pending[i] = prep(f)
+                H, W = sizes[i] = _stored_size(pending[i], device, nv12)
+                estimator._orient(codes[i])    # the stream keeps the code in force now; H, W: the picture's
+                h.track_begin(streams[i], W if codes[i] & 1 else H, H if codes[i] & 1 else W, rects[i])
+                loop.switch_on(streams[i], rspec, rule, vspec)     # (nothing is in flight yet)
+        flat = []
+        if source == "pinned":                 # the two pinned buffers, sized for the largest frame (nothing is in flight yet)
+            nbytes = max([p.size for p in pending if p is not None] + [3])
+            flat = [h.frame_buffer(b, 1, (nbytes + 2) // 3).reshape(-1) for b in range(2)]
         live = [p is not None for p in pending]
         while any(live):
             for i in range(n):
@@ -398,82 +519,28 @@ def track_many_on_device(estimator, videos, rects=None, transpose=False, timesta
                     continue
                 frame = pending[i]
                 t2d, t3d = estimator._stamps(next(tss[i]) if tss[i] is not None else None)
-                H, W = size_of(frame)
-                try:
-                    if device:
-                        if spec is not None:
-                            h.submit_tracked_device_preview(streams[i], frame, t2d, t3d, frame._producer, style, spec)
-                        elif style is not None:
-                            h.submit_tracked_device_draw(streams[i], frame, t2d, t3d, frame._producer, style)
-                        else:
-                            h.submit_tracked_device(streams[i], frame, t2d, t3d, frame._producer)
-                        held[count] = frame
-                    elif source == "pinned":
-                        b = count % 2                  # a frame captured into this buffer already (the view itself) is not copied
-                        view = flat[b][:frame.size].reshape(frame.shape)
-                        if frame.ctypes.data != view.ctypes.data:
-                            while any(k == count - 2 for _, k in inflight):   # the buffer's last frame must have been copied: collected
-                                yield collect()
-                            view[...] = frame
-                        if nv12:
-                            h.submit_tracked_pinned_nv12(streams[i], b, W, H * W, W, t2d, t3d)
-                        else:
-                            h.submit_tracked_pinned(streams[i], b, W * 3, t2d, t3d)
-                    else:
-                        slot = count % nslots
-                        estimator._orient(codes[i])    # (the slot holds the oriented frame from its upload on)
-                        if nv12:
-                            h.upload_frame_nv12(slot, frame)
-                        else:
-                            h.upload_frame(slot, frame)
-                        h.submit_tracked(streams[i], slot, t2d, t3d)
-                except _native.VnectError as e:           # as in track: every earlier frame's results first
-                    while inflight:
-                        yield collect()
-                    estimator._raise_like_reference(e)
-                inflight.append((i, count))
-                count += 1
-                while len(inflight) >= window:
-                    yield collect()
+                if device:
+                    yield submit_device, (streams[i], frame, t2d, t3d, frame._producer) + tail, frame, None
+                elif source == "pinned":
+                    H, W = sizes[i]
+                    b = loop.count % 2
+                    args = (streams[i], b, W, H * W, W, t2d, t3d) if nv12 else (streams[i], b, W * 3, t2d, t3d)
+                    view = flat[b][:frame.size].reshape(frame.shape)
+                    if frame.ctypes.data == view.ctypes.data:      # captured into this buffer already (the view itself): not copied
+                        yield submit_pinned, args, None, None
+                    else:                      # the buffer's last frame, two submissions back, must have been copied: collected
+                        yield copy_submit_pinned, (view, frame) + args, None, loop.count - 2
+                else:
+                    yield submit_resident, (streams[i], frame, t2d, t3d, codes[i]), None, None
                 f = next(its[i], None)
                 if f is None:
                     live[i] = False
                 else:
                     pending[i] = prep(f)
-                    if size_of(pending[i]) != (H, W):
+                    if _stored_size(pending[i], device, nv12) != sizes[i]:
                         raise ValueError("frames of one video must have one size")
-        while inflight:
-            yield collect()
-    finally:
-        while inflight:
-            inflight.popleft()
-            try:
-                h.collect_tracked()
-            except _native.VnectError:
-                pass
-        held.clear()
-        estimator._orient(None)                 # the estimator's own orientation again
-        if vspec is not None:                   # nothing is in flight any more: the streams render no view again
-            for i in range(n):
-                if pending[i] is not None:
-                    try:
-                        h.track_view3d(streams[i], None)
-                    except _native.VnectError:
-                        pass
-        if rspec is not None:                   # ... and they detect nobody again
-            for i in range(n):
-                if pending[i] is not None:
-                    try:
-                        h.track_redetect(streams[i], None, False)
-                    except _native.VnectError:
-                        pass
-        if rule is not None:                    # nothing is in flight any more: the streams' rule is off again
-            for i in range(n):
-                if pending[i] is not None:
-                    try:
-                        h.track_policy(streams[i], 0.0, 1, "off")
-                    except _native.VnectError:
-                        pass
+
+    yield from loop.run(submissions())
 
 
 def people_boxes(estimator, frame, people, pixel_format="bgr", orientation=None, stream=None, **spec):
@@ -481,7 +548,6 @@ def people_boxes(estimator, frame, people, pixel_format="bgr", orientation=None,
     ``estimator.detect_people`` ordered by area, largest first, equal areas by (y, x); the first ``people`` of them through ``cal_rect``;
     missing ones are the whole frame.  Host-only and deterministic.  Returns ``people`` rects [x, y, w, h] in the oriented picture's
     coordinates."""
-    from . import _native
     rects, _ = estimator.detect_people(frame, pixel_format=pixel_format, orientation=orientation, stream=stream, **spec)
     if _native.is_device_array(frame):
         f = _native.device_frame(frame, pixel_format)
@@ -513,9 +579,6 @@ def track_people_on_device(estimator, frames, rects, timestamps=None, ahead=1, s
     scaled (``render.resize_u8_exact``) -- computed on the device; the frame is written only if ``draw`` is given too.
     ``ahead``: frames submitted before the oldest is collected, clipped to what the unit limit (``max(lanes, 2)`` units in flight, a frame
     is ceil(P / 2) units paired, P unpaired) and the result ring (8) allow.  However the loop ends, nothing stays in flight."""
-    from collections import deque
-
-    from . import _native
     h = estimator.handle
     P = len(rects)
     if not 1 <= P <= int(getattr(h, "people", 0)):
@@ -523,129 +586,47 @@ def track_people_on_device(estimator, frames, rects, timestamps=None, ahead=1, s
     if source not in ("device", "resident"):
         raise ValueError("source must be 'device' or 'resident' (pinned sources are not supported in people mode)")
     device = source == "device"
-    style = None
-    if draw is not False and draw is not None:
-        if not device:
-            raise ValueError("draw= annotates frames in device memory: it needs source='device'")
-        style = draw if isinstance(draw, _native.OverlayStyle) else _native.overlay_style(parents=estimator.joint_parents)
-    spec = None
-    if preview is not False and preview is not None:
-        if not device:
-            raise ValueError("preview= scales frames in device memory: it needs source='device'")
-        if isinstance(preview, _native.PreviewSpec):
-            spec = _native.preview_spec(preview.factor, "rgb" if preview.out_format == _native.PIX_RGB else "bgr", style is not None)
-        else:
-            spec = _native.preview_spec(None if preview is True else float(preview), "bgr", style is not None)
-    vspec = None
-    if view3d is not False and view3d is not None:
-        vspec = view3d if isinstance(view3d, _native.View3dSpec) else _native.view3d_spec(parents=estimator.joint_parents)
+    style, spec, vspec, rule, _ = _loop_options(estimator, device, draw, preview, view3d, lost)
     nv12 = _nv12_checks(pixel_format, False, source)
     code = _orientations(estimator, orientation, 1, False)[0]
-    rule = lost_rule(lost)
     lanes = max(int(estimator._cfg.get("lanes", 1)), 1)
     paired = bool(getattr(h, "pair_people", False)) and P >= 2 and 2 * len(estimator.scales) <= 8
     units = (P + 1) // 2 if paired else P
-    window = max(0, min(int(ahead), max(lanes, 2) // units - 1, 8 // P - 1)) + 1
     ts = iter(timestamps) if timestamps is not None else None
     nslots = int(getattr(h, "num_frame_slots", 0) or 4)
-    inflight = deque()                         # submission numbers
-    held = {}                                  # submission number -> the device frame it reads, until its last person has been collected
-    count = 0
-    begun = False
+    extras = _extras(h, confidence, None, vspec, None)
+    def result(people):                        # (the frame's one picture came with its last person)
+        return (people, h.result_preview()) if spec is not None else (people,)
 
-    def size_of(f):                            # (H, W) of the picture a frame array holds, as it is stored
-        if device:
-            return (f.H, f.W)
-        return (f.shape[0] * 2 // 3, f.shape[1]) if nv12 else f.shape[:2]
+    loop = _InFlight(estimator, P, max(0, min(int(ahead), max(lanes, 2) // units - 1, 8 // P - 1)) + 1,
+                     lambda s, j2, j3, used: (j2, j3, used) + extras(), result)
 
-    def collect():
-        k = inflight.popleft()
-        people = []
-        try:
-            for p in range(P):
-                s, j2, j3, used = h.collect_tracked()
-                res = (j2, j3, used)
-                if confidence:
-                    res += h.result_confidence()
-                if vspec is not None:
-                    res += (h.result_view3d(),)
-                people.append(res)
-        except _native.VnectError as e:
-            for _ in range(P - 1 - len(people)):   # the frame's other persons: collected and dropped
-                try:
-                    h.collect_tracked()
-                except _native.VnectError:
-                    pass
-            estimator._raise_like_reference(e)
-        finally:
-            held.pop(k, None)
-        if spec is not None:                       # the frame's one picture came with its last person
-            return (people, h.result_preview())
-        return (people,)
+    def submit_resident(frame, t2d, t3d):
+        slot = loop.count % nslots
+        _upload(estimator, slot, frame, code, nv12)
+        h.submit_people(P, slot, t2d, t3d)
 
-    try:
+    def submissions():
+        size = None
         for f in frames:
-            if device:
-                frame = _native.device_frame(f, pixel_format)
-                frame._producer = _native.default_stream()
-            else:
-                frame = np.ascontiguousarray(f, dtype=np.uint8)
-            H, W = size_of(frame)
-            if not begun:
-                estimator._orient(code)        # every person keeps the code in force now; H, W below: the picture's
+            frame = _device_frame(f, pixel_format) if device else np.ascontiguousarray(f, dtype=np.uint8)
+            H, W = _stored_size(frame, device, nv12)
+            if size is None:
+                estimator._orient(code)        # every person keeps the code in force now; pH, pW: the picture's
                 pH, pW = (W, H) if code & 1 else (H, W)
                 h.people_begin(P, pH, pW, [[0, 0, pW, pH] if r is None else r for r in rects])
-                begun = True
                 for p in range(P):
-                    if rule is not None:
-                        h.track_policy(p, *rule)
-                    if vspec is not None:
-                        h.track_view3d(p, vspec)
+                    loop.switch_on(p, None, rule, vspec)
                 size = (H, W)
             elif (H, W) != size:
                 raise ValueError("frames of one video must have one size")
             t2d, t3d = estimator._stamps(next(ts) if ts is not None else None)
-            try:
-                if device:
-                    h.submit_people_device(P, frame, t2d, t3d, frame._producer, style, spec)
-                    held[count] = frame
-                else:
-                    slot = count % nslots
-                    estimator._orient(code)    # (the slot holds the oriented frame from its upload on)
-                    if nv12:
-                        h.upload_frame_nv12(slot, frame)
-                    else:
-                        h.upload_frame(slot, frame)
-                    h.submit_people(P, slot, t2d, t3d)
-            except _native.VnectError as e:    # as in track: every earlier frame's results first
-                while inflight:
-                    yield collect()
-                estimator._raise_like_reference(e)
-            inflight.append(count)
-            count += 1
-            while len(inflight) >= window:
-                yield collect()
-        while inflight:
-            yield collect()
-    finally:
-        while inflight:
-            inflight.popleft()
-            for _ in range(P):
-                try:
-                    h.collect_tracked()
-                except _native.VnectError:
-                    pass
-        held.clear()
-        estimator._orient(None)                 # the estimator's own orientation again
-        if begun:                               # nothing is in flight any more: no view, no rule
-            for p in range(P):
-                try:
-                    if vspec is not None:
-                        h.track_view3d(p, None)
-                    if rule is not None:
-                        h.track_policy(p, 0.0, 1, "off")
-                except _native.VnectError:
-                    pass
+            if device:
+                yield h.submit_people_device, (P, frame, t2d, t3d, frame._producer, style, spec), frame, None
+            else:
+                yield submit_resident, (frame, t2d, t3d), None, None
+
+    yield from loop.run(submissions())
 
 
 def synthetic_stream(stream, n_frames, height=368, width=368, smooth=True):
